@@ -32,6 +32,10 @@ Extra objects on the JSON line:
   cpu_baseline  the CPU oracle (restatement of the reference planner, -O3 -march=native) on a bounded sample of the
                 same workload, single thread like ReaK itself; host CPU model and core count stated
   cpu_baseline_all_cores  the same sample on every host core (one oracle process per core, independent seeds)
+
+--dump-outputs DIR writes what the last timed step computed (rrt_outputs: every problem's counters and best cost, a
+seeded sample of solution paths, tree vertices and loop iterations) as DIR/<name>.npy; the inputs depend only on the
+arguments, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -586,6 +590,72 @@ def run_c5(args, rank, world, local_rank, dist, reduce_device, lib, scenarios, d
         dist.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240611    # fixes which problems, vertices and iterations --dump-outputs samples
+DUMP_PROBLEMS = 8       # problems whose trees are sampled
+DUMP_ROWS = 16384       # vertices, and iterations, sampled per such problem
+
+
+def rrt_outputs(pl):
+    """What a caller of the C2 path receives from one step, as float64 arrays: the result counters and best cost of every
+    problem (rkh_planner_stats without edges_speculated / rounds, which describe the speculative schedule, not the
+    result), and for a fixed, seeded sample of problems the solution path and a seeded sample of tree vertices (state,
+    parent, goal-probe distance) and of loop iterations (nearest vertex, accept bit).  Root parent = 0xFFFFFFFF; solution
+    paths are padded with -1.  Every file is finite: best_cost (+inf without a solution) and tree_goal_dist (+inf where the
+    goal probe failed; the root has none, NaN) are split by split_nonfinite."""
+    stats = pl.all_stats
+    out = {k: np.array([getattr(s, k) for s in stats], dtype=np.float64)
+           for k in ("num_vertices", "iterations", "edges_checked", "num_solutions")}
+    out.update(split_nonfinite("best_cost", [s.best_cost for s in stats]))
+    problems = np.sort(np.random.default_rng(DUMP_SEED).choice(pl.P, size=min(pl.P, DUMP_PROBLEMS), replace=False))
+    paths = [pl.solution(int(p))[0] for p in problems]
+    sol = np.full((len(problems), max([1] + [len(q) for q in paths])), -1.0)
+    for i, q in enumerate(paths):
+        sol[i, :len(q)] = q
+    cols = {k: [] for k in ("tree_problem", "tree_vertex", "tree_pos", "tree_parent", "tree_goal_dist",
+                            "iter_problem", "iter_index", "iter_nn", "iter_accept")}
+    for p in problems:
+        t = pl.tree(int(p))
+        rng = np.random.default_rng([DUMP_SEED, int(p)])
+        nv, it = len(t["parent"]), len(t["accept"])
+        v = np.sort(rng.choice(nv, size=min(nv, DUMP_ROWS), replace=False))
+        i = np.sort(rng.choice(it, size=min(it, DUMP_ROWS), replace=False))
+        cols["tree_problem"].append(np.full(len(v), p))
+        cols["tree_vertex"].append(v)
+        cols["tree_pos"].append(t["pos"][v])
+        cols["tree_parent"].append(t["parent"][v])
+        cols["tree_goal_dist"].append(np.concatenate([[np.nan], t["goal_dist"]])[v])
+        cols["iter_problem"].append(np.full(len(i), p))
+        cols["iter_index"].append(i)
+        cols["iter_nn"].append(t["nn_seq"][i])
+        cols["iter_accept"].append(t["accept"][i])
+    out.update({"sample_problems": problems, "solution_length": [len(q) for q in paths], "solution_path": sol})
+    out.update({k: np.concatenate(v) for k, v in cols.items()})
+    out.update(split_nonfinite("tree_goal_dist", out.pop("tree_goal_dist")))
+    return out
+
+
+def split_nonfinite(name, a):
+    """{name: a with its non-finite entries set to 0, name + "_nonfinite": 0 finite, 1 +inf, 2 -inf, 3 NaN}."""
+    a = np.asarray(a, dtype=np.float64)
+    code = np.select([np.isposinf(a), np.isneginf(a), np.isnan(a)], [1.0, 2.0, 3.0], 0.0)
+    return {name: np.where(code == 0, a, 0.0), name + "_nonfinite": code}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64, all finite, at most DUMP_LIMIT_BYTES in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {bad}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -609,7 +679,14 @@ def main():
                     help="--workload c5, N > 1: RRT* loop iterations between two report-interval reductions")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-microbench", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, "
+                         "rank 0's problems; see rrt_outputs) so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs is implemented for --workload c2")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, RCCL rendezvous on
     # 127.0.0.1) before anything touches the GPU, and relay their output; under torchrun the world must match --gpus.
@@ -660,8 +737,9 @@ def main():
 
     nn_kernel = ["nn1_sweep_kernel"]
     interval_reports = [0]
+    kept = [None]
 
-    def run_step(step_index, timed):
+    def run_step(step_index, timed, keep=False):
         seeds = dist_utils.seeds_for_rank(step_index, rank, world, P)
         pl = lib.RrtPlannerPool(scene, [scn.rrt_params(seed=s, max_vertices=args.max_vertices) for s in seeds],
                                 groups=args.groups)
@@ -702,7 +780,10 @@ def main():
         steer_ms, steer_launches = pl.steer_profile()
         steer_steps = pl.steer_steps()
         nn_kernel[0] = lib.load().rkh_nn_kernel_name().decode()
-        pl.close()
+        if keep:
+            kept[0] = pl
+        else:
+            pl.close()
         return {"seconds": t1 - t0, "nodes": nodes, "edges": edges, "spec": spec, "rounds": rounds, "best": best,
                 "nn_ms": sum(p[0] for p in prof), "nn_bytes": sum(p[1] for p in prof), "nn_launches": sum(p[2] for p in prof),
                 "nn_pairs": nn_pairs, "steer_ms": steer_ms, "steer_launches": steer_launches, "steer_steps": steer_steps}
@@ -717,7 +798,7 @@ def main():
     torch.cuda.synchronize()
     t_begin = time.perf_counter()
     for k in range(args.steps):
-        r = run_step(k, True)
+        r = run_step(k, True, keep=bool(args.dump_outputs) and k == args.steps - 1)
         for key in tot:
             tot[key] += r[key]
         best = min(best, r["best"])
@@ -725,6 +806,14 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t_begin
+    if kept[0] is not None:
+        # the outputs are read back outside the clock; the planner's release, which every other step does inside it,
+        # is timed and added
+        if rank == 0:
+            write_outputs(args.dump_outputs, rrt_outputs(kept[0]))
+        t_close = time.perf_counter()
+        kept[0].close()
+        elapsed += time.perf_counter() - t_close
 
     # tree-size / edge counters (sum) and best solution cost (min) over all seeds: the only collectives
     elapsed, nodes_all, edges_all, spec_all, best = dist_utils.reduce_results(
