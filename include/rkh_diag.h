@@ -20,7 +20,7 @@ const char* rkh_nn_kernel_name(void);
 
 /* Shader-clock cycles of `iters` back-to-back f-evals + proximity tests.  One-wave-per-edge kernel: one wave per state,
  * cycles[B][8] = {sincos, forward sweep, jacobian columns, force sweep, mass matrix, cholesky, proximity, total};
- * two-lanes-per-edge kernels (RKH_LANES_PER_EDGE = 1 | 2 in the environment): one record per wave of 32 states,
+ * two-lanes-per-edge kernel (RKH_LANES_PER_EDGE = 2 in the environment): one record per wave of 32 states,
  * {frames + sincos, jacobian columns, mass matrix, force sweep, (assembly +) cholesky, proximity: joint frames, cull
  * (+ queueing), closed forms}. */
 rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double* u, uint32_t B, int iters,
@@ -48,7 +48,7 @@ rkh_status rkh_planner_steer_profile(rkh_planner* p, double* total_ms, uint64_t*
 /* Always on: RK4 steps the steer kernels of this planner integrated so far, over all edges (a step counts when it
  * starts from a live edge, the step that ends the edge included; steps skipped because the edge had ended do not).
  * The executed work of the steer launches -- an edge is launched for n_steps but stops at its first state that is not
- * free (MEAQR_topology.hpp:550-559).  (The first-generation lane kernel, RKH_LANE_VARIANT=1, does not count.) */
+ * free (MEAQR_topology.hpp:550-559). */
 rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps);
 
 /* The proximity test of the two-lanes steer kernels on B states (2 n_dof doubles each), counting what reaches each of

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
                                                            uint32_t* __restrict__ step_cnt) {
   __shared__ unsigned int s_waves;
   // live-edge counters of the step-wise steer launches of this round (launch_propagate_pair_steps)
-  if (step_cnt && threadIdx.x <= uint32_t(kMaxSteps) + 2u) step_cnt[threadIdx.x] = 0u;  // + the pool cursor (last word)
+  if (step_cnt && threadIdx.x <= uint32_t(kMaxSteps)) step_cnt[threadIdx.x] = 0u;
   // per-problem inputs of the batch formula, cached once (the bisection below evaluates it ten times per problem) and the
   // three count arrays, scanned in LDS; problems beyond the cache capacity fall back to global memory
   constexpr uint32_t kCache = 1024;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
       st->edges_speculated += B;
     }
     edges += B + st->n_new;
-    // counts of the three compact launch mappings (scanned below): steer waves (lane_kernel_edges_per_wave() edges each) per (candidates | probes) segment of
+    // counts of the three compact launch mappings (scanned below): steer waves (pair_kernel_edges_per_wave() edges each) per (candidates | probes) segment of
     // the two-lanes steer kernel, single edges per segment of the one-wave-per-edge kernel, query blocks of the NN sweep
     uint32_t* wb = cached ? s_scan[0] : wave_base;
     uint32_t* eb = cached ? s_scan[1] : edge_base;
@@ -414,52 +414,6 @@ __global__ __launch_bounds__(256) void gather_goal_dist_kernel(const GoalSeg* __
   for (uint64_t i = threadIdx.x; i < g.count; i += 256) out[g.dst_off + i] = g.src[i];
 }
 
-// Phase boundary of a split steer launch (launch_edges): the edges of a (problem, candidates | probes) segment whose
-// first `k_split` steps were all free go on, their ids are written to the segment's list (any order: edges are
-// independent and their results are indexed by the edge).  One block per segment.  Runs only when the two-lanes
-// mapping ran the first phase (the same gate); otherwise the lists are empty and the second launch finds no work.
-__global__ __launch_bounds__(256) void phase_compact_kernel(const EdgeIO* __restrict__ tab_a, const EdgeIO* __restrict__ tab_b,
-                                                             const EdgeIO* __restrict__ tab2_a,
-                                                             const EdgeIO* __restrict__ tab2_b, uint32_t k_split,
-                                                             uint32_t* __restrict__ cnt2, KernelGate gate) {
-  __shared__ uint32_t s_cnt;
-  const uint32_t prob = blockIdx.x, g = blockIdx.y;
-  const EdgeIO io = g ? tab_b[prob] : tab_a[prob];
-  uint32_t* ids = const_cast<uint32_t*>((g ? tab2_b[prob] : tab2_a[prob]).edge_ids);
-  if (threadIdx.x == 0) s_cnt = 0u;
-  __syncthreads();
-  bool run = true;
-  if (gate.count) {
-    const uint32_t c = *gate.count;
-    run = c >= gate.lo && c < gate.hi;
-  }
-  const uint32_t B = run ? (io.d_B ? *io.d_B : io.B) : 0u;
-  const int lane = threadIdx.x & 63;
-  for (uint32_t base = 0; base < B; base += 256) {
-    const uint32_t e = base + threadIdx.x;
-    const bool on = e < B && io.steps_free[e] == k_split;
-    const unsigned long long m = __ballot(on);
-    uint32_t off = 0;
-    if (lane == 0 && m) off = atomicAdd(&s_cnt, uint32_t(__popcll(m)));
-    off = __shfl(off, 0, 64);
-    if (on) ids[off + uint32_t(__popcll(m & ((1ull << lane) - 1ull)))] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) cnt2[2 * prob + g] = s_cnt;
-}
-
-// exclusive prefix of the second phase's working waves per segment (the KernelGate::wave_base of its launch)
-__global__ void phase_scan_kernel(const uint32_t* __restrict__ cnt2, uint32_t n_segments, uint32_t epw,
-                                  uint32_t* __restrict__ wave_base2) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  uint32_t acc = 0;
-  wave_base2[0] = 0;
-  for (uint32_t k = 0; k < n_segments; ++k) {
-    acc += (cnt2[k] + epw - 1u) / epw;
-    wave_base2[k + 1] = acc;
-  }
-}
-
 // before the flush launch: every pending probe rides, whatever the granule
 __global__ void probes_take_all_kernel(const ProblemDev* __restrict__ probs) {
   if (threadIdx.x != 0) return;
@@ -500,8 +454,6 @@ struct Problem {  // host view of one planning problem
   uint32_t* d_probe_steps = nullptr;
   void* d_mirror = nullptr;        // half-precision mirror of d_tree (nn_mirror.h)
   void* d_cand = nullptr;          // per-query scratch of the mirror sweep (nn1_mirror_carve), then one word: dx_max_bits
-  uint32_t* d_ids_c = nullptr;  // survivors of the first steer phase: candidates, goal probes (launch_edges)
-  uint32_t* d_ids_p = nullptr;
   double* d_goal = nullptr;
   double* d_part_dist = nullptr;
   uint32_t* d_part_idx = nullptr;
@@ -532,8 +484,7 @@ struct rkh_planner {
   uint32_t P = 0;
   std::vector<Problem> prob;
   uint32_t b_max = 1024;
-  int lanes_per_edge = 64;  // 64: one wavefront per candidate edge; 16: four candidates per wave; 1 / 2: two lanes per edge
-  int lane_variant = 2;     // throughput mapping of the automatic mode: 2 = propagate_pair.hip, 1 = propagate_lane.hip
+  int lanes_per_edge = 64;  // 64: one wavefront per candidate edge; 16: four candidates per wave; 2: two lanes per edge
   double* d_lane_ws = nullptr;  // workspace of the two-lanes-per-edge kernel
   double coord_bound = 0.0;     // max |coordinate| of vertices and samples (hyperbox bounds), 0 = unknown
   uint32_t* d_sel = nullptr;    // [2] edges of the current round (by round parity), see round_begin_kernel
@@ -557,25 +508,12 @@ struct rkh_planner {
   NnArgs* d_nn_args = nullptr;
   EdgeIO* d_io_steer = nullptr;
   EdgeIO* d_io_probe = nullptr;
-  // second phase of a split steer launch (launch_edges): the same records with the survivors' lists
-  EdgeIO* d_io_steer2 = nullptr;
-  EdgeIO* d_io_probe2 = nullptr;
-  uint32_t* d_cnt2 = nullptr;        // [2 P] survivors per (problem, candidates | probes) segment
-  uint32_t* d_wave_base2 = nullptr;  // [2 P + 1] prefix of their waves
-  uint32_t steer_split = 5;          // steps of the first phase (RKH_STEER_SPLIT; 0 = one launch for the whole edge)
-  // Step-wise steer launches (propagate_pair_step_kernel, the default; RKH_STEER_STEPWISE=0: the two-phase launch above):
-  // one launch per RK4 step over the live edges of all problems, survivors handed on through two ping-pong lists.
   bool nn_mirror = false;  // the NN search of a round runs over the trees' half-precision mirrors (nn_mirror.hip)
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
-  int steer_stepwise = 1;
-  // RKH_STEER_POOL=1: the first steer launch of a round in its POOL form (lane pairs refill from the round's pool).  Same
-  // results (test_stepwise_and_two_phase_...), measured SLOWER than one LIST launch per step (512 x 100 000: 6.45 against
-  // 7.57 M expansions/s): the lanes stay full while the pool lasts, but an edge started when it runs dry can still need
-  // 20 steps of >= 115 us each, and that tail is no shorter than the one every step-wise round has anyway.
-  int steer_pool = 0;
-  uint32_t pool_waves = 0;  // its grid: the resident steer waves of the device (RKH_STEER_POOL_WAVES: tests)
+  // Step-wise steer launches (propagate_pair_step_kernel): one launch per RK4 step over the live edges of all problems,
+  // survivors handed on through two ping-pong lists.
   uint2* d_step_list[2] = {nullptr, nullptr};  // (segment, edge) of the edges alive after step k (k odd / even)
-  uint32_t* d_step_cnt = nullptr;              // [kMaxSteps + 2] entries of the list launch k reads, + the pool cursor (cleared by round_begin_kernel)
+  uint32_t* d_step_cnt = nullptr;              // [kMaxSteps + 1] entries of the list launch k reads (cleared by round_begin_kernel)
   unsigned long long* d_steps_exec = nullptr;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
   uint32_t step_blocks_cap = 0;                // grid bound of a step launch (its blocks stride over the chunks beyond it)
   // rounds below this many edges keep the single whole-edge launch of the two-lanes mapping (RKH_STEER_SPLIT_MIN_EDGES;
@@ -711,20 +649,15 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
                           p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 64, tab_a, tab_b, p->P, nullptr,
                           gate_wave);
   if (st != RKH_OK) return st;
-  // The two-lanes mapping in two phases when the round is a regular one: half of the edges of a round end within a few
-  // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so the first
-  // steer_split steps run for every edge, the survivors are compacted per segment and only they run the remaining
-  // steps -- in fewer waves.  Same arithmetic per edge, same results.
-  const bool stepwise = p->steer_stepwise && p->d_step_cnt;
-  const bool split = compact && p->d_wave_base && p->d_io_steer2 && p->lane_variant == 2 && p->dyn.n_steps > 1 &&
-                     (stepwise || (p->steer_split > 0 && int(p->steer_split) < p->dyn.n_steps)) &&
-                     tab_a == p->d_io_steer && tab_b == p->d_io_probe;
-  if (!split)
+  // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
+  // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
+  // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
+  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1))
     return launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lane_variant, tab_a, tab_b,
-                            p->P, p->d_lane_ws, gate_lane);
-  // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes (64
-  // problems x 100 000 with the two-phase launch: 2.94 against 3.04 M expansions/s): such rounds take one launch
+                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
+                            p->d_lane_ws, gate_lane);
+  // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
+  // rounds take one whole-edge launch
   const uint32_t split_edges = p->split_min_edges;
   // host-side bound on the edges of this round (candidates + pending probes of all problems)
   const uint64_t edges_ub = std::min<uint64_t>(p->sum_batch_ub + p->prev_sum_batch_ub + uint64_t(p->P) * kProbeGranule,
@@ -732,43 +665,20 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   if (split_edges > gate_lane.lo) {
     KernelGate whole = gate_lane;
     whole.hi = split_edges;
-    whole.steps_exec = p->d_steps_exec;
     if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
       st = launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lane_variant, tab_a, tab_b,
-                            p->P, p->d_lane_ws, whole);
+                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
+                            p->d_lane_ws, whole);
       if (st != RKH_OK) return st;
     }
     gate_lane.lo = split_edges;
   }
   if (edges_ub < gate_lane.lo) return RKH_OK;
-  if (stepwise) {
-    const uint32_t epw = pair_kernel_edges_per_wave();
-    const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
-    // (the pool cursor is the last word of the step counters: round_begin_kernel clears it with them)
-    return launch_propagate_pair_steps(p->stream, p->n_dof, p->scene->d_scene, p->dyn, tab_a, tab_b, p->P,
-                                       p->d_wave_base + (2 * p->P + 1), p->d_step_list[0], p->d_step_list[1],
-                                       p->d_step_cnt, p->d_lane_ws, blocks, gate_lane, p->d_steps_exec,
-                                       p->steer_pool ? p->pool_waves : 0u, p->d_step_cnt + kMaxSteps + 2);
-  }
-  KernelGate g1 = gate_lane;
-  g1.step1 = p->steer_split;
-  st = launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                        p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lane_variant, tab_a, tab_b, p->P,
-                        p->d_lane_ws, g1);
-  if (st != RKH_OK) return st;
-  hipLaunchKernelGGL(phase_compact_kernel, dim3(p->P, 2), dim3(256), 0, p->stream, p->d_io_steer, p->d_io_probe,
-                     p->d_io_steer2, p->d_io_probe2, p->steer_split, p->d_cnt2, gate_lane);
-  hipLaunchKernelGGL(phase_scan_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cnt2, 2 * p->P,
-                     pair_kernel_edges_per_wave(), p->d_wave_base2);
-  RKH_HIP(hipGetLastError());
-  KernelGate g2 = gate_lane;
-  g2.wave_base = p->d_wave_base2;
-  g2.n_segments = 2 * p->P;
-  g2.step0 = p->steer_split;
-  return launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                          p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lane_variant, p->d_io_steer2,
-                          p->d_io_probe2, p->P, p->d_lane_ws, g2);
+  const uint32_t epw = pair_kernel_edges_per_wave();
+  const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
+  return launch_propagate_pair_steps(p->stream, p->n_dof, p->scene->d_scene, p->dyn, tab_a, tab_b, p->P,
+                                     p->d_wave_base + (2 * p->P + 1), p->d_step_list[0], p->d_step_list[1], p->d_step_cnt,
+                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec);
 }
 
 // goal probes still pending after the last enqueued round
@@ -826,7 +736,7 @@ rkh_status enqueue_round(rkh_planner* p) {
   hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs, p->P, slot, p->d_sel, p->round_parity,
                      fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base, p->d_nn_base,
                      p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries(),
-                     p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, lane_kernel_edges_per_wave(),
+                     p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
                      p->d_step_cnt);
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
@@ -861,7 +771,7 @@ rkh_status enqueue_round(rkh_planner* p) {
 void free_problem(Problem& q) {
   void* bufs[] = {q.d_tree, q.d_parent, q.d_node_sample, q.d_goal_dist, q.d_samples, q.d_nn_seq, q.d_accept_log,
                   q.d_nn_idx, q.d_nn_dist, q.d_x_out, q.d_steps, q.d_accept, q.d_probe_x, q.d_probe_steps, q.d_goal,
-                  q.d_part_dist, q.d_part_idx, q.d_round_n, q.d_mt, q.d_ids_c, q.d_ids_p, q.d_mirror, q.d_cand};
+                  q.d_part_dist, q.d_part_idx, q.d_round_n, q.d_mt, q.d_mirror, q.d_cand};
   for (void* b : bufs) (void)hipFree(b);
 }
 
@@ -894,7 +804,6 @@ rkh_status grow_sample_buffers(rkh_planner* p, uint32_t i, uint64_t new_cap) {
   RKH_HIP(hipMemcpy(&p->d_probs[i].accept_log, &na, sizeof(na), hipMemcpyHostToDevice));
   RKH_HIP(hipMemcpy(&p->d_nn_args[i].q, &cs, sizeof(cs), hipMemcpyHostToDevice));
   RKH_HIP(hipMemcpy(&p->d_io_steer[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
-  if (p->d_io_steer2) RKH_HIP(hipMemcpy(&p->d_io_steer2[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
   return RKH_OK;
 }
 
@@ -979,25 +888,17 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
     RKH_HIP(hipMalloc(&p->d_bounds, bounds.size() * sizeof(double)));
     RKH_HIP(hipMemcpy(p->d_bounds, bounds.data(), bounds.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  if (const char* e = getenv("RKH_LANE_VARIANT")) p->lane_variant = (atoi(e) == 1) ? 1 : 2;
   if (const char* e = getenv("RKH_WAVE_FIT")) p->wave_fit = atoi(e);
-  if (const char* e = getenv("RKH_STEER_SPLIT")) p->steer_split = uint32_t(std::max(0, atoi(e)));
   if (const char* e = getenv("RKH_WAVE_FILL")) p->wave_fill = atof(e);
-  if (const char* e = getenv("RKH_STEER_STEPWISE")) p->steer_stepwise = atoi(e);
-  if (const char* e = getenv("RKH_STEER_POOL")) p->steer_pool = atoi(e);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, scene->ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
-      p->wave_slots = uint32_t(prop.multiProcessorCount) * (p->lane_variant == 2 ? pair_kernel_waves_per_cu(scene->host.n_dof)
-                                                                                 : lane_kernel_waves_per_cu(scene->host.n_dof));
+      p->wave_slots = uint32_t(prop.multiProcessorCount) * pair_kernel_waves_per_cu(scene->host.n_dof);
     if (getenv("RKH_VERBOSE")) fprintf(stderr, "rkh planner: %d CUs, %u resident steer waves\n", prop.multiProcessorCount, p->wave_slots);
   }
-  // whole-edge launches below: step-wise, one 32-edge wave per SIMD; two-phase, one pass of steer waves (its optimum)
-  p->split_min_edges = (p->steer_stepwise ? p->wave_slots / 2 : p->wave_slots) * pair_kernel_edges_per_wave();
+  p->split_min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();
   if (const char* e = getenv("RKH_STEER_SPLIT_MIN_EDGES")) p->split_min_edges = uint32_t(std::max(0, atoi(e)));
   p->step_blocks_cap = 2 * p->wave_slots;
-  p->pool_waves = p->wave_slots;
-  if (const char* e = getenv("RKH_STEER_POOL_WAVES")) p->pool_waves = uint32_t(std::max(1, atoi(e)));
   // Many problems per planner: a round's candidates per problem stay within ONE query block of the mirror sweep (a
   // second block re-reads the whole tree for a handful of queries; 512 problems x 100 000: 7.45 -> 7.62 M expansions/s).
   // The batch rule only reaches the cap late in a run (1.25 sqrt(n) = 384 at n = 94 k) or through the wave fit's scale.
@@ -1008,16 +909,15 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   if (const char* e = getenv("RKH_DUO_THRESHOLD")) p->duo_threshold = uint32_t(std::max(0, atoi(e)));
   if (p->scene->host.has_meshes) p->duo_threshold = 0;  // (instantiated without the support-map query only)
   if (const char* e = getenv("RKH_LANES_PER_EDGE")) {
-    p->lanes_per_edge = (atoi(e) == 1) ? 1 : ((atoi(e) == 2) ? 2 : ((atoi(e) == 16) ? 16 : (atoi(e) == 0 ? 0 : 64)));
-  } else if (p->n_dof <= 6 && scene_fits_lane_kernel(scene->host, p->lane_variant)) {
+    p->lanes_per_edge = (atoi(e) == 2) ? 2 : ((atoi(e) == 16) ? 16 : (atoi(e) == 0 ? 0 : 64));
+  } else if (p->n_dof <= 6 && scene_fits_lane_kernel(scene->host)) {
     p->lanes_per_edge = 0;  // automatic, per round
   } else {
     // one wavefront per candidate is the latency-optimal mapping; once a round can offer more waves than the chip
     // has slots (256 CUs x 4 SIMDs x 2 waves) four candidates share a wave
     p->lanes_per_edge = (uint64_t(n_problems) * 2 * p->b_max > 4096) ? 16 : 64;
   }
-  if ((p->lanes_per_edge == 1 || p->lanes_per_edge == 2 || p->lanes_per_edge == 0) &&
-      !(p->n_dof <= 7 && scene_fits_lane_kernel(scene->host, p->lanes_per_edge == 1 ? 1 : p->lane_variant)))
+  if ((p->lanes_per_edge == 2 || p->lanes_per_edge == 0) && !(p->n_dof <= 7 && scene_fits_lane_kernel(scene->host)))
     p->lanes_per_edge = 64;  // the two-lanes-per-edge kernel does not take this scene
   if (p->lanes_per_edge == 16 && 2 * p->n_dof > 16) p->lanes_per_edge = 64;  // a 16-lane group holds at most 16 components
   if (scene->host.planar) p->lanes_per_edge = 64;  // planar chains have one mapping (one lane per edge, propagate_planar.hip)
@@ -1051,13 +951,23 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   RKH_HIP(hipMalloc(&p->d_nn_args, P * sizeof(NnArgs)));
   RKH_HIP(hipMalloc(&p->d_io_steer, P * sizeof(EdgeIO)));
   RKH_HIP(hipMalloc(&p->d_io_probe, P * sizeof(EdgeIO)));
-  if (!p->quasi_static && (p->lanes_per_edge == 1 || p->lanes_per_edge == 2 || p->lanes_per_edge == 0))
-    RKH_HIP(hipMalloc(&p->d_lane_ws, std::max(propagate_lanes_workspace_bytes(p->n_dof, p->b_max, p->b_max, P),
-                                              propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P))));
+  // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
+  // see prev_batch_ub and flush_probes)
+  if (!p->quasi_static && (p->lanes_per_edge == 2 || p->lanes_per_edge == 0))
+    RKH_HIP(hipMalloc(&p->d_lane_ws, propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max + kProbeGranule, P)));
   if (p->d_lane_ws) {
     // two prefix arrays of 2 P + 1 entries: waves of the two-lanes kernel, then single edges (one-wave-per-edge kernel)
     RKH_HIP(hipMalloc(&p->d_wave_base, 2 * (2 * size_t(P) + 1) * sizeof(uint32_t)));
     RKH_HIP(hipMemset(p->d_wave_base, 0, 2 * (2 * size_t(P) + 1) * sizeof(uint32_t)));
+    const size_t cap = size_t(P) * (2 * size_t(p->b_max) + kProbeGranule);
+    for (auto& l : p->d_step_list) RKH_HIP(hipMalloc(&l, cap * sizeof(uint2)));
+    RKH_HIP(hipMalloc(&p->d_step_cnt, (kMaxSteps + 1) * sizeof(uint32_t)));
+    RKH_HIP(hipMemset(p->d_step_cnt, 0, (kMaxSteps + 1) * sizeof(uint32_t)));
+    // the step kernel's blocks take their RK4 workspace out of the two-lanes workspace
+    if (propagate_pair_step_workspace_bytes(p->n_dof, p->step_blocks_cap) >
+        propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P))
+      p->step_blocks_cap = uint32_t(propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P) /
+                                    propagate_pair_step_workspace_bytes(p->n_dof, 1));
   }
   RKH_HIP(hipMalloc(&p->d_nn_base, (size_t(P) + 1) * sizeof(uint32_t)));
   RKH_HIP(hipMemset(p->d_nn_base, 0, (size_t(P) + 1) * sizeof(uint32_t)));
@@ -1211,39 +1121,6 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   RKH_HIP(hipMemcpy(p->d_nn_args, hn.data(), P * sizeof(NnArgs), hipMemcpyHostToDevice));
   RKH_HIP(hipMemcpy(p->d_io_steer, hio.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
   RKH_HIP(hipMemcpy(p->d_io_probe, hgp.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-  if (p->d_wave_base && !p->quasi_static) {  // second phase of a split steer launch: the same edges through the survivors' lists
-    RKH_HIP(hipMalloc(&p->d_io_steer2, P * sizeof(EdgeIO)));
-    RKH_HIP(hipMalloc(&p->d_io_probe2, P * sizeof(EdgeIO)));
-    RKH_HIP(hipMalloc(&p->d_cnt2, 2 * size_t(P) * sizeof(uint32_t)));
-    RKH_HIP(hipMemset(p->d_cnt2, 0, 2 * size_t(P) * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&p->d_wave_base2, (2 * size_t(P) + 1) * sizeof(uint32_t)));
-    RKH_HIP(hipMemset(p->d_wave_base2, 0, (2 * size_t(P) + 1) * sizeof(uint32_t)));
-    if (p->steer_stepwise && p->lane_variant == 2) {
-      const size_t cap = size_t(P) * (2 * size_t(p->b_max) + kProbeGranule);
-      for (auto& l : p->d_step_list) RKH_HIP(hipMalloc(&l, cap * sizeof(uint2)));
-      RKH_HIP(hipMalloc(&p->d_step_cnt, (kMaxSteps + 3) * sizeof(uint32_t)));
-      RKH_HIP(hipMemset(p->d_step_cnt, 0, (kMaxSteps + 3) * sizeof(uint32_t)));
-      // the step kernel's blocks take their RK4 workspace out of the two-lanes workspace
-      if (propagate_pair_step_workspace_bytes(p->n_dof, p->step_blocks_cap) >
-          propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P))
-        p->step_blocks_cap = uint32_t(propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P) /
-                                      propagate_pair_step_workspace_bytes(p->n_dof, 1));
-    }
-    std::vector<EdgeIO> hio2 = hio, hgp2 = hgp;
-    for (uint32_t i = 0; i < P; ++i) {
-      Problem& q = p->prob[i];
-      RKH_HIP(hipMalloc(&q.d_ids_c, size_t(p->b_max) * sizeof(uint32_t)));
-      RKH_HIP(hipMalloc(&q.d_ids_p, size_t(p->b_max + kProbeGranule) * sizeof(uint32_t)));
-      hio2[i].edge_ids = q.d_ids_c;
-      hio2[i].resume = hio[i].x_out;
-      hio2[i].d_B = p->d_cnt2 + 2 * i;
-      hgp2[i].edge_ids = q.d_ids_p;
-      hgp2[i].resume = hgp[i].x_out;
-      hgp2[i].d_B = p->d_cnt2 + 2 * i + 1;
-    }
-    RKH_HIP(hipMemcpy(p->d_io_steer2, hio2.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-    RKH_HIP(hipMemcpy(p->d_io_probe2, hgp2.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-  }
   *out = p;
   return RKH_OK;
 }
@@ -1280,10 +1157,6 @@ rkh_status rkh_planner_destroy(rkh_planner* p) {
   (void)hipFree(p->d_nn_args);
   (void)hipFree(p->d_io_steer);
   (void)hipFree(p->d_io_probe);
-  (void)hipFree(p->d_io_steer2);
-  (void)hipFree(p->d_io_probe2);
-  (void)hipFree(p->d_cnt2);
-  (void)hipFree(p->d_wave_base2);
   (void)hipFree(p->d_step_list[0]);
   (void)hipFree(p->d_step_list[1]);
   (void)hipFree(p->d_step_cnt);

@@ -2083,9 +2083,6 @@ rkh_status launch_propagate(hipStream_t s, int n_dof, int n_env, const SceneDev*
   if (is_planar_scene(d_scene))  // planar chains: one lane per edge, whatever mapping was asked for (propagate_planar.hip)
     return launch_propagate_planar(s, n_dof, d_scene, d_pairs, n_pairs, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b,
                                    n_problems, gate);
-  if (lanes_per_edge == 1)  // two lanes per edge, first generation (propagate_lane.hip)
-    return launch_propagate_lanes(s, n_dof, d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems, d_lane_ws,
-                                  gate);
   if (lanes_per_edge == 2)  // two lanes per edge, two waves per SIMD (propagate_pair.hip)
     return launch_propagate_pairs(s, n_dof, d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems, d_lane_ws,
                                   gate);

@@ -179,7 +179,6 @@ struct SceneDev {
   // (createProxFinderList, proxy_query_model.cpp:215-374: no finder for box-box, cylinder-cylinder, cylinder-box and
   // capped cylinder-cylinder)
   unsigned long long env_finder_mask[9][kMaxEnvShapes / 64];
-  int32_t has_ext_shapes;  // 1: the scene holds a plane or a cylinder (not handled by the first-generation lane kernel)
   int32_t has_meshes;      // 1: convex vertex sets among the shapes (GJK pairs; wave-per-edge and quasi-static kernels)
   const double* mesh_verts;  // device pointer: the vertex pool [n][3] the mesh shapes index into (dims[0], dims[1])
 };
@@ -286,10 +285,6 @@ struct EdgeIO {  // inputs / outputs of one propagate launch (all device pointer
   uint8_t* accept = nullptr;
   double* goal_dist = nullptr;         // indexed by source row - 1
   int* err_flag = nullptr;
-  // second and later phases of a split launch (two-lanes kernel): slot s of the launch is edge edge_ids[s], which
-  // resumes from row edge_ids[s] of `resume` (the x_out of the phase before) with KernelGate::step0 steps behind it
-  const uint32_t* edge_ids = nullptr;
-  const double* resume = nullptr;
 };
 
 // A steer kernel with a gate runs only if lo <= *count < hi (read on the device); count == nullptr: always.
@@ -302,8 +297,6 @@ struct KernelGate {
   // whatever the per-problem counts are (a (wave, problem) grid leaves holes that land unevenly on the XCDs).
   const uint32_t* wave_base = nullptr;
   uint32_t n_segments = 0;
-  // the steps [step0, min(step1, n_steps)) of every edge (two-lanes kernel; the whole edge by default)
-  uint32_t step0 = 0, step1 = 0xFFFFFFFFu;
   // optional diagnostics: the kernel adds the edge-steps it integrated (steps that began with a live edge, the one that
   // ended it included) -- the executed work of a launch, as opposed to n_steps per launched edge
   unsigned long long* steps_exec = nullptr;
@@ -314,16 +307,10 @@ rkh_status launch_propagate(hipStream_t s, int n_dof, int n_env, const SceneDev*
                             const EdgeIO* tab_a = nullptr, const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1,
                             double* d_lane_ws = nullptr, KernelGate gate = KernelGate());
 // the two-lanes-per-edge kernel handles one serial chain, with at most a tip-to-world beam
-inline bool scene_fits_lane_kernel(const SceneDev& S, int variant = 2) {
-  if (variant == 1 && S.has_ext_shapes) return false;  // propagate_lane.hip knows spheres, boxes and capped cylinders
-  if (S.has_meshes) return false;                       // GJK pairs run in the wave-per-edge / quasi-static kernels
+inline bool scene_fits_lane_kernel(const SceneDev& S) {
+  if (S.has_meshes) return false;  // GJK pairs run in the wave-per-edge / quasi-static kernels
   return S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
 }
-// one lane per edge (propagate_lane.hip); d_ws: propagate_lanes_workspace_bytes() of device memory
-size_t propagate_lanes_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edges_b, uint32_t n_problems);
-rkh_status launch_propagate_lanes(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn, const EdgeIO& io,
-                                  uint32_t grid_edges, const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a,
-                                  const EdgeIO* tab_b, uint32_t n_problems, double* d_ws, KernelGate gate = KernelGate());
 rkh_status launch_state_derivative(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x,
                                    const double* d_u, uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
 rkh_status launch_min_distance(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
@@ -337,10 +324,7 @@ rkh_status launch_feval_cycles_duo(hipStream_t s, int n_dof, int n_env, const Sc
 rkh_status launch_feval_cycles(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
                                int n_pairs, const double* d_x, const double* d_u, uint32_t B, int iters,
                                unsigned long long* d_out, double* d_sink);
-uint32_t lane_kernel_waves_per_cu(int n_dof);
-uint32_t lane_kernel_edges_per_wave();
-// second-generation two-lanes-per-edge kernel (propagate_pair.hip): registers + DPP instead of LDS, two waves per SIMD.
-// Same edges per wave, same scenes (scene_fits_lane_kernel), same results.
+// two-lanes-per-edge kernel (propagate_pair.hip): 32 edges per wave, two waves per SIMD; scenes: scene_fits_lane_kernel
 size_t propagate_pairs_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edges_b, uint32_t n_problems);
 // planar chains (propagate_planar.hip): one lane per edge; scenes register themselves at upload
 void register_planar_scene(const SceneDev* d_scene);
@@ -364,15 +348,12 @@ size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks);
 rkh_status launch_propagate_pair_steps(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn,
                                        const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
                                        const uint32_t* d_edge_base, uint2* d_list0, uint2* d_list1, uint32_t* d_cnt,
-                                       double* d_ws, uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec,
-                                       uint32_t pool_blocks = 0, uint32_t* d_pool_cursor = nullptr);
+                                       double* d_ws, uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
 uint32_t pair_kernel_waves_per_cu(int n_dof);
 uint32_t pair_kernel_edges_per_wave();
 rkh_status launch_pair_counts(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out);
 rkh_status launch_pair_cycles(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, const double* d_u,
-                              uint32_t B, int iters, unsigned long long* d_out, double* d_sink);
-rkh_status launch_lane_cycles(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, const double* d_u,
                               uint32_t B, int iters, unsigned long long* d_out, double* d_sink);
 rkh_status build_dyn_dev(const rkh_dyn_space& sp, double fraction, DynDev* out);
 }  // namespace rkh

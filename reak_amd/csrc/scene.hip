@@ -472,7 +472,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       set_error("rkh_scene_create: unsupported shape kind");
       return RKH_ERR_UNSUPPORTED;
     }
-    if (s.kind == RKH_SHAPE_PLANE || s.kind == RKH_SHAPE_CYLINDER) S.has_ext_shapes = 1;
     if (s.kind == RKH_SHAPE_MESH) S.has_meshes = 1;
     ShapeDev d;
     std::memset(&d, 0, sizeof(d));
@@ -734,15 +733,14 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   io.record = record ? drec.as<double>() : nullptr;
   io.record_stride = rec_stride;
   io.err_flag = scene->d_err;
-  // RKH_LANES_PER_EDGE = 128 (two waves per edge) | 64 | 16 | 2 | 1 selects the kernel mapping (identical results); by
+  // RKH_LANES_PER_EDGE = 128 (two waves per edge) | 64 | 16 | 2 selects the kernel mapping (identical results); by
   // default a call of few edges -- the adaptors steer ONE edge per call -- takes the lowest-latency mapping
   int lanes = (B <= 512) ? 128 : 64;
   if (const char* ev = getenv("RKH_LANES_PER_EDGE"))
-    lanes = (atoi(ev) == 1) ? 1 : (atoi(ev) == 2 ? 2 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 128 ? 128 : 64)));
-  if ((lanes == 1 || lanes == 2) && !(n <= 7 && scene_fits_lane_kernel(scene->host, lanes))) lanes = 64;  // not a scene for that mapping
+    lanes = (atoi(ev) == 2) ? 2 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 128 ? 128 : 64));
+  if (lanes == 2 && !(n <= 7 && scene_fits_lane_kernel(scene->host))) lanes = 64;  // not a scene for that mapping
   if (lanes == 16 && 2 * n > 16) lanes = 64;
   DevBuf dws;
-  if (lanes == 1) RKH_HIP(hipMalloc(&dws.p, propagate_lanes_workspace_bytes(n, B, 0, 1)));
   if (lanes == 2) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
   st = launch_propagate(s, n, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs_verdict, dyn, io, B, nullptr, 0,
                         lanes, nullptr, nullptr, 1, dws.as<double>());
@@ -769,11 +767,7 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
   RKH_HIP(hipMemcpyAsync(du.p, u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
   rkh_status st;
   const char* ev = getenv("RKH_LANES_PER_EDGE");
-  if (ev && atoi(ev) == 1) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
-    RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
-    st = launch_lane_cycles(s, n, scene->d_scene, dx.as<double>(), du.as<double>(), B, iters,
-                            dout.as<unsigned long long>(), dsink.as<double>());
-  } else if (ev && atoi(ev) == 2) {  // its second generation
+  if (ev && atoi(ev) == 2) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
     RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
     st = launch_pair_cycles(s, n, scene->d_scene, dx.as<double>(), du.as<double>(), B, iters,
                             dout.as<unsigned long long>(), dsink.as<double>());
@@ -796,7 +790,7 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
   if (scene && reject_branches(scene) != RKH_OK) return RKH_ERR_UNSUPPORTED;
   if (!scene || !x || !counts || B == 0) return RKH_ERR_BAD_ARG;
   const int n = scene->host.n_dof;
-  if (!(n <= 7 && scene_fits_lane_kernel(scene->host, 2))) {
+  if (!(n <= 7 && scene_fits_lane_kernel(scene->host))) {
     set_error("proximity counts: a scene of the two-lanes steer mapping is needed");
     return RKH_ERR_UNSUPPORTED;
   }

@@ -13,7 +13,7 @@ b = rng.uniform(lo, hi, size=(8192, 12))
 robot = [s for s in scn.shapes if s.anchor >= 0]; env = [s for s in scn.shapes if s.anchor < 0]
 def verdicts(s2, x, tgt):
     sc = lib.Scene(ctx, s2); r = {}
-    for lanes in ("64", "1", "2"):
+    for lanes in ("64", "2"):
         os.environ["RKH_LANES_PER_EDGE"] = lanes
         r[lanes] = sc.steer_position_toward(x, tgt)[1]
     return r

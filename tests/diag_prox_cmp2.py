@@ -18,7 +18,7 @@ for k in (1, 2, 3, 4, 5):
         for rs in ([0, k], [k, 0]):
             s2 = copy.copy(scn); s2.shapes = [robot[i] for i in rs] + [ob]
             sc = lib.Scene(ctx, s2); r = {}
-            for lanes in ("64", "1", "2"):
+            for lanes in ("64", "2"):
                 os.environ["RKH_LANES_PER_EDGE"] = lanes
                 r[lanes] = int(sc.steer_position_toward(x, t)[1][0])
             print("link", k, "obstacle kind", kind, "robot", rs, r, flush=True)

@@ -830,16 +830,16 @@ def test_propagate_mappings_are_bit_identical(L, ctx, oracle, c2, monkeypatch):
     a = a[osc.min_distance(a) > 0.01][:200]   # not a multiple of 64: the last wave is ragged
     b = rng.uniform(lo, hi, size=(a.shape[0], 12))
     res = {}
-    for lanes in ("64", "128", "16", "1", "2"):
+    for lanes in ("64", "128", "16", "2"):
         monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
         res[lanes] = sc.steer_position_toward(a, b, record=True)
-    for lanes in ("128", "16", "1", "2"):
+    for lanes in ("128", "16", "2"):
         assert np.array_equal(res[lanes][1], res["64"][1])
         assert np.array_equal(res[lanes][0], res["64"][0])
         assert np.array_equal(res[lanes][2], res["64"][2], equal_nan=True)
     rc, rout, rsteps, _ = osc.steer(a, b)
-    assert np.array_equal(res["1"][1], rsteps) and np.allclose(res["1"][0], rout, rtol=STATE_RTOL, atol=1e-12)
-    assert res["1"][1].min() < 20 <= res["1"][1].max()
+    assert np.array_equal(res["2"][1], rsteps) and np.allclose(res["2"][0], rout, rtol=STATE_RTOL, atol=1e-12)
+    assert res["2"][1].min() < 20 <= res["2"][1].max()
 
 
 def test_every_robot_shape_is_tested_by_every_mapping(L, ctx, oracle, c2, monkeypatch):
@@ -867,7 +867,7 @@ def test_every_robot_shape_is_tested_by_every_mapping(L, ctx, oracle, c2, monkey
                 sc, o2 = L.Scene(ctx, s2), oracle.OracleScene(s2)
                 rc, rout, rsteps, _ = o2.steer(x, t)
                 assert rsteps[0] == 0
-                for lanes in ("64", "128", "16", "1", "2"):
+                for lanes in ("64", "128", "16", "2"):
                     monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
                     assert sc.steer_position_toward(x, t)[1][0] == 0, (k, kind, order, lanes)
 
@@ -929,16 +929,16 @@ def test_steer_from_colliding_and_free_starts_matches_oracle(L, ctx, oracle, c2,
     b = rng.uniform(lo, hi, size=(B, 12))
     rc, rout, rsteps, _ = osc.steer(a, b)
     assert (rsteps == 0).sum() > 20 and (rsteps == 20).sum() > 500
-    for lanes in ("64", "1", "2"):
+    for lanes in ("64", "2"):
         monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
         out, steps, _ = sc.steer_position_toward(a, b)
         assert np.array_equal(steps, rsteps), lanes
         assert np.allclose(out, rout, rtol=STATE_RTOL, atol=1e-12), lanes
 
 
-@pytest.mark.parametrize("lanes", ["1", "2"])
+@pytest.mark.parametrize("lanes", ["2"])
 def test_rrt_tree_with_one_lane_per_edge(L, ctx, oracle, c2, monkeypatch, lanes):
-    """Every round through one of the two-lanes-per-edge kernels (1: LDS-resident, 2: registers + DPP, two waves / SIMD)."""
+    """Every round through the two-lanes-per-edge kernel (registers + DPP, two waves / SIMD)."""
     monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
     sc, osc = L.Scene(ctx, c2), oracle.OracleScene(c2)
     prm = c2.rrt_params(seed=2, max_vertices=1500)
@@ -976,10 +976,9 @@ def test_flexible_beam_dynamics_and_planner(L, ctx, oracle, monkeypatch):
     a = a[osc.min_distance(a) > 0.01][:60]
     b = rng.uniform(lo, hi, size=(a.shape[0], 12))
     res = {}
-    for lanes in ("64", "128", "1", "2"):
+    for lanes in ("64", "128", "2"):
         monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
         res[lanes] = sc.steer_position_toward(a, b)
-    assert np.array_equal(res["1"][0], res["64"][0]) and np.array_equal(res["1"][1], res["64"][1])
     assert np.array_equal(res["2"][0], res["64"][0]) and np.array_equal(res["2"][1], res["64"][1])
     assert np.array_equal(res["128"][0], res["64"][0]) and np.array_equal(res["128"][1], res["64"][1])
     rc, rout, rsteps, _ = osc.steer(a, b)
@@ -1021,7 +1020,7 @@ def test_steer_kernels_ragged_wave_sizes(L, ctx, oracle, c2, monkeypatch):
     b = rng.uniform(lo, hi, size=(a.shape[0], 12))
     for B in (1, 27, 28, 29, 57):
         rc, rout, rsteps, _ = osc.steer(a[:B], b[:B])
-        for lanes in ("64", "1", "2"):
+        for lanes in ("64", "2"):
             monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
             out, steps, _ = sc.steer_position_toward(a[:B], b[:B])
             assert np.array_equal(steps, rsteps) and np.allclose(out, rout, rtol=STATE_RTOL, atol=1e-12)
@@ -1261,10 +1260,9 @@ def test_random_chains_of_other_sizes(L, ctx, oracle, n, monkeypatch):
     a = x[osc.min_distance(x) > 0.01][:40]
     b = rng.uniform(lo, hi, size=(a.shape[0], 2 * n))
     res = {}
-    for lanes in ("64", "1", "2"):
+    for lanes in ("64", "2"):
         monkeypatch.setenv("RKH_LANES_PER_EDGE", lanes)
         res[lanes] = sc.steer_position_toward(a, b)
-    assert np.array_equal(res["1"][0], res["64"][0]) and np.array_equal(res["1"][1], res["64"][1])
     assert np.array_equal(res["2"][0], res["64"][0]) and np.array_equal(res["2"][1], res["64"][1])
     rc, rout, rsteps, _ = osc.steer(a, b)
     assert np.array_equal(res["64"][1], rsteps) and np.allclose(res["64"][0], rout, rtol=1e-9, atol=1e-10)
@@ -1486,28 +1484,19 @@ def test_planner_pool_splits_a_batch_without_changing_results(L, ctx, oracle, c2
     one.close()
 
 
-def test_stepwise_and_two_phase_steer_launches_do_not_change_results(L, ctx, oracle, c2, monkeypatch):
-    """The steer launch of a large round in its forms -- one launch for the whole edge, two phases with a compaction of
-    the survivors between them, one launch per RK4 step over the live edges of all problems, and the default: a resident
-    set of waves whose lane pairs take a new edge from the round's pool whenever theirs ends, followed by list launches
-    for the edges the waves hand over at the end -- runs the same arithmetic per edge.  The round sizes at which the planner switches between them are far above what a test can
-    afford (32 k / 65 k edges), so RKH_STEER_SPLIT_MIN_EDGES = 0 sends every round of the two-lanes mapping (>= 1024 edges)
-    through the form under test.  Trees, NN sequences, accept bits, goal probes and counters must be identical across
-    the forms, equal to the oracle's, and the executed-step counter must agree with the free-step counts."""
+def test_stepwise_and_whole_edge_steer_launches_do_not_change_results(L, ctx, oracle, c2, monkeypatch):
+    """The steer launch of a round of the two-lanes mapping in its two forms -- one launch for the whole edge (the
+    default below RKH_STEER_SPLIT_MIN_EDGES) and one launch per RK4 step over the live edges of all problems (the
+    default at and above it) -- runs the same arithmetic per edge.  The round sizes at which the planner switches
+    between them are far above what a test can afford (32 k / 65 k edges), so RKH_STEER_SPLIT_MIN_EDGES sends every
+    round of the two-lanes mapping (>= 1024 edges) through the form under test: 0 to the step-wise form, a bound no
+    round reaches to the whole-edge form.  Trees, NN sequences, accept bits, goal probes and counters must be identical
+    across the forms, equal to the oracle's, and the executed-step counter must agree with the free-step counts."""
     prms = [c2.rrt_params(seed=70 + i, max_vertices=2500) for i in range(40)]
     picks = (0, 17, 39)
     runs = {}
-    for name, env in (("whole", {"RKH_STEER_SPLIT": "0", "RKH_STEER_STEPWISE": "0"}),
-                      ("two_phase", {"RKH_STEER_STEPWISE": "0", "RKH_STEER_SPLIT": "5", "RKH_STEER_SPLIT_MIN_EDGES": "0"}),
-                      ("stepwise", {"RKH_STEER_STEPWISE": "1", "RKH_STEER_POOL": "0", "RKH_STEER_SPLIT_MIN_EDGES": "0"}),
-                      ("pool", {"RKH_STEER_STEPWISE": "1", "RKH_STEER_POOL": "1", "RKH_STEER_SPLIT_MIN_EDGES": "0"}),
-                      # few resident waves: every wave refills its lanes many times and hands orphans over at the end
-                      ("pool_few_waves", {"RKH_STEER_STEPWISE": "1", "RKH_STEER_POOL": "1", "RKH_STEER_SPLIT_MIN_EDGES": "0",
-                                          "RKH_STEER_POOL_WAVES": "24"})):
-        for k in ("RKH_STEER_SPLIT", "RKH_STEER_STEPWISE", "RKH_STEER_SPLIT_MIN_EDGES", "RKH_STEER_POOL", "RKH_STEER_POOL_WAVES"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for name, split_min_edges in (("whole", "1000000000"), ("stepwise", "0")):
+        monkeypatch.setenv("RKH_STEER_SPLIT_MIN_EDGES", split_min_edges)
         pl = L.RrtPlanner(L.Scene(ctx, c2), prms)
         pl.solve_planning_query()
         runs[name] = {"stats": [(int(s.num_vertices), int(s.iterations), int(s.edges_checked), int(s.num_solutions),
@@ -1515,15 +1504,13 @@ def test_stepwise_and_two_phase_steer_launches_do_not_change_results(L, ctx, ora
                       "trees": [pl.tree(i) for i in picks], "steps": pl.steer_steps(),
                       "spec": sum(int(s.edges_speculated) for s in pl.all_stats)}
         pl.close()
-    for name in ("two_phase", "stepwise", "pool", "pool_few_waves"):
-        assert runs[name]["stats"] == runs["whole"]["stats"], name
-        for a, b in zip(runs[name]["trees"], runs["whole"]["trees"]):
-            for key in ("parent", "nn_seq", "accept", "pos", "goal_dist"):
-                assert np.array_equal(a[key], b[key]), (name, key)
-    # executed work: every form integrates the same steps (a step counts when it starts from a live edge), fewer than
+    assert runs["stepwise"]["stats"] == runs["whole"]["stats"]
+    for a, b in zip(runs["stepwise"]["trees"], runs["whole"]["trees"]):
+        for key in ("parent", "nn_seq", "accept", "pos", "goal_dist"):
+            assert np.array_equal(a[key], b[key]), key
+    # executed work: both forms integrate the same steps (a step counts when it starts from a live edge), fewer than
     # the 20 per propagated edge the launches are sized for
-    assert runs["stepwise"]["steps"] == runs["whole"]["steps"] == runs["two_phase"]["steps"] == runs["pool"]["steps"]
-    assert runs["pool_few_waves"]["steps"] == runs["whole"]["steps"]
+    assert runs["stepwise"]["steps"] == runs["whole"]["steps"]
     assert 0 < runs["stepwise"]["steps"] < 20 * 2 * runs["stepwise"]["spec"]
     osc = oracle.OracleScene(c2, fast=True)
     rc, ro, rt = osc.rrt_dyn(prms[17])
