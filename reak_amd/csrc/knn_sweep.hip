@@ -21,6 +21,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "nn_device.h"
 #include "rkh_internal.h"
 
 namespace rkh {
@@ -111,13 +112,7 @@ __global__ __launch_bounds__(kThreads) void knn_sweep_kernel(KnnArgs single, con
     for (int k = 0; k < ROWS_PER_THREAD; ++k) {
       const int row = k * R + r;
       const double* p = tile + row * DP;
-      double df = qv[0] - p[0];
-      double s = df * df;
-#pragma unroll
-      for (int d = 1; d < DP; ++d) {
-        df = qv[d] - p[d];
-        s = s + df * df;
-      }
+      const double s = nn_exact_sq<DP>([&](int d) { return qv[d] - p[d]; });
       if (MODE == 0) {
         if (s < best_s) best_s = s;
       } else if (s <= thr_s && q_valid) {

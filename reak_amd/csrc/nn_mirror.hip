@@ -42,10 +42,10 @@
 
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
+#include "nn_device.h"
 #include "nn_mirror.h"
 #include "rkh_internal.h"
 
@@ -65,9 +65,6 @@ constexpr uint32_t kMirCandCap = 32;       // candidate rows kept per query (mor
 constexpr uint32_t kMirMaxSlices = 32;     // row slices per tree (rows of NnArgs::est)
 
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
-__device__ __forceinline__ bool lex_less_m(double da, uint32_t ia, double db, uint32_t ib) {
-  return (da < db) || (da == db && ia < ib);
-}
 
 // ---- once per round and query: the B operand and the query's share of the error bound
 // qinfo[q] = {|q_h|^2 (rounded up), dq = |q - q_h| (rounded up), |q| (rounded up)}
@@ -123,48 +120,21 @@ __global__ __launch_bounds__(256) void nn1_mirror_thr_kernel(const NnArgs* __res
   a.thr[qi] = cmin < INFINITY ? __double2float_ru(double(cmin) + band) : INFINITY;
 }
 
-// Work items as in the bf16 sweep: 1-D grid of 8 * ceil(W / 8) blocks for W = gx * (query blocks of all problems) items
-// (row slice, query block, problem); block L runs on XCD L % 8 as that XCD's (L / 8)-th block, XCD x takes the items
-// [x Wc, (x + 1) Wc), numbered with the query block fastest.
-__device__ __forceinline__ bool mirror_item(const uint32_t* __restrict__ yblock_base, uint32_t n_problems, uint32_t gx,
-                                            uint32_t* bx, uint32_t* by, uint32_t* bz) {
-  const uint32_t L = blockIdx.x;
-  const uint32_t ytot = yblock_base[n_problems];
-  const uint32_t W = ytot * gx, Wc = (W + 7) >> 3;
-  const uint32_t slot = L >> 3, w = (L & 7) * Wc + slot;
-  if (slot >= Wc || w >= W) return false;
-  const uint32_t yy = w / gx;
-  uint32_t p = 0, hi_p = n_problems;  // yblock_base[p] <= yy < yblock_base[hi_p]
-  while (hi_p - p > 1) {
-    const uint32_t mid = (p + hi_p) >> 1;
-    if (yblock_base[mid] <= yy) p = mid;
-    else hi_p = mid;
-  }
-  const uint32_t y0 = yblock_base[p], cnt = yblock_base[p + 1] - y0;
-  const uint32_t r = w - y0 * gx;
-  *bx = r / cnt;
-  *by = r - (*bx) * cnt;
-  *bz = p;
-  return true;
-}
-
 // PASS 1: minimum of the estimates per (slice, query) -> NnArgs::est.  PASS 2: rows at or below NnArgs::thr -> lists.
+// Work items as in the bf16 sweep (nn_xcd_item), always with a query-block prefix.
 template <int PASS>
 __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_kernel(const NnArgs* __restrict__ table,
                                                                     const uint32_t* __restrict__ yblock_base,
                                                                     uint32_t n_problems, uint32_t gx) {
   __shared__ float wave_min[PASS == 1 ? kMirThreads / 64 : 1][PASS == 1 ? kMirQueries : 1];
   uint32_t bx, by, bz;
-  if (!mirror_item(yblock_base, n_problems, gx, &bx, &by, &bz)) return;
-  auto uniform64 = [](uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-    return (uint64_t(hi) << 32) | lo;
-  };
+  __builtin_assume(yblock_base != nullptr);
+  if (!nn_xcd_item(yblock_base, n_problems, gx, 0u, bx, by, bz)) return;
   const NnArgs a = table[bz];
-  const uint4* __restrict__ mirror = reinterpret_cast<const uint4*>(uniform64(reinterpret_cast<uint64_t>(a.mirror)));
-  const uint4* __restrict__ qfrag = reinterpret_cast<const uint4*>(uniform64(reinterpret_cast<uint64_t>(a.qfrag)));
-  const uint32_t n = __builtin_amdgcn_readfirstlane(a.d_n ? *a.d_n : uint32_t(a.n));
-  const uint32_t B = __builtin_amdgcn_readfirstlane(a.d_B ? *a.d_B : a.B);
+  const uint4* __restrict__ mirror = static_cast<const uint4*>(nn_uniform(a.mirror));
+  const uint4* __restrict__ qfrag = nn_uniform(a.qfrag);
+  const uint32_t n = nn_uniform(a.d_n ? *a.d_n : uint32_t(a.n));
+  const uint32_t B = nn_queries(a);
   const uint32_t q0 = by * uint32_t(kMirQueries);
   if (q0 >= B) return;
   const int tid = threadIdx.x;
@@ -301,7 +271,7 @@ __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_ker
 // Exact evaluation of the candidates: one 16-lane group per query, lane j takes the candidates j, j + 16, ...; a list
 // that overflowed (more than kMirCandCap rows within the band: many coincident vertices) is replaced by the exact scan
 // of the whole tree.  Pad rows (past the end of the tree; a removed vertex evaluates to +inf by itself) are skipped.
-// The operation sequence is nn1_sweep_kernel's: left-to-right sum of squares, sqrt, lexicographic (distance, index).
+// The operation sequence is every sweep's (nn_exact_sq): left-to-right sum of squares, sqrt, lexicographic (distance, index).
 template <int DP>
 __global__ __launch_bounds__(256) void nn1_mirror_resolve_kernel(const NnArgs* __restrict__ table, int D) {
   const NnArgs a = table[blockIdx.y];
@@ -320,18 +290,8 @@ __global__ __launch_bounds__(256) void nn1_mirror_resolve_kernel(const NnArgs* _
   auto exact = [&](uint32_t row) {
     if (row >= n) return;
     const double* __restrict__ p = a.pos + uint64_t(row) * DP;
-    double s;
-    {
-      const double df = qv[0] - p[0];
-      s = df * df;
-    }
-#pragma unroll
-    for (int d = 1; d < DP; ++d) {
-      const double df = qv[d] - p[d];
-      s = s + df * df;
-    }
-    const double dd = sqrt(s);
-    if (lex_less_m(dd, row, bd, bi)) {
+    const double dd = sqrt(nn_exact_sq<DP>([&](int d) { return qv[d] - p[d]; }));
+    if (lex_less(dd, row, bd, bi)) {
       bd = dd;
       bi = row;
     }
@@ -345,7 +305,7 @@ __global__ __launch_bounds__(256) void nn1_mirror_resolve_kernel(const NnArgs* _
   for (int off = 8; off > 0; off >>= 1) {
     const double od = __shfl_xor(bd, off, 64);
     const uint32_t oi = __shfl_xor(bi, off, 64);
-    if (lex_less_m(od, oi, bd, bi)) {
+    if (lex_less(od, oi, bd, bi)) {
       bd = od;
       bi = oi;
     }
@@ -398,13 +358,9 @@ void nn1_mirror_carve(void* base, uint32_t b_max, NnArgs* a) {
   a->est_stride = b_max;
 }
 
-// does the mirror sweep take this problem shape?  (RKH_NN_MIRROR=0 keeps the bf16 sweep: diagnostics / A-B runs)
+// does the mirror sweep take this problem shape?
 bool nn1_mirror_applies(int D, double coord_bound) {
-  static const bool on = [] {
-    const char* e = getenv("RKH_NN_MIRROR");
-    return !(e && e[0] == '0');
-  }();
-  return on && D >= 1 && D <= kMirrorMaxDims && coord_bound >= 1e-3 && coord_bound <= kMirrorMaxBound;
+  return D >= 1 && D <= kMirrorMaxDims && coord_bound >= 1e-3 && coord_bound <= kMirrorMaxBound;
 }
 
 rkh_status launch_mirror_fill(hipStream_t s, void* d_mirror, uint64_t capacity_rows) {
@@ -434,11 +390,7 @@ rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32
   const uint32_t gy = (B_upper + kMirQueries - 1) / kMirQueries;
   const uint64_t slabs = (n_upper + 31) / 32;
   // row slices per tree: ~8 k blocks over the whole grid, at least 32 slabs (8 per wave) per block
-  static const long forced = [] {
-    const char* e = getenv("RKH_NN_MIRROR_SLICES");
-    return e ? atol(e) : 0L;
-  }();
-  uint64_t gx = forced > 0 ? uint64_t(forced) : 8192 / (uint64_t(gy) * n_problems);
+  uint64_t gx = 8192 / (uint64_t(gy) * n_problems);
   if (gx > slabs / 32) gx = slabs / 32;
   if (gx > kMirMaxSlices) gx = kMirMaxSlices;
   if (gx < 1) gx = 1;

@@ -18,18 +18,15 @@
 
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
+#include <type_traits>
 
+#include "nn_device.h"
 #include "rkh_internal.h"
 
 namespace rkh {
 
 static constexpr int kTileRows = 256;
 static constexpr int kThreads = 256;
-
-__device__ __forceinline__ bool lex_less(double da, uint32_t ia, double db, uint32_t ib) {
-  return (da < db) || (da == db && ia < ib);
-}
 
 // One block: rows [row0, row1) x queries [blockIdx.y*QB, +QB).
 // blockIdx.z selects the problem when a table of NnArgs is given (one launch sweeps many independent trees).
@@ -106,16 +103,7 @@ __global__ __launch_bounds__(kThreads) void nn1_sweep_kernel(NnArgs single, cons
     for (int k = 0; k < ROWS_PER_THREAD; ++k) {
       const int row = k * R + r;
       const double* p = tile + row * DP;
-      double s;
-      {
-        double df = qv[0] - p[0];
-        s = df * df;
-      }
-#pragma unroll
-      for (int d = 1; d < DP; ++d) {
-        double df = qv[d] - p[d];
-        s = s + df * df;
-      }
+      const double s = nn_exact_sq<DP>([&](int d) { return qv[d] - p[d]; });
       if (s <= best_thr) {  // rare after the first few rows
         const double dd = sqrt(s);
         if (dd < best_d) {
@@ -169,21 +157,15 @@ __global__ __launch_bounds__(kThreads, 2) void nn1_stream_kernel(NnArgs single, 
   __shared__ double red_d[kThreads / 64][QB];
   __shared__ uint32_t red_i[kThreads / 64][QB];
 
-  // everything read from the table entry is block-uniform by construction; the compiler has to be told (the entry
-  // arrives through vector loads), so that the row addresses get a scalar base and the queries scalar loads
-  auto uniform64 = [](uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-    return (uint64_t(hi) << 32) | lo;
-  };
+  // (block-uniform reads: the row addresses get a scalar base and the queries scalar loads)
   const NnArgs a = table ? table[blockIdx.z] : single;
   typedef const __attribute__((address_space(1))) nn_d2* nn_grow_p;  // global, not flat: flat loads would share
-  const uint64_t pos = uniform64(reinterpret_cast<uint64_t>(a.pos));   // the queries' scalar-load counter
-  const uint64_t n = uniform64(a.d_n ? uint64_t(*a.d_n) : a.n);
-  const uint32_t B = __builtin_amdgcn_readfirstlane(a.d_B ? *a.d_B : a.B);
+  const uint64_t pos = nn_uniform(reinterpret_cast<uint64_t>(a.pos));  // the queries' scalar-load counter
+  const uint64_t n = nn_rows(a);
+  const uint32_t B = nn_queries(a);
   if (B == 0) return;
   const int tid = threadIdx.x;
-  nn_cdouble_p qc =
-      (nn_cdouble_p)uniform64(reinterpret_cast<uint64_t>(a.q + (a.d_qoff ? uint64_t(*a.d_qoff) : 0ull) * DP));
+  nn_cdouble_p qc = (nn_cdouble_p)reinterpret_cast<uint64_t>(nn_query_rows(a, DP));
 
   const uint64_t tiles_total = (n + kTileRows - 1) / kTileRows;
   const uint64_t tiles_per_block = (tiles_total + gridDim.x - 1) / gridDim.x;
@@ -221,17 +203,7 @@ __global__ __launch_bounds__(kThreads, 2) void nn1_stream_kernel(NnArgs single, 
       for (int j = 0; j < G; ++j) {
         const int k = g + j;
         nn_cdouble_p qk = qc + uint32_t(uint32_t(k) < B ? k : B - 1) * DP;
-        double s;
-        {
-          const double df = qk[0] - cur[0].x;
-          s = df * df;
-        }
-#pragma unroll
-        for (int d = 1; d < DP; ++d) {
-          const double df = qk[d] - ((d & 1) ? cur[d >> 1].y : cur[d >> 1].x);
-          s = s + df * df;
-        }
-        sq[j] = s;
+        sq[j] = nn_exact_sq<DP>([&](int d) { return qk[d] - ((d & 1) ? cur[d >> 1].y : cur[d >> 1].x); });
       }
       bool hit = false;
 #pragma unroll
@@ -413,16 +385,7 @@ __global__ __launch_bounds__(kThreads) void nn1_sweep_f32_kernel(NnArgs single, 
       const float s32 = acc.x + acc.y;
       if (!(s32 > filt)) {  // survivors only: the exact fp64 sequence of nn1_sweep_kernel
         const double* p = tile + row * DP;
-        double s;
-        {
-          double df = qv[0] - p[0];
-          s = df * df;
-        }
-#pragma unroll
-        for (int d = 1; d < DP; ++d) {
-          double df = qv[d] - p[d];
-          s = s + df * df;
-        }
+        const double s = nn_exact_sq<DP>([&](int d) { return qv[d] - p[d]; });
         if (s <= best_thr) {
           const double dd = sqrt(s);
           if (dd < best_d) {
@@ -524,10 +487,7 @@ __device__ __forceinline__ float min_over_halves(float v) {
   return min3_raw(lo, hi, hi);
 }
 
-// Grid: 1-D, 8 * ceil(W / 8) blocks for W = gx * (query blocks of all problems) work items (row slice, query block,
-// problem).  Hardware deals consecutive blocks round-robin to the 8 XCDs, so block L runs on XCD L % 8 as that XCD's
-// (L / 8)-th block: XCD x takes the items [x Wc, (x + 1) Wc) in order, and items are numbered with the query block
-// fastest -- the query blocks that sweep the same row slice run back to back on one XCD and share its L2.
+// Grid: the XCD-ordered work items of nn_xcd_item (nn_device.h).
 template <int DP, bool SEED>
 __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs single, const NnArgs* __restrict__ table,
                                                                       int D, uint32_t Bpad, double coord_bound,
@@ -538,52 +498,18 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs 
   constexpr int kSlabs = kTileRows / 32;
   __shared__ __attribute__((aligned(16))) float tileT[DP * TS];
   __shared__ __attribute__((aligned(16))) float xn[kTileRows];
-  __shared__ uint32_t cand_key[SEED ? 1 : kCandCap][kMfmaThreads];
-  __shared__ uint32_t cand_mask[SEED ? 1 : kCandCap][kMfmaThreads];
-  __shared__ float cand_m[SEED ? 1 : kCandCap][kMfmaThreads];
+  __shared__ NnBandLds<SEED ? 1 : kCandCap, kMfmaThreads> cand;
 
   uint32_t bx, by, bz;
-  {
-    const uint32_t L = blockIdx.x;
-    const uint32_t ytot = yblock_base ? yblock_base[n_problems] : gy * n_problems;
-    const uint32_t W = ytot * gx, Wc = (W + 7) >> 3;
-    const uint32_t slot = L >> 3, w = (L & 7) * Wc + slot;
-    if (slot >= Wc || w >= W) return;
-    const uint32_t yy = w / gx;
-    uint32_t p = 0, y0, cnt;
-    if (yblock_base) {
-      uint32_t hi_p = n_problems;  // yblock_base[p] <= yy < yblock_base[hi_p]
-      while (hi_p - p > 1) {
-        const uint32_t mid = (p + hi_p) >> 1;
-        if (yblock_base[mid] <= yy) p = mid;
-        else hi_p = mid;
-      }
-      y0 = yblock_base[p];
-      cnt = yblock_base[p + 1] - y0;
-    } else {
-      p = yy / gy;
-      y0 = p * gy;
-      cnt = gy;
-    }
-    const uint32_t r = w - y0 * gx;
-    bx = r / cnt;
-    by = r - bx * cnt;
-    bz = p;
-  }
-  // everything read from the table entry is block-uniform; said explicitly, it lives in scalar registers
-  auto uniform64 = [](uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-    return (uint64_t(hi) << 32) | lo;
-  };
+  if (!nn_xcd_item(yblock_base, n_problems, gx, gy, bx, by, bz)) return;
   const NnArgs a = table ? table[bz] : single;
-  const double* __restrict__ pos = reinterpret_cast<const double*>(uniform64(reinterpret_cast<uint64_t>(a.pos)));
-  const uint64_t n = uniform64(a.d_n ? uint64_t(*a.d_n) : a.n);
-  const uint32_t B = __builtin_amdgcn_readfirstlane(a.d_B ? *a.d_B : a.B);
-  const double* __restrict__ q = reinterpret_cast<const double*>(
-      uniform64(reinterpret_cast<uint64_t>(a.q + (a.d_qoff ? uint64_t(*a.d_qoff) : 0ull) * D)));
-  uint32_t* __restrict__ seed = reinterpret_cast<uint32_t*>(uniform64(reinterpret_cast<uint64_t>(a.seed)));
-  double* __restrict__ part_dist = reinterpret_cast<double*>(uniform64(reinterpret_cast<uint64_t>(a.part_dist)));
-  uint32_t* __restrict__ part_idx = reinterpret_cast<uint32_t*>(uniform64(reinterpret_cast<uint64_t>(a.part_idx)));
+  const double* __restrict__ pos = nn_uniform(a.pos);
+  const uint64_t n = nn_rows(a);
+  const uint32_t B = nn_queries(a);
+  const double* __restrict__ q = nn_query_rows(a, D);
+  uint32_t* __restrict__ seed = nn_uniform(a.seed);
+  double* __restrict__ part_dist = nn_uniform(a.part_dist);
+  uint32_t* __restrict__ part_idx = nn_uniform(a.part_idx);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, hi = lane >> 5;
@@ -628,61 +554,21 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs 
   uint32_t best_i = 0xFFFFFFFFu;
   // running minimum of the estimates of this lane's query; NaN ("no seed") is dropped by fminf
   float cmin = (!SEED && seed) ? fminf(INFINITY, seed_decode(seed[qsrc])) : INFINITY;
-  int cnt = 0;                      // entries in the list
-
-  // exact fp64 distance of vertex `row` (global index): the operation sequence of nn1_sweep_kernel
+  // exact fp64 distance of vertex `row` (global index)
   auto resolve = [&](uint32_t row) {
     if (uint64_t(row) >= n) return;  // padding rows of the last tile
     const double* p = pos + uint64_t(row) * DP;
     const double* qq = q + uint64_t(qsrc) * D;
-    double s;
-    {
-      const double df = qq[0] - p[0];
-      s = df * df;
-    }
-#pragma unroll 3
-    for (int d = 1; d < DP; ++d) {  // (a few coordinates per memory round trip; fully unrolled it spills into the sweep)
-      const double df = (d < D ? qq[d] : 0.0) - p[d];
-      s = s + df * df;
-    }
-    const double dd = sqrt(s);
+    // (a few coordinates per memory round trip; fully unrolled it spills into the sweep)
+    const double dd = sqrt(nn_exact_sq<DP, 3>([&](int d) { return nn_qcoord(qq, d, D) - p[d]; }));
     if (lex_less(dd, row, best_d, best_i)) {
       best_d = dd;
       best_i = row;
     }
   };
-  // every flagged row of entry k: key = slab index counted from the block's first tile
-  auto resolve_entry = [&](int k) {
-    uint32_t mask = cand_mask[k][tid];
-    const uint32_t base = uint32_t(t_first) * uint32_t(kTileRows) + cand_key[k][tid] * 32u + 4u * uint32_t(hi);
-#pragma unroll 1
-    while (mask) {
-      const uint32_t i = uint32_t(__builtin_ctz(mask));
-      mask &= mask - 1;
-      resolve(base + 8u * (i >> 2) + (i & 3u));
-    }
-  };
-  // drop the entries the current minimum rules out; if the list is still full, resolve it
-  auto compact = [&](float lim) {
-    int w = 0;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k) {
-      const float mm = cand_m[k][tid];
-      if (mm <= lim) {
-        const uint32_t kk = cand_key[k][tid], mk = cand_mask[k][tid];
-        cand_m[w][tid] = mm;
-        cand_key[w][tid] = kk;
-        cand_mask[w][tid] = mk;
-        ++w;
-      }
-    }
-    cnt = w;
-    if (cnt == kCandCap) {
-#pragma unroll 1
-      for (int k = 0; k < cnt; ++k) resolve_entry(k);
-      cnt = 0;
-    }
-  };
+  // entry key = slab index counted from the block's first tile
+  auto rows = [&](uint32_t key) { return uint32_t(t_first) * uint32_t(kTileRows) + key * 32u + 4u * uint32_t(hi); };
+  NnBandList<SEED ? 1 : kCandCap, kMfmaThreads, decltype(rows)> list{cand, rows, tid, 0};
 
   constexpr int N2 = kTileRows * DP / 2;
   constexpr int PF = (N2 + kMfmaThreads - 1) / kMfmaThreads;
@@ -757,16 +643,7 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs 
         // over both lane halves: the pair then meets a new minimum as often as ONE sequence of twice the length would
         cmin = min_over_halves(cmin);
         const float lim = cmin + band;
-        if (m <= lim) {
-          if (cnt == kCandCap) compact(lim);
-          uint32_t mask = 0;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) mask |= (c[i] <= lim) ? (1u << i) : 0u;
-          cand_key[cnt][tid] = uint32_t(it) * uint32_t(kSlabs) + uint32_t(g);
-          cand_mask[cnt][tid] = mask;
-          cand_m[cnt][tid] = m;
-          ++cnt;
-        }
+        if (m <= lim) list.record(uint32_t(it) * uint32_t(kSlabs) + uint32_t(g), c, m, lim, resolve);
       };
       rkh_f16v c0, c1;
       float a0[H], a1[H];
@@ -791,21 +668,8 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs 
     if (hi == 0 && qi < B && t_count > 0) atomicMin(seed + qi, seed_encode(cmin));
     return;
   }
-  // resolve what the final minimum (of both halves) leaves of the list
-  {
-    const float lim = cmin + band;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k)
-      if (cand_m[k][tid] <= lim) resolve_entry(k);
-  }
-  {  // the two halves of the wave hold different rows of the same 32 queries
-    const double od = __shfl_xor(best_d, 32, 64);
-    const uint32_t oi = __shfl_xor(best_i, 32, 64);
-    if (lex_less(od, oi, best_d, best_i)) {
-      best_d = od;
-      best_i = oi;
-    }
-  }
+  list.finish(cmin + band, resolve);  // what the final minimum (of both halves) leaves of the list
+  nn_merge_lane_halves(best_d, best_i);
   if (hi == 0 && qi < B) {
     part_dist[uint64_t(bx) * Bpad + qi] = best_d;
     part_idx[uint64_t(bx) * Bpad + qi] = best_i;
@@ -829,13 +693,7 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_mfma_kernel(NnArgs 
 // magnitude 3 Dp M'^2 PER PRODUCT SLOT of four instructions (256 roundings; an IEEE f32 sum of them would stay below a
 // quarter of that); the float |x^|^2 chains and the double -> float rounding of the inputs as in the f32 kernel.  E is
 // their sum with a factor 2, the band 2 E plus the rounding of (running minimum + band).
-#ifndef RKH_BF16_PIPELINED
-#define RKH_BF16_PIPELINED 0
-#endif
-#ifndef RKH_BF16_CAP
-#define RKH_BF16_CAP 4
-#endif
-static constexpr int kBf16Cap = RKH_BF16_CAP;  // entries per lane of the bf16 sweep (LDS: a fourth block per CU)
+static constexpr int kBf16Cap = 4;  // entries per lane of the bf16 sweep (LDS: a fourth block per CU)
 typedef __bf16 rkh_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 rkh_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float rkh_f2v __attribute__((ext_vector_type(2)));
@@ -925,52 +783,18 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_bf16_kernel(NnArgs 
   constexpr int kSlabs = kTileRows / 32;
   // A operands of the tile: fragment i of (row, lane half) -- consecutive rows 16 bytes apart: conflict-free ds_read_b128
   __shared__ uint4 tileA[NI][2][kTileRows];
-  __shared__ uint32_t cand_key[kBf16Cap][kMfmaThreads];
-  __shared__ uint32_t cand_mask[kBf16Cap][kMfmaThreads];
-  __shared__ float cand_m[kBf16Cap][kMfmaThreads];
+  __shared__ NnBandLds<kBf16Cap, kMfmaThreads> cand;
 
   uint32_t bx, by, bz;
-  {
-    const uint32_t L = blockIdx.x;
-    const uint32_t ytot = yblock_base ? yblock_base[n_problems] : gy * n_problems;
-    const uint32_t W = ytot * gx, Wc = (W + 7) >> 3;
-    const uint32_t slot = L >> 3, w = (L & 7) * Wc + slot;
-    if (slot >= Wc || w >= W) return;
-    const uint32_t yy = w / gx;
-    uint32_t p = 0, y0, cnt;
-    if (yblock_base) {
-      uint32_t hi_p = n_problems;  // yblock_base[p] <= yy < yblock_base[hi_p]
-      while (hi_p - p > 1) {
-        const uint32_t mid = (p + hi_p) >> 1;
-        if (yblock_base[mid] <= yy) p = mid;
-        else hi_p = mid;
-      }
-      y0 = yblock_base[p];
-      cnt = yblock_base[p + 1] - y0;
-    } else {
-      p = yy / gy;
-      y0 = p * gy;
-      cnt = gy;
-    }
-    const uint32_t r = w - y0 * gx;
-    bx = r / cnt;
-    by = r - bx * cnt;
-    bz = p;
-  }
-  // everything read from the table entry is block-uniform; said explicitly, it lives in scalar registers
-  auto uniform64 = [](uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-    return (uint64_t(hi) << 32) | lo;
-  };
+  if (!nn_xcd_item(yblock_base, n_problems, gx, gy, bx, by, bz)) return;
   const NnArgs a = table ? table[bz] : single;
-  const double* __restrict__ pos = reinterpret_cast<const double*>(uniform64(reinterpret_cast<uint64_t>(a.pos)));
-  const uint64_t n = uniform64(a.d_n ? uint64_t(*a.d_n) : a.n);
-  const uint32_t B = __builtin_amdgcn_readfirstlane(a.d_B ? *a.d_B : a.B);
-  const double* __restrict__ q = reinterpret_cast<const double*>(
-      uniform64(reinterpret_cast<uint64_t>(a.q + (a.d_qoff ? uint64_t(*a.d_qoff) : 0ull) * D)));
-  uint32_t* __restrict__ seed = reinterpret_cast<uint32_t*>(uniform64(reinterpret_cast<uint64_t>(a.seed)));
-  double* __restrict__ part_dist = reinterpret_cast<double*>(uniform64(reinterpret_cast<uint64_t>(a.part_dist)));
-  uint32_t* __restrict__ part_idx = reinterpret_cast<uint32_t*>(uniform64(reinterpret_cast<uint64_t>(a.part_idx)));
+  const double* __restrict__ pos = nn_uniform(a.pos);
+  const uint64_t n = nn_rows(a);
+  const uint32_t B = nn_queries(a);
+  const double* __restrict__ q = nn_query_rows(a, D);
+  uint32_t* __restrict__ seed = nn_uniform(a.seed);
+  double* __restrict__ part_dist = nn_uniform(a.part_dist);
+  uint32_t* __restrict__ part_idx = nn_uniform(a.part_idx);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, hi = lane >> 5;
@@ -1003,61 +827,21 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_bf16_kernel(NnArgs 
   uint32_t best_i = 0xFFFFFFFFu;
   // running minimum of the estimates of this lane's query; NaN ("no seed") is dropped by fminf
   float cmin = seed ? fminf(INFINITY, seed_decode(seed[qsrc])) : INFINITY;
-  int cnt = 0;                      // entries in the list
-
-  // exact fp64 distance of vertex `row` (global index): the operation sequence of nn1_sweep_kernel
+  // exact fp64 distance of vertex `row` (global index)
   auto resolve = [&](uint32_t row) {
     if (uint64_t(row) >= n) return;  // padding rows of the last tile
     const double* p = pos + uint64_t(row) * DP;
     const double* qq = q + uint64_t(qsrc) * D;
-    double s;
-    {
-      const double df = qq[0] - p[0];
-      s = df * df;
-    }
-#pragma unroll 3
-    for (int d = 1; d < DP; ++d) {  // (a few coordinates per memory round trip; fully unrolled it spills into the sweep)
-      const double df = (d < D ? qq[d] : 0.0) - p[d];
-      s = s + df * df;
-    }
-    const double dd = sqrt(s);
+    // (a few coordinates per memory round trip; fully unrolled it spills into the sweep)
+    const double dd = sqrt(nn_exact_sq<DP, 3>([&](int d) { return nn_qcoord(qq, d, D) - p[d]; }));
     if (lex_less(dd, row, best_d, best_i)) {
       best_d = dd;
       best_i = row;
     }
   };
-  // every flagged row of entry k: key = slab index counted from the block's first tile
-  auto resolve_entry = [&](int k) {
-    uint32_t mask = cand_mask[k][tid];
-    const uint32_t base = uint32_t(t_first) * uint32_t(kTileRows) + cand_key[k][tid] * 32u + 4u * uint32_t(hi);
-#pragma unroll 1
-    while (mask) {
-      const uint32_t i = uint32_t(__builtin_ctz(mask));
-      mask &= mask - 1;
-      resolve(base + 8u * (i >> 2) + (i & 3u));
-    }
-  };
-  // drop the entries the current minimum rules out; if the list is still full, resolve it
-  auto compact = [&](float lim) {
-    int w = 0;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k) {
-      const float mm = cand_m[k][tid];
-      if (mm <= lim) {
-        const uint32_t kk = cand_key[k][tid], mk = cand_mask[k][tid];
-        cand_m[w][tid] = mm;
-        cand_key[w][tid] = kk;
-        cand_mask[w][tid] = mk;
-        ++w;
-      }
-    }
-    cnt = w;
-    if (cnt == kBf16Cap) {
-#pragma unroll 1
-      for (int k = 0; k < cnt; ++k) resolve_entry(k);
-      cnt = 0;
-    }
-  };
+  // entry key = slab index counted from the block's first tile
+  auto rows = [&](uint32_t key) { return uint32_t(t_first) * uint32_t(kTileRows) + key * 32u + 4u * uint32_t(hi); };
+  NnBandList<kBf16Cap, kMfmaThreads, decltype(rows)> list{cand, rows, tid, 0};
 
   // a thread stages two half rows per tile: pairs p = tid and tid + 256, pair p = (row p >> 1, half p & 1)
   constexpr int PP = 2 * kTileRows / kMfmaThreads;
@@ -1125,34 +909,8 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_bf16_kernel(NnArgs 
         // over both lane halves: the pair then meets a new minimum as often as ONE sequence of twice the length would
         cmin = min_over_halves(cmin);
         const float lim = cmin + band;
-        if (m <= lim) {
-          if (cnt == kBf16Cap) compact(lim);
-          uint32_t mask = 0;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) mask |= (c[i] <= lim) ? (1u << i) : 0u;
-          cand_key[cnt][tid] = uint32_t(it) * uint32_t(kSlabs) + uint32_t(g);
-          cand_mask[cnt][tid] = mask;
-          cand_m[cnt][tid] = m;
-          ++cnt;
-        }
+        if (m <= lim) list.record(uint32_t(it) * uint32_t(kSlabs) + uint32_t(g), c, m, lim, resolve);
       };
-#if RKH_BF16_PIPELINED
-      rkh_f16v c0, c1;
-      uint4 a0[NI], a1[NI];
-      load_ops(0, a0, c0);
-      chain(a0, c0);
-#pragma unroll
-      for (int g = 0; g < kSlabs; g += 2) {
-        load_ops(g + 1, a1, c1);
-        chain(a1, c1);
-        settle(g, c0);
-        if (g + 2 < kSlabs) {
-          load_ops(g + 2, a0, c0);
-          chain(a0, c0);
-        }
-        settle(g + 1, c1);
-      }
-#else
       // one accumulator: the bf16 matrix instructions overlap with the VALU work of the SIMD's other waves, and the
       // registers of a second accumulator are worth a fourth wave per SIMD
 #pragma unroll
@@ -1163,26 +921,12 @@ __global__ __launch_bounds__(kMfmaThreads, 4) void nn1_sweep_bf16_kernel(NnArgs 
         chain(a0, c0);
         settle(g, c0);
       }
-#endif
     }
     __syncthreads();
   }
   cmin = min_over_halves(cmin);
-  // resolve what the final minimum (of both halves) leaves of the list
-  {
-    const float lim = cmin + band;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k)
-      if (cand_m[k][tid] <= lim) resolve_entry(k);
-  }
-  {  // the two halves of the wave hold different rows of the same 32 queries
-    const double od = __shfl_xor(best_d, 32, 64);
-    const uint32_t oi = __shfl_xor(best_i, 32, 64);
-    if (lex_less(od, oi, best_d, best_i)) {
-      best_d = od;
-      best_i = oi;
-    }
-  }
+  list.finish(cmin + band, resolve);  // what the final minimum (of both halves) leaves of the list
+  nn_merge_lane_halves(best_d, best_i);
   if (hi == 0 && qi < B) {
     part_dist[uint64_t(bx) * Bpad + qi] = best_d;
     part_idx[uint64_t(bx) * Bpad + qi] = best_i;
@@ -1219,25 +963,18 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
   constexpr int H = DP / 2;
   constexpr int PD = kFewDepth;
   constexpr int kWaves = kFewThreads / 64;
-  __shared__ uint32_t cand_key[kCandCap][kFewThreads];
-  __shared__ uint32_t cand_mask[kCandCap][kFewThreads];
-  __shared__ float cand_m[kCandCap][kFewThreads];
+  __shared__ NnBandLds<kCandCap, kFewThreads> cand;
   __shared__ double red_d[kWaves][kFewQueries];
   __shared__ uint32_t red_i[kWaves][kFewQueries];
   __shared__ uint32_t blk_min[kFewQueries];  // seed_encode of the block's running minimum per query slot
 
-  auto uniform64 = [](uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-    return (uint64_t(hi) << 32) | lo;
-  };
   const NnArgs a = table ? table[blockIdx.z] : single;
   typedef const __attribute__((address_space(1))) double* nn_gdouble_p;
   typedef const __attribute__((address_space(1))) nn_d2* nn_grow_p;
-  const uint64_t pos = uniform64(reinterpret_cast<uint64_t>(a.pos));
-  const uint64_t n = uniform64(a.d_n ? uint64_t(*a.d_n) : a.n);
-  const uint32_t B = __builtin_amdgcn_readfirstlane(a.d_B ? *a.d_B : a.B);
-  const double* __restrict__ q = reinterpret_cast<const double*>(
-      uniform64(reinterpret_cast<uint64_t>(a.q + (a.d_qoff ? uint64_t(*a.d_qoff) : 0ull) * D)));
+  const uint64_t pos = nn_uniform(reinterpret_cast<uint64_t>(a.pos));
+  const uint64_t n = nn_rows(a);
+  const uint32_t B = nn_queries(a);
+  const double* __restrict__ q = nn_query_rows(a, D);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, hi = lane >> 5;
@@ -1262,11 +999,9 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
   double best_d = INFINITY;
   uint32_t best_i = 0xFFFFFFFFu;
   float cmin = live ? INFINITY : -INFINITY;
-  int cnt = 0;
 
-  // exact fp64 distance of a row: the operation sequence of nn1_sweep_kernel.  AT_ONCE: every coordinate is loaded
-  // before the first use (one round trip; the end of the sweep), otherwise a few per round trip (inside the sweep the
-  // registers belong to the slabs in flight)
+  // exact fp64 distance of a row.  AT_ONCE: every coordinate is loaded before the first use (one round trip; the end of
+  // the sweep), otherwise a few per round trip (inside the sweep the registers belong to the slabs in flight)
   auto resolve = [&](uint64_t row, auto at_once) {
     if (row >= n) return;
     nn_gdouble_p p = (nn_gdouble_p)(pos + row * (DP * sizeof(double)));
@@ -1279,25 +1014,9 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
         pv[d] = p[d];
         qv[d] = d < D ? qq[d] : 0.0;
       }
-      {
-        const double df = qv[0] - pv[0];
-        s = df * df;
-      }
-#pragma unroll
-      for (int d = 1; d < DP; ++d) {
-        const double df = qv[d] - pv[d];
-        s = s + df * df;
-      }
+      s = nn_exact_sq<DP>([&](int d) { return qv[d] - pv[d]; });
     } else {
-      {
-        const double df = qq[0] - p[0];
-        s = df * df;
-      }
-#pragma unroll 3
-      for (int d = 1; d < DP; ++d) {
-        const double df = (d < D ? qq[d] : 0.0) - p[d];
-        s = s + df * df;
-      }
+      s = nn_exact_sq<DP, 3>([&](int d) { return nn_qcoord(qq, d, D) - p[d]; });
     }
     const double dd = sqrt(s);
     if (lex_less(dd, uint32_t(row), best_d, best_i)) {
@@ -1305,36 +1024,11 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
       best_i = uint32_t(row);
     }
   };
-  auto resolve_entry = [&](int k, auto at_once) {
-    uint32_t mask = cand_mask[k][tid];
-    const uint64_t base = (uint64_t(cand_key[k][tid]) * step + first) * 32u + 4u * uint32_t(hi);
-#pragma unroll 1
-    while (mask) {
-      const uint32_t i = uint32_t(__builtin_ctz(mask));
-      mask &= mask - 1;
-      resolve(base + 8u * (i >> 2) + (i & 3u), at_once);
-    }
-  };
-  auto compact = [&](float lim) {
-    int w = 0;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k) {
-      const float mm = cand_m[k][tid];
-      if (mm <= lim) {
-        const uint32_t kk = cand_key[k][tid], mk = cand_mask[k][tid];
-        cand_m[w][tid] = mm;
-        cand_key[w][tid] = kk;
-        cand_mask[w][tid] = mk;
-        ++w;
-      }
-    }
-    cnt = w;
-    if (cnt == kCandCap) {
-#pragma unroll 1
-      for (int k = 0; k < cnt; ++k) resolve_entry(k, std::false_type{});
-      cnt = 0;
-    }
-  };
+  auto resolve_in_sweep = [&](uint64_t row) { resolve(row, std::false_type{}); };
+  auto resolve_at_end = [&](uint64_t row) { resolve(row, std::true_type{}); };
+  // entry key = the wave's slab counter
+  auto rows = [&](uint32_t key) { return (uint64_t(key) * step + first) * 32u + 4u * uint32_t(hi); };
+  NnBandList<kCandCap, kFewThreads, decltype(rows)> list{cand, rows, tid, 0};
 
   // half a row per lane; slabs past the wave's last one re-read it (the prefetches are unconditional, see
   // nn1_stream_kernel), rows past the tree re-read the last row and are replaced below
@@ -1381,14 +1075,7 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
     const float lim = cmin + band;
     if (m <= lim) {
       if (live && hi == 0 && cmin < seen) atomicMin(&blk_min[col], seed_encode(cmin));
-      if (cnt == kCandCap) compact(lim);
-      uint32_t mask = 0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mask |= (c[i] <= lim) ? (1u << i) : 0u;
-      cand_key[cnt][tid] = uint32_t(it);
-      cand_mask[cnt][tid] = mask;
-      cand_m[cnt][tid] = m;
-      ++cnt;
+      list.record(uint32_t(it), c, m, lim, resolve_in_sweep);
     }
   };
 
@@ -1422,20 +1109,9 @@ __global__ __launch_bounds__(kFewThreads, 4) void nn1_few_mfma_kernel(NnArgs sin
     if (live && hi == 0) atomicMin(&blk_min[col], seed_encode(cmin));
   }
   __syncthreads();
-  if (live && B > 0) {  // resolve what the block's minimum leaves of the list
-    const float lim = fminf(cmin, seed_decode(blk_min[col])) + band;
-#pragma unroll 1
-    for (int k = 0; k < cnt; ++k)
-      if (cand_m[k][tid] <= lim) resolve_entry(k, std::true_type{});
-  }
-  {  // the two halves of the wave hold different rows of the same 32 query slots
-    const double od = __shfl_xor(best_d, 32, 64);
-    const uint32_t oi = __shfl_xor(best_i, 32, 64);
-    if (lex_less(od, oi, best_d, best_i)) {
-      best_d = od;
-      best_i = oi;
-    }
-  }
+  if (live && B > 0)  // resolve what the block's minimum leaves of the list
+    list.finish(fminf(cmin, seed_decode(blk_min[col])) + band, resolve_at_end);
+  nn_merge_lane_halves(best_d, best_i);
   if (hi == 0) {
     red_d[wave][col] = best_d;
     red_i[wave][col] = best_i;
@@ -1502,57 +1178,70 @@ static int padded_dims(int D) {
 }
 int nn_padded_dims(int D) { return padded_dims(D); }
 
-// matrix-core pre-filter for batches of more than 64 queries (RKH_NN_MFMA=0 keeps the packed-fp32 VALU pre-filter)
-static bool mfma_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RKH_NN_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+// f(std::integral_constant<int, DP>()) for the padded width DP of D; false if D has none
+template <class F>
+static bool with_padded_dims(int D, F&& f) {
+  switch (padded_dims(D)) {
+    case 2: f(std::integral_constant<int, 2>()); return true;
+    case 4: f(std::integral_constant<int, 4>()); return true;
+    case 6: f(std::integral_constant<int, 6>()); return true;
+    case 8: f(std::integral_constant<int, 8>()); return true;
+    case 12: f(std::integral_constant<int, 12>()); return true;
+    case 16: f(std::integral_constant<int, 16>()); return true;
+    case 24: f(std::integral_constant<int, 24>()); return true;
+    case 32: f(std::integral_constant<int, 32>()); return true;
+  }
+  return false;
+}
+// f(std::integral_constant<int, QB>()) for the QB of Q... equal to qb; false if none is, or if f returns false
+template <int... Q, class F>
+static bool with_qb(uint32_t qb, F&& f) {
+  return ((qb == uint32_t(Q) && f(std::integral_constant<int, Q>())) || ...);
 }
 
+// ---- the launch plan ------------------------------------------------------------------------------------------------
 // The split-bf16 band is ~100x the f32 one: in very few dimensions, where the nearest neighbours of a dense cloud sit
 // close together, it lets more rows through to the exact test than the cheaper instructions save (unit cube, 1 Mi x 1024
-// queries, tests/diag_nn_lowdim.py: 3-D 159 against 154 us, 65 536 x 384: 27 against 23; 4-D 30 against 33; 6-D 123
-// against 199) -- from 6 padded dimensions on the bf16 form is used.
-static int bf16_min_dims() {  // RKH_NN_BF16_MIN_DIMS overrides (diagnostics)
-  static const int v = [] {
-    const char* e = getenv("RKH_NN_BF16_MIN_DIMS");
-    return e ? atoi(e) : 6;
-  }();
-  return v;
-}
-// RKH_NN_BF16=0 keeps the f32-input matrix instructions in the many-queries sweep (diagnostics: tests/prof_nn_variants.sh)
-static bool bf16_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RKH_NN_BF16");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
+// queries: 3-D 159 against 154 us, 65 536 x 384: 27 against 23; 4-D 30 against 33; 6-D 123 against 199) -- from 6
+// padded dimensions on the bf16 form is used.
+static constexpr int kBf16MinDims = 6;
+// Which few-queries sweeps take the matrix-core pre-filter (measured on 12-dimensional trees of 16 Ki .. 4 Mi rows,
+// tests/diag_nn_few.sh): from 5 queries on it beats the fp64 sweeps at every size (8 queries: 5.2 against 4.4 TB/s at
+// 4 Mi rows, 32 queries: 5.0 against 1.4); up to 4 queries the register-direct fp64 sweep is as fast or faster (5.8 TB/s
+// at one query) and stays, where it applies (D equal to its padded width).  Trees of a few tiles keep the tiled sweeps.
+static constexpr uint64_t kFewMinRows = 8192;
+static constexpr uint32_t kFewMaxStreamQueries = 4;
 
-static uint32_t pick_qb(uint32_t B, bool bounded = false) {
-  // queries per block: the smallest padded query count wins (a block computes all its QB slots); ties go to the larger
-  // block (fewer re-reads of the tiles).  With a coordinate bound 33..64 queries already take the matrix-core block of
-  // 128 (half of it padding, and still three times faster than the packed-fp32 pre-filter of a 64-query block: 51 against
-  // 147 us at 1 Mi rows); the row-slice count does not depend on this choice (one query block either way).
-  if (B <= 8) return 8;
-  if (B <= 16) return 16;
-  if (B <= 32) return 32;
-  if (B <= 64 && !(bounded && mfma_enabled() && bf16_enabled())) return 64;
-  if (mfma_enabled()) return kMfmaQueries;
-  const uint32_t pad128 = (B + 127) / 128 * 128, pad256 = (B + 255) / 256 * 256;
-  return pad128 < pad256 ? 128 : 256;
+// the forms the plan can select per padded width; nothing else is instantiated
+template <int DP>
+static constexpr bool kHasMatrixForms = DP <= 16;  // few-queries, f32-input and bf16 matrix-core sweeps, seed pass
+template <int DP, int QB>
+static constexpr bool kHasF32 = QB == 32 || (QB == 64 && !(DP >= kBf16MinDims && DP <= 16)) || (QB == 128 && DP > 16);
+
+enum class Nn1Form { stream, few, tiled, tiled_f32, mfma, bf16 };
+static const char* nn1_form_name(Nn1Form f) {
+  switch (f) {
+    case Nn1Form::stream: return "nn1_stream_kernel";
+    case Nn1Form::few: return "nn1_few_mfma_kernel";
+    case Nn1Form::tiled: return "nn1_sweep_kernel";
+    case Nn1Form::tiled_f32: return "nn1_sweep_f32_kernel";
+    case Nn1Form::mfma: return "nn1_sweep_mfma_kernel";
+    case Nn1Form::bf16: return "nn1_sweep_bf16_kernel";
+  }
+  return "";
 }
+struct Nn1Plan {
+  Nn1Form form = Nn1Form::tiled;
+  bool seed = false;  // the sampled-minimum pass (nn1_sweep_mfma_kernel<DP, true>) runs first
+  uint32_t qb = 0;    // queries per block (stream: per lane)
+  uint32_t gx = 1;    // row slices per problem = partial minima per query
+  uint32_t gy = 1;    // query blocks per problem
+};
 
 static uint32_t pick_gx(uint64_t n_upper, uint32_t gy) {
   uint64_t tiles = (n_upper + kTileRows - 1) / kTileRows;
   if (tiles < 1) tiles = 1;
-  static const long forced = [] {  // diagnostic override of the row-slice count
-    const char* e = getenv("RKH_NN_BLOCKS");
-    return e ? atol(e) : 0L;
-  }();
-  uint64_t want = forced > 0 ? uint64_t(forced) : 4096 / gy;  // ~16 blocks per CU over the whole grid
+  uint64_t want = 4096 / gy;  // ~16 blocks per CU over the whole grid
   if (want < 1) want = 1;
   // a block's fixed costs (query setup, resolving its candidates, one partial per query) are worth at least 4 tiles
   const uint64_t most = tiles >= 4 ? tiles / 4 : 1;
@@ -1560,9 +1249,9 @@ static uint32_t pick_gx(uint64_t n_upper, uint32_t gy) {
   return uint32_t(tiles < want ? tiles : want);
 }
 
-// the register-direct sweep: exactly one resident set of blocks (`resident` = what the occupancy of the instantiation
-// allows on the whole device; a partial second round of blocks would run at a fraction of the machine); a thread's
-// fixed costs (the merge of the lanes at the end) are worth at least 4 rows
+// the register-direct and few-queries sweeps: exactly one resident set of blocks (`resident` = what the occupancy of the
+// instantiation allows on the whole device; a partial second round of blocks would run at a fraction of the machine); a
+// thread's fixed costs (the merge of the lanes at the end) are worth at least 4 rows
 static constexpr uint32_t kStreamBlocksMax = 2048;  // 8 blocks of 256 threads on each of 256 CUs
 static uint32_t pick_gx_stream(uint64_t n_upper, uint32_t n_problems, uint32_t resident) {
   uint64_t tiles = (n_upper + kTileRows - 1) / kTileRows;
@@ -1574,51 +1263,142 @@ static uint32_t pick_gx_stream(uint64_t n_upper, uint32_t n_problems, uint32_t r
   if (want > most) want = most;
   return uint32_t(want);
 }
+template <class K>
+static uint32_t device_resident_blocks(K kernel, int threads) {
+  int per_cu = 0, cus = 0, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 1024u;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) return 1024u;
+  return uint32_t(per_cu) * uint32_t(cus);
+}
 template <int DP, int QB>
 static uint32_t stream_resident_blocks() {
-  static const uint32_t v = [] {
-    int per_cu = 0, cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nn1_stream_kernel<DP, QB>, kThreads, 0) != hipSuccess ||
-        per_cu <= 0)
-      return 1024u;
-    return uint32_t(per_cu) * uint32_t(cus);
-  }();
+  static const uint32_t v = device_resident_blocks(nn1_stream_kernel<DP, QB>, kThreads);
   return v;
 }
-
-// the few-queries matrix-core sweep: one resident set of blocks, like the register-direct sweep
 template <int DP>
 static uint32_t few_resident_blocks() {
-  static const uint32_t v = [] {
-    int per_cu = 0, cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nn1_few_mfma_kernel<DP>, kFewThreads, 0) != hipSuccess ||
-        per_cu <= 0)
-      return 1024u;
-    return uint32_t(per_cu) * uint32_t(cus);
-  }();
+  static const uint32_t v = device_resident_blocks(nn1_few_mfma_kernel<DP>, kFewThreads);
   return v;
 }
-// Which few-queries sweeps take the matrix-core pre-filter (measured on 12-dimensional trees of 16 Ki .. 4 Mi rows,
-// tests/diag_nn_few.sh): from 5 queries on it beats the fp64 sweeps at every size (8 queries: 5.2 against 4.4 TB/s at
-// 4 Mi rows, 32 queries: 5.0 against 1.4); up to 4 queries the register-direct fp64 sweep is as fast or faster (5.8 TB/s
-// at one query) and stays, where it applies (D equal to its padded width).  Trees of a few tiles keep the tiled sweeps.
-static constexpr uint64_t kFewMinRows = 8192;
-static bool few_applies(uint32_t B, int D, int DP, uint64_t n_upper, double coord_bound) {
-  if (!(coord_bound > 0.0) || B > uint32_t(kFewQueries) || DP > 16 || n_upper < kFewMinRows || !mfma_enabled()) return false;
-  return B > 4 || D != DP;
+
+// The one place that decides how a 1-NN sweep runs: B queries per problem over at most n_upper rows, n_problems problems;
+// coord_bound > 0 bounds every |coordinate| of rows and queries; seeded = a seed buffer is given (NnArgs::seed).
+template <int DP>
+static Nn1Plan plan_nn1(int D, uint32_t B, uint64_t n_upper, uint32_t n_problems, double coord_bound, bool seeded) {
+  // the error analysis of the pre-filters is relative to the bound: it assumes that neither the float products nor the
+  // bf16 pieces leave the normal range (and that 1e18, the stand-in for rows that must never qualify, is far outside
+  // the cloud).  Clouds scaled beyond that are swept by the exact kernels.
+  const bool bounded = coord_bound >= 1e-6 && coord_bound <= 1e6;
+  const uint32_t np = n_problems ? n_problems : 1;
+  Nn1Plan p;
+  // few queries over a large tree with known coordinate bounds: matrix-core pre-filter at the speed of HBM
+  if (bounded && kHasMatrixForms<DP> && B <= uint32_t(kFewQueries) && n_upper >= kFewMinRows &&
+      (B > kFewMaxStreamQueries || D != DP)) {
+    p.form = Nn1Form::few;
+    p.qb = kFewQueries;
+    if constexpr (kHasMatrixForms<DP>) p.gx = pick_gx_stream(n_upper, np, few_resident_blocks<DP>());
+    return p;
+  }
+  if (B <= 8 && D == DP) {  // HBM-bound regime: rows straight into registers
+    p.form = Nn1Form::stream;
+    p.qb = B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8));
+    with_qb<1, 2, 4, 8>(p.qb, [&](auto QB) {
+      p.gx = pick_gx_stream(n_upper, np, stream_resident_blocks<DP, decltype(QB)::value>());
+      return true;
+    });
+    return p;
+  }
+  // The tiled sweeps.  Queries per block: the smallest padded query count wins (a block computes all its QB slots).
+  // With a coordinate bound and the bf16 form, 33..64 queries already take the matrix-core block of 128 (half of it
+  // padding, and still three times faster than the packed-fp32 pre-filter of a 64-query block: 51 against 147 us at
+  // 1 Mi rows); the row-slice count does not depend on this choice (one query block either way).
+  const bool bf16 = bounded && DP >= kBf16MinDims && kHasMatrixForms<DP>;
+  p.qb = B <= 8 ? 8 : (B <= 16 ? 16 : (B <= 32 ? 32 : ((B <= 64 && !bf16) ? 64 : uint32_t(kMfmaQueries))));
+  p.gy = (B + p.qb - 1) / p.qb;
+  p.gx = pick_gx(n_upper, p.gy * np);
+  if (!bounded || p.qb < 32) {
+    p.form = Nn1Form::tiled;
+  } else if (p.qb == uint32_t(kMfmaQueries) && kHasMatrixForms<DP>) {  // compute-bound regime: the matrix cores
+    p.form = bf16 ? Nn1Form::bf16 : Nn1Form::mfma;
+    // the sampled-minimum pass (trees of at least kSeedMinTiles tiles; smaller ones leave "no seed" behind)
+    p.seed = seeded && (n_upper + kTileRows - 1) / kTileRows >= uint64_t(kSeedMinTiles);
+  } else {
+    p.form = Nn1Form::tiled_f32;
+  }
+  return p;
 }
 
-uint32_t nn1_partial_blocks(uint64_t n_upper, uint32_t B, uint32_t n_problems) {
-  const uint32_t qb = pick_qb(B);
-  const uint32_t gy = (B + qb - 1) / qb;
-  const uint32_t np = n_problems ? n_problems : 1;
-  const uint32_t a = pick_gx(n_upper, gy * np);
-  const uint32_t b = B <= uint32_t(kFewQueries) ? pick_gx_stream(n_upper, np, kStreamBlocksMax) : 0;
-  return a > b ? a : b;
+// the sweep kernels of a plan (false: the plan names a kernel that is not instantiated for DP)
+template <int DP>
+static bool launch_nn1_sweep(const Nn1Plan& p, hipStream_t s, int D, const NnArgs& single, const NnArgs* d_table,
+                             uint32_t n_problems, uint32_t B, double coord_bound, const uint32_t* d_yblock_base) {
+  const dim3 grid(p.gx, p.gy, n_problems), block(kThreads);
+  const uint32_t Bpad = B;
+  switch (p.form) {
+    case Nn1Form::stream:
+      return with_qb<1, 2, 4, 8>(p.qb, [&](auto QB) {
+        hipLaunchKernelGGL((nn1_stream_kernel<DP, decltype(QB)::value>), grid, block, 0, s, single, d_table, Bpad);
+        return true;
+      });
+    case Nn1Form::tiled:
+      return with_qb<8, 16, 32, 64, 128>(p.qb, [&](auto QB) {
+        hipLaunchKernelGGL((nn1_sweep_kernel<DP, decltype(QB)::value>), grid, block, 0, s, single, d_table, D, Bpad);
+        return true;
+      });
+    case Nn1Form::tiled_f32:
+      return with_qb<32, 64, 128>(p.qb, [&](auto QB) {
+        constexpr int Q = decltype(QB)::value;
+        if constexpr (kHasF32<DP, Q>) {
+          hipLaunchKernelGGL((nn1_sweep_f32_kernel<DP, Q>), grid, block, 0, s, single, d_table, D, Bpad, coord_bound);
+          return true;
+        }
+        return false;
+      });
+    case Nn1Form::few:
+      if constexpr (kHasMatrixForms<DP>) {
+        hipLaunchKernelGGL((nn1_few_mfma_kernel<DP>), dim3(p.gx, 1, n_problems), dim3(kFewThreads), 0, s, single, d_table,
+                           D, Bpad, coord_bound);
+        return true;
+      }
+      return false;
+    case Nn1Form::mfma:
+    case Nn1Form::bf16:
+      if constexpr (kHasMatrixForms<DP>) {
+        if (p.form != (DP >= kBf16MinDims ? Nn1Form::bf16 : Nn1Form::mfma)) return false;
+        const uint32_t* yb = d_table ? d_yblock_base : nullptr;
+        auto blocks_for = [&](uint32_t slices) { return dim3((slices * p.gy * n_problems + 7) / 8 * 8); };
+        if (p.seed) {  // kSeedSample sample tiles, four per seed block
+          const uint32_t gxs = kSeedSample / 4;
+          hipLaunchKernelGGL((nn1_sweep_mfma_kernel<DP, true>), blocks_for(gxs), dim3(kMfmaThreads), 0, s, single, d_table,
+                             D, Bpad, coord_bound, yb, n_problems, gxs, p.gy);
+        }
+        if constexpr (DP >= kBf16MinDims) {
+          hipLaunchKernelGGL((nn1_sweep_bf16_kernel<DP>), blocks_for(p.gx), dim3(kMfmaThreads), 0, s, single, d_table, D,
+                             Bpad, coord_bound, yb, n_problems, p.gx, p.gy);
+        } else {
+          hipLaunchKernelGGL((nn1_sweep_mfma_kernel<DP, false>), blocks_for(p.gx), dim3(kMfmaThreads), 0, s, single,
+                             d_table, D, Bpad, coord_bound, yb, n_problems, p.gx, p.gy);
+        }
+        return true;
+      }
+      return false;
+  }
+  return false;
+}
+
+// Partial minima per query that a sweep of at most B_max queries can write: the largest gx of the plans for 1 .. B_max
+// queries.  Beyond one matrix-core block (kMfmaQueries) every plan is a tiled one whose gx only falls as query blocks
+// are added, so the plans up to that size are the ones to look at.
+uint32_t nn1_partial_blocks(int D, uint64_t n_upper, uint32_t B_max, uint32_t n_problems, double coord_bound) {
+  uint32_t most = 1;
+  with_padded_dims(D, [&](auto dp) {
+    for (uint32_t B = 1; B <= B_max && B <= uint32_t(kMfmaQueries); ++B) {
+      const uint32_t gx = plan_nn1<decltype(dp)::value>(D, B, n_upper, n_problems, coord_bound, false).gx;
+      most = gx > most ? gx : most;
+    }
+  });
+  return most;
 }
 
 uint32_t nn1_mfma_queries() { return uint32_t(kMfmaQueries); }
@@ -1627,110 +1407,36 @@ static const char* g_last_kernel = "";
 const char* nn_last_kernel_name() { return g_last_kernel; }
 void nn_set_last_kernel_name(const char* name) { g_last_kernel = name; }
 
-template <int DP>
-static rkh_status launch_nn1_dp(hipStream_t s, int D, const NnArgs& single, const NnArgs* d_table, uint32_t n_problems,
-                                uint64_t n_upper, uint32_t B, uint32_t part_capacity_blocks, hipEvent_t ev0,
-                                hipEvent_t ev1, double coord_bound, const uint32_t* d_yblock_base, bool table_has_seed) {
-  const uint32_t qb = pick_qb(B, coord_bound > 0.0 && DP >= bf16_min_dims() && DP <= 16);
-  const uint32_t gy = (B + qb - 1) / qb;
-  // few queries over a large tree with known coordinate bounds: matrix-core pre-filter at the speed of HBM
-  const bool few = few_applies(B, D, DP, n_upper, coord_bound);
-  const bool stream = !few && B <= 8 && D == DP;  // HBM-bound regime: rows straight into registers
-  uint32_t gx = pick_gx(n_upper, gy * n_problems);
-  if (few) {
-    if constexpr (DP <= 16) gx = pick_gx_stream(n_upper, n_problems, few_resident_blocks<DP>());
-  } else if (stream) {
-    const uint32_t resident = B <= 1 ? stream_resident_blocks<DP, 1>()
-                                     : (B <= 2 ? stream_resident_blocks<DP, 2>()
-                                               : (B <= 4 ? stream_resident_blocks<DP, 4>() : stream_resident_blocks<DP, 8>()));
-    gx = pick_gx_stream(n_upper, n_problems, resident);
-  }
-  if (gx > part_capacity_blocks) gx = part_capacity_blocks;
-  const uint32_t Bpad = B;
-  dim3 grid(gx, gy, n_problems), block(kThreads);
-#define RKH_NN1_LAUNCH(QB) hipLaunchKernelGGL((nn1_sweep_kernel<DP, QB>), grid, block, 0, s, single, d_table, D, Bpad)
-#define RKH_NN1_LAUNCH_F32(QB) \
-  hipLaunchKernelGGL((nn1_sweep_f32_kernel<DP, QB>), grid, block, 0, s, single, d_table, D, Bpad, coord_bound)
-  if (ev0) (void)hipEventRecord(ev0, s);
-  const bool f32 = coord_bound > 0.0 && qb >= 32;  // compute-bound regime with known coordinate bounds
-  const bool mfma = f32 && qb == kMfmaQueries && mfma_enabled() && DP <= 16;
-  g_last_kernel = few ? "nn1_few_mfma_kernel"
-                      : (stream ? "nn1_stream_kernel"
-                                : (mfma ? "nn1_sweep_mfma_kernel" : (f32 ? "nn1_sweep_f32_kernel" : "nn1_sweep_kernel")));
-  if (few) {
-    if constexpr (DP <= 16)
-      hipLaunchKernelGGL((nn1_few_mfma_kernel<DP>), dim3(gx, 1, n_problems), dim3(kFewThreads), 0, s, single, d_table, D,
-                         Bpad, coord_bound);
-  } else if (stream) {
-#define RKH_STREAM(QB) hipLaunchKernelGGL((nn1_stream_kernel<DP, QB>), grid, block, 0, s, single, d_table, Bpad)
-    if (B <= 1) { RKH_STREAM(1); }
-    else if (B <= 2) { RKH_STREAM(2); }
-    else if (B <= 4) { RKH_STREAM(4); }
-    else { RKH_STREAM(8); }
-#undef RKH_STREAM
-  } else if (mfma) {
-    if constexpr (DP <= 16) {
-      const uint32_t* yb = d_table ? d_yblock_base : nullptr;
-      auto blocks_for = [&](uint32_t slices) { return dim3((slices * gy * n_problems + 7) / 8 * 8); };
-      // the sampled-minimum pass (trees of at least kSeedMinTiles tiles; smaller ones leave "no seed" behind)
-      const uint64_t tiles_upper = (n_upper + kTileRows - 1) / kTileRows;
-      const bool seeded = (d_table ? table_has_seed : single.seed != nullptr) && tiles_upper >= uint64_t(kSeedMinTiles);
-      if (seeded) {  // kSeedSample sample tiles, four per seed block
-        const uint32_t gxs = kSeedSample / 4;
-        hipLaunchKernelGGL((nn1_sweep_mfma_kernel<DP, true>), blocks_for(gxs), dim3(kMfmaThreads), 0, s, single, d_table, D,
-                           Bpad, coord_bound, yb, n_problems, gxs, gy);
-      }
-      if (bf16_enabled() && DP >= bf16_min_dims()) {
-        g_last_kernel = "nn1_sweep_bf16_kernel";
-        hipLaunchKernelGGL((nn1_sweep_bf16_kernel<DP>), blocks_for(gx), dim3(kMfmaThreads), 0, s, single, d_table, D, Bpad,
-                           coord_bound, yb, n_problems, gx, gy);
-      } else
-        hipLaunchKernelGGL((nn1_sweep_mfma_kernel<DP, false>), blocks_for(gx), dim3(kMfmaThreads), 0, s, single, d_table, D,
-                           Bpad, coord_bound, yb, n_problems, gx, gy);
-    }
-  } else
-  switch (qb) {
-    case 8: RKH_NN1_LAUNCH(8); break;
-    case 16: RKH_NN1_LAUNCH(16); break;
-    case 32: if (f32) RKH_NN1_LAUNCH_F32(32); else RKH_NN1_LAUNCH(32); break;
-    case 64: if (f32) RKH_NN1_LAUNCH_F32(64); else RKH_NN1_LAUNCH(64); break;
-    case 128: if (f32) RKH_NN1_LAUNCH_F32(128); else RKH_NN1_LAUNCH(128); break;
-    default: if (f32) RKH_NN1_LAUNCH_F32(256); else RKH_NN1_LAUNCH(256); break;
-  }
-#undef RKH_NN1_LAUNCH
-#undef RKH_NN1_LAUNCH_F32
-  if (ev1) (void)hipEventRecord(ev1, s);
-  hipLaunchKernelGGL(nn1_reduce_kernel, dim3((B + 3) / 4, n_problems), dim3(256), 0, s, single, d_table, gx, Bpad);
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
 // 1-NN of up to B queries per problem.  single: one problem given by value; d_table: n_problems NnArgs in HBM.
 // n_upper (host bound on the vertex count) and B (host bound on the query count) only size the grid.
 rkh_status launch_nn1(hipStream_t s, int D, const NnArgs& single, const NnArgs* d_table, uint32_t n_problems,
                       uint64_t n_upper, uint32_t B, uint32_t part_capacity_blocks, hipEvent_t ev0, hipEvent_t ev1,
                       double coord_bound, const uint32_t* d_yblock_base, bool table_has_seed) {
   if (B == 0 || n_problems == 0) return RKH_OK;
-  // the error analysis of the pre-filters is relative to the bound: it assumes that neither the float products nor the
-  // bf16 pieces leave the normal range (and that 1e18, the stand-in for rows that must never qualify, is far outside
-  // the cloud).  Clouds scaled beyond that are swept by the exact kernels.
-  if (!(coord_bound >= 1e-6 && coord_bound <= 1e6)) coord_bound = 0.0;
-  switch (padded_dims(D)) {
-#define RKH_CASE(DP) \
-  case DP: return launch_nn1_dp<DP>(s, D, single, d_table, n_problems, n_upper, B, part_capacity_blocks, ev0, ev1, coord_bound, \
-                                    d_yblock_base, table_has_seed)
-    RKH_CASE(2);
-    RKH_CASE(4);
-    RKH_CASE(6);
-    RKH_CASE(8);
-    RKH_CASE(12);
-    RKH_CASE(16);
-    RKH_CASE(24);
-    RKH_CASE(32);
-#undef RKH_CASE
+  const bool seeded = d_table ? table_has_seed : single.seed != nullptr;
+  bool launched = false;
+  uint32_t gx = 0;
+  const bool dims_ok = with_padded_dims(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    Nn1Plan p = plan_nn1<DP>(D, B, n_upper, n_problems, coord_bound, seeded);
+    if (p.gx > part_capacity_blocks) p.gx = part_capacity_blocks;  // (a guard: nn1_partial_blocks sizes for every plan)
+    g_last_kernel = nn1_form_name(p.form);
+    if (ev0) (void)hipEventRecord(ev0, s);
+    launched = launch_nn1_sweep<DP>(p, s, D, single, d_table, n_problems, B, coord_bound, d_yblock_base);
+    gx = p.gx;
+  });
+  if (!dims_ok) {
+    set_error("nn: unsupported dimension");
+    return RKH_ERR_BAD_ARG;
   }
-  set_error("nn: unsupported dimension");
-  return RKH_ERR_BAD_ARG;
+  if (!launched) {
+    set_error("nn: the launch plan names a kernel that is not built");
+    return RKH_ERR_UNSUPPORTED;
+  }
+  if (ev1) (void)hipEventRecord(ev1, s);
+  hipLaunchKernelGGL(nn1_reduce_kernel, dim3((B + 3) / 4, n_problems), dim3(256), 0, s, single, d_table, gx, B);
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
 }
 
 // ---- synthetic fill: uniform points in the unit hypercube, splitmix64 per element ------------------

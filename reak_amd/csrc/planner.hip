@@ -29,6 +29,7 @@
 #include <cstring>
 #include <random>
 
+#include "nn_device.h"
 #include "nn_mirror.h"
 #include "rkh_internal.h"
 
@@ -243,13 +244,7 @@ __global__ __launch_bounds__(256) void fixup_kernel(const ProblemDev* __restrict
   for (uint32_t j = lane; j < b; j += 64) {
     if (!pr.accept[j]) continue;
     const double* p = pr.x_out + uint64_t(j) * D;
-    double df = qv[0] - p[0];
-    double s = df * df;
-#pragma unroll
-    for (int d = 1; d < DP; ++d) {
-      df = qv[d] - (d < D ? p[d] : 0.0);
-      s = s + df * df;
-    }
+    const double s = nn_exact_sq<DP>([&](int d) { return qv[d] - nn_qcoord(p, d, D); });
     if (s < smin) smin = s;
   }
 #pragma unroll
@@ -870,12 +865,11 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   }
   p->DP = nn_padded_dims(p->D);
   // vertices and samples lie inside the hyperbox (is_free / random_point): bound for the NN sweep's float pre-filter
-  if (!getenv("RKH_NN_F64_ONLY"))
-    for (int d = 0; d < p->D; ++d) {
-      p->coord_bound = std::max(p->coord_bound, std::max(std::fabs(p->lower[d]), std::fabs(p->upper[d])));
-      for (uint32_t i = 0; i < n_problems; ++i)  // the root is a vertex too
-        p->coord_bound = std::max(p->coord_bound, std::fabs(prms[i].start[d]));
-    }
+  for (int d = 0; d < p->D; ++d) {
+    p->coord_bound = std::max(p->coord_bound, std::max(std::fabs(p->lower[d]), std::fabs(p->upper[d])));
+    for (uint32_t i = 0; i < n_problems; ++i)  // the root is a vertex too
+      p->coord_bound = std::max(p->coord_bound, std::fabs(prms[i].start[d]));
+  }
   RKH_HIP(hipSetDevice(scene->ctx->device));
   RKH_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   RKH_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
@@ -979,7 +973,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
     const uint64_t cap = (uint64_t(prms[i].max_vertices) + 1 + 255) / 256 * 256;
     p->max_capacity = std::max(p->max_capacity, cap);
   }
-  p->part_blocks = std::max(nn1_partial_blocks(p->max_capacity, p->b_max, P), nn1_partial_blocks(p->max_capacity, 1, P));
+  p->part_blocks = nn1_partial_blocks(p->D, p->max_capacity, p->b_max, P, p->coord_bound);
   p->n_ub.assign(P, 1);
   std::vector<PlannerState> hs(P);
   std::vector<ProblemDev> hp(P);

@@ -165,7 +165,7 @@ rkh_status rkh_nn_append(rkh_nn* nn, const double* pts, uint64_t n) {
 }
 
 static rkh_status ensure_partials(rkh_nn* nn, uint32_t B) {
-  const uint32_t blocks = nn1_partial_blocks(nn->n, B);
+  const uint32_t blocks = nn1_partial_blocks(nn->st.D, nn->n, B, 1, nn->coord_bound);
   const uint64_t need = uint64_t(blocks) * B;
   if (need > nn->part_cap) {
     hipFree(nn->d_part_dist);

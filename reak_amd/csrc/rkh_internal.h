@@ -82,9 +82,10 @@ rkh_status launch_nn1(hipStream_t s, int D, const NnArgs& single, const NnArgs* 
 // d_yblock_base (table launches, matrix-core kernel): [n_problems + 1] exclusive prefix of ceil(B_p / nn1_mfma_queries())
 // over the problems; the grid's blocks then take the working (row slice, query block) pairs in dispatch order.
 uint32_t nn1_mfma_queries();
-// coord_bound > 0: every |coordinate| of rows and queries is <= coord_bound; sweeps with >= 32 queries then run the
-// single-precision pre-filter variant (identical results).
-uint32_t nn1_partial_blocks(uint64_t n_upper, uint32_t B, uint32_t n_problems = 1);
+// launch_nn1 with coord_bound > 0: every |coordinate| of rows and queries is <= coord_bound; sweeps with >= 32 queries
+// then run the single-precision pre-filter variant (identical results).
+// Partial minima per query (row slices) that launch_nn1 may write for at most B_max queries per problem.
+uint32_t nn1_partial_blocks(int D, uint64_t n_upper, uint32_t B_max, uint32_t n_problems, double coord_bound);
 // k-NN with radius (knn_sweep.hip).  ws: device workspace from knn_workspace_bytes(); *d_overflow is set (non-zero)
 // if a query met more than the candidate capacity (pathological ties).
 struct KnnWorkspace {

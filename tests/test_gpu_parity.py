@@ -108,7 +108,7 @@ def test_nn1_mirror_sweep_is_bit_exact(L, ctx, oracle, D, n, B, bound):
         q[::7] = pts[rng.integers(0, n, size=len(q[::7]))]                 # queries on vertices
         q[1::7] = np.clip(pts[dup[rng.integers(0, len(dup), size=len(q[1::7]))]] + rng.normal(0, 1e-9 * bound, size=(len(q[1::7]), D)),
                           -bound, bound)
-    if n > 400:  # 24 + 15 coincident vertices: beyond the 16 candidate rows a query keeps
+    if n > 400:  # 24 + 15 coincident vertices: beyond the 32 candidate rows a query keeps (kMirCandCap)
         pts[100:124] = pts[100]
         pts[300:400:7] = pts[100]
         q[2 % B] = np.clip(pts[100] + 1e-9 * bound, -bound, bound)

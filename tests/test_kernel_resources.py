@@ -61,7 +61,7 @@ def test_committed_resource_table_matches_the_build(res):
         rows[name] = [int(x) for x in rest]
     checked = 0
     for k, d in res.items():
-        if not any(t in k for t in ("propagate_pair", "propagate_kernel<6", "nn1_mirror_kernel", "edge_points_kernel<6")):
+        if not any(t in k for t in ("propagate_pair", "propagate_kernel<6", "nn1_", "edge_points_kernel<6")):
             continue
         got = [d["vgpr_count"], d["agpr_count"], d["vgpr_spill_count"], d["sgpr_count"], d["private_segment_fixed_size"],
                d["group_segment_fixed_size"]]
