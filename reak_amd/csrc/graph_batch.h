@@ -256,7 +256,7 @@ struct GraphBatch {
   QsDev qs;
   bool dynamic = false;  // edges are RK4 propagations through the steerable dynamic space (D = 2 n_dof states)
   DynDev dyn;
-  int n_dof = 0, D = 0, DP = 0;
+  int D = 0, DP = 0;
   uint32_t P = 0, kmax = 0, emax = 0;
   std::vector<GbProblem> prob;
   static constexpr size_t kKnnWsBytes = 128 * 1024;
@@ -273,7 +273,6 @@ struct GraphBatch {
   unsigned char* h_res_dev = nullptr;            // h_res as the device sees it
   uint32_t *h_flag = nullptr, *h_flag_dev = nullptr, *d_arrivals = nullptr;
   uint32_t flag_seq = 0;
-  bool spin_download = true;
   size_t res_stride = 0, off_kidx = 0, off_kdist = 0, off_nchk = 0, off_accept = 0, off_xout = 0, off_anchk = 0,
          off_aaccept = 0, off_axout = 0;
   bool any_knn = false, any_edges = false, any_append = false, any_stage_a = false;
@@ -295,7 +294,7 @@ struct GraphBatch {
     if (st != RKH_OK) return st;
     dynamic = true;
     std::memset(&qs, 0, sizeof(qs));
-    return init_common(sc, space->n_dof, 2 * space->n_dof, n_problems, capacities, kmax_);
+    return init_common(sc, 2 * space->n_dof, n_problems, capacities, kmax_);
   }
   rkh_status init(rkh_scene* sc, const rkh_qs_space* space, uint32_t n_problems, const uint64_t* capacities,
                   uint32_t kmax_) {
@@ -307,11 +306,10 @@ struct GraphBatch {
       qs.lower[d] = space->lower[d];
       qs.upper[d] = space->upper[d];
     }
-    return init_common(sc, space->n_dof, space->n_dof, n_problems, capacities, kmax_);
+    return init_common(sc, space->n_dof, n_problems, capacities, kmax_);
   }
-  rkh_status init_common(rkh_scene* sc, int n_dof_, int D_, uint32_t n_problems, const uint64_t* capacities, uint32_t kmax_) {
+  rkh_status init_common(rkh_scene* sc, int D_, uint32_t n_problems, const uint64_t* capacities, uint32_t kmax_) {
     scene = sc;
-    n_dof = n_dof_;
     D = D_;
     DP = nn_padded_dims(D);
     P = n_problems;
@@ -348,8 +346,6 @@ struct GraphBatch {
     RKH_HIP(hipMemset(d_res, 0, res_stride * P));
     std::memset(h_res, 0, res_stride * P);
     {  // results written to the host by the device + a flag word the host spins on (gb_download_kernel)
-      const char* env = getenv("RKH_GB_SPIN");
-      spin_download = !env || atoi(env) != 0;
       RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_flag), 64, hipHostMallocDefault));
       *h_flag = 0u;
       RKH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_flag_dev), h_flag, 0));
@@ -684,10 +680,9 @@ struct GraphBatch {
     RKH_HIP(hipMemcpyAsync(d_cmd, h_cmd, cmd_bytes, hipMemcpyHostToDevice, s));
     if (any_append) hipLaunchKernelGGL(gb_prep_kernel, dim3(P), dim3(64), 0, s, d_aux, DP);
     if (any_stage_a) {
-      rkh_status st = dynamic ? launch_propagate(s, n_dof, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs_verdict,
-                                                 dyn, EdgeIO(), kGbStageA, nullptr, 0, duo_lanes(kGbStageA), d_ioa, nullptr, P)
-                              : launch_edge_check(s, n_dof, scene->host.n_env, scene->d_scene, scene->d_pairs,
-                                                  scene->n_pairs_verdict, qs, EdgeIO(), kGbStageA, nullptr, 0, d_ioa, nullptr, P);
+      rkh_status st = dynamic ? launch_propagate(s, *scene, dyn, EdgeIO(), kGbStageA, nullptr, 0, duo_lanes(kGbStageA), d_ioa,
+                                                 nullptr, P)
+                              : launch_edge_check(s, *scene, qs, EdgeIO(), kGbStageA, nullptr, 0, d_ioa, nullptr, P);
       if (st != RKH_OK) return st;
       hipLaunchKernelGGL(gb_select_kernel, dim3(P), dim3(64), 0, s, d_aux, D, DP);
     }
@@ -698,31 +693,25 @@ struct GraphBatch {
     hipLaunchKernelGGL(gb_list_kernel, dim3(P), dim3(64), 0, s, d_aux);
     if (any_edges) {
       // one wave per edge: a step holds at most 2 k candidates per problem, far from filling the two-lanes mappings
-      rkh_status st = dynamic ? launch_propagate(s, n_dof, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs_verdict,
-                                                 dyn, EdgeIO(), emax, nullptr, 0, duo_lanes(emax), d_io, nullptr, P)
-                              : launch_edge_check(s, n_dof, scene->host.n_env, scene->d_scene, scene->d_pairs,
-                                                  scene->n_pairs_verdict, qs, EdgeIO(), emax, nullptr, 0, d_io, nullptr, P);
+      rkh_status st = dynamic ? launch_propagate(s, *scene, dyn, EdgeIO(), emax, nullptr, 0, duo_lanes(emax), d_io, nullptr, P)
+                              : launch_edge_check(s, *scene, qs, EdgeIO(), emax, nullptr, 0, d_io, nullptr, P);
       if (st != RKH_OK) return st;
     }
-    if (spin_download) {
-      const uint32_t tag = ++flag_seq;
-      hipLaunchKernelGGL(gb_download_kernel, dim3(P), dim3(256), 0, s, reinterpret_cast<const uint4*>(d_res),
-                         reinterpret_cast<uint4*>(h_res_dev), uint32_t(res_stride / 16), d_arrivals, h_flag_dev, tag);
-      RKH_HIP(hipGetLastError());
-      for (uint32_t spins = 0; *reinterpret_cast<volatile uint32_t*>(h_flag) != tag; ++spins) {
-        __builtin_ia32_pause();
-        if ((spins & 0xFFFFu) == 0xFFFFu) {  // a failed launch or a device fault must not hang the host
-          const hipError_t q = hipStreamQuery(s);
-          if (q != hipSuccess && q != hipErrorNotReady) RKH_HIP(q);
-          if (q == hipSuccess && *reinterpret_cast<volatile uint32_t*>(h_flag) != tag) {
-            set_error("graph batch: the step's results never arrived");
-            return RKH_ERR_DEVICE;
-          }
+    // the results land in pinned host memory; the acquire load of the step word orders the reads of h_res after it
+    const uint32_t tag = ++flag_seq;
+    hipLaunchKernelGGL(gb_download_kernel, dim3(P), dim3(256), 0, s, reinterpret_cast<const uint4*>(d_res),
+                       reinterpret_cast<uint4*>(h_res_dev), uint32_t(res_stride / 16), d_arrivals, h_flag_dev, tag);
+    RKH_HIP(hipGetLastError());
+    for (uint32_t spins = 0; __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != tag; ++spins) {
+      __builtin_ia32_pause();
+      if ((spins & 0xFFFFu) == 0xFFFFu) {  // a failed launch or a device fault must not hang the host
+        const hipError_t q = hipStreamQuery(s);
+        if (q != hipSuccess && q != hipErrorNotReady) RKH_HIP(q);
+        if (q == hipSuccess && __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != tag) {
+          set_error("graph batch: the step's results never arrived");
+          return RKH_ERR_DEVICE;
         }
       }
-    } else {
-      RKH_HIP(hipMemcpyAsync(h_res, d_res, res_stride * P, hipMemcpyDeviceToHost, s));
-      RKH_HIP(hipStreamSynchronize(s));
     }
     ++steps;
     for (uint32_t i = 0; i < P; ++i)

@@ -610,11 +610,9 @@ uint32_t batch_upper_bound(const PlannerState& st, uint64_t n_ub, float batch_sc
 rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
                         bool compact = false) {
   if (p->quasi_static)
-    return launch_edge_check(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                             p->scene->n_pairs_verdict, p->qs, EdgeIO(), grid_a, nullptr, grid_b, tab_a, tab_b, p->P);
+    return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, nullptr, grid_b, tab_a, tab_b, p->P);
   if (p->lanes_per_edge != 0)
-    return launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lanes_per_edge, tab_a, tab_b,
+    return launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lanes_per_edge, tab_a, tab_b,
                             p->P, p->d_lane_ws);
   // automatic: both mappings are launched; on the device each compares the round's edge count with the threshold and
   // the one that is not chosen exits at once.  Small rounds -> one wave per edge (latency), large -> 32 edges per wave.
@@ -634,22 +632,19 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate gate_duo = gate_wave;
     gate_duo.hi = std::min(p->duo_threshold, p->lane_threshold);
     gate_wave.lo = gate_duo.hi;
-    st = launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                          p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 128, tab_a, tab_b, p->P, nullptr,
+    st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 128, tab_a, tab_b, p->P, nullptr,
                           gate_duo);
     if (st != RKH_OK) return st;
   }
   if (gate_wave.lo < gate_wave.hi)
-    st = launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                          p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 64, tab_a, tab_b, p->P, nullptr,
+    st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 64, tab_a, tab_b, p->P, nullptr,
                           gate_wave);
   if (st != RKH_OK) return st;
   // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
   // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
   // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
   if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1))
-    return launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
+    return launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
                             p->d_lane_ws, gate_lane);
   // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
   // rounds take one whole-edge launch
@@ -661,8 +656,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate whole = gate_lane;
     whole.hi = split_edges;
     if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
-      st = launch_propagate(p->stream, p->n_dof, p->scene->host.n_env, p->scene->d_scene, p->scene->d_pairs,
-                            p->scene->n_pairs_verdict, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
+      st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
                             p->d_lane_ws, whole);
       if (st != RKH_OK) return st;
     }

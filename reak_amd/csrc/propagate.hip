@@ -30,7 +30,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <unordered_set>
 
 #include "device_math.h"
 #include "proximity_device.h"
@@ -1244,114 +1243,55 @@ __global__ __launch_bounds__(64) void state_derivative_kernel(const SceneDev* __
 // Kernel: quasi-static edge walk interp_topo_move_position_toward_pred
 // (ctrl/interpolation/interpolated_topologies.hpp:137-163) over joint positions (D = N), with
 // manip_quasi_static_env::is_free (manip_free_workspace.hpp:154-156) as the predicate.
-// One block of W waves per edge; its (64 / GL) W lane groups test that many consecutive interpolation points at a time
+// Planar scenes (SceneDev::planar) only: 3D scenes walk in edge_points_kernel below, whose verdict may take the pairs
+// in any order, while a planar verdict depends on the finder order (proximity_min_planar).
+// One block of W waves per edge; its 4 * W 16-lane groups test that many consecutive interpolation points at a time
 // (the points of a straight edge are independent), and the first colliding one is found from the groups' verdicts.
 // dist_cur is accumulated by repeated addition exactly like the reference loop (":157 dist_cur += min_interval"),
-// so the number of tested points is the same integer.  Three shapes of the same code (launch_edge_check):
-//   GL = 16, W = 1  -- a launch with thousands of edges (the batch planner's rounds) fills the machine with one wave per
-//                      edge, 4 points at a time, each 16-lane group running the chain kinematics once for its point;
-//   GL = 16, W = 4  -- a few hundred to a few thousand edges (a step of a batch of graph planners): 16 points at a time;
-//   GL = 64, W = 16 -- a few hundred edges (a step of one or a few graph planners): the machine is empty and the step
-//                      waits for the longest edge, so a whole wave scans the shape pairs of ONE point (300 pairs in
-//                      5 passes instead of 19) and 16 waves take 16 points at a time.  A single-problem RRT* spent 85 %
-//                      of its time in this kernel at 230 us per launch with one wave per edge.
-template <int N, int GL, int W>
+// so the number of tested points is the same integer.  W (launch_edge_check) grows as the launch has fewer edges:
+// 1 wave for thousands (the batch planner's rounds fill the machine with one wave per edge), up to 8 for a few hundred
+// (a step of one or a few graph planners, which waits for its longest edge).
+constexpr int kEdgeGL = 16;  // lanes per point
+template <int N, int W>
 struct BlockLdsQsW {
+  static constexpr int G = (64 / kEdgeGL) * W;  // groups of the block = points per pass
   JointLds joints[N];
   double base[10];
-  double sink[64][4];     // dummy store targets of the non-leading lanes (never read; shared by the waves)
-  GroupWsQs<N> g[(64 / GL) * W];
-  double pts[(64 / GL) * W][N];   // the groups' interpolation points (space coordinates)
+  GroupWsQs<N> g[G];
+  double pts[G][N];       // the groups' interpolation points (space coordinates)
   uint32_t masks[W];      // per wave: bit t = group t's point lies on the edge, bit 4 + t = it passed the predicate
-  // block-level verdicts (proximity_verdicts_block): per group bit 0 = its point is to be tested, bit 1 = a shape pair
-  // of it is closer than 0; the (pair, group) combinations that survive the bounding-sphere cull
-  static constexpr int kQueueCap = 128 * W;
-  uint32_t flags[(64 / GL) * W];
-  uint32_t q_cnt;
-  uint32_t queue[kQueueCap];
-  ShapeDev robot[2 * N];  // the scene's robot shapes (SceneDev::robot)
 };
-template <int N, int GL, int W>
+template <int N, int W>
 struct SmemLayoutQsW {
-  static constexpr size_t block_bytes = (sizeof(BlockLdsQsW<N, GL, W>) + 15) / 16 * 16;
+  static constexpr size_t block_bytes = (sizeof(BlockLdsQsW<N, W>) + 15) / 16 * 16;
   // env shapes, then (if it fits: edge_check_kernel's pairs_staged) the proxy pair list
   static size_t bytes(int n_env, int n_pairs_staged) {
     return block_bytes + size_t(n_env) * sizeof(ShapeDev) + size_t(n_pairs_staged) * sizeof(PairDev);
   }
 };
-// The predicate's proximity half for all G points of a pass at once (3D scenes; robot shape poses already in
-// lds.g[t], lds.flags[t] = 1 for the points to test, lds.q_cnt = 0).  is_free only asks whether SOME proxy pair is
-// closer than 0 (manip_free_workspace.hpp:154-156), so the pairs need no order: every thread culls (pair, point)
-// combinations by the bounding spheres -- exactly findMinimumDistance's test against a running minimum of 0
-// (proxy_query_model.cpp:384-389), behind a cheaper test on squares that only ever skips what that one skips -- and
-// pushes the survivors into an LDS queue; then the block's threads take one surviving combination each and run its
-// closed form (bit 1 of the point's flag word = some pair of it is closer than 0).  A lane group walking the pair list
-// by itself (proximity_min) pays one closed form per 16 pairs as soon as any lane of the WAVE has a survivor: 9-19 in a
-// row per point; here a pass costs n_pairs G / threads culls and, nearly always, ONE round of closed forms.  Should the
-// survivors not fit the queue, the pair list is redone in slices that fit whatever survives.
-template <int N, int GL, int W, bool GJK>
-__device__ __forceinline__ void proximity_verdicts_block(const SceneDev* __restrict__ sc, const ShapeDev* __restrict__ env_lds,
-                                                         const PairDev* __restrict__ pairs, int n_pairs,
-                                                         BlockLdsQsW<N, GL, W>& lds, int tid) {
-  constexpr int G = (64 / GL) * W, QCAP = BlockLdsQsW<N, GL, W>::kQueueCap;
-  int p_lo = 0, p_step = n_pairs;
-  while (p_lo < n_pairs) {
-    const int p_hi = (p_lo + p_step < n_pairs) ? p_lo + p_step : n_pairs;
-    for (int idx = p_lo * G + tid; idx < p_hi * G; idx += 64 * W) {
-      const int t = idx % G, p = idx / G;
-      if (lds.flags[t] != 1u) continue;
-      const PairDev pr = pairs[p];
-      const ShapeDev& rs = lds.robot[pr.robot];
-      const ShapeDev& es = env_lds[pr.env];
-      const d3 ca = ld3(lds.g[t].Rpos[pr.robot]), cb = ld3(es.pos);
-      const d3 dc = pr.s1_is_robot ? cb - ca : ca - cb;
-      const double r1 = pr.s1_is_robot ? rs.brad : es.brad, r2 = pr.s1_is_robot ? es.brad : rs.brad;
-      const double sq = ((0.0 + dc.x * dc.x) + dc.y * dc.y) + dc.z * dc.z, rr = r1 + r2;
-      if (sq > (rr * rr) * (1.0 + 1e-9)) continue;   // clearly apart: the exact test below skips it too
-      if (sqrt(sq) - r1 - r2 > 0.0) continue;        // |c2 - c1| - r1 - r2 > 0 (transformToGlobal(0) is the shape's position)
-      const uint32_t slot = atomicAdd(&lds.q_cnt, 1u);
-      if (slot < uint32_t(QCAP)) lds.queue[slot] = uint32_t(t) | (uint32_t(p) << 8);
-    }
-    __syncthreads();
-    const uint32_t cnt = lds.q_cnt;
-    __syncthreads();
-    if (tid == 0) lds.q_cnt = 0u;
-    if (cnt > uint32_t(QCAP)) {  // (block-uniform) does not fit: slices of QCAP / G pairs always do
-      p_step = QCAP / G;
-      __syncthreads();
-      continue;
-    }
-    for (uint32_t i = tid; i < cnt; i += 64 * W) {
-      const uint32_t ent = lds.queue[i];
-      const int t = int(ent & 255u);
-      if (lds.flags[t] != 1u) continue;              // this point already has a colliding pair
-      const PairDev pr = pairs[ent >> 8];
-      const ShapeDev& rs = lds.robot[pr.robot];
-      const ShapeDev& es = env_lds[pr.env];
-      ShapeG A, Bv;
-      A.kind = rs.kind;
-      A.pos = ld3(lds.g[t].Rpos[pr.robot]);
-      A.q = ld4(lds.g[t].Rquat[pr.robot]);
-      A.d0 = rs.dims[0]; A.d1 = rs.dims[1]; A.d2 = rs.dims[2];
-      Bv.kind = es.kind;
-      Bv.pos = ld3(es.pos);
-      Bv.q = ld4(es.quat);
-      Bv.d0 = es.dims[0]; Bv.d1 = es.dims[1]; Bv.d2 = es.dims[2];
-      const double d = pr.s1_is_robot ? pair_distance<GJK>(pr.routine, A, Bv, sc->mesh_verts)
-                                      : pair_distance<GJK>(pr.routine, Bv, A, sc->mesh_verts);
-      if (d < 0.0) atomicOr(&lds.flags[t], 2u);
-    }
-    __syncthreads();
-    p_lo = p_hi;
-  }
-}
+
+// The arguments of both edge walk kernels (edge_check_kernel, edge_points_kernel), which read them through the kernarg
+// segment pointer: a by-value record indexed at run time -- qs.speed[j], the choice between io_a and io_b -- would be
+// copied to scratch.
+struct EdgeWalkArgs {
+  const SceneDev* sc;
+  const PairDev* pairs;
+  int n_pairs;
+  QsDev qs;
+  EdgeIO io_a, io_b;
+  const EdgeIO* tab_a;
+  const EdgeIO* tab_b;
+  uint32_t grid_a;
+  int pairs_staged;
+};
+typedef const __attribute__((address_space(4))) EdgeWalkArgs* EdgeWalkArgP;
 
 // One edge walk of edge_check_kernel (the block's groups test G consecutive points per pass).
-template <int N, int GL, int W, bool GJK>
+template <int N, int W>
 __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs, int n_pairs,
-                                          const QsDev& qs, const EdgeIO& io, BlockLdsQsW<N, GL, W>& lds,
+                                          const QsDev& qs, const EdgeIO& io, BlockLdsQsW<N, W>& lds,
                                           const ShapeDev* __restrict__ env_lds, uint32_t e) {
-  constexpr int GPW = 64 / GL, G = GPW * W;  // groups per wave, groups (= points per pass) of the block
+  constexpr int GL = kEdgeGL, GPW = 64 / GL, G = GPW * W;  // lanes per group, groups per wave, groups of the block
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int g = tid / GL, gl = lane % GL, gb = (lane / GL) * GL;  // group of the block, lane of the group, its base lane in the wave
@@ -1386,20 +1326,10 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
       else oob = (b_d > lo) || (b_d < hi);
     }
     const unsigned long long mo = __ballot(oob);
-    const bool group_oob = (GL == 64 ? mo : ((mo >> gb) & ((1ull << (GL & 63)) - 1ull))) != 0ull;
-    bool is_free;
-    if (!sc->planar) {
-      if (gl == 0) lds.flags[g] = (g == 0 && !group_oob) ? 1u : 0u;
-      if (tid == 0) lds.q_cnt = 0u;
-      __syncthreads();
-      proximity_frames<N, GL>(sc, lds.robot, cp, lds.base, ws, lds.sink[lane], gl);
-      proximity_verdicts_block<N, GL, W, GJK>(sc, env_lds, pairs, n_pairs, lds, tid);
-      is_free = (lds.flags[0] == 1u);
-    } else {
-      __syncthreads();
-      const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
-      is_free = !group_oob && !(dmin < 0.0);
-    }
+    const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
+    __syncthreads();
+    const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
+    const bool is_free = !group_oob && !(dmin < 0.0);
     if (g == 0 && gl < N) io.x_out[uint64_t(e) * N + gl] = b_d;
     if (tid == 0) {
       io.steps_free[e] = 1;
@@ -1442,20 +1372,10 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
         else oob = (pt > lo) || (pt < hi);
       }
       const unsigned long long mo = __ballot(oob);
-      const bool group_oob = (GL == 64 ? mo : ((mo >> gb) & ((1ull << (GL & 63)) - 1ull))) != 0ull;
-      bool is_free;
-      if (!sc->planar) {
-        if (gl == 0) lds.flags[g] = (valid && !group_oob) ? 1u : 0u;
-        if (tid == 0) lds.q_cnt = 0u;
-        __syncthreads();
-        proximity_frames<N, GL>(sc, lds.robot, cp, lds.base, ws, lds.sink[lane], gl);
-        proximity_verdicts_block<N, GL, W, GJK>(sc, env_lds, pairs, n_pairs, lds, tid);
-        is_free = (lds.flags[g] == 1u);
-      } else {  // planar scenes: the verdict depends on the finder order (proximity_min_planar)
-        __syncthreads();
-        const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
-        is_free = valid && !group_oob && !(dmin < 0.0);
-      }
+      const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
+      __syncthreads();
+      const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
+      const bool is_free = valid && !group_oob && !(dmin < 0.0);
       {  // the wave's verdicts -> LDS, then every thread scans the block's groups in edge order
         const unsigned long long mv = __ballot(valid && gl == 0), mf = __ballot(is_free && gl == 0);
         uint32_t m = 0;
@@ -1522,55 +1442,56 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
 }
 
 
-template <int N, int GL, int W>
+template <int N, int W>
 __device__ __forceinline__ const PairDev* edge_check_stage(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
-                                                           int n_pairs, int pairs_staged, BlockLdsQsW<N, GL, W>& lds,
+                                                           int n_pairs, int pairs_staged, BlockLdsQsW<N, W>& lds,
                                                            ShapeDev* env_lds) {
   const int tid = threadIdx.x, lane = tid & 63;
   stage_chain<N>(sc, lds.joints, lds.base, lane);  // (every wave writes the same values)
   stage_env(sc, env_lds, lane);
-  // robot shapes and, when the launch made room for it, the pair list: the cull loop reads both per combination
-  const int n_words = sc->n_robot * int(sizeof(ShapeDev) / sizeof(double));
-  for (int i = tid; i < n_words; i += 64 * W)
-    reinterpret_cast<double*>(lds.robot)[i] = reinterpret_cast<const double*>(sc->robot)[i];
+  // and, when the launch made room for it, the pair list, which every point scans
   if (!pairs_staged) return pairs;
   PairDev* pl = reinterpret_cast<PairDev*>(env_lds + sc->n_env);
   for (int i = tid; i < n_pairs; i += 64 * W) pl[i] = pairs[i];
   return pl;
 }
 
-template <int N, int GL, int W, bool GJK>
-__global__ __launch_bounds__(64 * W) void edge_check_kernel(const SceneDev* __restrict__ sc,
-                                                            const PairDev* __restrict__ pairs, int n_pairs, QsDev qs,
-                                                            EdgeIO io_a, EdgeIO io_b, const EdgeIO* __restrict__ tab_a,
-                                                            const EdgeIO* __restrict__ tab_b, uint32_t grid_a,
-                                                            int pairs_staged) {
+template <int N, int W>
+__global__ __launch_bounds__(64 * W) void edge_check_kernel(EdgeWalkArgs) {
+  EdgeWalkArgP ka = (EdgeWalkArgP)__builtin_amdgcn_kernarg_segment_ptr();
+  const SceneDev* __restrict__ sc = ka->sc;
+  const int n_pairs = ka->n_pairs;
+  const uint32_t grid_a = ka->grid_a;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  BlockLdsQsW<N, GL, W>& lds = *reinterpret_cast<BlockLdsQsW<N, GL, W>*>(smem_raw);
-  ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQsW<N, GL, W>::block_bytes);
+  BlockLdsQsW<N, W>& lds = *reinterpret_cast<BlockLdsQsW<N, W>*>(smem_raw);
+  ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQsW<N, W>::block_bytes);
   const bool group_b = blockIdx.x >= grid_a;
-  const EdgeIO io = tab_a ? (group_b ? tab_b[blockIdx.y] : tab_a[blockIdx.y]) : (group_b ? io_b : io_a);
+  const EdgeIO* iok = (const EdgeIO*)(group_b ? &ka->io_b : &ka->io_a);
+  const EdgeIO io = ka->tab_a ? (group_b ? ka->tab_b[blockIdx.y] : ka->tab_a[blockIdx.y]) : *iok;
   const uint32_t B = io.d_B ? *io.d_B : io.B;
   const uint32_t e = group_b ? blockIdx.x - grid_a : blockIdx.x;
   if (e >= B) return;
-  pairs = edge_check_stage<N, GL, W>(sc, pairs, n_pairs, pairs_staged, lds, env_lds);
-  edge_walk<N, GL, W, GJK>(sc, pairs, n_pairs, qs, io, lds, env_lds, e);
+  const PairDev* pairs = edge_check_stage<N, W>(sc, ka->pairs, n_pairs, ka->pairs_staged, lds, env_lds);
+  edge_walk<N, W>(sc, pairs, n_pairs, *(const QsDev*)&ka->qs, io, lds, env_lds, e);
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same edge walk for 3D scenes with ONE LANE PER POINT in the chain kinematics (edge_points_kernel).  In
-// edge_check_kernel a point belongs to a 16-lane group whose lanes all run the serial base -> tip chain of that one
-// point: ~1.2 k fp64 instructions per wave for 4 points.  Here a block of 4 waves takes G = 64 (32 for chains of more
-// than 7 joints) consecutive points per pass and every phase is spread over what it is parallel in:
+// The same edge walk for 3D scenes, with ONE LANE PER POINT in the chain kinematics (edge_points_kernel).  A 16-lane
+// group per point, as in edge_check_kernel, would run the serial base -> tip chain once per point: ~1.2 k fp64
+// instructions per wave for 4 points.  Here a block of 4 waves takes G = 64 (32 for chains of more than 7 joints)
+// consecutive points per pass and every phase is spread over what it is parallel in:
 //   half-angle sin / cos   one (point, joint) per thread
 //   joint end frames       one POINT per lane of the first wave: the serial chain, once per 64 points
 //   robot shape poses      one (point, shape) per thread
-//   bounding-sphere cull   one (point, pair) per thread -> survivors into the LDS queue (as proximity_verdicts_block)
+//   bounding-sphere cull   one (point, pair) per thread -> survivors into the LDS queue
 //   closed forms           one surviving (point, pair) per thread
-// and the first colliding point comes out of two ballots.  Per-point data sit in LDS component-major ([..][G]: lanes of
-// a wave = consecutive points = consecutive addresses).  Same arithmetic per point as edge_check_kernel (the same
-// device functions in the same order), so n_checked, results and verdicts are the same bits; planar scenes, whose
-// verdict depends on the finder order, stay on edge_check_kernel.
+// and the first colliding point comes out of two ballots.  is_free only asks whether SOME proxy pair is closer than 0
+// (manip_free_workspace.hpp:154-156), so the pairs need no order: the cull is exactly findMinimumDistance's test
+// against a running minimum of 0 (proxy_query_model.cpp:384-389), behind a cheaper test on squares that only ever skips
+// what that one skips, and a pass nearly always needs ONE round of closed forms.  Should the survivors not fit the
+// queue, the pair list is redone in slices that fit whatever survives.  Per-point data sit in LDS component-major
+// ([..][G]: lanes of a wave = consecutive points = consecutive addresses).  Planar scenes, whose verdict depends on the
+// finder order, walk in edge_check_kernel.
 struct EdgePointsCfg {
   static constexpr int T = 256;                // threads per block
   static constexpr int QCAP = 1024;            // surviving (point, pair) combinations per round of closed forms
@@ -1595,28 +1516,14 @@ struct __attribute__((aligned(16))) EdgePointsLds {
 template <int N, int G>
 struct EdgePointsSmem {
   static constexpr size_t block_bytes = (sizeof(EdgePointsLds<N, G>) + 15) / 16 * 16;
-  static size_t bytes(int n_env, int n_pairs_staged) {
+  static constexpr size_t bytes(int n_env, int n_pairs_staged) {
     return block_bytes + size_t(n_env) * sizeof(ShapeDev) + size_t(n_pairs_staged) * sizeof(PairDev);
   }
 };
 
-struct EdgePointsArgs {
-  const SceneDev* sc;
-  const PairDev* pairs;
-  int n_pairs;
-  QsDev qs;
-  EdgeIO io_a, io_b;
-  const EdgeIO* tab_a;
-  const EdgeIO* tab_b;
-  uint32_t grid_a;
-  int pairs_staged;
-};
-typedef const __attribute__((address_space(4))) EdgePointsArgs* EdgePointsArgP;
 template <int N, bool GJK, int G>
-__global__ __launch_bounds__(256) void edge_points_kernel(EdgePointsArgs) {
-  // arguments are read through the kernarg segment pointer (a by-value record indexed at run time -- qs.speed[j], the
-  // choice between io_a and io_b -- would be copied to scratch)
-  EdgePointsArgP ka = (EdgePointsArgP)__builtin_amdgcn_kernarg_segment_ptr();
+__global__ __launch_bounds__(256) void edge_points_kernel(EdgeWalkArgs) {
+  EdgeWalkArgP ka = (EdgeWalkArgP)__builtin_amdgcn_kernarg_segment_ptr();
   const SceneDev* __restrict__ sc = ka->sc;
   const PairDev* __restrict__ pairs = ka->pairs;
   const int n_pairs = ka->n_pairs, pairs_staged = ka->pairs_staged;
@@ -1721,7 +1628,7 @@ __global__ __launch_bounds__(256) void edge_points_kernel(EdgePointsArgs) {
       lds.R[r][3][t] = gq.w; lds.R[r][4][t] = gq.x; lds.R[r][5][t] = gq.y; lds.R[r][6][t] = gq.z;
     }
     __syncthreads();
-    // bounding-sphere cull of every (pair, point), survivors -> queue -> closed forms (see proximity_verdicts_block)
+    // bounding-sphere cull of every (pair, point), survivors -> queue -> closed forms (see above)
     int p_lo = 0, p_step = n_pairs;
     while (p_lo < n_pairs) {
       const int p_hi = (p_lo + p_step < n_pairs) ? p_lo + p_step : n_pairs;
@@ -2026,29 +1933,14 @@ __global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __rest
     case 7: { constexpr int N = 7; CALL; } break; \
     case 12: { constexpr int N = 12; CALL; } break; \
     default:                         \
-      set_error("propagate: chains with this number of joints are not instantiated (1,2,3,4,6,7,12)"); \
-      return RKH_ERR_UNSUPPORTED;    \
-  }
-
-#define RKH_DISPATCH_N_QS(N_, CALL)  \
-  switch (N_) {                      \
-    case 1: { constexpr int N = 1; CALL; } break; \
-    case 2: { constexpr int N = 2; CALL; } break; \
-    case 3: { constexpr int N = 3; CALL; } break; \
-    case 4: { constexpr int N = 4; CALL; } break; \
-    case 6: { constexpr int N = 6; CALL; } break; \
-    case 7: { constexpr int N = 7; CALL; } break; \
-    case 12: { constexpr int N = 12; CALL; } break; \
-    default:                         \
-      set_error("quasi-static kernels: chains with this number of joints are not instantiated (1,2,3,4,6,7,12)"); \
+      set_error("chains with this number of joints are not instantiated (1,2,3,4,6,7,12)"); \
       return RKH_ERR_UNSUPPORTED;    \
   }
 
 template <int N, int GL, bool GJK, bool DUO = false>
-static void launch_propagate_t(hipStream_t s, int n_env, const SceneDev* d_scene, const PairDev* d_pairs, int n_pairs,
-                               const DynDev& dyn, const EdgeIO& io, uint32_t edges_a, const EdgeIO& io_b,
-                               uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
-                               KernelGate gate) {
+static void launch_propagate_t(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
+                               const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                               uint32_t n_problems, KernelGate gate) {
   constexpr uint32_t G = 64 / GL;
   const uint32_t ga = (edges_a + G - 1) / G, gbk = (edges_b + G - 1) / G;
   dim3 grid(ga + gbk, n_problems);
@@ -2059,9 +1951,9 @@ static void launch_propagate_t(hipStream_t s, int n_env, const SceneDev* d_scene
     grid = dim3(uint32_t(std::min<uint64_t>(all, gate.hi)), 1);
   }
   WaveArgs args;
-  args.sc = d_scene;
-  args.pairs = d_pairs;
-  args.n_pairs = n_pairs;
+  args.sc = scene.d_scene;
+  args.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  args.n_pairs = scene.n_pairs_verdict;
   args.dyn = dyn;
   args.io_a = io;
   args.io_b = io_b;
@@ -2069,94 +1961,89 @@ static void launch_propagate_t(hipStream_t s, int n_env, const SceneDev* d_scene
   args.tab_b = tab_b;
   args.grid_a = ga;
   args.gate = gate;
-  hipLaunchKernelGGL((propagate_kernel<N, GL, GJK, DUO>), grid, dim3(DUO ? 128 : 64), (SmemLayout<N, GL>::bytes(n_env)), s, args);
+  hipLaunchKernelGGL((propagate_kernel<N, GL, GJK, DUO>), grid, dim3(DUO ? 128 : 64), (SmemLayout<N, GL>::bytes(scene.host.n_env)),
+                     s, args);
 }
 
 // Steer `grid_edges` (+ `grid_b` of a second group) edges per problem.  Either the two EdgeIO are given by value
 // (n_problems = 1) or as device tables of n_problems entries each.
-rkh_status launch_propagate(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                            int n_pairs, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges, const EdgeIO* io_b,
-                            uint32_t grid_b, int lanes_per_edge, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                            uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges,
+                            const EdgeIO* io_b, uint32_t grid_b, int lanes_per_edge, const EdgeIO* tab_a,
+                            const EdgeIO* tab_b, uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
   const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
-  if (is_planar_scene(d_scene))  // planar chains: one lane per edge, whatever mapping was asked for (propagate_planar.hip)
-    return launch_propagate_planar(s, n_dof, d_scene, d_pairs, n_pairs, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b,
-                                   n_problems, gate);
+  const int n_dof = scene.host.n_dof;
+  if (scene.host.planar)  // planar chains: one lane per edge, whatever mapping was asked for (propagate_planar.hip)
+    return launch_propagate_planar(s, n_dof, scene.d_scene, scene.d_pairs, scene.n_pairs_verdict, dyn, io, grid_edges, io_b,
+                                   grid_b, tab_a, tab_b, n_problems, gate);
   if (lanes_per_edge == 2)  // two lanes per edge, two waves per SIMD (propagate_pair.hip)
-    return launch_propagate_pairs(s, n_dof, d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems, d_lane_ws,
-                                  gate);
+    return launch_propagate_pairs(s, n_dof, scene.d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems,
+                                  d_lane_ws, gate);
   const EdgeIO second = io_b ? *io_b : EdgeIO();
-  const PairDev* pp = static_cast<const PairDev*>(d_pairs);
-  if (lanes_per_edge == 128 && !is_mesh_scene(d_scene)) {  // two waves per edge (scenes without vertex-set shapes)
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false, true>(s, n_env, d_scene, pp, n_pairs, dyn, io, grid_edges, second, eb,
-                                                                  tab_a, tab_b, n_problems, gate)));
+  const bool gjk = scene.host.has_meshes;
+  if (lanes_per_edge == 128 && !gjk) {  // two waves per edge (scenes without vertex-set shapes)
+    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b,
+                                                                  n_problems, gate)));
   } else if (lanes_per_edge == 16) {
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 16, true>(s, n_env, d_scene, pp, n_pairs, dyn, io, grid_edges, second, eb, tab_a,
-                                                           tab_b, n_problems, gate)));
-  } else if (is_mesh_scene(d_scene)) {
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, true>(s, n_env, d_scene, pp, n_pairs, dyn, io, grid_edges, second, eb, tab_a,
-                                                           tab_b, n_problems, gate)));
+    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 16, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
+                                                           gate)));
+  } else if (gjk) {
+    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
+                                                           gate)));
   } else {  // no vertex-set shapes: the instantiation without the support-map query (no private segment)
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false>(s, n_env, d_scene, pp, n_pairs, dyn, io, grid_edges, second, eb, tab_a,
-                                                            tab_b, n_problems, gate)));
+    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
+                                                            gate)));
   }
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_state_derivative(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x,
-                                   const double* d_u, uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err) {
+rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   double* d_pd, double* d_M, double* d_f, int* d_err) {
   if (B == 0) return RKH_OK;
-  if (is_planar_scene(d_scene)) return launch_state_derivative_planar(s, n_dof, d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
-  RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, d_scene, d_x, d_u, B,
+  const int n_dof = scene.host.n_dof;
+  if (scene.host.planar)
+    return launch_state_derivative_planar(s, n_dof, scene.d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+  RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
                                            d_pd, d_M, d_f, d_err));
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-static std::unordered_set<const void*>& mesh_scenes() {
-  static std::unordered_set<const void*> s;
-  return s;
-}
-void register_mesh_scene(const SceneDev* d_scene) { mesh_scenes().insert(d_scene); }
-void forget_mesh_scene(const SceneDev* d_scene) { mesh_scenes().erase(d_scene); }
-bool is_mesh_scene(const SceneDev* d_scene) { return mesh_scenes().count(d_scene) != 0; }
-
-// The shape of an edge_check_kernel launch, by the number of edges and by what fits 64 KB of LDS -- 0: GL 16 x 1 wave,
-// 1: GL 16 x 4 waves, 2: GL 16 x 2 waves, 3: GL 16 x 8 waves -- and whether the pair list rides in LDS too.
+// The number of waves W of a planar edge_check_kernel launch, by the number of edges (1 for launches of 4096 edges and
+// more, 4 below that, 8 below 512) and by what fits 64 KB of LDS (2 where 4 does not fit, 1 where neither does), and
+// whether the pair list rides in LDS too.
 template <int N>
-static void edge_check_shape(int n_env, int n_pairs, uint64_t n_edges, int* shape, int* staged) {
+static int edge_check_shape(int n_env, int n_pairs, uint64_t n_edges, int* staged) {
   auto fit = [&](size_t with_pairs, size_t without) { return with_pairs <= 65536 ? 2 : (without <= 65536 ? 1 : 0); };
-  const int f1 = fit(SmemLayoutQsW<N, 16, 1>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 16, 1>::bytes(n_env, 0));
-  const int f2 = fit(SmemLayoutQsW<N, 16, 2>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 16, 2>::bytes(n_env, 0));
-  const int f4 = fit(SmemLayoutQsW<N, 16, 4>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 16, 4>::bytes(n_env, 0));
-  const int f8 = fit(SmemLayoutQsW<N, 16, 8>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 16, 8>::bytes(n_env, 0));
-  *shape = 0;
+  const int f1 = fit(SmemLayoutQsW<N, 1>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 1>::bytes(n_env, 0));
+  const int f2 = fit(SmemLayoutQsW<N, 2>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 2>::bytes(n_env, 0));
+  const int f4 = fit(SmemLayoutQsW<N, 4>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 4>::bytes(n_env, 0));
+  const int f8 = fit(SmemLayoutQsW<N, 8>::bytes(n_env, n_pairs), SmemLayoutQsW<N, 8>::bytes(n_env, 0));
+  int w = 1;
   *staged = f1 == 2;
   if (n_edges < 4096) {
-    if (f4) *shape = 1, *staged = f4 == 2;
-    else if (f2) *shape = 2, *staged = f2 == 2;
+    if (f4) w = 4, *staged = f4 == 2;
+    else if (f2) w = 2, *staged = f2 == 2;
   }
-  if (n_edges < 512 && f8) *shape = 3, *staged = f8 == 2;
+  if (n_edges < 512 && f8) w = 8, *staged = f8 == 2;
+  return w;
+}
+
+template <int N, int W>
+static void launch_edge_check_t(hipStream_t s, dim3 grid, int n_env, const EdgeWalkArgs& ka) {
+  hipLaunchKernelGGL((edge_check_kernel<N, W>), grid, dim3(64 * W),
+                     (SmemLayoutQsW<N, W>::bytes(n_env, ka.pairs_staged ? ka.n_pairs : 0)), s, ka);
 }
 
 template <int N, bool GJK, int G>
-static rkh_status launch_edge_points_t(hipStream_t s, dim3 grid, size_t smem, const SceneDev* d_scene, const PairDev* pp,
-                                       int n_pairs, const QsDev& qs, const EdgeIO& io, const EdgeIO& second,
-                                       const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t grid_a, int staged) {
+static rkh_status launch_edge_points_t(hipStream_t s, dim3 grid, int n_env, EdgeWalkArgs ka) {
+  // a scene holds fewer than kMaxEnvShapes environment shapes: they always fit next to the block's data
+  static_assert(EdgePointsSmem<N, G>::bytes(kMaxEnvShapes, 0) <= 160 * 1024, "edge_points_kernel: LDS over 160 KB");
+  const size_t with_pairs = EdgePointsSmem<N, G>::bytes(n_env, ka.n_pairs);
+  ka.pairs_staged = with_pairs <= 160 * 1024;
+  const size_t smem = ka.pairs_staged ? with_pairs : EdgePointsSmem<N, G>::bytes(n_env, 0);
   auto kern = edge_points_kernel<N, GJK, G>;
-  EdgePointsArgs ka;
-  ka.sc = d_scene;
-  ka.pairs = pp;
-  ka.n_pairs = n_pairs;
-  ka.qs = qs;
-  ka.io_a = io;
-  ka.io_b = second;
-  ka.tab_a = tab_a;
-  ka.tab_b = tab_b;
-  ka.grid_a = grid_a;
-  ka.pairs_staged = staged;
   static bool big_lds = false;  // (per instantiation) more than the default 64 KB of dynamic LDS: ask once
   if (smem > 65536 && !big_lds) {
     RKH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2166,92 +2053,79 @@ static rkh_status launch_edge_points_t(hipStream_t s, dim3 grid, size_t smem, co
   return RKH_OK;
 }
 
-rkh_status launch_edge_check(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                             int n_pairs, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges, const EdgeIO* io_b,
-                             uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems) {
+// The form of a quasi-static edge walk launch.  3D scenes: edge_points_kernel, 64 points per pass for launches of fewer
+// than 2048 edges and chains of at most 7 joints, 32 otherwise, the support-map query only for scenes with vertex-set
+// shapes.  Planar scenes: edge_check_kernel with edge_check_shape's W.  Both stage the pair list in LDS if it fits.
+template <int N>
+static rkh_status launch_edge_walk(hipStream_t s, dim3 grid, const rkh_scene& scene, const EdgeWalkArgs& ka) {
+  const int n_env = scene.host.n_env;
+  const uint64_t n_edges = uint64_t(grid.x) * grid.y;
+  if (scene.host.planar) {
+    EdgeWalkArgs pa = ka;
+    switch (edge_check_shape<N>(n_env, ka.n_pairs, n_edges, &pa.pairs_staged)) {
+      case 8: launch_edge_check_t<N, 8>(s, grid, n_env, pa); break;
+      case 4: launch_edge_check_t<N, 4>(s, grid, n_env, pa); break;
+      case 2: launch_edge_check_t<N, 2>(s, grid, n_env, pa); break;
+      default: launch_edge_check_t<N, 1>(s, grid, n_env, pa); break;
+    }
+    return RKH_OK;
+  }
+  constexpr int GW = N <= 7 ? 64 : 32;
+  const bool wide = n_edges < 2048;
+  if (scene.host.has_meshes)
+    return wide ? launch_edge_points_t<N, true, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, true, 32>(s, grid, n_env, ka);
+  return wide ? launch_edge_points_t<N, false, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, false, 32>(s, grid, n_env, ka);
+}
+
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                             uint32_t n_problems) {
   const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
-  const EdgeIO second = io_b ? *io_b : EdgeIO();
-  const PairDev* pp = static_cast<const PairDev*>(d_pairs);
-  const bool gjk = is_mesh_scene(d_scene);  // scenes without vertex-set shapes run the instantiations without GJK (no scratch)
-  static const bool by_points = [] { const char* e = getenv("RKH_EDGE_POINTS"); return !e || atoi(e) != 0; }();
-  if (by_points && !is_planar_scene(d_scene)) {  // 3D scenes: one lane per point in the chain kinematics
-    const bool narrow = n_dof > 7 || uint64_t(grid_edges + eb) * n_problems >= 2048;  // 32 points per pass
-    size_t with_pairs = 0, without = 0;
-    if (narrow) {
-      RKH_DISPATCH_N_QS(n_dof, (with_pairs = EdgePointsSmem<N, 32>::bytes(n_env, n_pairs), without = EdgePointsSmem<N, 32>::bytes(n_env, 0)));
-    } else {
-      RKH_DISPATCH_N_QS(n_dof, (with_pairs = EdgePointsSmem<N, 64>::bytes(n_env, n_pairs), without = EdgePointsSmem<N, 64>::bytes(n_env, 0)));
-    }
-    const size_t lds_max = 160 * 1024;
-    if (without <= lds_max) {
-      const int staged = with_pairs <= lds_max;
-      const size_t smem = staged ? with_pairs : without;
-      rkh_status st = RKH_OK;
-      const dim3 grid(grid_edges + eb, n_problems);
-#define RKH_POINTS_ARGS s, grid, smem, d_scene, pp, n_pairs, qs, io, second, tab_a, tab_b, grid_edges, staged
-      if (narrow) {
-        if (gjk) {
-          RKH_DISPATCH_N_QS(n_dof, (st = launch_edge_points_t<N, true, 32>(RKH_POINTS_ARGS)));
-        } else {
-          RKH_DISPATCH_N_QS(n_dof, (st = launch_edge_points_t<N, false, 32>(RKH_POINTS_ARGS)));
-        }
-      } else {
-        if (gjk) {
-          RKH_DISPATCH_N_QS(n_dof, (st = launch_edge_points_t<N, true, (N <= 7 ? 64 : 32)>(RKH_POINTS_ARGS)));
-        } else {
-          RKH_DISPATCH_N_QS(n_dof, (st = launch_edge_points_t<N, false, (N <= 7 ? 64 : 32)>(RKH_POINTS_ARGS)));
-        }
-      }
-#undef RKH_POINTS_ARGS
-      if (st != RKH_OK) return st;
-      RKH_HIP(hipGetLastError());
-      return RKH_OK;
-    }
-  }
-  // the shape of the launch (see edge_check_kernel): by the number of edges, and by what fits 64 KB of LDS
-  const uint64_t n_edges = uint64_t(grid_edges + eb) * n_problems;
-  int shape = 0, staged = 0;
-  RKH_DISPATCH_N_QS(n_dof, (edge_check_shape<N>(n_env, n_pairs, n_edges, &shape, &staged)));
-#define RKH_EDGE_LAUNCH(GL_, W_, GJK_)                                                                                          \
-  RKH_DISPATCH_N_QS(n_dof, hipLaunchKernelGGL((edge_check_kernel<N, GL_, W_, GJK_>), dim3(grid_edges + eb, n_problems),   \
-                                           dim3(64 * W_), (SmemLayoutQsW<N, GL_, W_>::bytes(n_env, staged ? n_pairs : 0)), s, \
-                                           d_scene, pp, n_pairs, qs, io, second, tab_a, tab_b, grid_edges, staged))
-  // (planar scenes, and 3D ones with RKH_EDGE_POINTS=0: one instantiation per shape, support-map query included)
-  switch (shape) {
-    case 1: RKH_EDGE_LAUNCH(16, 4, true); break;
-    case 2: RKH_EDGE_LAUNCH(16, 2, true); break;
-    case 3: RKH_EDGE_LAUNCH(16, 8, true); break;
-    default: RKH_EDGE_LAUNCH(16, 1, true); break;
-  }
-#undef RKH_EDGE_LAUNCH
+  EdgeWalkArgs ka;
+  ka.sc = scene.d_scene;
+  ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  ka.n_pairs = scene.n_pairs_verdict;
+  ka.qs = qs;
+  ka.io_a = io;
+  ka.io_b = io_b ? *io_b : EdgeIO();
+  ka.tab_a = tab_a;
+  ka.tab_b = tab_b;
+  ka.grid_a = grid_edges;
+  ka.pairs_staged = 0;
+  const dim3 grid(grid_edges + eb, n_problems);
+  rkh_status st = RKH_OK;
+  RKH_DISPATCH_N(scene.host.n_dof, (st = launch_edge_walk<N>(s, grid, scene, ka)));
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_feval_cycles_duo(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const double* d_x,
-                                   const double* d_u, uint32_t B, int iters, unsigned long long* d_out, double* d_sink) {
-  RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128), (SmemLayout<N, 64>::bytes(n_env)),
-                                           s, d_scene, d_x, d_u, iters, d_out, d_sink));
+rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   int iters, unsigned long long* d_out, double* d_sink) {
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128),
+                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene, d_x, d_u,
+                                                      iters, d_out, d_sink));
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_feval_cycles(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                               int n_pairs, const double* d_x, const double* d_u, uint32_t B, int iters,
-                               unsigned long long* d_out, double* d_sink) {
-  RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64), (SmemLayout<N, 64>::bytes(n_env)),
-                                           s, d_scene, static_cast<const PairDev*>(d_pairs), n_pairs, d_x, d_u, iters, d_out,
-                                           d_sink));
+rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                               int iters, unsigned long long* d_out, double* d_sink) {
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64),
+                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
+                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, d_u,
+                                                      iters, d_out, d_sink));
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_min_distance(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs, int n_pairs,
-                               const double* d_x, uint32_t B, double* d_dist) {
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
   if (B == 0) return RKH_OK;
-  RKH_DISPATCH_N_QS(n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(n_env)), s,
-                                           d_scene, static_cast<const PairDev*>(d_pairs), n_pairs, d_x, B, d_dist));
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64),
+                                                      (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
+                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B,
+                                                      d_dist));
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }

@@ -18,7 +18,6 @@
 
 #include <cfloat>
 #include <cmath>
-#include <unordered_set>
 
 #include "proximity_planar_device.h"
 #include "rkh_internal.h"
@@ -413,14 +412,6 @@ __global__ __launch_bounds__(64) void planar_state_derivative_kernel(const Scene
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static std::unordered_set<const void*>& planar_scenes() {
-  static std::unordered_set<const void*> s;
-  return s;
-}
-void register_planar_scene(const SceneDev* d_scene) { planar_scenes().insert(d_scene); }
-void forget_planar_scene(const SceneDev* d_scene) { planar_scenes().erase(d_scene); }
-bool is_planar_scene(const SceneDev* d_scene) { return planar_scenes().count(d_scene) != 0; }
-
 #define RKH_DISPATCH_N_PLANAR(N_, CALL)                                                                  \
   switch (N_) {                                                                                          \
     case 1: { constexpr int N = 1; CALL; } break;                                                        \

@@ -302,8 +302,9 @@ struct KernelGate {
   // ended it included) -- the executed work of a launch, as opposed to n_steps per launched edge
   unsigned long long* steps_exec = nullptr;
 };
-rkh_status launch_propagate(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                            int n_pairs, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges,
+// The launchers below that take the scene read its kind (planar, vertex-set shapes) from scene.host; the verdict
+// kernels (propagate, edge walk) scan its first n_pairs_verdict pairs, min_distance and the f-eval probes all n_pairs.
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges,
                             const EdgeIO* io_b = nullptr, uint32_t grid_b = 0, int lanes_per_edge = 64,
                             const EdgeIO* tab_a = nullptr, const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1,
                             double* d_lane_ws = nullptr, KernelGate gate = KernelGate());
@@ -312,29 +313,19 @@ inline bool scene_fits_lane_kernel(const SceneDev& S) {
   if (S.has_meshes) return false;  // GJK pairs run in the wave-per-edge / quasi-static kernels
   return S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
 }
-rkh_status launch_state_derivative(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x,
-                                   const double* d_u, uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
-rkh_status launch_min_distance(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                               int n_pairs, const double* d_x, uint32_t B, double* d_dist);
-rkh_status launch_edge_check(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                             int n_pairs, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   double* d_pd, double* d_M, double* d_f, int* d_err);
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              const EdgeIO* io_b = nullptr, uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr,
                              const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1);
-rkh_status launch_feval_cycles_duo(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const double* d_x,
-                                   const double* d_u, uint32_t B, int iters, unsigned long long* d_out, double* d_sink);
-rkh_status launch_feval_cycles(hipStream_t s, int n_dof, int n_env, const SceneDev* d_scene, const void* d_pairs,
-                               int n_pairs, const double* d_x, const double* d_u, uint32_t B, int iters,
-                               unsigned long long* d_out, double* d_sink);
+rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   int iters, unsigned long long* d_out, double* d_sink);
+rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                               int iters, unsigned long long* d_out, double* d_sink);
 // two-lanes-per-edge kernel (propagate_pair.hip): 32 edges per wave, two waves per SIMD; scenes: scene_fits_lane_kernel
 size_t propagate_pairs_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edges_b, uint32_t n_problems);
-// planar chains (propagate_planar.hip): one lane per edge; scenes register themselves at upload
-void register_planar_scene(const SceneDev* d_scene);
-void forget_planar_scene(const SceneDev* d_scene);
-bool is_planar_scene(const SceneDev* d_scene);
-// scenes with vertex-set shapes (PR_GJK pairs); the others may run kernels compiled without the support-map query
-void register_mesh_scene(const SceneDev* d_scene);
-void forget_mesh_scene(const SceneDev* d_scene);
-bool is_mesh_scene(const SceneDev* d_scene);
+// planar chains (propagate_planar.hip): one lane per edge
 rkh_status launch_propagate_planar(hipStream_t s, int n_dof, const SceneDev* d_scene, const void* d_pairs, int n_pairs,
                                    const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges, const EdgeIO* io_b,
                                    uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,

@@ -173,8 +173,6 @@ static rkh_status upload_scene(rkh_ctx* ctx, rkh_scene* sc, const std::vector<Pa
   if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs, pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
   RKH_HIP(hipMalloc(&sc->d_err, sizeof(int)));
   RKH_HIP(hipMemset(sc->d_err, 0, sizeof(int)));
-  if (S.planar) register_planar_scene(sc->d_scene);
-  if (S.has_meshes) register_mesh_scene(sc->d_scene);
   *out = sc;
   return RKH_OK;
 }
@@ -612,8 +610,6 @@ rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_sha
 
 rkh_status rkh_scene_destroy(rkh_scene* scene) {
   if (!scene) return RKH_OK;
-  forget_planar_scene(scene->d_scene);  // (a later allocation may get the same address)
-  forget_mesh_scene(scene->d_scene);
   hipFree(scene->d_scene);
   hipFree(scene->d_pairs);
   if (scene->d_mesh_verts) hipFree(scene->d_mesh_verts);
@@ -669,8 +665,8 @@ rkh_status rkh_state_derivative(rkh_scene* scene, const double* x, const double*
   RKH_HIP(hipMalloc(&df.p, size_t(B) * n * 8));
   RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
   RKH_HIP(hipMemcpyAsync(du.p, u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  rkh_status st = launch_state_derivative(s, n, scene->d_scene, dx.as<double>(), du.as<double>(), B, dpd.as<double>(),
-                                          dM.as<double>(), df.as<double>(), scene->d_err);
+  rkh_status st = launch_state_derivative(s, *scene, dx.as<double>(), du.as<double>(), B, dpd.as<double>(), dM.as<double>(),
+                                          df.as<double>(), scene->d_err);
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(pd, dpd.p, size_t(B) * 2 * n * 8, hipMemcpyDeviceToHost, s));
   if (M) RKH_HIP(hipMemcpyAsync(M, dM.p, size_t(B) * n * n * 8, hipMemcpyDeviceToHost, s));
@@ -688,8 +684,7 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
   RKH_HIP(hipMalloc(&dx.p, size_t(B) * 2 * n * 8));
   RKH_HIP(hipMalloc(&dd.p, size_t(B) * 8));
   RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  rkh_status st = launch_min_distance(s, n, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs,
-                                      dx.as<double>(), B, dd.as<double>());
+  rkh_status st = launch_min_distance(s, *scene, dx.as<double>(), B, dd.as<double>());
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(dist, dd.p, size_t(B) * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
@@ -742,8 +737,7 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   if (lanes == 16 && 2 * n > 16) lanes = 64;
   DevBuf dws;
   if (lanes == 2) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
-  st = launch_propagate(s, n, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs_verdict, dyn, io, B, nullptr, 0,
-                        lanes, nullptr, nullptr, 1, dws.as<double>());
+  st = launch_propagate(s, *scene, dyn, io, B, nullptr, 0, lanes, nullptr, nullptr, 1, dws.as<double>());
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(x_out, dxo.p, size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(steps_free, dsf.p, size_t(B) * 4, hipMemcpyDeviceToHost, s));
@@ -773,12 +767,12 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
                             dout.as<unsigned long long>(), dsink.as<double>());
   } else if (ev && atoi(ev) == 128) {  // two waves per edge: B / 2 states, rows 2 b / 2 b + 1 = the two waves' counters
     RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
-    st = (B >= 2) ? launch_feval_cycles_duo(s, n, scene->host.n_env, scene->d_scene, dx.as<double>(), du.as<double>(), B, iters,
-                                            dout.as<unsigned long long>(), dsink.as<double>())
+    st = (B >= 2) ? launch_feval_cycles_duo(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
+                                            dsink.as<double>())
                   : RKH_ERR_BAD_ARG;
   } else {
-    st = launch_feval_cycles(s, n, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs, dx.as<double>(),
-                             du.as<double>(), B, iters, dout.as<unsigned long long>(), dsink.as<double>());
+    st = launch_feval_cycles(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
+                             dsink.as<double>());
   }
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(cycles, dout.p, size_t(B) * 8 * 8, hipMemcpyDeviceToHost, s));
@@ -843,7 +837,7 @@ rkh_status rkh_edge_check(rkh_scene* scene, const double* lower, const double* u
   io.x_out = dxo.as<double>();
   io.steps_free = dnc.as<uint32_t>();
   io.err_flag = scene->d_err;
-  rkh_status st = launch_edge_check(s, n, scene->host.n_env, scene->d_scene, scene->d_pairs, scene->n_pairs_verdict, qs, io, B);
+  rkh_status st = launch_edge_check(s, *scene, qs, io, B);
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(out, dxo.p, size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(n_checked, dnc.p, size_t(B) * 4, hipMemcpyDeviceToHost, s));

@@ -38,7 +38,8 @@ def test_throughput_steer_kernels_hold_two_waves_per_simd_without_scratch(res):
 def test_latency_kernels_of_scenes_without_vertex_sets_do_not_spill(res):
     """The one-wave-per-edge steer kernel (small rounds, single problems) and the quasi-static edge walk (graph planners)
     as instantiated for scenes without vertex-set shapes: no spilled registers, (next to) no private segment -- the
-    support-map query's run-time-indexed simplex arrays are what needs one, and only the `true` instantiations carry it."""
+    support-map query's run-time-indexed simplex arrays are what needs one, and only the `true` instantiations carry it.
+    The planar edge walk has no support-map query: none of its forms spills or has a private segment."""
     for k in ("rkh::propagate_kernel<6, 64, false, false>", "rkh::propagate_kernel<6, 64, false, true>"):  # one / two waves per edge
         d = res[k]
         assert d["vgpr_spill_count"] == 0 and d["private_segment_fixed_size"] <= 64, d
@@ -47,6 +48,10 @@ def test_latency_kernels_of_scenes_without_vertex_sets_do_not_spill(res):
         assert d["vgpr_count"] <= 256 and d["vgpr_spill_count"] == 0 and d["private_segment_fixed_size"] == 0, d
     d = res["rkh::edge_points_kernel<12, false, 32>"]
     assert d["vgpr_count"] <= 256 and d["vgpr_spill_count"] == 0 and d["private_segment_fixed_size"] == 0, d
+    for n in (1, 2, 3, 4, 6, 7, 12):
+        for w in (1, 2, 4, 8):
+            d = res[f"rkh::edge_check_kernel<{n}, {w}>"]
+            assert d["vgpr_count"] <= 256 and d["vgpr_spill_count"] == 0 and d["private_segment_fixed_size"] == 0, d
 
 
 def test_committed_resource_table_matches_the_build(res):
@@ -61,7 +66,7 @@ def test_committed_resource_table_matches_the_build(res):
         rows[name] = [int(x) for x in rest]
     checked = 0
     for k, d in res.items():
-        if not any(t in k for t in ("propagate_pair", "propagate_kernel<6", "nn1_", "edge_points_kernel<6")):
+        if not any(t in k for t in ("propagate_pair", "propagate_kernel<6", "nn1_", "edge_points_kernel<6", "edge_check_kernel")):
             continue
         got = [d["vgpr_count"], d["agpr_count"], d["vgpr_spill_count"], d["sgpr_count"], d["private_segment_fixed_size"],
                d["group_segment_fixed_size"]]
