@@ -122,7 +122,10 @@ rkh_status rkh_nn_fill_uniform(rkh_nn* nn, uint64_t n, uint64_t seed);
  * geometry/proximity/proxy_query_model.cpp:215-402).  The HIP kernels cover serial chains of
  * {driving_actuator_gen, inertia_gen, revolute_joint_3D, rigid_link_3D, inertia_3D} groups
  * (the pattern of examples/robot_airship/old/CRS_A465_models.cpp:751-785); anything else returns
- * RKH_ERR_UNSUPPORTED. */
+ * RKH_ERR_UNSUPPORTED.  A prismatic_joint_3D may take the place of the revolute joint in any group of a
+ * SERIAL chain (the CRS A465's track, :300-346), also after the optional mount link; such a scene runs on the
+ * one-wave-per-edge and quasi-static kernels.  Refused with a prismatic joint: branching chains, a
+ * flexible_beam_3D, mesh shapes, and a plane paired with a shape the joint carries (its travel is unbounded). */
 rkh_status rkh_scene_create(rkh_ctx* ctx, const rkh_kte_op* prog, int n_ops, const rkh_chain_base* base,
                             const rkh_shape* shapes, int n_shapes, rkh_scene** out);
 /* The same with convex vertex sets among the shapes (RKH_SHAPE_MESH): mesh_vertices = the pool [n_mesh_vertices][3] the

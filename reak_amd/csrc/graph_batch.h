@@ -672,7 +672,7 @@ struct GraphBatch {
   // bound of edges leaves half the SIMDs idle (RKH_DUO_THRESHOLD, as in the batch planner)
   int duo_lanes(uint32_t edges_per_problem) const {
     static const uint32_t thr = [] { const char* e = getenv("RKH_DUO_THRESHOLD"); return e ? uint32_t(std::max(0, atoi(e))) : 512u; }();
-    return (uint64_t(edges_per_problem) * P <= thr && !scene->host.has_meshes) ? 128 : 64;
+    return (uint64_t(edges_per_problem) * P <= thr && !scene->host.has_meshes && !scene->host.has_prismatic) ? 128 : 64;
   }
 
   rkh_status run() {

@@ -895,7 +895,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   p->b_max = std::min<uint32_t>(p->b_max, 4096);
   if (const char* e = getenv("RKH_LANE_THRESHOLD")) p->lane_threshold = uint32_t(std::max(0, atoi(e)));
   if (const char* e = getenv("RKH_DUO_THRESHOLD")) p->duo_threshold = uint32_t(std::max(0, atoi(e)));
-  if (p->scene->host.has_meshes) p->duo_threshold = 0;  // (instantiated without the support-map query only)
+  if (p->scene->host.has_meshes || p->scene->host.has_prismatic) p->duo_threshold = 0;  // (not instantiated for these)
   if (const char* e = getenv("RKH_LANES_PER_EDGE")) {
     p->lanes_per_edge = (atoi(e) == 2) ? 2 : ((atoi(e) == 16) ? 16 : (atoi(e) == 0 ? 0 : 64));
   } else if (p->n_dof <= 6 && scene_fits_lane_kernel(scene->host)) {
@@ -909,6 +909,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
     p->lanes_per_edge = 64;  // the two-lanes-per-edge kernel does not take this scene
   if (p->lanes_per_edge == 16 && 2 * p->n_dof > 16) p->lanes_per_edge = 64;  // a 16-lane group holds at most 16 components
   if (scene->host.planar) p->lanes_per_edge = 64;  // planar chains have one mapping (one lane per edge, propagate_planar.hip)
+  if (scene->host.has_prismatic) p->lanes_per_edge = 64;  // prismatic joints: one wave per edge only
   if (const char* e = getenv("RKH_PROFILE_NN")) p->profile_nn = atoi(e) != 0;
   // candidates per round = batch_factor * sqrt(n) per problem (results do not depend on it).  More candidates per
   // round mean fewer rounds but more discarded speculation (0.89 of the propagated edges are committed at 1.25, 0.72 at

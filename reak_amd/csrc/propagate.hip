@@ -24,6 +24,11 @@
 // Chain parameters, obstacle table and all per-edge intermediates live in LDS.
 // Compiled with -ffp-contract=off: products and sums round exactly as in the CPU reference; only
 // sin/cos (OCML vs glibc) differ by ulps (stated tolerance: 1e-10 relative on propagated states).
+//
+// Scenes with prismatic joints (SceneDev::has_prismatic) run on forms of the one-wave steer, f-eval, distance and
+// 3D edge-walk kernels compiled from this same text in a translation unit of their own (propagate_prismatic.hip
+// defines RKH_PRISMATIC_FORMS and includes this file): there everything below lives in rkh::prismatic and kPrismatic
+// is true.  Here kPrismatic is false and the prismatic branches compile away, so the revolute kernels keep their code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +42,12 @@
 #include "rkh_internal.h"
 
 namespace rkh {
+#ifdef RKH_PRISMATIC_FORMS
+namespace prismatic {
+constexpr bool kPrismatic = true;
+#else
+constexpr bool kPrismatic = false;
+#endif
 
 struct __attribute__((aligned(16))) JointLds {  // chain parameters of one joint group, staged in LDS
   double axis[3], joint_inertia;
@@ -172,7 +183,9 @@ __device__ __forceinline__ void stage_env(const SceneDev* __restrict__ sc, Shape
 
 // x' = f(x,u) for the lane group's edge.  ws.x / ws.u hold the state and the input (already staged).
 // Returns dp for lane gl (< 2N); sets *singular if a Cholesky pivot is < 1e-8.
-template <int N, int GL>
+// PRISM: the scene may hold prismatic joints (SceneDev::prismatic_mask; serial chains without a beam); false compiles the
+// revolute-only code unchanged.
+template <int N, int GL, bool PRISM = false>
 __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const CPack<N>& cp,
                                    const JointLds* __restrict__ jl, const double* __restrict__ base, GroupWs<N>& ws,
                                    double* __restrict__ sink, int gl, int gb, bool* singular,
@@ -219,14 +232,29 @@ __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const C
       const d3 axis_n = cget3(cp, jb + JC_AXISN);
       const double c2 = ws.cs[j][0], s2 = ws.cs[j][1];
       const double qd = ws.x[2 * j + 1];
-      // revolute_joint_3D::doMotion (revolute_joint.cpp:121-148)
-      const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
-      const m33 R2 = rotmat(tq);
-      const d4 EQ = qmul(Q, tq);
-      const d3 wb = mulT(w, R2);
-      const d3 qa = qd * axis;
-      const d3 Ew = wb + qa;
-      const d3 Ealpha = mulT(alpha, R2) + cross(wb, qa);
+      d4 EQ;
+      d3 Ew, Ealpha;
+      if (PRISM && ((sc_beam->prismatic_mask >> j) & 1u)) {
+        // prismatic_joint_3D::doMotion (prismatic_joint.cpp:116-148), q_ddot = 0: the end frame keeps the base's
+        // orientation and rates and moves by R(Q) (q a)
+        const d3 tmp_pos = ws.x[2 * j] * axis;
+        const d3 tmp_vel = qd * axis;
+        const m33 Rb = rotmat(Q);
+        acc = acc + mul(Rb, (cross(w, cross(w, tmp_pos)) + 2.0 * cross(w, tmp_vel)) + cross(alpha, tmp_pos));
+        pos = pos + mul(Rb, tmp_pos);
+        EQ = Q;
+        Ew = w;
+        Ealpha = alpha;
+      } else {
+        // revolute_joint_3D::doMotion (revolute_joint.cpp:121-148)
+        const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
+        const m33 R2 = rotmat(tq);
+        EQ = qmul(Q, tq);
+        const d3 wb = mulT(w, R2);
+        const d3 qa = qd * axis;
+        Ew = wb + qa;
+        Ealpha = mulT(alpha, R2) + cross(wb, qa);
+      }
       st3(lead ? ws.Epos[j] : sink, pos);
       st4(lead ? ws.Equat[j] : sink, EQ);
       // rigid_link_3D::doMotion = frame * pose (frame_3D.hpp:240-255)
@@ -296,8 +324,12 @@ __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const C
     const d4 f2q = qmul(iq, bq);
     const m33 Rf = rotmat(f2q);
     const d3 axis = ld3(jl[c].axis);
-    const d3 wt = mulT(axis, Rf);
-    const d3 vt = mulT(cross(axis, f2pos), Rf);
+    d3 wt = mulT(axis, Rf);
+    d3 vt = mulT(cross(axis, f2pos), Rf);
+    if (PRISM && ((sc_beam->prismatic_mask >> c) & 1u)) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0
+      vt = mulT(axis, Rf);
+      wt = mk3(0, 0, 0);
+    }
     st3(ws.Tcm[b][c], vt);
     st3(ws.Tcm[b][c] + 3, wt);
   }
@@ -335,15 +367,27 @@ __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const C
       const d3 op = cget3(cp, jb + JC_OFFP);
       const d3 tmp_force = mul(Ro, LF);
       const d3 ET = mul(Ro, LT) + cross(op, tmp_force);
-      // revolute_joint_3D::doForce (revolute_joint.cpp:170-181)
-      const m33 Ra = axis_angle_rotmat(ws.cs[j][2], ws.cs[j][3], cget3(cp, jb + JC_AXISN));
-      const double ta = dot(ET, axis);
-      LF = mul(Ra, tmp_force);
-      LT = mul(Ra, ET - ta * axis);
-      // inertia_gen::doForce: f -= q_ddot * mass with q_ddot = 0 ; driving_actuator_gen::doForce
       const double uj = ws.u[j];
-      const double fj = ta + uj;
-      LT = LT - uj * axis;
+      double fj;
+      if (PRISM && ((sc_beam->prismatic_mask >> j) & 1u)) {
+        // prismatic_joint_3D::doForce (prismatic_joint.cpp:150-170): the force along the axis goes to the coordinate
+        const double tf = dot(tmp_force, axis);
+        LF = tmp_force - tf * axis;
+        LT = ET + cross(ws.x[2 * j] * axis, tmp_force);
+        // inertia_gen::doForce (q_ddot = 0) ; driving_actuator_gen::doForce with prismatic_joint_3D::applyReactionForce
+        // (prismatic_joint.cpp:219-222): a force on the base frame
+        fj = tf + uj;
+        LF = LF - uj * axis;
+      } else {
+        // revolute_joint_3D::doForce (revolute_joint.cpp:170-181)
+        const m33 Ra = axis_angle_rotmat(ws.cs[j][2], ws.cs[j][3], cget3(cp, jb + JC_AXISN));
+        const double ta = dot(ET, axis);
+        LF = mul(Ra, tmp_force);
+        LT = mul(Ra, ET - ta * axis);
+        // inertia_gen::doForce: f -= q_ddot * mass with q_ddot = 0 ; driving_actuator_gen::doForce
+        fj = ta + uj;
+        LT = LT - uj * axis;
+      }
       f_mine = (gl == j) ? fj : f_mine;
     }
   }
@@ -846,7 +890,7 @@ __device__ double proximity_min_planar(const SceneDev* __restrict__ sc, const CP
 // stops once every edge of the wave has met a negative distance.
 // Global poses of the robot shapes at the configuration in ws.x (ws.Rpos / ws.Rquat), every lane group for its own
 // point; ends on a block barrier.
-template <int N, int GL, typename WS>
+template <int N, int GL, typename WS, bool PRISM = false>
 __device__ __forceinline__ void proximity_frames(const SceneDev* __restrict__ sc, const ShapeDev* __restrict__ robot,
                                                  const CPack<N>& cp, const double* __restrict__ base, WS& ws,
                                                  double* __restrict__ sink, int gl) {
@@ -872,8 +916,14 @@ __device__ __forceinline__ void proximity_frames(const SceneDev* __restrict__ sc
       }
       const d3 axis_n = cget3(cp, jb + JC_AXISN);
       const double c2 = ws.cs[j][0], s2 = ws.cs[j][1];
-      const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
-      const d4 EQ = qmul(Q, tq);
+      d4 EQ;
+      if (PRISM && ((sc->prismatic_mask >> j) & 1u)) {  // prismatic_joint_3D: translate by R(Q) (q a), keep Q
+        pos = pos + mul(rotmat(Q), ws.x[2 * j] * cget3(cp, jb + JC_AXIS));
+        EQ = Q;
+      } else {
+        const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
+        EQ = qmul(Q, tq);
+      }
       st3(lead ? ws.Epos[j] : sink, pos);
       st4(lead ? ws.Equat[j] : sink, EQ);
       const m33 R = rotmat(EQ);
@@ -895,13 +945,13 @@ __device__ __forceinline__ void proximity_frames(const SceneDev* __restrict__ sc
   __syncthreads();
 }
 
-template <int N, int GL, typename WS, bool GJK = true>
+template <int N, int GL, typename WS, bool GJK = true, bool PRISM = false>
 __device__ double proximity_min(const SceneDev* __restrict__ sc, const CPack<N>& cp,
                                 const double* __restrict__ base, const ShapeDev* __restrict__ env_lds,
                                 const PairDev* __restrict__ pairs, int n_pairs, WS& ws,
                                 double* __restrict__ sink, int gl, int gb, bool cull_positive, bool group_done) {
-  if (sc->planar) return proximity_min_planar<N, GL>(sc, cp, base, env_lds, pairs, n_pairs, ws, gl, gb);
-  proximity_frames<N, GL>(sc, sc->robot, cp, base, ws, sink, gl);
+  if (!PRISM && sc->planar) return proximity_min_planar<N, GL>(sc, cp, base, env_lds, pairs, n_pairs, ws, gl, gb);
+  proximity_frames<N, GL, WS, PRISM>(sc, sc->robot, cp, base, ws, sink, gl);
   double dmin = INFINITY;
   bool hit = group_done;  // finished edges of the wave do not hold the scan open
   for (int p0 = 0; p0 < n_pairs; p0 += GL) {
@@ -1098,7 +1148,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
     bool free_pt = gm == 0ull;
     if (gl < D) ws.x[gl] = x;
     __syncthreads();
-    const double dmin = proximity_min<N, GL, GroupWs<N>, GJK>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lds.sink[lane], gl, gb, true, !free_pt);
+    const double dmin = proximity_min<N, GL, GroupWs<N>, GJK, kPrismatic>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lds.sink[lane], gl, gb, true, !free_pt);
     if (dmin < 0.0) free_pt = false;
     if (edge_valid && gl == 0 && writer) edge_io()->accept[e] = free_pt ? 1 : 0;
   }
@@ -1134,7 +1184,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
         if (gl < D) ws.x[gl] = xe;
         __syncthreads();
         const double dp = DUO ? state_derivative_duo<N>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], gl, wave, &sing_now)
-                              : state_derivative<N, GL>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], gl, gb, &sing_now);
+                              : state_derivative<N, GL, kPrismatic>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], gl, gb, &sing_now);
         const int stage = ev & 3;
         if (stage == 0) {
           w = xe;
@@ -1169,7 +1219,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
     if (!__any(alive)) break;
     if (gl < D) ws.x[gl] = xe;
     __syncthreads();
-    const double dmin = proximity_min<N, GL, GroupWs<N>, GJK>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lds.sink[lane], gl, gb, true, !alive);
+    const double dmin = proximity_min<N, GL, GroupWs<N>, GJK, kPrismatic>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lds.sink[lane], gl, gb, true, !alive);
     if (dmin < 0.0) alive = false;
     if (alive) {
       x = xe;
@@ -1225,7 +1275,7 @@ __global__ __launch_bounds__(64) void state_derivative_kernel(const SceneDev* __
   __syncthreads();
   const CPack<N> cp = load_cpack<N>(lds.joints, lane);
   bool singular = false;
-  const double dp = state_derivative<N, 64>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], lane, 0, &singular);
+  const double dp = state_derivative<N, 64, kPrismatic>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], lane, 0, &singular);
   if (lane < D) pd[uint64_t(e) * D + lane] = dp;
   if (singular && lane == 0) atomicExch(err_flag, int(RKH_ERR_SINGULAR));
   // exports for the kernel-level parity tests: the symmetric M is rebuilt from Mf (ws.M now holds its
@@ -1605,8 +1655,14 @@ __global__ __launch_bounds__(256) void edge_points_kernel(EdgeWalkArgs) {
         }
         const d3 axis_n = cget3(cp, jb + JC_AXISN);
         const double c2 = lds.cs[j][0][t], s2 = lds.cs[j][1][t];
-        const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
-        const d4 EQ = qmul(Q, tq);
+        d4 EQ;
+        if (kPrismatic && ((sc->prismatic_mask >> j) & 1u)) {  // prismatic_joint_3D: translate by R(Q) (q a), keep Q
+          pos = pos + mul(rotmat(Q), (lds.pts[j][t] * qs.speed[j]) * cget3(cp, jb + JC_AXIS));
+          EQ = Q;
+        } else {
+          const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
+          EQ = qmul(Q, tq);
+        }
         lds.E[j][0][t] = pos.x; lds.E[j][1][t] = pos.y; lds.E[j][2][t] = pos.z;
         lds.E[j][3][t] = EQ.w; lds.E[j][4][t] = EQ.x; lds.E[j][5][t] = EQ.y; lds.E[j][6][t] = EQ.z;
         const m33 Rm = rotmat(EQ);
@@ -1918,11 +1974,14 @@ __global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __rest
   if (lane < D) ws.x[lane] = x[uint64_t(e) * D + lane];
   __syncthreads();
   const CPack<N> cp = load_cpack<N>(lds.joints, lane);
-  const double dmin = proximity_min<N, 64>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lds.sink[lane], lane, 0, false, false);
+  // (prismatic scenes hold no vertex sets: their form leaves the support-map query out)
+  const double dmin = proximity_min<N, 64, GroupWsQs<N>, !kPrismatic, kPrismatic>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws,
+                                                                                  lds.sink[lane], lane, 0, false, false);
   if (lane == 0) dist[e] = dmin;
 }
 
 // ---- host launchers ------------------------------------------------------------------------
+#ifndef RKH_PRISMATIC_FORMS
 #define RKH_DISPATCH_N(N_, CALL)     \
   switch (N_) {                      \
     case 1: { constexpr int N = 1; CALL; } break; \
@@ -1976,6 +2035,9 @@ rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev&
   if (scene.host.planar)  // planar chains: one lane per edge, whatever mapping was asked for (propagate_planar.hip)
     return launch_propagate_planar(s, n_dof, scene.d_scene, scene.d_pairs, scene.n_pairs_verdict, dyn, io, grid_edges, io_b,
                                    grid_b, tab_a, tab_b, n_problems, gate);
+  if (scene.host.has_prismatic)  // one wave per edge whatever mapping was asked for (propagate_prismatic.hip)
+    return prismatic::launch_propagate(s, scene, dyn, io, grid_edges, io_b ? *io_b : EdgeIO(), eb, tab_a, tab_b, n_problems,
+                                       gate);
   if (lanes_per_edge == 2)  // two lanes per edge, two waves per SIMD (propagate_pair.hip)
     return launch_propagate_pairs(s, n_dof, scene.d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems,
                                   d_lane_ws, gate);
@@ -2004,6 +2066,7 @@ rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const 
   const int n_dof = scene.host.n_dof;
   if (scene.host.planar)
     return launch_state_derivative_planar(s, n_dof, scene.d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+  if (scene.host.has_prismatic) return prismatic::launch_state_derivative(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
   RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
                                            d_pd, d_M, d_f, d_err));
   RKH_HIP(hipGetLastError());
@@ -2082,6 +2145,8 @@ rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev&
                              uint32_t n_problems) {
   const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
+  if (scene.host.has_prismatic)
+    return prismatic::launch_edge_check(s, scene, qs, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems);
   EdgeWalkArgs ka;
   ka.sc = scene.d_scene;
   ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
@@ -2103,6 +2168,10 @@ rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev&
 
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink) {
+  if (scene.host.has_prismatic) {
+    set_error("rkh_diag_feval_cycles: scenes with prismatic joints are not instrumented");
+    return RKH_ERR_UNSUPPORTED;
+  }
   RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128),
                                                       (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene, d_x, d_u,
                                                       iters, d_out, d_sink));
@@ -2112,6 +2181,10 @@ rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const 
 
 rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                int iters, unsigned long long* d_out, double* d_sink) {
+  if (scene.host.has_prismatic) {
+    set_error("rkh_diag_feval_cycles: scenes with prismatic joints are not instrumented");
+    return RKH_ERR_UNSUPPORTED;
+  }
   RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64),
                                                       (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
                                                       static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, d_u,
@@ -2122,6 +2195,7 @@ rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const doub
 
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
   if (B == 0) return RKH_OK;
+  if (scene.host.has_prismatic) return prismatic::launch_min_distance(s, scene, d_x, B, d_dist);
   RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64),
                                                       (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
                                                       static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B,
@@ -2129,5 +2203,102 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
+
+#else   // RKH_PRISMATIC_FORMS: the launchers of the prismatic forms (rkh_internal.h), chains of 1, 2, 3, 4, 6 and 7 joints
+#define RKH_DISPATCH_N(N_, CALL)     \
+  switch (N_) {                      \
+    case 1: { constexpr int N = 1; CALL; } break; \
+    case 2: { constexpr int N = 2; CALL; } break; \
+    case 3: { constexpr int N = 3; CALL; } break; \
+    case 4: { constexpr int N = 4; CALL; } break; \
+    case 6: { constexpr int N = 6; CALL; } break; \
+    case 7: { constexpr int N = 7; CALL; } break; \
+    default:                         \
+      set_error("chains with prismatic joints are instantiated for 1, 2, 3, 4, 6 and 7 joints"); \
+      return RKH_ERR_UNSUPPORTED;    \
+  }
+
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
+                            const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                            uint32_t n_problems, KernelGate gate) {
+  WaveArgs args;
+  args.sc = scene.d_scene;
+  args.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  args.n_pairs = scene.n_pairs_verdict;
+  args.dyn = dyn;
+  args.io_a = io;
+  args.io_b = io_b;
+  args.tab_a = tab_a;
+  args.tab_b = tab_b;
+  args.grid_a = edges_a;
+  args.gate = gate;
+  dim3 grid(edges_a + edges_b, n_problems);
+  if (gate.wave_base) grid = dim3(uint32_t(std::min<uint64_t>(uint64_t(edges_a + edges_b) * n_problems, gate.hi)), 1);
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((propagate_kernel<N, 64, false>), grid, dim3(64),
+                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, args));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   double* d_pd, double* d_M, double* d_f, int* d_err) {
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, scene.d_scene,
+                                                      d_x, d_u, B, d_pd, d_M, d_f, d_err));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
+  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64),
+                                                      (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
+                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B,
+                                                      d_dist));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+template <int N, int G>
+static rkh_status launch_edge_points_t(hipStream_t s, dim3 grid, int n_env, EdgeWalkArgs ka) {
+  static_assert(EdgePointsSmem<N, G>::bytes(kMaxEnvShapes, 0) <= 160 * 1024, "edge_points_kernel: LDS over 160 KB");
+  const size_t with_pairs = EdgePointsSmem<N, G>::bytes(n_env, ka.n_pairs);
+  ka.pairs_staged = with_pairs <= 160 * 1024;
+  const size_t smem = ka.pairs_staged ? with_pairs : EdgePointsSmem<N, G>::bytes(n_env, 0);
+  auto kern = edge_points_kernel<N, false, G>;
+  static bool big_lds = false;  // (per instantiation) more than the default 64 KB of dynamic LDS: ask once
+  if (smem > 65536 && !big_lds) {
+    RKH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    big_lds = true;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, ka);
+  return RKH_OK;
+}
+
+// the 3D edge walk's form choice (rkh::launch_edge_walk) without the support-map query
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                             uint32_t n_problems) {
+  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
+  EdgeWalkArgs ka;
+  ka.sc = scene.d_scene;
+  ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  ka.n_pairs = scene.n_pairs_verdict;
+  ka.qs = qs;
+  ka.io_a = io;
+  ka.io_b = io_b ? *io_b : EdgeIO();
+  ka.tab_a = tab_a;
+  ka.tab_b = tab_b;
+  ka.grid_a = grid_edges;
+  ka.pairs_staged = 0;
+  const dim3 grid(grid_edges + eb, n_problems);
+  const bool wide = uint64_t(grid.x) * grid.y < 2048;
+  rkh_status st = RKH_OK;
+  RKH_DISPATCH_N(scene.host.n_dof, (st = wide ? launch_edge_points_t<N, 64>(s, grid, scene.host.n_env, ka)
+                                              : launch_edge_points_t<N, 32>(s, grid, scene.host.n_env, ka)));
+  if (st != RKH_OK) return st;
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+}  // namespace prismatic
+#endif  // RKH_PRISMATIC_FORMS
 
 }  // namespace rkh

@@ -182,6 +182,9 @@ struct SceneDev {
   unsigned long long env_finder_mask[9][kMaxEnvShapes / 64];
   int32_t has_meshes;      // 1: convex vertex sets among the shapes (GJK pairs; wave-per-edge and quasi-static kernels)
   const double* mesh_verts;  // device pointer: the vertex pool [n][3] the mesh shapes index into (dims[0], dims[1])
+  // prismatic_joint_3D groups (serial chains only): bit j = joint j translates along JointDev::axis (mAxis as given)
+  uint32_t prismatic_mask;
+  int32_t has_prismatic;   // 1: prismatic_mask != 0 (the prismatic instantiations of the one-wave and quasi-static kernels)
 };
 
 }  // namespace rkh
@@ -311,6 +314,7 @@ rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev&
 // the two-lanes-per-edge kernel handles one serial chain, with at most a tip-to-world beam
 inline bool scene_fits_lane_kernel(const SceneDev& S) {
   if (S.has_meshes) return false;  // GJK pairs run in the wave-per-edge / quasi-static kernels
+  if (S.has_prismatic) return false;  // prismatic joints: the one-wave-per-edge kernel
   return S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
 }
 rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
@@ -319,6 +323,19 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              const EdgeIO* io_b = nullptr, uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr,
                              const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1);
+// Scenes with prismatic joints (SceneDev::has_prismatic; propagate_prismatic.hip): one wave per edge, no support-map
+// query; the launchers above route these scenes here whatever mapping was asked for.
+namespace prismatic {
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
+                            const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                            uint32_t n_problems, KernelGate gate);
+rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                                   double* d_pd, double* d_M, double* d_f, int* d_err);
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                             uint32_t n_problems);
+}  // namespace prismatic
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink);
 rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,

@@ -183,6 +183,11 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
                                       const rkh_shape* shapes, int n_shapes, rkh_scene** out) {
   // position level: {revolute_joint_2D, rigid_link_2D} per joint; with dynamics: {driving_actuator_gen, inertia_gen,
   // revolute_joint_2D, rigid_link_2D, inertia_2D on the link's end frame} per joint
+  for (int k = 0; k < n_ops; ++k)
+    if (prog[k].kind == RKH_KTE_PRISMATIC_JOINT_3D) {
+      set_error("rkh_scene_create: prismatic joints are not supported in planar chains");
+      return RKH_ERR_UNSUPPORTED;
+    }
   const bool dynamics = prog[0].kind == RKH_KTE_DRIVING_ACTUATOR_GEN;
   const int per = dynamics ? 5 : 2;
   const int n = n_ops / per;
@@ -342,8 +347,8 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       k += 5;
     }
     if (k < 0 || groups.empty() || int(groups.size()) > kMaxDof) {
-      set_error("rkh_scene_create: KTE program is not a chain of [mount link] {actuator, inertia_gen, revolute, link, "
-                "inertia_3D} groups (optionally followed by one flexible_beam_3D), or has too many joints");
+      set_error("rkh_scene_create: KTE program is not a chain of [mount link] {actuator, inertia_gen, revolute or "
+                "prismatic joint, link, inertia_3D} groups (optionally followed by one flexible_beam_3D), or has too many joints");
       return RKH_ERR_UNSUPPORTED;
     }
   }
@@ -388,7 +393,8 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     S.branch_first[j] = branch_first;
     const uint32_t branch_mask = ((j + 1 >= 32 ? 0xFFFFFFFFu : ((1u << (j + 1)) - 1u))) & ~((1u << branch_first) - 1u);
     const bool ok = act.kind == RKH_KTE_DRIVING_ACTUATOR_GEN && gen.kind == RKH_KTE_INERTIA_GEN &&
-                    rev.kind == RKH_KTE_REVOLUTE_JOINT_3D && lnk.kind == RKH_KTE_RIGID_LINK_3D &&
+                    (rev.kind == RKH_KTE_REVOLUTE_JOINT_3D || rev.kind == RKH_KTE_PRISMATIC_JOINT_3D) &&
+                    lnk.kind == RKH_KTE_RIGID_LINK_3D &&
                     ine.kind == RKH_KTE_INERTIA_3D && act.coord == j && gen.coord == j && rev.coord == j &&
                     act.joint_op == k0 + 2 && gen.upstream == (1u << j) &&
                     (first && groups[j].mount_op < 0 ? rev.base_frame == 0 : rev.base_frame == expect_base) &&
@@ -402,6 +408,7 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     prev_end = lnk.end_frame;
     joint_end_frame[j] = rev.end_frame;
     link_end_frame[j] = lnk.end_frame;
+    if (rev.kind == RKH_KTE_PRISMATIC_JOINT_3D) S.prismatic_mask |= 1u << j;
     JointDev& J = S.joints[j];
     for (int i = 0; i < 3; ++i) J.axis[i] = rev.axis[i];
     {  // axis_angle ctor normalisation (rotations_3D.hpp:1961-1974)
@@ -420,6 +427,18 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     host_rotmat(J.off_quat, J.off_R);
     J.mass = ine.mass;
     for (int i = 0; i < 6; ++i) J.inertia[i] = ine.inertia[i];
+  }
+  S.has_prismatic = S.prismatic_mask != 0u ? 1 : 0;
+  if (S.has_prismatic) {
+    // a mount link on the first joint keeps the chain serial; any later branch start does not
+    bool branching = false;
+    for (int j = 1; j < n; ++j) branching = branching || S.branch_start[j] != 0;
+    const char* why = branching ? "a branching chain" : (has_beam ? "a flexible_beam_3D" : nullptr);
+    if (why) {
+      delete sc;
+      set_error(std::string("rkh_scene_create: prismatic joints are supported in serial chains only, not with ") + why);
+      return RKH_ERR_UNSUPPORTED;
+    }
   }
   if (has_beam) {
     const rkh_kte_op& bm = prog[n_ops];
@@ -483,7 +502,7 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
         if (joint_end_frame[j] == s.anchor) link = j;
       if (link < 0 || S.n_robot >= 2 * kMaxDof) {
         delete sc;
-        set_error("rkh_scene_create: robot shapes must be anchored on a revolute joint's end frame");
+        set_error("rkh_scene_create: robot shapes must be anchored on a joint's end frame");
         return RKH_ERR_UNSUPPORTED;
       }
       d.link = link;
@@ -511,9 +530,17 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       env_key.push_back(std::sqrt(d2) - d.brad);
     }
   }
+  if (S.has_prismatic && S.has_meshes) {
+    delete sc;
+    set_error("rkh_scene_create: prismatic joints are not supported together with mesh shapes");
+    return RKH_ERR_UNSUPPORTED;
+  }
+  // robot shape r rides on a prismatic joint (its travel has no bound in the scene: no static reach, no plane pairs)
+  auto on_prismatic = [&](int r) { return (S.prismatic_mask & ((2u << S.robot[r].link) - 1u)) != 0u; };
   for (int r = 0; r < S.n_robot; ++r) {
     S.robot_n_reach[r] = S.n_env;
     if (S.n_branches != 0 || S.planar) continue;  // serial 3D chains only: every joint hangs off the previous link
+    if (on_prismatic(r)) continue;
     double reach = 0.0;
     for (int i = 0; i < S.robot[r].link; ++i) {
       const double* o = S.joints[i].off_pos;
@@ -554,6 +581,12 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       p.routine = uint8_t(host_pair_routine(ki, kj, &robot_first));
       if (p.routine == 0) continue;  // no finder in the reference
       p.s1_is_robot = robot_first ? 1 : 0;
+      if ((ki == RKH_SHAPE_PLANE || kj == RKH_SHAPE_PLANE) && on_prismatic(i)) {
+        delete sc;
+        set_error("rkh_scene_create: a plane cannot be paired with a shape carried by a prismatic joint (the plane rule "
+                  "below needs a finite reach)");
+        return RKH_ERR_UNSUPPORTED;
+      }
       if (ki == RKH_SHAPE_PLANE || kj == RKH_SHAPE_PLANE) {
         // findMinimumDistance skips a finder whose bounding spheres are further apart than the running minimum
         // (proxy_query_model.cpp:384-389).  For bounded shapes that cannot change the minimum; a plane's bounding radius

@@ -11,7 +11,8 @@ serializables carry `type_ID` and `version` only).  Field names and type ids fol
                proxy_query_model_3D (mShapeList)                                   R/geometry/proximity/proxy_query_model.hpp:181
   kinetostatics pose_3D (Parent, Position, Quat), frame_3D (+ Velocity .. Torque), gen_coord (q, q_dot, q_ddot, f),
                vect<double,N> (N x "q"), quaternion ("q[0]" .. "q[3]"), mat<double,symmetric> (q, rowCount)
-  KTE chain    kte_map_chain (mKTEs) of revolute_joint_3D (mAngle, mAxis, mBase, mEnd, mJacobian), rigid_link_3D (mBase,
+  KTE chain    kte_map_chain (mKTEs) of revolute_joint_3D (mAngle, mAxis, mBase, mEnd, mJacobian), prismatic_joint_3D
+               (mCoord, mAxis, mBase, mEnd, mJacobian; prismatic_joint.hpp:157-163), rigid_link_3D (mBase,
                mEnd, mPoseOffset), inertia_3D (mCenterOfMass = joint_dependent_frame_3D, mMass, mInertiaTensor),
                inertia_gen (mCenterOfMass = joint_dependent_gen_coord, mMass), driving_actuator_gen (mFrame, mJoint,
                mDriveForce)                                                        R/ctrl/mbd_kte/*.hpp
@@ -42,6 +43,7 @@ TYPE_IDS = {
     "plane": ([0xC310000F], 1), "sphere": ([0xC3100010], 1), "capped_cylinder": ([0xC3100011], 1),
     "cylinder": ([0xC3100012], 1), "box": ([0xC3100013], 1), "proxy_query_model_3D": ([0xC320001B], 1),
     "kte_map_chain": ([0xC2100002], 1), "revolute_joint_3D": ([0xC2100004], 1), "rigid_link_3D": ([0xC2100009], 1),
+    "prismatic_joint_3D": ([0xC2100006], 1),
     "inertia_gen": ([0xC210000A], 1), "inertia_3D": ([0xC210000C], 1), "driving_actuator_gen": ([0xC2100023], 1),
     "joint_dependent_gen_coord": ([0xC2000002], 1), "joint_dependent_frame_3D": ([0xC2000004], 1),
 }
@@ -287,6 +289,9 @@ def chain_objects(ops, base, n_frames, n_coords):
         elif op.kind == T.KTE_REVOLUTE_JOINT_3D:
             o = Obj("revolute_joint_3D", name=f"joint_{op.coord}", mAngle=coords[op.coord], mAxis=vect(op.axis),
                     mBase=frames[op.base_frame], mEnd=frames[op.end_frame], mJacobian=None)
+        elif op.kind == T.KTE_PRISMATIC_JOINT_3D:
+            o = Obj("prismatic_joint_3D", name=f"joint_{op.coord}", mCoord=coords[op.coord], mAxis=vect(op.axis),
+                    mBase=frames[op.base_frame], mEnd=frames[op.end_frame], mJacobian=None)
         elif op.kind == T.KTE_RIGID_LINK_3D:
             o = Obj("rigid_link_3D", name=f"link_{k}", mBase=frames[op.base_frame], mEnd=frames[op.end_frame],
                     mPoseOffset=pose_3d(op.offset))
@@ -349,7 +354,7 @@ def read_scene(text, template):
     kte_index = {id(o): i for i, o in enumerate(ktes)}
     base_frame = None
     for o in ktes:  # pass 1: number the frames like serial_chain_ops does (joint base, joint end, link end)
-        if o.cls in ("revolute_joint_3D", "rigid_link_3D"):
+        if o.cls in ("revolute_joint_3D", "prismatic_joint_3D", "rigid_link_3D"):
             if base_frame is None:
                 base_frame = o["mBase"]
             fidx(o["mBase"])
@@ -365,6 +370,11 @@ def read_scene(text, template):
                                upstream=int(dep["mUpStreamMask"]), mass=float(o["mMass"])))
         elif o.cls == "revolute_joint_3D":
             op = T.KteOp(kind=T.KTE_REVOLUTE_JOINT_3D, coord=cidx(o["mAngle"]), base_frame=fidx(o["mBase"]),
+                         end_frame=fidx(o["mEnd"]), joint_op=-1)
+            op.axis[:] = o["mAxis"]["q"]
+            ops.append(op)
+        elif o.cls == "prismatic_joint_3D":
+            op = T.KteOp(kind=T.KTE_PRISMATIC_JOINT_3D, coord=cidx(o["mCoord"]), base_frame=fidx(o["mBase"]),
                          end_frame=fidx(o["mEnd"]), joint_op=-1)
             op.axis[:] = o["mAxis"]["q"]
             ops.append(op)

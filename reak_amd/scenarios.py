@@ -57,11 +57,13 @@ class Scenario:
         return p
 
 
-def serial_chain_ops(axes, link_offsets, link_masses, link_inertias, joint_inertias):
-    """Flatten a serial revolute chain into kte_map_chain order.  Frame 0 is the base;
-    joint j: revolute base=2j, end=2j+1 ; link base=2j+1, end=2j+2 ; inertia_3D on frame 2j+2."""
+def serial_chain_ops(axes, link_offsets, link_masses, link_inertias, joint_inertias, kinds=None):
+    """Flatten a serial chain into kte_map_chain order.  Frame 0 is the base;
+    joint j: joint base=2j, end=2j+1 ; link base=2j+1, end=2j+2 ; inertia_3D on frame 2j+2.
+    kinds[j] (default: all T.KTE_REVOLUTE_JOINT_3D) may be T.KTE_PRISMATIC_JOINT_3D: axes[j] is then its mAxis."""
     ops = []
     n = len(axes)
+    kinds = [T.KTE_REVOLUTE_JOINT_3D] * n if kinds is None else list(kinds)
     for j in range(n):
         rev_index = 5 * j + 2
         a = T.KteOp(kind=T.KTE_DRIVING_ACTUATOR_GEN, coord=j, base_frame=-1, end_frame=-1, joint_op=rev_index)
@@ -69,7 +71,7 @@ def serial_chain_ops(axes, link_offsets, link_masses, link_inertias, joint_inert
         g = T.KteOp(kind=T.KTE_INERTIA_GEN, coord=j, base_frame=-1, end_frame=-1, joint_op=-1,
                     upstream=(1 << j), mass=float(joint_inertias[j]))
         ops.append(g)
-        r = T.KteOp(kind=T.KTE_REVOLUTE_JOINT_3D, coord=j, base_frame=2 * j, end_frame=2 * j + 1, joint_op=-1)
+        r = T.KteOp(kind=kinds[j], coord=j, base_frame=2 * j, end_frame=2 * j + 1, joint_op=-1)
         r.axis[:] = [float(v) for v in axes[j]]
         ops.append(r)
         l = T.KteOp(kind=T.KTE_RIGID_LINK_3D, coord=-1, base_frame=2 * j + 1, end_frame=2 * j + 2, joint_op=-1)
@@ -512,6 +514,77 @@ def make_c4(world_seed=1, n_obstacles=200, capsule_radius=0.05, mount_y=0.35, mi
                     meta={"lower": np.full(n, -np.pi), "upper": np.full(n, np.pi), "min_interval": min_interval,
                           "world_seed": world_seed, "n_obstacles": n_obstacles, "obstacle_kinds": kinds},
                     mesh_vertices=(np.concatenate(pool) if pool else None))
+
+
+def make_crs_a465_track(world_seed=1, n_obstacles=40, capsule_radius=0.05, steps_per_edge=20, dt=1e-3, min_interval=0.05):
+    """The CRS A465 on its linear track (examples/robot_airship/old/CRS_A465_models.cpp:300-346): a 7-DOF chain whose
+    first group is track_actuator -> track_joint_inertia (1.0) -> track_joint (prismatic_joint_3D along the base x axis)
+    -> link_0 (identity offset) -> link_0_inertia (mass 1.0, identity tensor), followed by crs_like_chain()'s six
+    revolute groups.  The base sits at (0, -3.3, 0.3) rotated by 90 degrees about z, so the track runs along global +y;
+    gravity enters as base acceleration.  Obstacles line both sides of the track and hang above its far part, clear of
+    the arm held upright; the goal lies 2 m down the track, out of the arm's reach without it.  meta carries the
+    quasi-static box (lower, upper, min_interval)."""
+    rng = np.random.Generator(np.random.PCG64(9100 + world_seed))
+    axes6, lengths6, offsets6, masses6, inertias6, joint_inertias6 = crs_like_chain()
+    axes = [(1.0, 0.0, 0.0)] + axes6
+    offsets = [(0.0, 0.0, 0.0)] + offsets6
+    masses = [1.0] + masses6
+    inertias = [(1.0, 0.0, 0.0, 1.0, 0.0, 1.0)] + inertias6
+    joint_inertias = [1.0] + joint_inertias6
+    kinds = [T.KTE_PRISMATIC_JOINT_3D] + [T.KTE_REVOLUTE_JOINT_3D] * 6
+    n = len(axes)
+    ops = serial_chain_ops(axes, offsets, masses, inertias, joint_inertias, kinds)
+    base = T.ChainBase()
+    half = 0.25 * np.pi  # axis_angle(pi/2, z) as a quaternion
+    base.pose = T.make_pose((0.0, -3.3, 0.3), (float(np.cos(half)), 0.0, 0.0, float(np.sin(half))))
+    base.acceleration[:] = [0.0, 0.0, 9.81]
+    shapes = []
+    for j in range(1, n):  # one capsule per arm link, on the joint's end frame
+        L = lengths6[j - 1]
+        s = T.Shape(kind=T.SHAPE_CCYLINDER, anchor=2 * j + 1)
+        s.pose = T.make_pose((0.0, 0.0, 0.5 * L))
+        s.dims[:] = [L, capsule_radius, 0.0]
+        shapes.append(s)
+    # keep-out: the volume the upright arm sweeps along the track (x = 0, y in [-3.3, -1.0], z in [0.3, 1.4])
+    track_lo, track_hi, z_lo, z_hi = -3.6, -0.7, 0.3, 0.3 + sum(lengths6)
+    placed = 0
+    while placed < n_obstacles:
+        kind = [T.SHAPE_SPHERE, T.SHAPE_BOX, T.SHAPE_CCYLINDER][int(rng.integers(0, 3))]
+        c = rng.uniform([-1.4, -4.0, 0.0], [1.4, -0.2, 2.0])
+        if kind == T.SHAPE_SPHERE:
+            r = rng.uniform(0.05, 0.2)
+            dims, brad, quat = [r, 0.0, 0.0], r, (1.0, 0.0, 0.0, 0.0)
+        elif kind == T.SHAPE_BOX:
+            d = rng.uniform(0.1, 0.4, size=3)
+            dims, brad, quat = list(d), 0.5 * np.linalg.norm(d), _random_unit_quat(rng)
+        else:
+            L, r = rng.uniform(0.1, 0.4), rng.uniform(0.03, 0.1)
+            dims, brad, quat = [L, r, 0.0], 0.5 * L + r, _random_unit_quat(rng)
+        gap = np.array([c[0], max(0.0, track_lo - c[1], c[1] - track_hi), max(0.0, z_lo - c[2], c[2] - z_hi)])
+        if np.linalg.norm(gap) < brad + capsule_radius + 0.3:
+            continue
+        s = T.Shape(kind=kind, anchor=-1)
+        s.pose = T.make_pose(c, quat)
+        s.dims[:] = [float(v) for v in dims]
+        shapes.append(s)
+        placed += 1
+    dyn = T.DynSpace()
+    dyn.n_dof = n
+    dyn.steps_per_edge = steps_per_edge
+    dyn.dt = dt
+    dyn.kp, dyn.kd, dyn.u_max = 50.0, 10.0, 50.0
+    dyn.goal_tol = 1e-3
+    lower = np.array([-0.2] + [-np.pi] * 6)
+    upper = np.array([2.5] + [np.pi] * 6)
+    for j in range(n):
+        dyn.lower[2 * j], dyn.upper[2 * j] = lower[j], upper[j]
+        dyn.lower[2 * j + 1], dyn.upper[2 * j + 1] = -2.0, 2.0
+    start = np.zeros(2 * n)
+    goal = np.zeros(2 * n)
+    goal[0::2] = [2.0, 0.6, 0.3, -0.4, 0.2, 0.3, -0.2]
+    return Scenario(name="crs_a465_track", ops=ops, base=base, shapes=shapes, dyn=dyn, n_dof=n, n_frames=2 * n + 1,
+                    start=start, goal=goal, meta={"world_seed": world_seed, "lower": lower, "upper": upper,
+                                                  "min_interval": min_interval})
 
 
 def make_random_chain(n, seed=1, n_obstacles=12):

@@ -17,6 +17,7 @@ KTE_FLEXIBLE_BEAM_3D = 6
 KTE_REVOLUTE_JOINT_2D = 7
 KTE_RIGID_LINK_2D = 8
 KTE_INERTIA_2D = 9
+KTE_PRISMATIC_JOINT_3D = 10  # mAxis as given (prismatic_joint_3D does not normalise it)
 
 # rkh_shape_kind
 SHAPE_SPHERE = 1
