@@ -11,7 +11,8 @@ is reported next to it.  Inputs (scene, sample stream chunks) are device-residen
 Multi-GPU: independent seeds shard across ranks ("scaling": "weak"), no data-path collective; after the timed
 region one all-reduce(min) of the best solution cost and all-reduce(sum) of the counters.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line: the headline and the
+objects the timed region's own counters and HIP events give,
   roofline      NN-sweep kernel of the timed region against HBM, exactly as SURVEY.md 8(d) defines it: achieved =
                 sweeps * n * D * 8 bytes / kernel time (HIP events on the planner stream), peak 8 TB/s; `traffic` = HBM bytes
                 per launch from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same workload
@@ -19,19 +20,27 @@ Extra objects on the JSON line:
                 kernel is bound by the (vertex, query) pair arithmetic, not by these bytes: see nn_sweep_mfma_timed.
   nn_sweep_mfma_timed  the same launches against the matrix pipes: algorithmic rate (24 flops per pair) against the dense
                 f32-input MFMA peak, and the bf16 instructions the split estimate actually issues against the bf16 peak
+
+--full adds what needs work of its own after the timed region; a plain run computes none of it:
+  steer_kernels the dominant kernels of the timed region: share of the step time, edges/s inside the kernel, fp64
+                operation rate against the no-FMA VALU peak with the EXACT operation count of one f-eval as the restated
+                reference performs it (oracle/flop_count.cpp; `useful` = without its products over structural zeros)
+and, on a single GPU, unless --no-microbench:
   nn_sweep_hbm  the sweep in its HBM-bound regime (tree larger than the 256 MiB Infinity Cache, 8 queries per sweep, the
                 cloud's hyperbox declared: matrix-core pre-filter in front of the exact fp64 test), measured outside the
                 timed region; beside it 1 / 4 / 32 queries per sweep and the all-fp64 sweep without a declared bound
   nn_sweep_mfma the matrix-core sweep alone on one 1 Mi-row tree
-  steer_kernels the dominant kernels of the timed region: share of the step time, edges/s inside the kernel, fp64
-                operation rate against the no-FMA VALU peak with the EXACT operation count of one f-eval as the restated
-                reference performs it (oracle/flop_count.cpp; `useful` = without its products over structural zeros)
+  single_problem  P = 1 and P = 16 (one / sixteen problems per GPU, 20 000 vertices each), outside the timed region
   collide       the proximity test inside the steer kernels: (robot shape, obstacle) pair tests per second
                 before culling, and the fraction each stage lets through (static reach, bounding cull, closed forms)
-  single_problem  P = 1 and P = 16 (one / sixteen problems per GPU, 20 000 vertices each), outside the timed region
+  c3_rrtstar    BASELINE config C3: RRT* for 16 problems, and its k-NN sweep alone on a 1 Mi-vertex tree
+  c4_prm_meshes BASELINE config C4: PRM on the 12-DOF dual arm among 200 convex mesh obstacles, 16 problems
+and, on a single GPU, unless --no-cpu-baseline:
   cpu_baseline  the CPU oracle (restatement of the reference planner, -O3 -march=native) on a bounded sample of the
                 same workload, single thread like ReaK itself; host CPU model and core count stated
   cpu_baseline_all_cores  the same sample on every host core (one oracle process per core, independent seeds)
+  nn_published_config  the reference's published NN-search configuration (6-D, 25 000 vertices): the GPU
+                sweep beside the oracle's linear search and DVP-tree on the host CPU
 
 --dump-outputs DIR writes what the last timed step computed (rrt_outputs: every problem's counters and best cost, a
 seeded sample of solution paths, tree vertices and loop iterations) as DIR/<name>.npy; the inputs depend only on the
@@ -677,8 +686,12 @@ def main():
     ap.add_argument("--c5-problems", type=int, default=1, help="RRT* seeds per GPU of --workload c5")
     ap.add_argument("--c5-report-iterations", type=int, default=20000,
                     help="--workload c5, N > 1: RRT* loop iterations between two report-interval reductions")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-microbench", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: steer_kernels, and on "
+                         "one GPU the side microbenchmarks, other configurations and the CPU baselines (see the module "
+                         "docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-microbench", action="store_true", help="--full without the GPU side runs")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, "
                          "rank 0's problems; see rrt_outputs) so that two builds can be compared output for output")
@@ -877,7 +890,7 @@ def main():
         if not profiled_all:
             for k in ("roofline", "nn_sweep_mfma_timed"):
                 out[k]["note"] = "INCOMPLETE: only the first profiled_rounds rounds were timed (profile_coverage); " + out[k]["note"]
-        if tot["steer_ms"] > 0 and profiled_all:
+        if args.full and tot["steer_ms"] > 0 and profiled_all:
             fe = feval_ops(scn)
             n_steps = 20
             # EXECUTED work: the kernels count the RK4 steps they integrate (an edge stops at its first state that is not
@@ -903,8 +916,9 @@ def main():
                                     "note": "executed f-eval operations only (proximity tests excluded; edges = candidates + "
                                             "goal probes); rank-0 launches of the timed region; `useful` operations of the "
                                             "reference's f-eval, i.e. without its dense products over structural zeros"}
-        # the microbenchmarks and the CPU baselines are single-GPU extras: rank 0 at N = 1 only
-        if not args.no_microbench and world == 1:
+        # the microbenchmarks and the CPU baselines are single-GPU extras of --full: rank 0 at N = 1 only
+        extras = args.full and world == 1
+        if extras and not args.no_microbench:
             # the cloud's hyperbox (the unit cube) is declared, as a planner's topology does: from 5 queries per sweep on
             # that selects the matrix-core pre-filter (same answers); up to 4 the register-direct fp64 sweep runs
             rows = 4 * 1024 * 1024
@@ -917,14 +931,14 @@ def main():
             out["nn_sweep_hbm"]["no_coordinate_bound"] = {
                 k: v for k, v in nn_sweep_microbench(lib, ctx, events, rows, 8, 20).items() if k in keep}
             out["nn_sweep_mfma"] = nn_mfma_microbench(lib, ctx, events)
-        if not args.no_microbench and world == 1:
+        if extras and not args.no_microbench:
             out["single_problem"] = [single_problem_rate(lib, scene, scn, 1, 20000),
                                      single_problem_rate(lib, scene, scn, 16, 20000)]
             if tot["steer_ms"] > 0:
                 out["collide"] = collide_counts(lib, scene, scn, tot["steer_steps"] / (tot["steer_ms"] * 1e-3))
             out["c3_rrtstar"] = c3_rrtstar_rate(lib, ctx, events)
             out["c4_prm_meshes"] = c4_prm_rate(lib, ctx)
-        if not args.no_cpu_baseline and world == 1:
+        if extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(lib, scene, scn, args.max_vertices)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(lib, scene, scn, args.max_vertices)
             out["nn_published_config"] = nn_published_config(lib, ctx, events)

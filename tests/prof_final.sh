@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out
 TAG=$1
 mkdir -p $OUT
 cd $ROOT
-timeout -k 10 900 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench failed"; tail -5 $OUT/${TAG}_bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench failed"; tail -5 $OUT/${TAG}_bench.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench.json"))

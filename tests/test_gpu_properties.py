@@ -204,3 +204,32 @@ def test_c5_workload_on_one_rank():
     assert abs(rec["vertices_per_s"] * secs - P * (nv + 2)) < 1.0
     assert rec["value"] * secs >= P * nv and rec["edges_collision_checked_per_s"] > rec["value"]
     assert rec["best_solution_cost"] is not None and 0.0 < rec["best_solution_cost"] < 50.0
+
+
+def test_c2_plain_run_prints_the_headline_only_and_full_adds_the_rest():
+    """`bench.py` without --full prints the headline and what the timed steps measure (roofline), none of the objects
+    that take runs of their own; --full adds them (here steer_kernels alone: --no-microbench / --no-cpu-baseline leave
+    out the side runs).  A small C2 workload, so that the two child processes take seconds."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--problems", "8",
+            "--max-vertices", "3000"]
+    side = ("steer_kernels", "nn_sweep_hbm", "nn_sweep_mfma", "single_problem", "collide", "c3_rrtstar", "c4_prm_meshes",
+            "cpu_baseline", "cpu_baseline_all_cores", "nn_published_config")
+    recs = []
+    for extra in ([], ["--full", "--no-microbench", "--no-cpu-baseline"]):
+        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        recs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    plain, full = recs
+    for rec in recs:
+        assert rec["unit"] == "valid node expansions/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+        assert rec["steps"] == 1 and rec["warmup"] == 0 and rec["config"]["problems_per_gpu"] == 8
+        assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 - 8 * 3000) < 1.0   # every tree grown to its budget
+        assert rec["roofline"]["launches"] > 0
+    assert not any(k in plain for k in side)
+    assert full["steer_kernels"]["executed_steps"] > 0 and not any(k in full for k in side if k != "steer_kernels")

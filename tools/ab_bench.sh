@@ -11,7 +11,7 @@ i=0
 for v in "$@"; do
   envs=${v%%|*}; args=${v#*|}
   f=$OUT/v$i.json
-  env $envs timeout -k 10 300 python bench.py --no-cpu-baseline --no-microbench $args > $f 2> $OUT/v$i.err || { echo "variant $i failed"; tail -3 $OUT/v$i.err; exit 1; }
+  env $envs timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-microbench $args > $f 2> $OUT/v$i.err || { echo "variant $i failed"; tail -3 $OUT/v$i.err; exit 1; }
   python - "$f" "$v" <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
