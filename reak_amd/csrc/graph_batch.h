@@ -256,6 +256,7 @@ struct GraphBatch {
   QsDev qs;
   bool dynamic = false;  // edges are RK4 propagations through the steerable dynamic space (D = 2 n_dof states)
   DynDev dyn;
+  SteerRequest steer_req;  // RKH_DUO_THRESHOLD, read at create (dynamic space)
   int D = 0, DP = 0;
   uint32_t P = 0, kmax = 0, emax = 0;
   std::vector<GbProblem> prob;
@@ -293,6 +294,7 @@ struct GraphBatch {
     rkh_status st = build_dyn_dev(*space, 1.0, &dyn);
     if (st != RKH_OK) return st;
     dynamic = true;
+    steer_req = steer_request();
     std::memset(&qs, 0, sizeof(qs));
     return init_common(sc, 2 * space->n_dof, n_problems, capacities, kmax_);
   }
@@ -668,11 +670,10 @@ struct GraphBatch {
     any_edges = true;
   }
 
-  // the steer mapping of a step's launch: one wave per edge, or two (state_derivative_duo) while even the launch's upper
-  // bound of edges leaves half the SIMDs idle (RKH_DUO_THRESHOLD, as in the batch planner)
-  int duo_lanes(uint32_t edges_per_problem) const {
-    static const uint32_t thr = [] { const char* e = getenv("RKH_DUO_THRESHOLD"); return e ? uint32_t(std::max(0, atoi(e))) : 512u; }();
-    return (uint64_t(edges_per_problem) * P <= thr && !scene->host.has_meshes && !scene->host.has_prismatic) ? 128 : 64;
+  // the steer mapping of a step's launch of up to `edges` edges per problem: one wave per edge, or two
+  // (state_derivative_duo) while even that bound leaves half the SIMDs idle (steer_mapping)
+  SteerMapping steer(uint32_t edges) const {
+    return steer_mapping(scene->host, SteerEntry::GraphPlanner, steer_req, edges, P, 0);
   }
 
   rkh_status run() {
@@ -680,9 +681,8 @@ struct GraphBatch {
     RKH_HIP(hipMemcpyAsync(d_cmd, h_cmd, cmd_bytes, hipMemcpyHostToDevice, s));
     if (any_append) hipLaunchKernelGGL(gb_prep_kernel, dim3(P), dim3(64), 0, s, d_aux, DP);
     if (any_stage_a) {
-      rkh_status st = dynamic ? launch_propagate(s, *scene, dyn, EdgeIO(), kGbStageA, nullptr, 0, duo_lanes(kGbStageA), d_ioa,
-                                                 nullptr, P)
-                              : launch_edge_check(s, *scene, qs, EdgeIO(), kGbStageA, nullptr, 0, d_ioa, nullptr, P);
+      rkh_status st = dynamic ? launch_propagate(s, *scene, steer(kGbStageA), dyn, EdgeIO(), kGbStageA, 0, d_ioa, nullptr, P)
+                              : launch_edge_check(s, *scene, qs, EdgeIO(), kGbStageA, 0, d_ioa, nullptr, P);
       if (st != RKH_OK) return st;
       hipLaunchKernelGGL(gb_select_kernel, dim3(P), dim3(64), 0, s, d_aux, D, DP);
     }
@@ -693,8 +693,8 @@ struct GraphBatch {
     hipLaunchKernelGGL(gb_list_kernel, dim3(P), dim3(64), 0, s, d_aux);
     if (any_edges) {
       // one wave per edge: a step holds at most 2 k candidates per problem, far from filling the two-lanes mappings
-      rkh_status st = dynamic ? launch_propagate(s, *scene, dyn, EdgeIO(), emax, nullptr, 0, duo_lanes(emax), d_io, nullptr, P)
-                              : launch_edge_check(s, *scene, qs, EdgeIO(), emax, nullptr, 0, d_io, nullptr, P);
+      rkh_status st = dynamic ? launch_propagate(s, *scene, steer(emax), dyn, EdgeIO(), emax, 0, d_io, nullptr, P)
+                              : launch_edge_check(s, *scene, qs, EdgeIO(), emax, 0, d_io, nullptr, P);
       if (st != RKH_OK) return st;
     }
     // the results land in pinned host memory; the acquire load of the step word orders the reads of h_res after it

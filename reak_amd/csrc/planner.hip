@@ -479,7 +479,7 @@ struct rkh_planner {
   uint32_t P = 0;
   std::vector<Problem> prob;
   uint32_t b_max = 1024;
-  int lanes_per_edge = 64;  // 64: one wavefront per candidate edge; 16: four candidates per wave; 2: two lanes per edge
+  SteerMapping steer = SteerMapping::Wave;  // the form of every round's steer launches (steer_mapping; dynamic space)
   double* d_lane_ws = nullptr;  // workspace of the two-lanes-per-edge kernel
   double coord_bound = 0.0;     // max |coordinate| of vertices and samples (hyperbox bounds), 0 = unknown
   uint32_t* d_sel = nullptr;    // [2] edges of the current round (by round parity), see round_begin_kernel
@@ -493,7 +493,7 @@ struct rkh_planner {
   int wave_fit = 1;          // per-round batch scale chosen on the device (round_begin_kernel); RKH_WAVE_FIT=0: off
   double wave_fill = 0.99;   // target fill of the last pass of steer waves (RKH_WAVE_FILL)
   uint32_t wave_slots = 1024;    // SIMDs of the device = concurrent waves of the two-lanes steer kernel
-  uint32_t duo_threshold = 512;   // rounds below this many edges: two waves per edge (RKH_DUO_THRESHOLD; 0 = never)
+  uint32_t duo_threshold = 0;     // Auto rounds below this many edges: two waves per edge (RKH_DUO_THRESHOLD; 0 = never)
   uint32_t lane_threshold = 1024;  // rounds with at least this many edges go to the two-lanes-per-edge kernel (one wave-per-edge pass fills the 1024 SIMDs; measured optimum at 4, 16 and 32 problems, tests/diag_lane_threshold.sh)
   uint32_t part_blocks = 0;
   uint64_t max_capacity = 0;
@@ -610,12 +610,15 @@ uint32_t batch_upper_bound(const PlannerState& st, uint64_t n_ub, float batch_sc
 rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
                         bool compact = false) {
   if (p->quasi_static)
-    return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, nullptr, grid_b, tab_a, tab_b, p->P);
-  if (p->lanes_per_edge != 0)
-    return launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, p->lanes_per_edge, tab_a, tab_b,
-                            p->P, p->d_lane_ws);
-  // automatic: both mappings are launched; on the device each compares the round's edge count with the threshold and
-  // the one that is not chosen exits at once.  Small rounds -> one wave per edge (latency), large -> 32 edges per wave.
+    return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P);
+  if (p->steer != SteerMapping::Auto)
+    return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
+                            p->d_lane_ws);
+  // Auto: every form of the sequence is launched; on the device each compares the round's edge count with its gate and
+  // the ones not chosen exit at once.  Small rounds -> Duo / Wave (latency), large -> Pair (32 edges per wave).
+  auto run = [&](SteerMapping m, double* ws, const KernelGate& gate) {
+    return launch_propagate(p->stream, *p->scene, m, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P, ws, gate);
+  };
   KernelGate gate_wave{p->d_sel + p->round_parity, 0u, p->lane_threshold};
   KernelGate gate_lane{p->d_sel + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
   gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec;
@@ -632,20 +635,15 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate gate_duo = gate_wave;
     gate_duo.hi = std::min(p->duo_threshold, p->lane_threshold);
     gate_wave.lo = gate_duo.hi;
-    st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 128, tab_a, tab_b, p->P, nullptr,
-                          gate_duo);
+    st = run(SteerMapping::Duo, nullptr, gate_duo);
     if (st != RKH_OK) return st;
   }
-  if (gate_wave.lo < gate_wave.hi)
-    st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 64, tab_a, tab_b, p->P, nullptr,
-                          gate_wave);
+  if (gate_wave.lo < gate_wave.hi) st = run(SteerMapping::Wave, nullptr, gate_wave);
   if (st != RKH_OK) return st;
   // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
   // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
   // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
-  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1))
-    return launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
-                            p->d_lane_ws, gate_lane);
+  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws, gate_lane);
   // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
   // rounds take one whole-edge launch
   const uint32_t split_edges = p->split_min_edges;
@@ -656,8 +654,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate whole = gate_lane;
     whole.hi = split_edges;
     if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
-      st = launch_propagate(p->stream, *p->scene, p->dyn, EdgeIO(), grid_a, nullptr, grid_b, 2, tab_a, tab_b, p->P,
-                            p->d_lane_ws, whole);
+      st = run(SteerMapping::Pair, p->d_lane_ws, whole);
       if (st != RKH_OK) return st;
     }
     gate_lane.lo = split_edges;
@@ -665,7 +662,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   if (edges_ub < gate_lane.lo) return RKH_OK;
   const uint32_t epw = pair_kernel_edges_per_wave();
   const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
-  return launch_propagate_pair_steps(p->stream, p->n_dof, p->scene->d_scene, p->dyn, tab_a, tab_b, p->P,
+  return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
                                      p->d_wave_base + (2 * p->P + 1), p->d_step_list[0], p->d_step_list[1], p->d_step_cnt,
                                      p->d_lane_ws, blocks, gate_lane, p->d_steps_exec);
 }
@@ -704,7 +701,7 @@ rkh_status enqueue_round(rkh_planner* p) {
     }
   }
   // the round's batch scale is chosen on the device (round_begin_kernel); the launches are sized for its upper end
-  const bool fit = p->wave_fit && !p->quasi_static && p->lanes_per_edge == 0;
+  const bool fit = p->wave_fit && p->steer == SteerMapping::Auto;
   const float scale = fit ? 1.4f : 1.0f;
   // launch sizes of this round from the host-side bounds
   uint32_t batch_ub = 1;
@@ -878,7 +875,21 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   }
   if (const char* e = getenv("RKH_WAVE_FIT")) p->wave_fit = atoi(e);
   if (const char* e = getenv("RKH_WAVE_FILL")) p->wave_fill = atof(e);
-  {
+  // Many problems per planner: a round's candidates per problem stay within ONE query block of the mirror sweep (a
+  // second block re-reads the whole tree for a handful of queries; 512 problems x 100 000: 7.45 -> 7.62 M expansions/s).
+  // The batch rule only reaches the cap late in a run (1.25 sqrt(n) = 384 at n = 94 k) or through the wave fit's scale.
+  if (nn1_mirror_applies(p->D, p->coord_bound) && n_problems >= 64) p->b_max = std::min(p->b_max, nn1_mirror_queries());
+  if (const char* e = getenv("RKH_BATCH_MAX")) p->b_max = std::max(8, atoi(e));
+  p->b_max = std::min<uint32_t>(p->b_max, 4096);
+  if (const char* e = getenv("RKH_LANE_THRESHOLD")) p->lane_threshold = uint32_t(std::max(0, atoi(e)));
+  if (!p->quasi_static) {
+    const SteerRequest req = steer_request();
+    p->steer = steer_mapping(scene->host, SteerEntry::BatchPlanner, req, 0, n_problems, p->b_max);
+    p->duo_threshold = req.duo_threshold;
+  }
+  // the lane kernel's residency sizes the wave fit and the step-wise launches (the mappings that run it)
+  const bool lane_kernel = p->steer == SteerMapping::Auto || p->steer == SteerMapping::Pair;
+  if (lane_kernel) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, scene->ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
       p->wave_slots = uint32_t(prop.multiProcessorCount) * pair_kernel_waves_per_cu(scene->host.n_dof);
@@ -887,29 +898,6 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   p->split_min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();
   if (const char* e = getenv("RKH_STEER_SPLIT_MIN_EDGES")) p->split_min_edges = uint32_t(std::max(0, atoi(e)));
   p->step_blocks_cap = 2 * p->wave_slots;
-  // Many problems per planner: a round's candidates per problem stay within ONE query block of the mirror sweep (a
-  // second block re-reads the whole tree for a handful of queries; 512 problems x 100 000: 7.45 -> 7.62 M expansions/s).
-  // The batch rule only reaches the cap late in a run (1.25 sqrt(n) = 384 at n = 94 k) or through the wave fit's scale.
-  if (nn1_mirror_applies(p->D, p->coord_bound) && n_problems >= 64) p->b_max = std::min(p->b_max, nn1_mirror_queries());
-  if (const char* e = getenv("RKH_BATCH_MAX")) p->b_max = std::max(8, atoi(e));
-  p->b_max = std::min<uint32_t>(p->b_max, 4096);
-  if (const char* e = getenv("RKH_LANE_THRESHOLD")) p->lane_threshold = uint32_t(std::max(0, atoi(e)));
-  if (const char* e = getenv("RKH_DUO_THRESHOLD")) p->duo_threshold = uint32_t(std::max(0, atoi(e)));
-  if (p->scene->host.has_meshes || p->scene->host.has_prismatic) p->duo_threshold = 0;  // (not instantiated for these)
-  if (const char* e = getenv("RKH_LANES_PER_EDGE")) {
-    p->lanes_per_edge = (atoi(e) == 2) ? 2 : ((atoi(e) == 16) ? 16 : (atoi(e) == 0 ? 0 : 64));
-  } else if (p->n_dof <= 6 && scene_fits_lane_kernel(scene->host)) {
-    p->lanes_per_edge = 0;  // automatic, per round
-  } else {
-    // one wavefront per candidate is the latency-optimal mapping; once a round can offer more waves than the chip
-    // has slots (256 CUs x 4 SIMDs x 2 waves) four candidates share a wave
-    p->lanes_per_edge = (uint64_t(n_problems) * 2 * p->b_max > 4096) ? 16 : 64;
-  }
-  if ((p->lanes_per_edge == 2 || p->lanes_per_edge == 0) && !(p->n_dof <= 7 && scene_fits_lane_kernel(scene->host)))
-    p->lanes_per_edge = 64;  // the two-lanes-per-edge kernel does not take this scene
-  if (p->lanes_per_edge == 16 && 2 * p->n_dof > 16) p->lanes_per_edge = 64;  // a 16-lane group holds at most 16 components
-  if (scene->host.planar) p->lanes_per_edge = 64;  // planar chains have one mapping (one lane per edge, propagate_planar.hip)
-  if (scene->host.has_prismatic) p->lanes_per_edge = 64;  // prismatic joints: one wave per edge only
   if (const char* e = getenv("RKH_PROFILE_NN")) p->profile_nn = atoi(e) != 0;
   // candidates per round = batch_factor * sqrt(n) per problem (results do not depend on it).  More candidates per
   // round mean fewer rounds but more discarded speculation (0.89 of the propagated edges are committed at 1.25, 0.72 at
@@ -942,7 +930,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   RKH_HIP(hipMalloc(&p->d_io_probe, P * sizeof(EdgeIO)));
   // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
   // see prev_batch_ub and flush_probes)
-  if (!p->quasi_static && (p->lanes_per_edge == 2 || p->lanes_per_edge == 0))
+  if (lane_kernel)
     RKH_HIP(hipMalloc(&p->d_lane_ws, propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max + kProbeGranule, P)));
   if (p->d_lane_ws) {
     // two prefix arrays of 2 P + 1 entries: waves of the two-lanes kernel, then single edges (one-wave-per-edge kernel)

@@ -1981,25 +1981,18 @@ __global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __rest
 }
 
 // ---- host launchers ------------------------------------------------------------------------
-#ifndef RKH_PRISMATIC_FORMS
-#define RKH_DISPATCH_N(N_, CALL)     \
-  switch (N_) {                      \
-    case 1: { constexpr int N = 1; CALL; } break; \
-    case 2: { constexpr int N = 2; CALL; } break; \
-    case 3: { constexpr int N = 3; CALL; } break; \
-    case 4: { constexpr int N = 4; CALL; } break; \
-    case 6: { constexpr int N = 6; CALL; } break; \
-    case 7: { constexpr int N = 7; CALL; } break; \
-    case 12: { constexpr int N = 12; CALL; } break; \
-    default:                         \
-      set_error("chains with this number of joints are not instantiated (1,2,3,4,6,7,12)"); \
-      return RKH_ERR_UNSUPPORTED;    \
-  }
+// Written once for both joint kinds: the prismatic translation unit compiles them in rkh::prismatic for its chain sizes
+// and without the duo, 16-lane, support-map and planar forms; the revolute launchers hand scenes with prismatic joints on.
+template <class F>
+static rkh_status with_chain_n(int n, F&& f) {
+  if constexpr (kPrismatic) return with_n<1, 2, 3, 4, 6, 7>(n, f);
+  else return with_n<1, 2, 3, 4, 6, 7, 12>(n, f);
+}
 
-template <int N, int GL, bool GJK, bool DUO = false>
-static void launch_propagate_t(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
-                               const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                               uint32_t n_problems, KernelGate gate) {
+template <int GL, bool GJK, bool DUO = false>
+static rkh_status launch_propagate_t(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                     uint32_t edges_a, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                     uint32_t n_problems, KernelGate gate) {
   constexpr uint32_t G = 64 / GL;
   const uint32_t ga = (edges_a + G - 1) / G, gbk = (edges_b + G - 1) / G;
   dim3 grid(ga + gbk, n_problems);
@@ -2015,47 +2008,47 @@ static void launch_propagate_t(hipStream_t s, const rkh_scene& scene, const DynD
   args.n_pairs = scene.n_pairs_verdict;
   args.dyn = dyn;
   args.io_a = io;
-  args.io_b = io_b;
+  args.io_b = EdgeIO();
   args.tab_a = tab_a;
   args.tab_b = tab_b;
   args.grid_a = ga;
   args.gate = gate;
-  hipLaunchKernelGGL((propagate_kernel<N, GL, GJK, DUO>), grid, dim3(DUO ? 128 : 64), (SmemLayout<N, GL>::bytes(scene.host.n_env)),
-                     s, args);
+  return with_chain_n(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((propagate_kernel<N, GL, GJK, DUO>), grid, dim3(DUO ? 128 : 64),
+                       (SmemLayout<N, GL>::bytes(scene.host.n_env)), s, args);
+  });
 }
 
-// Steer `grid_edges` (+ `grid_b` of a second group) edges per problem.  Either the two EdgeIO are given by value
-// (n_problems = 1) or as device tables of n_problems entries each.
-rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges,
-                            const EdgeIO* io_b, uint32_t grid_b, int lanes_per_edge, const EdgeIO* tab_a,
-                            const EdgeIO* tab_b, uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
-  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
+                            uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                            uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
+  const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
-  const int n_dof = scene.host.n_dof;
-  if (scene.host.planar)  // planar chains: one lane per edge, whatever mapping was asked for (propagate_planar.hip)
-    return launch_propagate_planar(s, n_dof, scene.d_scene, scene.d_pairs, scene.n_pairs_verdict, dyn, io, grid_edges, io_b,
-                                   grid_b, tab_a, tab_b, n_problems, gate);
-  if (scene.host.has_prismatic)  // one wave per edge whatever mapping was asked for (propagate_prismatic.hip)
-    return prismatic::launch_propagate(s, scene, dyn, io, grid_edges, io_b ? *io_b : EdgeIO(), eb, tab_a, tab_b, n_problems,
-                                       gate);
-  if (lanes_per_edge == 2)  // two lanes per edge, two waves per SIMD (propagate_pair.hip)
-    return launch_propagate_pairs(s, n_dof, scene.d_scene, dyn, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems,
-                                  d_lane_ws, gate);
-  const EdgeIO second = io_b ? *io_b : EdgeIO();
-  const bool gjk = scene.host.has_meshes;
-  if (lanes_per_edge == 128 && !gjk) {  // two waves per edge (scenes without vertex-set shapes)
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b,
-                                                                  n_problems, gate)));
-  } else if (lanes_per_edge == 16) {
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 16, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
-                                                           gate)));
-  } else if (gjk) {
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, true>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
-                                                           gate)));
-  } else {  // no vertex-set shapes: the instantiation without the support-map query (no private segment)
-    RKH_DISPATCH_N(n_dof, (launch_propagate_t<N, 64, false>(s, scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems,
-                                                            gate)));
+  rkh_status st;
+  if constexpr (kPrismatic) {
+    st = launch_propagate_t<64, false>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
+  } else {
+    switch (m) {
+      case SteerMapping::Planar:
+        return launch_propagate_planar(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
+      case SteerMapping::Prismatic:
+        return prismatic::launch_propagate(s, scene, m, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_lane_ws, gate);
+      case SteerMapping::Pair:
+        return launch_propagate_pairs(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_lane_ws, gate);
+      case SteerMapping::Duo:
+        st = launch_propagate_t<64, false, true>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
+        break;
+      case SteerMapping::Wave16:
+        st = launch_propagate_t<16, true>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
+        break;
+      default:  // Wave; without vertex-set shapes the instantiation without the support-map query (no private segment)
+        st = scene.host.has_meshes
+                 ? launch_propagate_t<64, true>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate)
+                 : launch_propagate_t<64, false>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
+    }
   }
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -2063,12 +2056,15 @@ rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev&
 rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    double* d_pd, double* d_M, double* d_f, int* d_err) {
   if (B == 0) return RKH_OK;
-  const int n_dof = scene.host.n_dof;
-  if (scene.host.planar)
-    return launch_state_derivative_planar(s, n_dof, scene.d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
-  if (scene.host.has_prismatic) return prismatic::launch_state_derivative(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
-  RKH_DISPATCH_N(n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
-                                           d_pd, d_M, d_f, d_err));
+  if constexpr (!kPrismatic) {
+    if (scene.host.planar) return launch_state_derivative_planar(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+    if (scene.host.has_prismatic) return prismatic::launch_state_derivative(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+  }
+  const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((state_derivative_kernel<decltype(c)::value>), dim3(B), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
+                       d_pd, d_M, d_f, d_err);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -2123,58 +2119,66 @@ template <int N>
 static rkh_status launch_edge_walk(hipStream_t s, dim3 grid, const rkh_scene& scene, const EdgeWalkArgs& ka) {
   const int n_env = scene.host.n_env;
   const uint64_t n_edges = uint64_t(grid.x) * grid.y;
-  if (scene.host.planar) {
-    EdgeWalkArgs pa = ka;
-    switch (edge_check_shape<N>(n_env, ka.n_pairs, n_edges, &pa.pairs_staged)) {
-      case 8: launch_edge_check_t<N, 8>(s, grid, n_env, pa); break;
-      case 4: launch_edge_check_t<N, 4>(s, grid, n_env, pa); break;
-      case 2: launch_edge_check_t<N, 2>(s, grid, n_env, pa); break;
-      default: launch_edge_check_t<N, 1>(s, grid, n_env, pa); break;
-    }
-    return RKH_OK;
-  }
   constexpr int GW = N <= 7 ? 64 : 32;
   const bool wide = n_edges < 2048;
-  if (scene.host.has_meshes)
-    return wide ? launch_edge_points_t<N, true, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, true, 32>(s, grid, n_env, ka);
+  if constexpr (!kPrismatic) {
+    if (scene.host.planar) {
+      EdgeWalkArgs pa = ka;
+      switch (edge_check_shape<N>(n_env, ka.n_pairs, n_edges, &pa.pairs_staged)) {
+        case 8: launch_edge_check_t<N, 8>(s, grid, n_env, pa); break;
+        case 4: launch_edge_check_t<N, 4>(s, grid, n_env, pa); break;
+        case 2: launch_edge_check_t<N, 2>(s, grid, n_env, pa); break;
+        default: launch_edge_check_t<N, 1>(s, grid, n_env, pa); break;
+      }
+      return RKH_OK;
+    }
+    if (scene.host.has_meshes)
+      return wide ? launch_edge_points_t<N, true, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, true, 32>(s, grid, n_env, ka);
+  }
   return wide ? launch_edge_points_t<N, false, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, false, 32>(s, grid, n_env, ka);
 }
 
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
-                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                             uint32_t n_problems) {
-  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
+                             uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems) {
+  const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
-  if (scene.host.has_prismatic)
-    return prismatic::launch_edge_check(s, scene, qs, io, grid_edges, io_b, grid_b, tab_a, tab_b, n_problems);
+  if constexpr (!kPrismatic)
+    if (scene.host.has_prismatic)
+      return prismatic::launch_edge_check(s, scene, qs, io, grid_edges, eb, tab_a, tab_b, n_problems);
   EdgeWalkArgs ka;
   ka.sc = scene.d_scene;
   ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
   ka.n_pairs = scene.n_pairs_verdict;
   ka.qs = qs;
   ka.io_a = io;
-  ka.io_b = io_b ? *io_b : EdgeIO();
+  ka.io_b = EdgeIO();
   ka.tab_a = tab_a;
   ka.tab_b = tab_b;
   ka.grid_a = grid_edges;
   ka.pairs_staged = 0;
   const dim3 grid(grid_edges + eb, n_problems);
   rkh_status st = RKH_OK;
-  RKH_DISPATCH_N(scene.host.n_dof, (st = launch_edge_walk<N>(s, grid, scene, ka)));
+  const rkh_status sn =
+      with_chain_n(scene.host.n_dof, [&](auto c) { st = launch_edge_walk<decltype(c)::value>(s, grid, scene, ka); });
+  if (sn != RKH_OK) return sn;
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
+#ifndef RKH_PRISMATIC_FORMS  // the f-eval cycle probes instrument the revolute forms only
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink) {
   if (scene.host.has_prismatic) {
     set_error("rkh_diag_feval_cycles: scenes with prismatic joints are not instrumented");
     return RKH_ERR_UNSUPPORTED;
   }
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128),
-                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene, d_x, d_u,
-                                                      iters, d_out, d_sink));
+  const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128), (SmemLayout<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene, d_x, d_u, iters, d_out, d_sink);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -2185,120 +2189,33 @@ rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const doub
     set_error("rkh_diag_feval_cycles: scenes with prismatic joints are not instrumented");
     return RKH_ERR_UNSUPPORTED;
   }
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64),
-                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
-                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, d_u,
-                                                      iters, d_out, d_sink));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
-rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
-  if (B == 0) return RKH_OK;
-  if (scene.host.has_prismatic) return prismatic::launch_min_distance(s, scene, d_x, B, d_dist);
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64),
-                                                      (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
-                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B,
-                                                      d_dist));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
-#else   // RKH_PRISMATIC_FORMS: the launchers of the prismatic forms (rkh_internal.h), chains of 1, 2, 3, 4, 6 and 7 joints
-#define RKH_DISPATCH_N(N_, CALL)     \
-  switch (N_) {                      \
-    case 1: { constexpr int N = 1; CALL; } break; \
-    case 2: { constexpr int N = 2; CALL; } break; \
-    case 3: { constexpr int N = 3; CALL; } break; \
-    case 4: { constexpr int N = 4; CALL; } break; \
-    case 6: { constexpr int N = 6; CALL; } break; \
-    case 7: { constexpr int N = 7; CALL; } break; \
-    default:                         \
-      set_error("chains with prismatic joints are instantiated for 1, 2, 3, 4, 6 and 7 joints"); \
-      return RKH_ERR_UNSUPPORTED;    \
-  }
-
-rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
-                            const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                            uint32_t n_problems, KernelGate gate) {
-  WaveArgs args;
-  args.sc = scene.d_scene;
-  args.pairs = static_cast<const PairDev*>(scene.d_pairs);
-  args.n_pairs = scene.n_pairs_verdict;
-  args.dyn = dyn;
-  args.io_a = io;
-  args.io_b = io_b;
-  args.tab_a = tab_a;
-  args.tab_b = tab_b;
-  args.grid_a = edges_a;
-  args.gate = gate;
-  dim3 grid(edges_a + edges_b, n_problems);
-  if (gate.wave_base) grid = dim3(uint32_t(std::min<uint64_t>(uint64_t(edges_a + edges_b) * n_problems, gate.hi)), 1);
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((propagate_kernel<N, 64, false>), grid, dim3(64),
-                                                      (SmemLayout<N, 64>::bytes(scene.host.n_env)), s, args));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
-rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
-                                   double* d_pd, double* d_M, double* d_f, int* d_err) {
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((state_derivative_kernel<N>), dim3(B), dim3(64), 0, s, scene.d_scene,
-                                                      d_x, d_u, B, d_pd, d_M, d_f, d_err));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
-rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
-  RKH_DISPATCH_N(scene.host.n_dof, hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64),
-                                                      (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s, scene.d_scene,
-                                                      static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B,
-                                                      d_dist));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
-template <int N, int G>
-static rkh_status launch_edge_points_t(hipStream_t s, dim3 grid, int n_env, EdgeWalkArgs ka) {
-  static_assert(EdgePointsSmem<N, G>::bytes(kMaxEnvShapes, 0) <= 160 * 1024, "edge_points_kernel: LDS over 160 KB");
-  const size_t with_pairs = EdgePointsSmem<N, G>::bytes(n_env, ka.n_pairs);
-  ka.pairs_staged = with_pairs <= 160 * 1024;
-  const size_t smem = ka.pairs_staged ? with_pairs : EdgePointsSmem<N, G>::bytes(n_env, 0);
-  auto kern = edge_points_kernel<N, false, G>;
-  static bool big_lds = false;  // (per instantiation) more than the default 64 KB of dynamic LDS: ask once
-  if (smem > 65536 && !big_lds) {
-    RKH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    big_lds = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, ka);
-  return RKH_OK;
-}
-
-// the 3D edge walk's form choice (rkh::launch_edge_walk) without the support-map query
-rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
-                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                             uint32_t n_problems) {
-  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
-  EdgeWalkArgs ka;
-  ka.sc = scene.d_scene;
-  ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
-  ka.n_pairs = scene.n_pairs_verdict;
-  ka.qs = qs;
-  ka.io_a = io;
-  ka.io_b = io_b ? *io_b : EdgeIO();
-  ka.tab_a = tab_a;
-  ka.tab_b = tab_b;
-  ka.grid_a = grid_edges;
-  ka.pairs_staged = 0;
-  const dim3 grid(grid_edges + eb, n_problems);
-  const bool wide = uint64_t(grid.x) * grid.y < 2048;
-  rkh_status st = RKH_OK;
-  RKH_DISPATCH_N(scene.host.n_dof, (st = wide ? launch_edge_points_t<N, 64>(s, grid, scene.host.n_env, ka)
-                                              : launch_edge_points_t<N, 32>(s, grid, scene.host.n_env, ka)));
+  const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64), (SmemLayout<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, d_u, iters, d_out,
+                       d_sink);
+  });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
-}  // namespace prismatic
-#endif  // RKH_PRISMATIC_FORMS
+#endif
 
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
+  if (B == 0) return RKH_OK;
+  if constexpr (!kPrismatic)
+    if (scene.host.has_prismatic) return prismatic::launch_min_distance(s, scene, d_x, B, d_dist);
+  const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B, d_dist);
+  });
+  if (st != RKH_OK) return st;
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+#ifdef RKH_PRISMATIC_FORMS
+}  // namespace prismatic
+#endif
 }  // namespace rkh

@@ -1188,25 +1188,6 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   }
 }
 
-template <int N>
-static void launch_pair_step_t(hipStream_t s, const PairStepArgs& args, uint32_t blocks) {
-  hipLaunchKernelGGL((propagate_pair_step_kernel<N>), dim3(blocks), dim3(64), 0, s, args);
-}
-static rkh_status launch_pair_step_n(hipStream_t s, int n_dof, const PairStepArgs& args, uint32_t blocks) {
-  switch (n_dof) {
-    case 1: launch_pair_step_t<1>(s, args, blocks); break;
-    case 2: launch_pair_step_t<2>(s, args, blocks); break;
-    case 3: launch_pair_step_t<3>(s, args, blocks); break;
-    case 4: launch_pair_step_t<4>(s, args, blocks); break;
-    case 6: launch_pair_step_t<6>(s, args, blocks); break;
-    case 7: launch_pair_step_t<7>(s, args, blocks); break;
-    default:
-      set_error("propagate: chains with this number of joints are not instantiated (1,2,3,4,6,7)");
-      return RKH_ERR_UNSUPPORTED;
-  }
-  return RKH_OK;
-}
-
 size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks) {
   return size_t(blocks) * size_t(6 * ((n_dof + 1) / 2)) * 64 * sizeof(double);
 }
@@ -1214,13 +1195,13 @@ size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks) {
 // The steer launches of a round, one per step, over two ping-pong lists; d_cnt[k] = entries of the list launch k reads
 // (d_cnt[1 .. n_steps] must be zero when the first launch starts: round_begin_kernel clears them).  `blocks` bounds the
 // grids; a launch with more chunks than blocks strides over them.
-rkh_status launch_propagate_pair_steps(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn,
-                                       const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
-                                       const uint32_t* d_edge_base, uint2* d_list0, uint2* d_list1, uint32_t* d_cnt,
-                                       double* d_ws, uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec) {
+rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
+                                       const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
+                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
+                                       KernelGate gate, unsigned long long* d_steps_exec) {
   if (blocks == 0 || n_problems == 0) return RKH_OK;
   PairStepArgs args;
-  args.sc = d_scene;
+  args.sc = scene.d_scene;
   args.dyn = dyn;
   args.tab_a = tab_a;
   args.tab_b = tab_b;
@@ -1229,15 +1210,17 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, int n_dof, const SceneDev*
   args.edge_base = d_edge_base;
   args.n_segments = 2 * n_problems;
   args.steps_exec = d_steps_exec;
-  for (int k = 0; k < dyn.n_steps; ++k) {
-    args.step = uint32_t(k);
-    args.list_in = (k & 1) ? d_list1 : d_list0;
-    args.list_out = (k & 1) ? d_list0 : d_list1;
-    args.cnt_in = d_cnt + k;
-    args.cnt_out = d_cnt + k + 1;
-    const rkh_status st = launch_pair_step_n(s, n_dof, args, blocks);
-    if (st != RKH_OK) return st;
-  }
+  const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    for (int k = 0; k < dyn.n_steps; ++k) {
+      args.step = uint32_t(k);
+      args.list_in = (k & 1) ? d_list1 : d_list0;
+      args.list_out = (k & 1) ? d_list0 : d_list1;
+      args.cnt_in = d_cnt + k;
+      args.cnt_out = d_cnt + k + 1;
+      hipLaunchKernelGGL((propagate_pair_step_kernel<decltype(c)::value>), dim3(blocks), dim3(64), 0, s, args);
+    }
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -1313,26 +1296,25 @@ __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __re
   }
 }
 
-rkh_status launch_pair_counts(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, uint32_t B,
+rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out) {
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
-  switch (n_dof) {
-    case 6: hipLaunchKernelGGL((pair_counts_kernel<6>), dim3(waves), dim3(64), 0, s, d_scene, d_x, B, d_out); break;
-    case 3: hipLaunchKernelGGL((pair_counts_kernel<3>), dim3(waves), dim3(64), 0, s, d_scene, d_x, B, d_out); break;
-    default: set_error("pair diagnostics: instantiated for 3 and 6 joints"); return RKH_ERR_UNSUPPORTED;
-  }
+  const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, B, d_out);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_pair_cycles(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, const double* d_u,
-                              uint32_t B, int iters, unsigned long long* d_out, double* d_sink) {
+rkh_status launch_pair_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                              int iters, unsigned long long* d_out, double* d_sink) {
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
-  switch (n_dof) {
-    case 6: hipLaunchKernelGGL((pair_cycles_kernel<6>), dim3(waves), dim3(64), 0, s, d_scene, d_x, d_u, B, iters, d_out, d_sink); break;
-    case 3: hipLaunchKernelGGL((pair_cycles_kernel<3>), dim3(waves), dim3(64), 0, s, d_scene, d_x, d_u, B, iters, d_out, d_sink); break;
-    default: set_error("pair diagnostics: instantiated for 3 and 6 joints"); return RKH_ERR_UNSUPPORTED;
-  }
+  const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((pair_cycles_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
+                       iters, d_out, d_sink);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
@@ -1345,45 +1327,30 @@ size_t propagate_pairs_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edg
   return waves * slots * 64 * sizeof(double);
 }
 
-template <int N>
-static void launch_pair_t(hipStream_t s, const SceneDev* d_scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
-                          const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                          uint32_t n_problems, double* d_ws, KernelGate gate) {
-  const uint32_t ga = (edges_a + kPairEdges - 1) / kPairEdges, gbk = (edges_b + kPairEdges - 1) / kPairEdges;
-  PairArgs args;
-  args.sc = d_scene;
-  args.dyn = dyn;
-  args.io_a = io;
-  args.io_b = io_b;
-  args.tab_a = tab_a;
-  args.tab_b = tab_b;
-  args.grid_a = ga;
-  args.ws_all = d_ws;
-  args.gate = gate;
-  hipLaunchKernelGGL((propagate_pair_kernel<N>), dim3(ga + gbk, n_problems), dim3(64), 0, s, args);
-}
-
-rkh_status launch_propagate_pairs(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn, const EdgeIO& io,
-                                  uint32_t grid_edges, const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a,
-                                  const EdgeIO* tab_b, uint32_t n_problems, double* d_ws, KernelGate gate) {
-  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
+rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                  uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                  uint32_t n_problems, double* d_ws, KernelGate gate) {
+  const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
   if (!d_ws) {
     set_error("propagate (two lanes per edge): no workspace");
     return RKH_ERR_BAD_ARG;
   }
-  const EdgeIO second = io_b ? *io_b : EdgeIO();
-  switch (n_dof) {
-    case 1: launch_pair_t<1>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    case 2: launch_pair_t<2>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    case 3: launch_pair_t<3>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    case 4: launch_pair_t<4>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    case 6: launch_pair_t<6>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    case 7: launch_pair_t<7>(s, d_scene, dyn, io, grid_edges, second, eb, tab_a, tab_b, n_problems, d_ws, gate); break;
-    default:
-      set_error("propagate: chains with this number of joints are not instantiated (1,2,3,4,6,7)");
-      return RKH_ERR_UNSUPPORTED;
-  }
+  const uint32_t ga = (grid_edges + kPairEdges - 1) / kPairEdges, gbk = (eb + kPairEdges - 1) / kPairEdges;
+  PairArgs args;
+  args.sc = scene.d_scene;
+  args.dyn = dyn;
+  args.io_a = io;
+  args.io_b = EdgeIO();
+  args.tab_a = tab_a;
+  args.tab_b = tab_b;
+  args.grid_a = ga;
+  args.ws_all = d_ws;
+  args.gate = gate;
+  const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((propagate_pair_kernel<decltype(c)::value>), dim3(ga + gbk, n_problems), dim3(64), 0, s, args);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -1394,15 +1361,9 @@ uint32_t pair_kernel_edges_per_wave() { return uint32_t(kPairEdges); }
 uint32_t pair_kernel_waves_per_cu(int n_dof) {
   int blocks = 0;
   hipError_t e = hipErrorInvalidValue;
-  switch (n_dof) {
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<1>, 64, 0); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<2>, 64, 0); break;
-    case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<3>, 64, 0); break;
-    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<4>, 64, 0); break;
-    case 6: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<6>, 64, 0); break;
-    case 7: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<7>, 64, 0); break;
-    default: break;
-  }
+  with_n<1, 2, 3, 4, 6, 7>(n_dof, [&](auto c) {
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, propagate_pair_kernel<decltype(c)::value>, 64, 0);
+  });
   return (e == hipSuccess && blocks > 0) ? uint32_t(blocks) : 8u;
 }
 

@@ -412,41 +412,32 @@ __global__ __launch_bounds__(64) void planar_state_derivative_kernel(const Scene
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-#define RKH_DISPATCH_N_PLANAR(N_, CALL)                                                                  \
-  switch (N_) {                                                                                          \
-    case 1: { constexpr int N = 1; CALL; } break;                                                        \
-    case 2: { constexpr int N = 2; CALL; } break;                                                        \
-    case 3: { constexpr int N = 3; CALL; } break;                                                        \
-    case 4: { constexpr int N = 4; CALL; } break;                                                        \
-    case 6: { constexpr int N = 6; CALL; } break;                                                        \
-    case 7: { constexpr int N = 7; CALL; } break;                                                        \
-    default:                                                                                             \
-      set_error("planar dynamics: chains with this number of joints are not instantiated (1,2,3,4,6,7)"); \
-      return RKH_ERR_UNSUPPORTED;                                                                        \
-  }
-
-rkh_status launch_propagate_planar(hipStream_t s, int n_dof, const SceneDev* d_scene, const void* d_pairs, int n_pairs,
-                                   const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges, const EdgeIO* io_b,
-                                   uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
-                                   KernelGate gate) {
-  const uint32_t eb = (io_b || tab_b) ? grid_b : 0u;
+rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                   uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                   uint32_t n_problems, KernelGate gate) {
+  const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
   const uint32_t blocks_a = (grid_edges + 63) / 64, blocks_b = (eb + 63) / 64;
-  const EdgeIO second = io_b ? *io_b : EdgeIO();
   gate.wave_base = nullptr;  // the compact wave numbering of the 3D mappings does not apply: plain (block, problem) grid
   gate.n_segments = 0;
-  RKH_DISPATCH_N_PLANAR(n_dof, hipLaunchKernelGGL((planar_propagate_kernel<N>), dim3(blocks_a + blocks_b, n_problems), dim3(64),
-                                                  0, s, d_scene, static_cast<const PairDev*>(d_pairs), n_pairs, dyn, io, second,
-                                                  tab_a, tab_b, blocks_a, gate));
+  const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((planar_propagate_kernel<decltype(c)::value>), dim3(blocks_a + blocks_b, n_problems), dim3(64), 0, s,
+                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs_verdict, dyn, io, EdgeIO(),
+                       tab_a, tab_b, blocks_a, gate);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-rkh_status launch_state_derivative_planar(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x,
-                                          const double* d_u, uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err) {
+rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u,
+                                          uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err) {
   if (B == 0) return RKH_OK;
-  RKH_DISPATCH_N_PLANAR(n_dof, hipLaunchKernelGGL((planar_state_derivative_kernel<N>), dim3((B + 63) / 64), dim3(64), 0, s,
-                                                  d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err));
+  const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    hipLaunchKernelGGL((planar_state_derivative_kernel<decltype(c)::value>), dim3((B + 63) / 64), dim3(64), 0, s,
+                       scene.d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+  });
+  if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }

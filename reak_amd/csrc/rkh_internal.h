@@ -2,9 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rkh.h"
@@ -22,6 +25,17 @@ void set_error(const std::string& msg);
       return (_e == hipErrorOutOfMemory) ? RKH_ERR_OOM : RKH_ERR_DEVICE;                       \
     }                                                                                          \
   } while (0)
+
+// Calls f(std::integral_constant<int, N>()) for the N of Ns... equal to n: the chain sizes a launcher's kernels are
+// instantiated for.  Any other n: RKH_ERR_UNSUPPORTED, with the list in the error message.
+template <int... Ns, class F>
+rkh_status with_n(int n, F&& f) {
+  if ((... || (n == Ns && (f(std::integral_constant<int, Ns>()), true)))) return RKH_OK;
+  std::string list;
+  ((list += (list.empty() ? "" : ", ") + std::to_string(Ns)), ...);
+  set_error("chains of " + std::to_string(n) + " joints: these kernels are instantiated for " + list + " joints");
+  return RKH_ERR_UNSUPPORTED;
+}
 
 constexpr int kMaxDof = 12;         // joints of a scene (dynamics kernels: 1, 2, 3, 6; quasi-static kernels also 12)
 constexpr int kMaxEnvShapes = 256;  // environment shapes resident in LDS
@@ -305,36 +319,109 @@ struct KernelGate {
   // ended it included) -- the executed work of a launch, as opposed to n_steps per launched edge
   unsigned long long* steps_exec = nullptr;
 };
-// The launchers below that take the scene read its kind (planar, vertex-set shapes) from scene.host; the verdict
-// kernels (propagate, edge walk) scan its first n_pairs_verdict pairs, min_distance and the f-eval probes all n_pairs.
-rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges,
-                            const EdgeIO* io_b = nullptr, uint32_t grid_b = 0, int lanes_per_edge = 64,
-                            const EdgeIO* tab_a = nullptr, const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1,
-                            double* d_lane_ws = nullptr, KernelGate gate = KernelGate());
-// the two-lanes-per-edge kernel handles one serial chain, with at most a tip-to-world beam
+// ---- steer mapping ---------------------------------------------------------------------------------------------------
+// The kernel form that steers the edges of a dynamic-space launch.
+enum class SteerMapping : uint8_t {
+  Auto,       // batch planner rounds: Duo, Wave or Pair by the round's edge count, read on the device (launch_edges)
+  Duo,        // two waves per edge (state_derivative_duo)
+  Wave,       // one wave per edge (the form with the support-map query for scenes with vertex-set shapes)
+  Wave16,     // four edges per wave, 16 lanes each (the form with the support-map query)
+  Pair,       // two lanes per edge, 32 edges per wave (propagate_pair.hip)
+  Planar,     // planar chains: one lane per edge (propagate_planar.hip)
+  Prismatic,  // chains with prismatic joints: one wave per edge, no support-map query (propagate_prismatic.hip)
+};
+enum class SteerEntry : uint8_t { BatchPlanner, GraphPlanner, Propagate, CycleProbe };
+
+// The knobs of the mapping, read when a planner is created or rkh_propagate / the cycle probe is called.
+struct SteerRequest {
+  bool lanes_set = false;
+  int lanes = 0;                 // RKH_LANES_PER_EDGE
+  uint32_t duo_threshold = 512;  // RKH_DUO_THRESHOLD (0: never)
+};
+inline SteerRequest steer_request() {
+  SteerRequest r;
+  if (const char* e = getenv("RKH_LANES_PER_EDGE")) r.lanes_set = true, r.lanes = atoi(e);
+  if (const char* e = getenv("RKH_DUO_THRESHOLD")) r.duo_threshold = uint32_t(std::max(0, atoi(e)));
+  return r;
+}
+
+// the two-lanes-per-edge kernel handles one serial chain of at most 7 joints, with at most a tip-to-world beam
 inline bool scene_fits_lane_kernel(const SceneDev& S) {
   if (S.has_meshes) return false;  // GJK pairs run in the wave-per-edge / quasi-static kernels
   if (S.has_prismatic) return false;  // prismatic joints: the one-wave-per-edge kernel
-  return S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
+  return S.n_dof <= 7 && S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
 }
+
+// The steer plan: the one place that chooses the form steering a launch of `edges` edges per problem for n_problems
+// problems (b_max: the batch planner's final bound of candidates per problem and round).
+//   Batch planner (rkh_planner_create*, dynamic space), at create: RKH_LANES_PER_EDGE 0 -> Auto, 2 -> Pair, 16 -> Wave16,
+//     any other value (128 included) -> Wave.  Unset: Auto if n_dof <= 6 and scene_fits_lane_kernel, else Wave16 if
+//     n_problems * 2 * b_max > 4096 (a round offers more waves than the chip has slots), else Wave.  Auto rounds run
+//     Duo below min(RKH_DUO_THRESHOLD, lane threshold) edges (compact rounds only; Auto never sees vertex-set shapes or
+//     prismatic joints), Wave below the lane threshold and Pair from there on.
+//   rkh_propagate, every call: unset -> Duo if edges <= 512, else Wave; 2 -> Pair, 16 -> Wave16, 128 -> Duo, any other
+//     value -> Wave.
+//   Graph planners (dynamic space), every launch: Duo if edges * n_problems <= RKH_DUO_THRESHOLD (read at create), else
+//     Wave; RKH_LANES_PER_EDGE does not apply.
+//   Then for these three: Pair or Auto on a scene the lane kernel does not fit -> Wave; Wave16 with 2 n_dof > 16 (a
+//     16-lane group holds at most 16 components) -> Wave; planar chains -> Planar; prismatic joints -> Prismatic; Duo on
+//     a scene with vertex-set shapes -> Wave (its support-map form).
+//   Cycle probe (rkh_diag_feval_cycles), every call: 2 -> Pair, 128 -> Duo, any other value -> Wave; no scene rule.
+//   rkh_diag_proximity_counts: scenes of scene_fits_lane_kernel only.
+inline SteerMapping steer_mapping(const SceneDev& S, SteerEntry entry, const SteerRequest& req, uint64_t edges,
+                                  uint32_t n_problems, uint32_t b_max) {
+  using M = SteerMapping;
+  M m = M::Wave;
+  switch (entry) {
+    case SteerEntry::BatchPlanner:
+      if (req.lanes_set) m = req.lanes == 0 ? M::Auto : (req.lanes == 2 ? M::Pair : (req.lanes == 16 ? M::Wave16 : M::Wave));
+      else if (S.n_dof <= 6 && scene_fits_lane_kernel(S)) m = M::Auto;
+      else m = (uint64_t(n_problems) * 2 * b_max > 4096) ? M::Wave16 : M::Wave;
+      break;
+    case SteerEntry::Propagate:
+      if (!req.lanes_set) m = edges <= 512 ? M::Duo : M::Wave;
+      else m = req.lanes == 2 ? M::Pair : (req.lanes == 16 ? M::Wave16 : (req.lanes == 128 ? M::Duo : M::Wave));
+      break;
+    case SteerEntry::GraphPlanner:
+      m = (edges * n_problems <= req.duo_threshold) ? M::Duo : M::Wave;
+      break;
+    case SteerEntry::CycleProbe:
+      return req.lanes == 2 ? M::Pair : (req.lanes == 128 ? M::Duo : M::Wave);
+  }
+  if ((m == M::Pair || m == M::Auto) && !scene_fits_lane_kernel(S)) m = M::Wave;
+  if (m == M::Wave16 && 2 * S.n_dof > 16) m = M::Wave;
+  if (S.planar) return M::Planar;
+  if (S.has_prismatic) return M::Prismatic;
+  if (m == M::Duo && S.has_meshes) m = M::Wave;
+  return m;
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------
+// They read the scene's kind (planar, vertex-set shapes, prismatic joints) from scene.host; the verdict kernels
+// (propagate, edge walk) scan its first n_pairs_verdict pairs, min_distance and the f-eval probes all n_pairs.  Edge
+// launches take grid_edges (+ grid_b of a second group) edges per problem: `io` by value (n_problems = 1, no second
+// group) or two device tables of n_problems entries each.
+// launch_propagate runs the form `m` it is given (steer_mapping chooses it; Pair needs d_lane_ws).
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
+                            uint32_t grid_edges, uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr,
+                            const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1, double* d_lane_ws = nullptr,
+                            KernelGate gate = KernelGate());
 rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    double* d_pd, double* d_M, double* d_f, int* d_err);
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
-                             const EdgeIO* io_b = nullptr, uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr,
-                             const EdgeIO* tab_b = nullptr, uint32_t n_problems = 1);
-// Scenes with prismatic joints (SceneDev::has_prismatic; propagate_prismatic.hip): one wave per edge, no support-map
-// query; the launchers above route these scenes here whatever mapping was asked for.
+                             uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr, const EdgeIO* tab_b = nullptr,
+                             uint32_t n_problems = 1);
+// The same four compiled for chains with prismatic joints (propagate_prismatic.hip); the ones above hand these scenes on.
 namespace prismatic {
-rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io, uint32_t edges_a,
-                            const EdgeIO& io_b, uint32_t edges_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                            uint32_t n_problems, KernelGate gate);
+rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
+                            uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                            uint32_t n_problems, double* d_lane_ws, KernelGate gate);
 rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    double* d_pd, double* d_M, double* d_f, int* d_err);
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
-                             const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                             uint32_t n_problems);
+                             uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems);
 }  // namespace prismatic
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink);
@@ -342,27 +429,26 @@ rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const doub
                                int iters, unsigned long long* d_out, double* d_sink);
 // two-lanes-per-edge kernel (propagate_pair.hip): 32 edges per wave, two waves per SIMD; scenes: scene_fits_lane_kernel
 size_t propagate_pairs_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edges_b, uint32_t n_problems);
-// planar chains (propagate_planar.hip): one lane per edge
-rkh_status launch_propagate_planar(hipStream_t s, int n_dof, const SceneDev* d_scene, const void* d_pairs, int n_pairs,
-                                   const DynDev& dyn, const EdgeIO& io, uint32_t grid_edges, const EdgeIO* io_b,
-                                   uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
-                                   KernelGate gate);
-rkh_status launch_state_derivative_planar(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x,
-                                          const double* d_u, uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
-rkh_status launch_propagate_pairs(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn, const EdgeIO& io,
-                                  uint32_t grid_edges, const EdgeIO* io_b, uint32_t grid_b, const EdgeIO* tab_a,
-                                  const EdgeIO* tab_b, uint32_t n_problems, double* d_ws, KernelGate gate = KernelGate());
+rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                  uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                  uint32_t n_problems, double* d_ws, KernelGate gate);
 // the same mapping, one launch per RK4 step over the live edges of all problems (see propagate_pair_step_kernel)
 size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks);
-rkh_status launch_propagate_pair_steps(hipStream_t s, int n_dof, const SceneDev* d_scene, const DynDev& dyn,
-                                       const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems,
-                                       const uint32_t* d_edge_base, uint2* d_list0, uint2* d_list1, uint32_t* d_cnt,
-                                       double* d_ws, uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
+rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
+                                       const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
+                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
+                                       KernelGate gate, unsigned long long* d_steps_exec);
 uint32_t pair_kernel_waves_per_cu(int n_dof);
 uint32_t pair_kernel_edges_per_wave();
-rkh_status launch_pair_counts(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, uint32_t B,
+rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out);
-rkh_status launch_pair_cycles(hipStream_t s, int n_dof, const SceneDev* d_scene, const double* d_x, const double* d_u,
-                              uint32_t B, int iters, unsigned long long* d_out, double* d_sink);
+rkh_status launch_pair_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
+                              int iters, unsigned long long* d_out, double* d_sink);
+// planar chains (propagate_planar.hip): one lane per edge
+rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                   uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                   uint32_t n_problems, KernelGate gate);
+rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u,
+                                          uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
 rkh_status build_dyn_dev(const rkh_dyn_space& sp, double fraction, DynDev* out);
 }  // namespace rkh

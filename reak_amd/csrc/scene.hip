@@ -761,16 +761,12 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   io.record = record ? drec.as<double>() : nullptr;
   io.record_stride = rec_stride;
   io.err_flag = scene->d_err;
-  // RKH_LANES_PER_EDGE = 128 (two waves per edge) | 64 | 16 | 2 selects the kernel mapping (identical results); by
-  // default a call of few edges -- the adaptors steer ONE edge per call -- takes the lowest-latency mapping
-  int lanes = (B <= 512) ? 128 : 64;
-  if (const char* ev = getenv("RKH_LANES_PER_EDGE"))
-    lanes = (atoi(ev) == 2) ? 2 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 128 ? 128 : 64));
-  if (lanes == 2 && !(n <= 7 && scene_fits_lane_kernel(scene->host))) lanes = 64;  // not a scene for that mapping
-  if (lanes == 16 && 2 * n > 16) lanes = 64;
+  // the mapping (identical results): by default a call of few edges -- the adaptors steer ONE edge per call -- takes the
+  // lowest-latency one (steer_mapping)
+  const SteerMapping m = steer_mapping(scene->host, SteerEntry::Propagate, steer_request(), B, 1, 0);
   DevBuf dws;
-  if (lanes == 2) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
-  st = launch_propagate(s, *scene, dyn, io, B, nullptr, 0, lanes, nullptr, nullptr, 1, dws.as<double>());
+  if (m == SteerMapping::Pair) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
+  st = launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, dws.as<double>());
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(x_out, dxo.p, size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(steps_free, dsf.p, size_t(B) * 4, hipMemcpyDeviceToHost, s));
@@ -793,12 +789,12 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
   RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
   RKH_HIP(hipMemcpyAsync(du.p, u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
   rkh_status st;
-  const char* ev = getenv("RKH_LANES_PER_EDGE");
-  if (ev && atoi(ev) == 2) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
+  const SteerMapping m = steer_mapping(scene->host, SteerEntry::CycleProbe, steer_request(), B, 1, 0);
+  if (m == SteerMapping::Pair) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
     RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
-    st = launch_pair_cycles(s, n, scene->d_scene, dx.as<double>(), du.as<double>(), B, iters,
-                            dout.as<unsigned long long>(), dsink.as<double>());
-  } else if (ev && atoi(ev) == 128) {  // two waves per edge: B / 2 states, rows 2 b / 2 b + 1 = the two waves' counters
+    st = launch_pair_cycles(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
+                            dsink.as<double>());
+  } else if (m == SteerMapping::Duo) {  // two waves per edge: B / 2 states, rows 2 b / 2 b + 1 = the two waves' counters
     RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
     st = (B >= 2) ? launch_feval_cycles_duo(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
                                             dsink.as<double>())
@@ -817,7 +813,7 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
   if (scene && reject_branches(scene) != RKH_OK) return RKH_ERR_UNSUPPORTED;
   if (!scene || !x || !counts || B == 0) return RKH_ERR_BAD_ARG;
   const int n = scene->host.n_dof;
-  if (!(n <= 7 && scene_fits_lane_kernel(scene->host))) {
+  if (!scene_fits_lane_kernel(scene->host)) {
     set_error("proximity counts: a scene of the two-lanes steer mapping is needed");
     return RKH_ERR_UNSUPPORTED;
   }
@@ -827,7 +823,7 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
   RKH_HIP(hipMalloc(&dout.p, 8 * 8));
   RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
   RKH_HIP(hipMemsetAsync(dout.p, 0, 8 * 8, s));
-  const rkh_status st = launch_pair_counts(s, n, scene->d_scene, dx.as<double>(), B, dout.as<unsigned long long>());
+  const rkh_status st = launch_pair_counts(s, *scene, dx.as<double>(), B, dout.as<unsigned long long>());
   if (st != RKH_OK) return st;
   RKH_HIP(hipMemcpyAsync(counts, dout.p, 8 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
