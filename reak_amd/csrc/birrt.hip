@@ -13,25 +13,14 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <random>
 
-#include "graph_batch.h"
-#include "rkh_internal.h"
+#include "graph_planner.h"
 
 using namespace rkh;
 
 namespace {
-constexpr uint32_t NIL = 0xFFFFFFFFu;
-
-double euclid(const double* a, const double* b, int D) {  // vect_distance_metrics.hpp:126-137
-  double r = 0.0;
-  for (int i = 0; i < D; ++i) {
-    const double d = a[i] - b[i];
-    r += d * d;
-  }
-  return std::sqrt(r);
-}
-
 struct BiProblem {
   rkh_rrt_params prm;
   std::mt19937 eng;
@@ -52,11 +41,7 @@ struct BiProblem {
 };
 }  // namespace
 
-struct rkh_birrt {
-  GraphBatch gb;
-  int D = 0;
-  uint32_t P = 0;
-  double lower[RKH_MAX_DOF], upper[RKH_MAX_DOF];
+struct rkh_birrt : GraphHandle {
   std::vector<BiProblem> prob;
 };
 
@@ -66,14 +51,8 @@ bool keep_going(const BiProblem& q) {
   return (q.iteration_count < q.prm.max_vertices) && (q.prm.max_results > q.num_solutions);
 }
 
-void draw_sample(rkh_birrt* p, BiProblem& q, std::vector<double>& out) {  // hyperbox_topology::random_point
-  for (int d = 0; d < p->D; ++d) {
-    double u;
-    do {
-      u = double(q.eng()) * (1.0 / 4294967296.0);
-    } while (!(u < 1.0));
-    out[d] = p->lower[d] + u * (p->upper[d] - p->lower[d]);
-  }
+void draw_sample(rkh_birrt* p, BiProblem& q, std::vector<double>& out) {
+  hyperbox_point(q.eng, p->lower, p->upper, p->D, out.data());
   ++q.samples;
 }
 
@@ -110,25 +89,14 @@ rkh_status rkh_birrt_create_qs_batch(rkh_scene* scene, const rkh_qs_space* space
     set_error("rkh_birrt_create: n_dof mismatch or min_interval <= 0");
     return RKH_ERR_BAD_ARG;
   }
-  rkh_birrt* p = new rkh_birrt();
-  p->D = space->n_dof;
-  p->P = n_problems;
+  std::vector<uint32_t> max_vertices(n_problems);
+  for (uint32_t i = 0; i < n_problems; ++i) max_vertices[i] = prms[i].max_vertices;
+  auto p = std::make_unique<rkh_birrt>();
+  rkh_status st = p->init(scene, space, nullptr, max_vertices, 2, 1);  // two trees per problem, 1-NN
+  if (st != RKH_OK) return st;
   const int D = p->D;
-  for (int d = 0; d < D; ++d) {
-    p->lower[d] = space->lower[d];
-    p->upper[d] = space->upper[d];
-  }
-  std::vector<uint64_t> caps(2 * size_t(n_problems));
-  for (uint32_t i = 0; i < n_problems; ++i) caps[2 * i] = caps[2 * i + 1] = uint64_t(prms[i].max_vertices) + 2;
-  rkh_status st = p->gb.init(scene, space, 2 * n_problems, caps.data(), 1);
-  if (st != RKH_OK) {
-    p->gb.destroy();
-    delete p;
-    return st;
-  }
   p->prob.resize(n_problems);
-  p->gb.begin();
-  for (uint32_t i = 0; i < n_problems && st == RKH_OK; ++i) {
+  for (uint32_t i = 0; i < n_problems; ++i) {
     BiProblem& q = p->prob[i];
     q.prm = prms[i];
     q.eng.seed(prms[i].seed);
@@ -139,22 +107,14 @@ rkh_status rkh_birrt_create_qs_batch(rkh_scene* scene, const rkh_qs_space* space
     q.parent[1].push_back(NIL);
     q.p_target[0].assign(prms[i].goal, prms[i].goal + D);   // p_target1 = position of tree 2's root
     q.p_target[1].assign(prms[i].start, prms[i].start + D);  // p_target2 = position of tree 1's root
-    st = p->gb.cmd_append(2 * i, q.pos[0].data());
-    if (st == RKH_OK) st = p->gb.cmd_append(2 * i + 1, q.pos[1].data());
   }
-  if (st == RKH_OK) st = p->gb.run();
-  if (st != RKH_OK) {
-    p->gb.destroy();
-    delete p;
-    return st;
-  }
-  *out = p;
+  st = p->append_initial_rows(1, [&](int, uint32_t slot) { return p->prob[slot / 2].pos[slot % 2].data(); });
+  if (st != RKH_OK) return st;
+  *out = p.release();
   return RKH_OK;
 }
 
 rkh_status rkh_birrt_destroy(rkh_birrt* p) {
-  if (!p) return RKH_OK;
-  p->gb.destroy();
   delete p;
   return RKH_OK;
 }
@@ -277,12 +237,12 @@ rkh_status rkh_birrt_get_trees(rkh_birrt* p, uint32_t problem, double* pos1, uin
                                uint32_t* parent2, uint32_t* nn_seq, uint8_t* accept) {
   if (!p || problem >= p->P) return RKH_ERR_BAD_ARG;
   const BiProblem& q = p->prob[problem];
-  if (pos1) std::memcpy(pos1, q.pos[0].data(), q.pos[0].size() * sizeof(double));
-  if (parent1) std::memcpy(parent1, q.parent[0].data(), q.parent[0].size() * sizeof(uint32_t));
-  if (pos2) std::memcpy(pos2, q.pos[1].data(), q.pos[1].size() * sizeof(double));
-  if (parent2) std::memcpy(parent2, q.parent[1].data(), q.parent[1].size() * sizeof(uint32_t));
-  if (nn_seq) std::memcpy(nn_seq, q.nn_seq.data(), q.nn_seq.size() * sizeof(uint32_t));
-  if (accept) std::memcpy(accept, q.accept.data(), q.accept.size());
+  copy_out(pos1, q.pos[0]);
+  copy_out(parent1, q.parent[0]);
+  copy_out(pos2, q.pos[1]);
+  copy_out(parent2, q.parent[1]);
+  copy_out(nn_seq, q.nn_seq);
+  copy_out(accept, q.accept);
   return RKH_OK;
 }
 

@@ -35,8 +35,6 @@
 
 namespace rkh {
 
-int nn_padded_dims(int D);
-
 struct PlannerState {  // device-resident, one per problem
   uint32_t n;            // vertices in the tree
   uint32_t s0;           // next sample (== generate_rrt iterations so far)

@@ -29,53 +29,26 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <random>
 #include <set>
 
-#include "graph_batch.h"
-#include "rkh_internal.h"
+#include "graph_planner.h"
 
 using namespace rkh;
 
 namespace {
-constexpr uint32_t NIL = 0xFFFFFFFFu;
 constexpr uint32_t kConstructBatch = 4;  // samples tested per construct step
 constexpr uint32_t kWalkAttempts = 11;   // do { ... } while (++i <= 10)
-
-size_t highest_set_bit(size_t N) {  // core/base/misc_math.hpp:50-59
-  size_t temp = 0;
-  for (size_t shift = sizeof(size_t) * 4; (shift && (N != 1)); shift >>= 1) {
-    if (N >> shift) {
-      temp |= shift;
-      N >>= shift;
-    }
-  }
-  return temp;
-}
-
-double euclid(const double* a, const double* b, int D) {  // vect_distance_metrics.hpp:126-137
-  double r = 0.0;
-  for (int i = 0; i < D; ++i) {
-    const double d = a[i] - b[i];
-    r += d * d;
-  }
-  return std::sqrt(r);
-}
 
 // the global mt19937 with a replay window: speculated draws can be handed back
 struct RngStream {
   std::mt19937 eng;
   std::vector<uint32_t> buf;
   size_t cur = 0;
-  uint32_t next() {
+  uint32_t operator()() {
     if (cur == buf.size()) buf.push_back(uint32_t(eng()));
     return buf[cur++];
-  }
-  double uniform_01() {  // boost::uniform_01 on a 32-bit engine
-    for (;;) {
-      const double r = double(next()) * (1.0 / 4294967296.0);
-      if (r < 1.0) return r;
-    }
   }
   void compact() {  // only between iterations (no stream position of a step in flight is held)
     if (cur > 65536) {
@@ -116,11 +89,7 @@ struct PrmProblem {
 };
 }  // namespace
 
-struct rkh_prm {
-  GraphBatch gb;
-  int D = 0;
-  uint32_t P = 0;
-  double lower[RKH_MAX_DOF], upper[RKH_MAX_DOF];
+struct rkh_prm : GraphHandle {
   std::vector<PrmProblem> prob;
 };
 
@@ -130,8 +99,8 @@ bool keep_going(const PrmProblem& q) {
   return (q.iteration_count < q.prm.base.max_vertices) && (q.prm.base.max_results > 0u);
 }
 
-void random_point(rkh_prm* p, PrmProblem& q, double* out) {  // hyperbox_topology::random_point
-  for (int d = 0; d < p->D; ++d) out[d] = p->lower[d] + q.rng.uniform_01() * (p->upper[d] - p->lower[d]);
+void random_point(rkh_prm* p, PrmProblem& q, double* out) {
+  hyperbox_point(q.rng, p->lower, p->upper, p->D, out);
   ++q.samples;
 }
 
@@ -229,43 +198,20 @@ rkh_status connect_vertex(rkh_prm* p, uint32_t i, const double* pt, uint32_t x_n
   return RKH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-// qs != nullptr: quasi-static free space; dyn != nullptr: steerable dynamic free space (vertices = states, D = 2 n_dof)
 rkh_status prm_create(rkh_scene* scene, const rkh_qs_space* space, const rkh_dyn_space* dyn, const rkh_prm_params* prms,
                       uint32_t n_problems, rkh_prm** out) {
-  for (uint32_t i = 0; i < n_problems; ++i)
+  std::vector<uint32_t> max_vertices(n_problems);
+  for (uint32_t i = 0; i < n_problems; ++i) {
     if (!(prms[i].sampling_radius > 0.0)) {
       set_error("rkh_prm_create: sampling_radius must be positive");
       return RKH_ERR_BAD_ARG;
     }
-  rkh_prm* p = new rkh_prm();
-  p->D = space ? space->n_dof : 2 * dyn->n_dof;
-  p->P = n_problems;
+    max_vertices[i] = prms[i].base.max_vertices;
+  }
+  auto p = std::make_unique<rkh_prm>();
+  rkh_status st = p->init(scene, space, dyn, max_vertices, 1, star_kmax(max_vertices));
+  if (st != RKH_OK) return st;
   const int D = p->D;
-  for (int d = 0; d < D; ++d) {
-    p->lower[d] = space ? space->lower[d] : dyn->lower[d];
-    p->upper[d] = space ? space->upper[d] : dyn->upper[d];
-  }
-  uint32_t max_v = 0;
-  std::vector<uint64_t> caps(n_problems);
-  for (uint32_t i = 0; i < n_problems; ++i) {
-    max_v = std::max(max_v, prms[i].base.max_vertices);
-    caps[i] = uint64_t(prms[i].base.max_vertices) + 2;
-  }
-  const uint32_t kmax = uint32_t(4 * (highest_set_bit(size_t(max_v) + 2) + 1));
-  rkh_status st = space ? p->gb.init(scene, space, n_problems, caps.data(), kmax)
-                        : p->gb.init_dynamic(scene, dyn, n_problems, caps.data(), kmax);
-  if (st != RKH_OK) {
-    p->gb.destroy();
-    delete p;
-    return st;
-  }
   p->prob.resize(n_problems);
   for (uint32_t i = 0; i < n_problems; ++i) {
     PrmProblem& q = p->prob[i];
@@ -284,17 +230,9 @@ rkh_status prm_create(rkh_scene* scene, const rkh_qs_space* space, const rkh_dyn
     q.cc_set.insert(1);
     q.gamma = 3.0 * euclid(prms[i].base.start, prms[i].base.goal, D);
   }
-  for (int r = 0; r < 2; ++r) {  // the two initial rows: one append per step
-    p->gb.begin();
-    for (uint32_t i = 0; i < n_problems && st == RKH_OK; ++i) st = p->gb.cmd_append(i, &p->prob[i].pos[size_t(r) * D]);
-    if (st == RKH_OK) st = p->gb.run();
-    if (st != RKH_OK) {
-      p->gb.destroy();
-      delete p;
-      return st;
-    }
-  }
-  *out = p;
+  st = p->append_initial_rows(2, [&](int r, uint32_t i) { return &p->prob[i].pos[size_t(r) * D]; });
+  if (st != RKH_OK) return st;
+  *out = p.release();
   return RKH_OK;
 }
 }  // namespace
@@ -322,8 +260,6 @@ rkh_status rkh_prm_create_batch(rkh_scene* scene, const rkh_dyn_space* space, co
 }
 
 rkh_status rkh_prm_destroy(rkh_prm* p) {
-  if (!p) return RKH_OK;
-  p->gb.destroy();
   delete p;
   return RKH_OK;
 }
@@ -344,7 +280,7 @@ rkh_status rkh_prm_solve(rkh_prm* p, int64_t max_loop_iterations, rkh_prm_stats*
         if (!(keep_going(q) && (max_loop_iterations < 0 || int64_t(q.loop_iterations) < max_loop_iterations))) continue;
         ++q.loop_iterations;
         q.rng.compact();
-        const double rand_value = q.rng.uniform_01();
+        const double rand_value = uniform_01(q.rng);
         if (rand_value > q.prm.expand_probability) {
           q.in_construct = true;
         } else if (q.Q.data.empty()) {
@@ -357,9 +293,9 @@ rkh_status rkh_prm_solve(rkh_prm* p, int64_t max_loop_iterations, rkh_prm_stats*
       any = true;
       GbAux& a = gb.h_aux[i];
       const size_t N = q.density.size();
-      const size_t log_N = highest_set_bit(N) + 1;  // star_neighborhood (neighborhood_functors.hpp:95-102)
-      const uint32_t k = uint32_t(4 * log_N);
-      const double radius = q.gamma * std::pow(log_N / double(N), 1.0 / double(D));
+      uint32_t k;
+      double radius;
+      star_neighbourhood(N, q.gamma, D, &k, &radius);
       rkh_status st;
       if (q.in_construct) {
         // construction node (:229-235): the next kConstructBatch samples of the rejection loop
@@ -381,7 +317,7 @@ rkh_status rkh_prm_solve(rkh_prm* p, int64_t max_loop_iterations, rkh_prm_stats*
         for (uint32_t c = 0; c < kWalkAttempts; ++c) {
           for (int d = 0; d < D; ++d) a.pts[c][d] = pv[d] + dp[d];
           const double dist = euclid(pv, a.pts[c], D);
-          const double target_dist = q.rng.uniform_01() * q.prm.sampling_radius;
+          const double target_dist = uniform_01(q.rng) * q.prm.sampling_radius;
           a.frac[c] = target_dist / dist;
           a.target_dist[c] = target_dist;
           q.target_dist[c] = target_dist;
@@ -463,14 +399,14 @@ rkh_status rkh_prm_get_graph(rkh_prm* p, uint32_t problem, double* pos, uint32_t
                              double* edge_w, double* density, uint32_t* cc_root, uint8_t* kind, uint32_t* expanded) {
   if (!p || problem >= p->P) return RKH_ERR_BAD_ARG;
   const PrmProblem& q = p->prob[problem];
-  if (pos) std::memcpy(pos, q.pos.data(), q.pos.size() * sizeof(double));
-  if (edge_u) std::memcpy(edge_u, q.edge_u.data(), q.edge_u.size() * sizeof(uint32_t));
-  if (edge_v) std::memcpy(edge_v, q.edge_v.data(), q.edge_v.size() * sizeof(uint32_t));
-  if (edge_w) std::memcpy(edge_w, q.edge_w.data(), q.edge_w.size() * sizeof(double));
-  if (density) std::memcpy(density, q.density.data(), q.density.size() * sizeof(double));
-  if (cc_root) std::memcpy(cc_root, q.cc_root.data(), q.cc_root.size() * sizeof(uint32_t));
-  if (kind) std::memcpy(kind, q.kind.data(), q.kind.size());
-  if (expanded) std::memcpy(expanded, q.expanded.data(), q.expanded.size() * sizeof(uint32_t));
+  copy_out(pos, q.pos);
+  copy_out(edge_u, q.edge_u);
+  copy_out(edge_v, q.edge_v);
+  copy_out(edge_w, q.edge_w);
+  copy_out(density, q.density);
+  copy_out(cc_root, q.cc_root);
+  copy_out(kind, q.kind);
+  copy_out(expanded, q.expanded);
   return RKH_OK;
 }
 

@@ -23,29 +23,14 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <random>
 
-#include "graph_batch.h"
-#include "rkh_internal.h"
+#include "graph_planner.h"
 
 using namespace rkh;
 
 namespace {
-constexpr uint32_t NIL = 0xFFFFFFFFu;
-
-// math::highest_set_bit (core/base/misc_math.hpp:50-59) and star_neighborhood::operator()
-// (ctrl/graph_alg/neighborhood_functors.hpp:95-102): integer log2 and the fp64 radius, host side
-size_t highest_set_bit(size_t N) {
-  size_t temp = 0;
-  for (size_t shift = sizeof(size_t) * 4; (shift && (N != 1)); shift >>= 1) {
-    if (N >> shift) {
-      temp |= shift;
-      N >>= shift;
-    }
-  }
-  return temp;
-}
-
 enum StarState { ST_IDLE, ST_GENERATE, ST_CONNECT, ST_CONNECT_PRED, ST_CONNECT_SUCC };
 
 struct StarProblem {
@@ -86,26 +71,13 @@ struct StarProblem {
 };
 }  // namespace
 
-struct rkh_rrtstar {
-  GraphBatch gb;
+struct rkh_rrtstar : GraphHandle {
   bool bidirectional = false;
   bool branch_and_bound = false;
-  int D = 0;
-  uint32_t P = 0;
-  double lower[RKH_MAX_DOF], upper[RKH_MAX_DOF];
   std::vector<StarProblem> prob;
 };
 
 namespace {
-
-double euclid(const double* a, const double* b, int D) {  // vect_distance_metrics.hpp:126-137
-  double r = 0.0;
-  for (int i = 0; i < D; ++i) {
-    const double d = a[i] - b[i];
-    r += d * d;
-  }
-  return std::sqrt(r);
-}
 
 bool keep_going(const StarProblem& q) {
   return (q.iteration_count < q.prm.max_vertices) && (q.prm.max_results > q.num_solutions);
@@ -145,110 +117,144 @@ rkh_status remove_vertex(rkh_rrtstar* p, uint32_t i, uint32_t v) {
   return p->gb.remove_row(i, v);
 }
 
-void star_params(const StarProblem& q, int D, uint32_t* k, double* radius) {
-  const size_t N = q.pred.size() - size_t(q.pruned);  // num_vertices(g)
-  const size_t log_N = highest_set_bit(N) + 1;
-  *k = uint32_t(4 * log_N);
-  *radius = q.gamma * std::pow(log_N / double(N), 1.0 / double(D));
+void draw_sample(rkh_rrtstar* p, StarProblem& q) {
+  hyperbox_point(q.eng, p->lower, p->upper, p->D, q.p_new.data());
+  ++q.samples;
 }
 
-void draw_sample(rkh_rrtstar* p, StarProblem& q) {  // hyperbox_topology::random_point (hyperbox_topology.hpp:97-103)
-  for (int d = 0; d < p->D; ++d) {
-    double u;
-    do {
-      u = double(q.eng()) * (1.0 / 4294967296.0);
-    } while (!(u < 1.0));
-    q.p_new[d] = p->lower[d] + u * (p->upper[d] - p->lower[d]);
+// One side of the motion graph as the connector's rules see it: the forward tree (predecessor links, cost from the
+// start) or the backward tree of the bidirectional planner (successor links, cost to the goal).
+struct TreeSide {
+  std::vector<uint32_t>& link;               // pred / succ
+  std::vector<double>& cost;                 // accumulated along the links
+  std::vector<double>& weight;               // of the edge to the link
+  std::vector<std::vector<uint32_t>>& adj;   // children / parents
+  uint64_t& rewires;
+  bool backward;  // an edge that links v into this tree runs (u -> v) in the forward tree, (v -> u) in the backward one
+};
+TreeSide forward_tree(StarProblem& q) { return {q.pred, q.dist, q.weight, q.children, q.rewires, false}; }
+TreeSide backward_tree(StarProblem& q) { return {q.succ, q.fwd_dist, q.fwd_weight, q.parents, q.fwd_rewires, true}; }
+
+// The newest vertex v of a problem and the verdicts of its CONNECT step: for neighbour e, verdict e is
+// can_be_connected(u_e, v) and verdict K + e is can_be_connected(v, u_e); x_out is where the walk stopped, and it
+// replaces the far end of the edge when the edge is weighed.
+struct Connect {
+  StarProblem& q;
+  int D;
+  uint32_t v;
+  GraphBatch::Verdicts nb;
+  const double* pos(uint32_t u) const { return &q.pos[size_t(u) * D]; }
+  double length(bool from_v, uint32_t u) const { return from_v ? euclid(pos(v), pos(u), D) : euclid(pos(u), pos(v), D); }
+  bool accepted(bool from_v, uint32_t e) const { return nb.accept[from_v ? nb.K + e : e] != 0; }
+  double travelled(bool from_v, uint32_t e) const {
+    return from_v ? euclid(pos(v), &nb.x_out[size_t(nb.K + e) * D], D) : euclid(pos(nb.id[e]), &nb.x_out[size_t(e) * D], D);
   }
-  ++q.samples;
+};
+
+// connect_best_predecessor / connect_best_successor (lazy_connector.hpp:79-123 / :125-168): the vertex of the side's
+// tree through which v costs least.  *x / *ep: the generator's choice and its edge weight on entry (NIL: none)
+void best_link(Connect& c, const TreeSide& s, uint32_t* x, double* ep) {
+  const uint32_t orig = *x;
+  double d_near = std::numeric_limits<double>::infinity();
+  if (orig != NIL) d_near = s.cost[orig] + *ep;
+  for (uint32_t e = 0; e < c.nb.K; ++e) {
+    const uint32_t u = c.nb.id[e];
+    if (u == orig || s.link[u] == NIL) continue;
+    const double d = c.length(s.backward, u) + s.cost[u];
+    if (d < d_near) {
+      ++c.q.edges_checked;
+      if (c.accepted(s.backward, e)) {
+        *x = u;
+        d_near = d;
+        *ep = c.travelled(s.backward, e);
+      }
+    }
+  }
+}
+
+// create_pred_edge / create_succ_edge (pruned_connector.hpp:366-382 / :388-404)
+void create_link(TreeSide& s, uint32_t v, uint32_t x, double ep) {
+  s.cost[v] = ep + s.cost[x];
+  s.link[v] = x;
+  s.weight[v] = ep;
+  s.adj[x].push_back(v);
+}
+
+// connect_successors / connect_predecessors (lazy_connector.hpp:230-275 / :170-227): every neighbour that costs less
+// through v is re-linked to it.  x: the link of v itself; vertices linked into the other tree are left alone; a
+// removed old link (branch and bound) has no adjacency list to edit any more
+void rewire_neighbours(Connect& c, TreeSide& s, const TreeSide& other, uint32_t x) {
+  const uint32_t v = c.v;
+  for (uint32_t e = 0; e < c.nb.K; ++e) {
+    const uint32_t u = c.nb.id[e];
+    if (u == x || other.link[u] != NIL) continue;
+    const double d_in = c.length(!s.backward, u) + s.cost[v];
+    if (d_in < s.cost[u]) {
+      ++c.q.edges_checked;
+      if (c.accepted(!s.backward, e)) {
+        s.cost[u] = d_in;
+        const uint32_t old = s.link[u];
+        s.link[u] = v;
+        s.weight[u] = c.travelled(!s.backward, e);
+        s.adj[v].push_back(u);
+        if (old != u && old != NIL && !c.q.removed[old]) {
+          std::vector<uint32_t>& a = s.adj[old];
+          auto it = std::find(a.begin(), a.end(), u);
+          if (it != a.end()) a.erase(it);
+        }
+        ++s.rewires;
+      }
+    }
+  }
+}
+
+// update_successors / update_predecessors (pruned_connector.hpp:310-332 / :338-360): the new cost of v goes down the
+// adjacency lists; changed(t) for every vertex whose cost was rewritten
+template <class F>
+void propagate_costs(TreeSide& s, uint32_t v, F changed) {
+  std::vector<uint32_t> incons(1, v);
+  while (!incons.empty()) {
+    const uint32_t a = incons.back();
+    incons.pop_back();
+    for (uint32_t t : s.adj[a]) {
+      if (s.link[t] != a) continue;
+      s.cost[t] = s.cost[a] + s.weight[t];
+      changed(t);
+      incons.push_back(t);
+    }
+  }
 }
 
 // lazy_node_connector::operator() (lazy_connector.hpp:332-372) on the verdicts of the CONNECT step
 rkh_status connect_vertex(rkh_rrtstar* p, uint32_t i) {
   StarProblem& q = p->prob[i];
   const int D = p->D;
-  const uint32_t v = uint32_t(q.pred.size() - 1);
-  GraphBatch::Verdicts nb;
-  rkh_status vst = p->gb.verdicts(i, q.pos.data(), &q.pos[size_t(v) * D], &nb, q.removed.data());
-  if (vst != RKH_OK) return vst;
-  const uint32_t K = nb.K;
-  const uint32_t* kidx = nb.id.data();
-  const uint8_t* accept = nb.accept.data();
-  const double* x_out = nb.x_out.data();
+  Connect c{q, D, uint32_t(q.pred.size() - 1)};
+  const uint32_t v = c.v;
+  rkh_status st = p->gb.verdicts(i, q.pos.data(), c.pos(v), &c.nb, q.removed.data());
+  if (st != RKH_OK) return st;
+  TreeSide fwd = forward_tree(q), bwd = backward_tree(q);  // no vertex is ever linked into the backward tree here
   uint32_t x_near = q.x_near;
   double eweight = q.eweight;
-  // connect_best_predecessor (:79-123)
-  {
-    const uint32_t x_near_original = x_near;
-    double d_near = q.dist[x_near] + eweight;
-    for (uint32_t e = 0; e < K; ++e) {
-      const uint32_t u = kidx[e];
-      if (u == x_near_original || q.pred[u] == NIL) continue;
-      const double tentative_weight = euclid(&q.pos[size_t(u) * D], &q.pos[size_t(v) * D], D);
-      const double d_out = tentative_weight + q.dist[u];
-      if (d_out < d_near) {
-        ++q.edges_checked;
-        if (accept[e]) {  // can_be_connected(u, v)
-          x_near = u;
-          d_near = d_out;
-          eweight = euclid(&q.pos[size_t(u) * D], &x_out[size_t(e) * D], D);
-        }
-      }
-    }
-  }
-  // create_pred_edge (pruned_connector.hpp:366-382)
-  q.dist[v] = eweight + q.dist[x_near];
-  q.pred[v] = x_near;
-  q.weight[v] = eweight;
-  q.children[x_near].push_back(v);
+  best_link(c, fwd, &x_near, &eweight);
+  create_link(fwd, v, x_near, eweight);
   const bool bnb = p->branch_and_bound;
   if (bnb) {  // branch_and_bound_connector::operator() (branch_and_bound_connector.hpp:311-320)
     if (q.pred[1] != NIL && q.dist[v] + q.dist_to_goal > q.dist[1]) return remove_vertex(p, i, v);
     q.key[v] = q.dist[v] + q.dist_to_goal;
     q.Q.push(v);
   }
-  // connect_successors (:230-275)
-  for (uint32_t e = 0; e < K; ++e) {
-    const uint32_t u = kidx[e];
-    if (u == x_near) continue;
-    const double tentative_weight = euclid(&q.pos[size_t(v) * D], &q.pos[size_t(u) * D], D);
-    const double d_in = tentative_weight + q.dist[v];
-    if (d_in < q.dist[u]) {
-      ++q.edges_checked;
-      if (accept[K + e]) {  // can_be_connected(v, u)
-        q.dist[u] = d_in;
-        const uint32_t old_pred = q.pred[u];
-        q.pred[u] = v;
-        q.weight[u] = euclid(&q.pos[size_t(v) * D], &x_out[size_t(K + e) * D], D);
-        q.children[v].push_back(u);
-        if (old_pred != u && old_pred != NIL && !q.removed[old_pred]) {
-          std::vector<uint32_t>& ch = q.children[old_pred];
-          auto it = std::find(ch.begin(), ch.end(), u);
-          if (it != ch.end()) ch.erase(it);
-        }
-        ++q.rewires;
-      }
-    }
-  }
-  // update_successors (pruned_connector.hpp:310-332; with pruning: branch_and_bound_connector.hpp:142-185 -- the vertices
-  // whose cost changed are re-keyed (sift-up only), then every vertex whose key exceeds the goal's cost is removed)
-  std::vector<uint32_t> incons(1, v);
-  while (!incons.empty()) {
-    const uint32_t s = incons.back();
-    incons.pop_back();
-    for (uint32_t t : q.children[s]) {
-      if (q.pred[t] != s) continue;
-      q.dist[t] = q.dist[s] + q.weight[t];
-      if (bnb) {
-        q.key[t] = q.dist[t] + euclid(&q.pos[size_t(t) * D], &q.pos[size_t(1) * D], D);
-        q.Q.push_or_update(t);
-      }
-      incons.push_back(t);
-    }
-  }
+  rewire_neighbours(c, fwd, bwd, x_near);
+  // with pruning (branch_and_bound_connector.hpp:142-185): the vertices whose cost changed are re-keyed (sift-up only),
+  // then every vertex whose key exceeds the goal's cost is removed
+  propagate_costs(fwd, v, [&](uint32_t t) {
+    if (!bnb) return;
+    q.key[t] = q.dist[t] + euclid(c.pos(t), c.pos(1), D);
+    q.Q.push_or_update(t);
+  });
   if (bnb && q.pred[1] != NIL) {
     while (!q.Q.data.empty() && q.key[q.Q.data[0]] > q.dist[1]) {
-      const rkh_status st = remove_vertex(p, i, q.Q.data[0]);
+      st = remove_vertex(p, i, q.Q.data[0]);
       if (st != RKH_OK) return st;
       q.Q.pop();
     }
@@ -256,177 +262,39 @@ rkh_status connect_vertex(rkh_rrtstar* p, uint32_t i) {
   return RKH_OK;
 }
 
-// the bidirectional lazy_node_connector::operator() (lazy_connector.hpp:465-518) on the verdicts of a CONNECT step:
-// verdict e = can_be_connected(u_e, v), verdict K + e = can_be_connected(v, u_e)
+// the bidirectional lazy_node_connector::operator() (lazy_connector.hpp:465-518) on the verdicts of a CONNECT step
 rkh_status connect_vertex_bidir(rkh_rrtstar* p, uint32_t i, uint32_t x_pred, double ep_pred, uint32_t x_succ,
                                 double ep_succ) {
   StarProblem& q = p->prob[i];
-  const int D = p->D;
-  const double inf = std::numeric_limits<double>::infinity();
-  const uint32_t v = uint32_t(q.pred.size() - 1);
-  GraphBatch::Verdicts nb;
-  rkh_status vst = p->gb.verdicts(i, q.pos.data(), &q.pos[size_t(v) * D], &nb);
-  if (vst != RKH_OK) return vst;
-  const uint32_t K = nb.K;
-  const uint32_t* kidx = nb.id.data();
-  const uint8_t* accept = nb.accept.data();
-  const double* x_out = nb.x_out.data();
-  const double* pv = &q.pos[size_t(v) * D];
-  auto P = [&](uint32_t u) { return &q.pos[size_t(u) * D]; };
-  {  // connect_best_predecessor (:79-123)
-    const uint32_t orig = x_pred;
-    double d_near = inf;
-    if (x_pred != NIL) d_near = q.dist[x_pred] + ep_pred;
-    for (uint32_t e = 0; e < K; ++e) {
-      const uint32_t u = kidx[e];
-      if (u == orig || q.pred[u] == NIL) continue;
-      const double d_out = euclid(P(u), pv, D) + q.dist[u];
-      if (d_out < d_near) {
-        ++q.edges_checked;
-        if (accept[e]) {
-          x_pred = u;
-          d_near = d_out;
-          ep_pred = euclid(P(u), &x_out[size_t(e) * D], D);
-        }
-      }
-    }
-  }
-  {  // connect_best_successor (:125-168)
-    const uint32_t orig = x_succ;
-    double d_near = inf;
-    if (x_succ != NIL) d_near = q.fwd_dist[x_succ] + ep_succ;
-    for (uint32_t e = 0; e < K; ++e) {
-      const uint32_t u = kidx[e];
-      if (u == orig || q.succ[u] == NIL) continue;
-      const double d_in = euclid(pv, P(u), D) + q.fwd_dist[u];
-      if (d_in < d_near) {
-        ++q.edges_checked;
-        if (accept[K + e]) {
-          x_succ = u;
-          d_near = d_in;
-          ep_succ = euclid(pv, &x_out[size_t(K + e) * D], D);
-        }
-      }
-    }
-  }
+  Connect c{q, p->D, uint32_t(q.pred.size() - 1)};
+  const uint32_t v = c.v;
+  rkh_status st = p->gb.verdicts(i, q.pos.data(), c.pos(v), &c.nb);
+  if (st != RKH_OK) return st;
+  TreeSide fwd = forward_tree(q), bwd = backward_tree(q);
+  best_link(c, fwd, &x_pred, &ep_pred);
+  best_link(c, bwd, &x_succ, &ep_succ);
   if (x_pred == NIL && x_succ == NIL) return RKH_OK;  // (the reference removes the vertex here; unreachable from the loop)
-  if (x_pred != NIL) {  // create_pred_edge (pruned_connector.hpp:366-382)
-    q.dist[v] = ep_pred + q.dist[x_pred];
-    q.pred[v] = x_pred;
-    q.weight[v] = ep_pred;
-    q.children[x_pred].push_back(v);
-  }
-  if (x_succ != NIL) {  // create_succ_edge (:388-404)
-    q.fwd_dist[v] = ep_succ + q.fwd_dist[x_succ];
-    q.succ[v] = x_succ;
-    q.fwd_weight[v] = ep_succ;
-    q.parents[x_succ].push_back(v);
-  }
+  if (x_pred != NIL) create_link(fwd, v, x_pred, ep_pred);
+  if (x_succ != NIL) create_link(bwd, v, x_succ, ep_succ);
   if (q.pred[v] != NIL && q.succ[v] != NIL) {  // a joining vertex (the reference registers nothing for it)
     ++q.joins;
     if (q.dist[v] + q.fwd_dist[v] < q.best_join_cost) q.best_join_cost = q.dist[v] + q.fwd_dist[v];
   }
-  // connect_successors (:230-275): vertices that have a successor belong to the backward tree and are left alone
-  for (uint32_t e = 0; e < K; ++e) {
-    const uint32_t u = kidx[e];
-    if (u == x_pred || q.succ[u] != NIL) continue;
-    const double d_in = euclid(pv, P(u), D) + q.dist[v];
-    if (d_in < q.dist[u]) {
-      ++q.edges_checked;
-      if (accept[K + e]) {
-        q.dist[u] = d_in;
-        const uint32_t old_pred = q.pred[u];
-        q.pred[u] = v;
-        q.weight[u] = euclid(pv, &x_out[size_t(K + e) * D], D);
-        q.children[v].push_back(u);
-        if (old_pred != u && old_pred != NIL) {
-          std::vector<uint32_t>& ch = q.children[old_pred];
-          ch.erase(std::find(ch.begin(), ch.end(), u));
-        }
-        ++q.rewires;
-      }
-    }
-  }
-  {  // update_successors (pruned_connector.hpp:310-332)
-    std::vector<uint32_t> incons(1, v);
-    while (!incons.empty()) {
-      const uint32_t s = incons.back();
-      incons.pop_back();
-      for (uint32_t t : q.children[s]) {
-        if (q.pred[t] != s) continue;
-        q.dist[t] = q.dist[s] + q.weight[t];
-        incons.push_back(t);
-      }
-    }
-  }
-  // connect_predecessors (:170-227): vertices that have a predecessor belong to the forward tree and are left alone
-  for (uint32_t e = 0; e < K; ++e) {
-    const uint32_t u = kidx[e];
-    if (u == x_succ || q.pred[u] != NIL) continue;
-    const double d_in = euclid(P(u), pv, D) + q.fwd_dist[v];
-    if (d_in < q.fwd_dist[u]) {
-      ++q.edges_checked;
-      if (accept[e]) {
-        q.fwd_dist[u] = d_in;
-        const uint32_t old_succ = q.succ[u];
-        q.succ[u] = v;
-        q.fwd_weight[u] = euclid(P(u), &x_out[size_t(e) * D], D);
-        q.parents[v].push_back(u);
-        if (old_succ != u && old_succ != NIL) {
-          std::vector<uint32_t>& pa = q.parents[old_succ];
-          pa.erase(std::find(pa.begin(), pa.end(), u));
-        }
-        ++q.fwd_rewires;
-      }
-    }
-  }
-  {  // update_predecessors (pruned_connector.hpp:338-360)
-    std::vector<uint32_t> incons(1, v);
-    while (!incons.empty()) {
-      const uint32_t t = incons.back();
-      incons.pop_back();
-      for (uint32_t s : q.parents[t]) {
-        if (q.succ[s] != t) continue;
-        q.fwd_dist[s] = q.fwd_dist[t] + q.fwd_weight[s];
-        incons.push_back(s);
-      }
-    }
-  }
+  auto no_hook = [](uint32_t) {};
+  rewire_neighbours(c, fwd, bwd, x_pred);
+  propagate_costs(fwd, v, no_hook);
+  rewire_neighbours(c, bwd, fwd, x_succ);
+  propagate_costs(bwd, v, no_hook);
   return RKH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-// qs != nullptr: quasi-static free space (vertices = joint positions); dyn != nullptr: steerable dynamic free space
-// (vertices = states (q, qd), D = 2 n_dof; edges are RK4 propagations)
 rkh_status rrtstar_create(rkh_scene* scene, const rkh_qs_space* qs, const rkh_dyn_space* dyn, const rkh_rrt_params* prms,
                           uint32_t n_problems, rkh_rrtstar** out) {
-  rkh_rrtstar* p = new rkh_rrtstar();
-  p->D = qs ? qs->n_dof : 2 * dyn->n_dof;
-  p->P = n_problems;
-  for (int d = 0; d < p->D; ++d) {
-    p->lower[d] = qs ? qs->lower[d] : dyn->lower[d];
-    p->upper[d] = qs ? qs->upper[d] : dyn->upper[d];
-  }
-  uint32_t max_v = 0;
-  std::vector<uint64_t> caps(n_problems);
-  for (uint32_t i = 0; i < n_problems; ++i) {
-    max_v = std::max(max_v, prms[i].max_vertices);
-    caps[i] = uint64_t(prms[i].max_vertices) + 2;
-  }
-  const uint32_t kmax = uint32_t(4 * (highest_set_bit(size_t(max_v) + 2) + 1));
-  rkh_status st = qs ? p->gb.init(scene, qs, n_problems, caps.data(), kmax)
-                     : p->gb.init_dynamic(scene, dyn, n_problems, caps.data(), kmax);
-  if (st != RKH_OK) {
-    p->gb.destroy();
-    delete p;
-    return st;
-  }
+  std::vector<uint32_t> max_vertices(n_problems);
+  for (uint32_t i = 0; i < n_problems; ++i) max_vertices[i] = prms[i].max_vertices;
+  auto p = std::make_unique<rkh_rrtstar>();
+  rkh_status st = p->init(scene, qs, dyn, max_vertices, 1, star_kmax(max_vertices));
+  if (st != RKH_OK) return st;
   p->prob.resize(n_problems);
   const int D = p->D;
   for (uint32_t i = 0; i < n_problems; ++i) {
@@ -440,21 +308,56 @@ rkh_status rrtstar_create(rkh_scene* scene, const rkh_qs_space* qs, const rkh_dy
     add_vertex(D, q, prms[i].goal, std::numeric_limits<double>::infinity(), NIL);
     q.gamma = 3.0 * euclid(prms[i].start, prms[i].goal, D);  // 3 * heuristic(start -> goal) (:303,322)
   }
-  // the two initial rows: one append per step
-  for (int r = 0; r < 2; ++r) {
-    p->gb.begin();
-    for (uint32_t i = 0; i < n_problems; ++i) {
-      st = p->gb.cmd_append(i, &p->prob[i].pos[size_t(r) * D]);
-      if (st != RKH_OK) break;
-    }
-    if (st == RKH_OK) st = p->gb.run();
-    if (st != RKH_OK) {
-      p->gb.destroy();
-      delete p;
-      return st;
-    }
+  st = p->append_initial_rows(2, [&](int r, uint32_t i) { return &p->prob[i].pos[size_t(r) * D]; });
+  if (st != RKH_OK) return st;
+  *out = p.release();
+  return RKH_OK;
+}
+
+// the top of generate_rrt_star_loop (rrt_star.hpp:169-190) / generate_rrt_star_bidir_loop (:197-236): start the next
+// iteration of a problem that keeps going, for at most max_loop_iterations loop passes (< 0 = unlimited)
+void next_iteration(StarProblem& q, bool keep_going, int64_t max_loop_iterations) {
+  if (keep_going && (max_loop_iterations < 0 || int64_t(q.loop_iterations) < max_loop_iterations)) {
+    ++q.loop_iterations;
+    q.tries = 0;
+    q.x_near = NIL;
+    q.x_succ = NIL;
+    q.state = ST_GENERATE;
+  } else {
+    q.state = ST_IDLE;
   }
-  *out = p;
+}
+
+// The next device step of every running problem; *any = false when none is left.
+//   GENERATE: sample, neighbourhood, one walk from each neighbour in order (rrg_node_generator, node_generators.hpp:
+//     137-172: EDGE_STEER_ACCEPT; rrg_bidir_generator, :215-277: EDGE_STEER_BOTH).
+//   CONNECT*: lazy_node_connector::operator() (lazy_connector.hpp:332-372): select_neighborhood(p) before create_vertex
+//     (:347-350); then every neighbour in both directions, (u -> v) and (v -> u), for the point being connected.
+rkh_status build_step(rkh_rrtstar* p, int steer_mode, bool* any) {
+  GraphBatch& gb = p->gb;
+  gb.begin();
+  *any = false;
+  for (uint32_t i = 0; i < p->P; ++i) {
+    StarProblem& q = p->prob[i];
+    if (q.state == ST_IDLE) continue;
+    *any = true;
+    uint32_t k;
+    double radius;
+    star_neighbourhood(q.pred.size() - size_t(q.pruned), q.gamma, p->D, &k, &radius);  // N = num_vertices(g)
+    rkh_status st = RKH_OK;
+    if (q.state == ST_GENERATE) {
+      draw_sample(p, q);
+      st = gb.cmd_knn(i, q.p_new.data(), q.pred.size(), k, radius);
+      gb.cmd_edges(i, GB_LIST_KNN_TO_QUERY, 0, steer_mode, q.prm.steer_tol);
+    } else {
+      const double* pt = q.state == ST_CONNECT_SUCC ? q.p_succ.data() : q.p_new.data();
+      const uint64_t n_before = q.pred.size();
+      st = gb.cmd_knn(i, pt, n_before, k, radius);
+      if (st == RKH_OK) st = gb.cmd_append(i, pt);
+      gb.cmd_edges(i, GB_LIST_KNN_BIDIR, uint32_t(n_before), EDGE_CONNECT, q.prm.conn_tol);
+    }
+    if (st != RKH_OK) return st;
+  }
   return RKH_OK;
 }
 }  // namespace
@@ -482,8 +385,6 @@ rkh_status rkh_rrtstar_create_batch(rkh_scene* scene, const rkh_dyn_space* space
 }
 
 rkh_status rkh_rrtstar_destroy(rkh_rrtstar* p) {
-  if (!p) return RKH_OK;
-  p->gb.destroy();
   delete p;
   return RKH_OK;
 }
@@ -494,48 +395,14 @@ rkh_status rkh_rrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_rr
   const int D = p->D;
   const double inf = std::numeric_limits<double>::infinity();
   GraphBatch& gb = p->gb;
-  // start (or resume) every problem at the top of generate_rrt_star_loop (rrt_star.hpp:169-190)
-  auto next_iteration = [&](StarProblem& q) {
-    if (keep_going(q) && (max_loop_iterations < 0 || int64_t(q.loop_iterations) < max_loop_iterations)) {
-      ++q.loop_iterations;
-      q.tries = 0;
-      q.x_near = NIL;
-      q.state = ST_GENERATE;
-    } else {
-      q.state = ST_IDLE;
-    }
-  };
-  for (StarProblem& q : p->prob) next_iteration(q);
+  auto next = [&](StarProblem& q) { next_iteration(q, keep_going(q), max_loop_iterations); };
+  for (StarProblem& q : p->prob) next(q);
   for (;;) {
-    // ---- build the next device step of every running problem
-    gb.begin();
-    bool any = false;
-    for (uint32_t i = 0; i < p->P; ++i) {
-      StarProblem& q = p->prob[i];
-      if (q.state == ST_IDLE) continue;
-      any = true;
-      uint32_t k;
-      double radius;
-      star_params(q, D, &k, &radius);
-      rkh_status st = RKH_OK;
-      if (q.state == ST_GENERATE) {
-        // rrg_node_generator (node_generators.hpp:137-172): sample, neighbourhood, steer from each neighbour in order
-        draw_sample(p, q);
-        st = gb.cmd_knn(i, q.p_new.data(), q.pred.size(), k, radius);
-        gb.cmd_edges(i, GB_LIST_KNN_TO_QUERY, 0, EDGE_STEER_ACCEPT, q.prm.steer_tol);
-      } else {
-        // lazy_node_connector::operator() (lazy_connector.hpp:332-372): select_neighborhood(p) before create_vertex
-        // (:347-350); then every neighbour in both directions: (u -> v) for connect_best_predecessor, (v -> u)
-        // for connect_successors
-        const uint64_t n_before = q.pred.size();
-        st = gb.cmd_knn(i, q.p_new.data(), n_before, k, radius);
-        if (st == RKH_OK) st = gb.cmd_append(i, q.p_new.data());
-        gb.cmd_edges(i, GB_LIST_KNN_BIDIR, uint32_t(n_before), EDGE_CONNECT, q.prm.conn_tol);
-      }
-      if (st != RKH_OK) return st;
-    }
+    bool any;
+    rkh_status st = build_step(p, EDGE_STEER_ACCEPT, &any);
+    if (st != RKH_OK) return st;
     if (!any) break;
-    rkh_status st = gb.run();
+    st = gb.run();
     if (st != RKH_OK) return st;
     // ---- apply the sequential rules to the verdicts
     for (uint32_t i = 0; i < p->P; ++i) {
@@ -572,14 +439,14 @@ rkh_status rkh_rrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_rr
         if (gen_done) {
           q.near_seq.push_back(q.x_near);
           if (q.x_near == NIL || q.dist[q.x_near] == inf) {
-            next_iteration(q);  // rrt_star.hpp:181-182
+            next(q);  // rrt_star.hpp:181-182
           } else if (p->branch_and_bound) {
             // branch_and_bound_connector::operator() (:284-293): a point that cannot lie on a better path is dropped
             const double dist_from_start = euclid(&q.pos[0], q.p_new.data(), D);
             q.dist_to_goal = euclid(q.p_new.data(), &q.pos[size_t(1) * D], D);
             if (q.pred[1] != NIL && dist_from_start + q.dist_to_goal > q.dist[1]) {
               ++q.skipped;
-              next_iteration(q);
+              next(q);
             } else {
               q.state = ST_CONNECT;
             }
@@ -596,7 +463,7 @@ rkh_status rkh_rrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_rr
         }
         st = connect_vertex(p, i);
         if (st != RKH_OK) return st;
-        next_iteration(q);
+        next(q);
       }
     }
   }
@@ -637,8 +504,7 @@ rkh_status rkh_rrtstar_set_branch_and_bound(rkh_rrtstar* p, int enabled) {
 // removed[num_vertices]: 1 for the vertices taken out of the graph (branch-and-bound pruning)
 rkh_status rkh_rrtstar_get_removed(rkh_rrtstar* p, uint32_t problem, uint8_t* removed) {
   if (!p || problem >= p->P || !removed) return RKH_ERR_BAD_ARG;
-  const StarProblem& q = p->prob[problem];
-  std::memcpy(removed, q.removed.data(), q.removed.size());
+  copy_out(removed, p->prob[problem].removed);
   return RKH_OK;
 }
 
@@ -671,10 +537,10 @@ rkh_status rkh_rrtstar_get_graph(rkh_rrtstar* p, uint32_t problem, double* pos, 
                                  uint32_t* near_seq) {
   if (!p || problem >= p->P) return RKH_ERR_BAD_ARG;
   const StarProblem& q = p->prob[problem];
-  if (pos) std::memcpy(pos, q.pos.data(), q.pos.size() * sizeof(double));
-  if (pred) std::memcpy(pred, q.pred.data(), q.pred.size() * sizeof(uint32_t));
-  if (dist) std::memcpy(dist, q.dist.data(), q.dist.size() * sizeof(double));
-  if (near_seq) std::memcpy(near_seq, q.near_seq.data(), q.near_seq.size() * sizeof(uint32_t));
+  copy_out(pos, q.pos);
+  copy_out(pred, q.pred);
+  copy_out(dist, q.dist);
+  copy_out(near_seq, q.near_seq);
   return RKH_OK;
 }
 
@@ -716,45 +582,16 @@ rkh_status rkh_birrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_
   if (!p || !p->bidirectional) return RKH_ERR_BAD_ARG;
   const int D = p->D;
   GraphBatch& gb = p->gb;
-  auto keep = [&](const StarProblem& q) { return q.iteration_count < q.prm.max_vertices && q.prm.max_results > 0; };
-  auto next_iteration = [&](StarProblem& q) {
-    if (keep(q) && (max_loop_iterations < 0 || int64_t(q.loop_iterations) < max_loop_iterations)) {
-      ++q.loop_iterations;
-      q.tries = 0;
-      q.x_near = NIL;
-      q.x_succ = NIL;
-      q.state = ST_GENERATE;
-    } else {
-      q.state = ST_IDLE;
-    }
+  auto next = [&](StarProblem& q) {
+    next_iteration(q, q.iteration_count < q.prm.max_vertices && q.prm.max_results > 0, max_loop_iterations);
   };
-  for (StarProblem& q : p->prob) next_iteration(q);
+  for (StarProblem& q : p->prob) next(q);
   for (;;) {
-    gb.begin();
-    bool any = false;
-    for (uint32_t i = 0; i < p->P; ++i) {
-      StarProblem& q = p->prob[i];
-      if (q.state == ST_IDLE) continue;
-      any = true;
-      uint32_t k;
-      double radius;
-      star_params(q, D, &k, &radius);
-      rkh_status st = RKH_OK;
-      if (q.state == ST_GENERATE) {
-        draw_sample(p, q);
-        st = gb.cmd_knn(i, q.p_new.data(), q.pred.size(), k, radius);
-        gb.cmd_edges(i, GB_LIST_KNN_TO_QUERY, 0, EDGE_STEER_BOTH, q.prm.steer_tol);
-      } else {
-        const double* pt = q.state == ST_CONNECT_PRED ? q.p_new.data() : q.p_succ.data();
-        const uint64_t n_before = q.pred.size();
-        st = gb.cmd_knn(i, pt, n_before, k, radius);
-        if (st == RKH_OK) st = gb.cmd_append(i, pt);
-        gb.cmd_edges(i, GB_LIST_KNN_BIDIR, uint32_t(n_before), EDGE_CONNECT, q.prm.conn_tol);
-      }
-      if (st != RKH_OK) return st;
-    }
+    bool any;
+    rkh_status st = build_step(p, EDGE_STEER_BOTH, &any);
+    if (st != RKH_OK) return st;
     if (!any) break;
-    rkh_status st = gb.run();
+    st = gb.run();
     if (st != RKH_OK) return st;
     for (uint32_t i = 0; i < p->P; ++i) {
       StarProblem& q = p->prob[i];
@@ -810,7 +647,7 @@ rkh_status rkh_birrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_
           q.near_succ.push_back(q.x_succ);
           if (q.x_near != NIL) q.state = ST_CONNECT_PRED;
           else if (q.x_succ != NIL) q.state = ST_CONNECT_SUCC;
-          else next_iteration(q);
+          else next(q);
         }
       } else if (q.state == ST_CONNECT_PRED || q.state == ST_CONNECT_SUCC) {
         const bool first = q.state == ST_CONNECT_PRED;
@@ -820,7 +657,7 @@ rkh_status rkh_birrtstar_solve(rkh_rrtstar* p, int64_t max_loop_iterations, rkh_
                    : connect_vertex_bidir(p, i, NIL, 0.0, q.x_succ, q.eweight_succ);
         if (st != RKH_OK) return st;
         if (first && q.x_succ != NIL) q.state = ST_CONNECT_SUCC;
-        else next_iteration(q);
+        else next(q);
       }
     }
   }
@@ -844,13 +681,13 @@ rkh_status rkh_birrtstar_get_graph(rkh_rrtstar* p, uint32_t problem, double* pos
                                    double* fwd_dist, uint32_t* near_pred, uint32_t* near_succ) {
   if (!p || !p->bidirectional || problem >= p->P) return RKH_ERR_BAD_ARG;
   const StarProblem& q = p->prob[problem];
-  if (pos) std::memcpy(pos, q.pos.data(), q.pos.size() * sizeof(double));
-  if (pred) std::memcpy(pred, q.pred.data(), q.pred.size() * sizeof(uint32_t));
-  if (dist) std::memcpy(dist, q.dist.data(), q.dist.size() * sizeof(double));
-  if (succ) std::memcpy(succ, q.succ.data(), q.succ.size() * sizeof(uint32_t));
-  if (fwd_dist) std::memcpy(fwd_dist, q.fwd_dist.data(), q.fwd_dist.size() * sizeof(double));
-  if (near_pred) std::memcpy(near_pred, q.near_pred.data(), q.near_pred.size() * sizeof(uint32_t));
-  if (near_succ) std::memcpy(near_succ, q.near_succ.data(), q.near_succ.size() * sizeof(uint32_t));
+  copy_out(pos, q.pos);
+  copy_out(pred, q.pred);
+  copy_out(dist, q.dist);
+  copy_out(succ, q.succ);
+  copy_out(fwd_dist, q.fwd_dist);
+  copy_out(near_pred, q.near_pred);
+  copy_out(near_succ, q.near_succ);
   return RKH_OK;
 }
 
