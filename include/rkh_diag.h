@@ -17,6 +17,9 @@ extern "C" {
 rkh_status rkh_nn_set_events(rkh_nn* nn, void* ev_start, void* ev_stop);
 /* Name of the sweep kernel the last query launched (for profile bookkeeping). */
 const char* rkh_nn_kernel_name(void);
+/* The mapping the steer plan chose at this thread's last rkh_propagate or rkh_planner_create* over a dynamic space:
+ * "auto", "duo", "wave", "wave16", "pair", "planar" or "prismatic" (one wave per edge, prismatic form). */
+const char* rkh_steer_mapping_name(void);
 
 /* Shader-clock cycles of `iters` back-to-back f-evals + proximity tests.  One-wave-per-edge kernel: one wave per state,
  * cycles[B][8] = {sincos, forward sweep, jacobian columns, force sweep, mass matrix, cholesky, proximity, total};
@@ -55,7 +58,8 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps);
  * its stages ("collide"): counts[0] = states tested, [1] = (robot shape, obstacle) pairs that pass the
  * static reach and the bounding cull, [2] = closed forms evaluated, [3] = golden-section searches (capped cylinder /
  * box), [4] = states found in collision, [5] = proxy pairs of the scene (the tests per state before any culling),
- * [6] = those within the shapes' static reach.  Scenes of the two-lanes mapping only (serial chains of <= 7 joints). */
+ * [6] = those within the shapes' static reach.  Scenes of the two-lanes mapping only (serial chains of 3 or 6 joints,
+ * revolute or prismatic). */
 rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t B, uint64_t counts[8]);
 
 #ifdef __cplusplus

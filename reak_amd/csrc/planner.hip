@@ -609,9 +609,12 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
                         bool compact = false) {
   if (p->quasi_static)
     return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P);
-  if (p->steer != SteerMapping::Auto)
+  if (p->steer != SteerMapping::Auto) {
+    KernelGate always;  // no gate; the executed steps are counted like Auto's (rkh_planner_steer_steps)
+    always.steps_exec = p->d_steps_exec;
     return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
-                            p->d_lane_ws);
+                            p->d_lane_ws, always);
+  }
   // Auto: every form of the sequence is launched; on the device each compares the round's edge count with its gate and
   // the ones not chosen exit at once.  Small rounds -> Duo / Wave (latency), large -> Pair (32 edges per wave).
   auto run = [&](SteerMapping m, double* ws, const KernelGate& gate) {
@@ -627,7 +630,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     gate_wave.n_segments = 2 * p->P;
   }
   rkh_status st = RKH_OK;
-  if (p->duo_threshold > 0 && compact && p->d_wave_base) {
+  if (p->duo_threshold > 0 && compact && p->d_wave_base && !p->scene->host.has_prismatic) {
     // the smallest rounds (at most half the chip's SIMDs at one wave per edge: a single problem, a few young trees):
     // two waves per edge (state_derivative_duo), the f-eval's critical path instead of its instruction count
     KernelGate gate_duo = gate_wave;
@@ -636,7 +639,9 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     st = run(SteerMapping::Duo, nullptr, gate_duo);
     if (st != RKH_OK) return st;
   }
-  if (gate_wave.lo < gate_wave.hi) st = run(SteerMapping::Wave, nullptr, gate_wave);
+  // (chains with prismatic joints have no Duo form: their one-wave form covers [0, lane threshold))
+  if (gate_wave.lo < gate_wave.hi)
+    st = run(p->scene->host.has_prismatic ? SteerMapping::Prismatic : SteerMapping::Wave, nullptr, gate_wave);
   if (st != RKH_OK) return st;
   // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
   // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
@@ -883,6 +888,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   if (!p->quasi_static) {
     const SteerRequest req = steer_request();
     p->steer = steer_mapping(scene->host, SteerEntry::BatchPlanner, req, 0, n_problems, p->b_max);
+    note_steer_mapping(p->steer);
     p->duo_threshold = req.duo_threshold;
   }
   // the lane kernel's residency sizes the wave fit and the step-wise launches (the mappings that run it)
@@ -890,7 +896,7 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   if (lane_kernel) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, scene->ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
-      p->wave_slots = uint32_t(prop.multiProcessorCount) * pair_kernel_waves_per_cu(scene->host.n_dof);
+      p->wave_slots = uint32_t(prop.multiProcessorCount) * pair_kernel_waves_per_cu(scene->host.n_dof, scene->host.has_prismatic != 0);
     if (getenv("RKH_VERBOSE")) fprintf(stderr, "rkh planner: %d CUs, %u resident steer waves\n", prop.multiProcessorCount, p->wave_slots);
   }
   p->split_min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();

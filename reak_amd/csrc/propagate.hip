@@ -2029,13 +2029,15 @@ rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping 
   if constexpr (kPrismatic) {
     st = launch_propagate_t<64, false>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
   } else {
+    // a scene with prismatic joints never reaches a revolute form: whatever one-wave mapping was asked for is theirs
+    if (scene.host.has_prismatic && m != SteerMapping::Pair) m = SteerMapping::Prismatic;
     switch (m) {
       case SteerMapping::Planar:
         return launch_propagate_planar(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
       case SteerMapping::Prismatic:
         return prismatic::launch_propagate(s, scene, m, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_lane_ws, gate);
       case SteerMapping::Pair:
-        return launch_propagate_pairs(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_lane_ws, gate);
+        return rkh::launch_propagate_pairs(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_lane_ws, gate);
       case SteerMapping::Duo:
         st = launch_propagate_t<64, false, true>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
         break;

@@ -20,6 +20,11 @@
 //     the link forces (6N), the joint frames of the proximity test (7N - 3) and the assembled mass matrix (N^2))
 //     = 19.3 KB per wave: eight waves per CU;
 //   * the RK4 stage vectors are split between the edge's lanes (lane h updates the joints 2r + h).
+//
+// Chains with prismatic joints (SceneDev::has_prismatic) run on forms compiled from this same text in a translation unit
+// of their own (propagate_pair_prismatic.hip defines RKH_PRISMATIC_FORMS and includes this file): there the kernels and
+// their launchers live in rkh::prismatic and kPrismatic is true.  Here kPrismatic is false and the prismatic branches
+// compile away, so the revolute kernels keep their code; the launchers below hand prismatic scenes on.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +36,12 @@
 #include "rkh_internal.h"
 
 namespace rkh {
+#ifdef RKH_PRISMATIC_FORMS
+namespace prismatic {
+constexpr bool kPrismatic = true;
+#else
+constexpr bool kPrismatic = false;
+#endif
 
 namespace {
 
@@ -68,6 +79,16 @@ RKH_DI m33 pair_axis_angle_rotmat(double ca, double sa, d3 ax) {  // axis_angle:
 }
 
 constexpr int kPairEdges = 32;  // edges per wave: every lane in use
+
+// The two lanes of an edge hand values over through LDS without a barrier: one lane stores under a condition on h, then
+// both read (one wave: the instructions execute in order).  The compiler models the lanes as independent threads, so it
+// may read a slot BEFORE the neighbour's conditional store where it can prove that this thread does not store -- it did,
+// in the one-joint prismatic form (the all-unrolled chain: the odd lane read the mass matrix slot early and found its
+// edges singular).  The prismatic forms therefore close every such hand-over with a compiler-level memory barrier (no
+// instruction); the revolute forms are left as they compile today.
+RKH_DI void pair_lds_handover() {
+  if (kPrismatic) asm volatile("" : : : "memory");
+}
 
 template <int N>
 struct PairLayout {
@@ -149,6 +170,7 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
   }
   // this lane's rows i = 2r + h of Tcm^T (Mcm Tcm): Mo[r][rr] = column 2rr + h (own parity), Mp[r][rr] = column
   // 2rr + 1 - h (the neighbour's parity).  inertia_gen rows: Tcm = 1 on the diagonal.
+  const uint32_t pmask = kPrismatic ? sc->prismatic_mask : 0u;  // bit j: joint j translates (read in uniform control flow)
   double Mo[R][R], Mp[R][R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -180,23 +202,38 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
     const auto& J = sc->joints[j];
     const d3 axis = ldg3(J.axis), axis_n = ldg3(J.axis_n);
     const double q = RKH_LD(L_::XE + 2 * j), qd = RKH_LD(L_::XE + 2 * j + 1);
-    // one sincos per lane: half angle on lane h = 0, full angle on lane h = 1 (kept for the tip->base sweep)
-    double sn, cs;
-    sincos(h ? q : 0.5 * q, &sn, &cs);
-    const double cs_o = xchg(cs), sn_o = xchg(sn);
-    const double c2 = h ? cs_o : cs, s2 = h ? sn_o : sn;
-    if (h) {
-      RKH_LD(L_::CS + 2 * j) = cs;
-      RKH_LD(L_::CS + 2 * j + 1) = sn;
+    d4 EQ;
+    d3 Ew, Ealpha;
+    if (kPrismatic && ((pmask >> j) & 1u)) {  // (uniform: j is)
+      // prismatic_joint_3D::doMotion (prismatic_joint.cpp:116-148), q_ddot = 0: the end frame keeps the base's
+      // orientation and rates and moves by R(Q) (q a); no sincos, nothing in the cos / sin slots
+      const d3 tmp_pos = q * axis;
+      const d3 tmp_vel = qd * axis;
+      const m33 Rb = rotmat(Q);
+      acc = acc + mul(Rb, (cross(w, cross(w, tmp_pos)) + 2.0 * cross(w, tmp_vel)) + cross(alpha, tmp_pos));
+      pos = pos + mul(Rb, tmp_pos);
+      EQ = Q;
+      Ew = w;
+      Ealpha = alpha;
+    } else {
+      // one sincos per lane: half angle on lane h = 0, full angle on lane h = 1 (kept for the tip->base sweep)
+      double sn, cs;
+      sincos(h ? q : 0.5 * q, &sn, &cs);
+      const double cs_o = xchg(cs), sn_o = xchg(sn);
+      const double c2 = h ? cs_o : cs, s2 = h ? sn_o : sn;
+      if (h) {
+        RKH_LD(L_::CS + 2 * j) = cs;
+        RKH_LD(L_::CS + 2 * j + 1) = sn;
+      }
+      // revolute_joint_3D::doMotion (revolute_joint.cpp:121-148)
+      const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
+      const m33 R2 = rotmat(tq);
+      EQ = qmul(Q, tq);
+      const d3 wb = mulT(w, R2);
+      const d3 qa = qd * axis;
+      Ew = wb + qa;
+      Ealpha = mulT(alpha, R2) + cross(wb, qa);
     }
-    // revolute_joint_3D::doMotion (revolute_joint.cpp:121-148)
-    const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
-    const m33 R2 = rotmat(tq);
-    const d4 EQ = qmul(Q, tq);
-    const d3 wb = mulT(w, R2);
-    const d3 qa = qd * axis;
-    const d3 Ew = wb + qa;
-    const d3 Ealpha = mulT(alpha, R2) + cross(wb, qa);
     {  // the joint's end frame, kept by the lane that owns column j
       const bool mine = ((j & 1) == h);
       const int rj = j >> 1;
@@ -246,8 +283,14 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
         const m33 Rf = rotmat(f2q);
         const int c = 2 * r + h;  // <= N: the spare row of lds.axis covers an odd chain's last slot
         const d3 ax_c = mk3(lds.axis[c][0], lds.axis[c][1], lds.axis[c][2]);
-        const d3 wt = mulT(ax_c, Rf);
-        const d3 vt = mulT(cross(ax_c, f2pos), Rf);
+        d3 wt = mulT(ax_c, Rf);
+        d3 vt = mulT(cross(ax_c, f2pos), Rf);
+        if (kPrismatic) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0.  The column differs between the edge's
+          // lanes: selects.  wt = +0 adds +-0 products to sums that are never -0, like a column beyond j below.
+          const bool pc = ((pmask >> c) & 1u) != 0u;
+          vt = mk3(pc ? wt.x : vt.x, pc ? wt.y : vt.y, pc ? wt.z : vt.z);
+          wt = mk3(pc ? 0.0 : wt.x, pc ? 0.0 : wt.y, pc ? 0.0 : wt.z);
+        }
         // A column beyond j is an exact +0 vector: Mcm * 0 = +0 and s + (+-0) = s bit for bit (the sums start from +0
         // or from a joint inertia, so they are never -0), hence the accumulation below needs no masks.
         const bool act = (c <= j);
@@ -292,6 +335,7 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
   }
 
   // ---- tip -> base sweep (kte_map_chain::doForce in reverse op order)
+  pair_lds_handover();  // FT, CS
   {
     d3 LF = mk3(0, 0, 0), LT = mk3(0, 0, 0);
     if (sc->beam_on) {  // flexible_beam_3D::doForce: listed last, so first in the reverse pass (first term of the sums)
@@ -310,6 +354,17 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
       const d3 op = ldg3(J.off_pos);
       const d3 tmp_force = mul(Ro, LF);
       const d3 ET = mul(Ro, LT) + cross(op, tmp_force);
+      if (kPrismatic && ((pmask >> j) & 1u)) {  // (uniform)
+        // prismatic_joint_3D::doForce (prismatic_joint.cpp:150-170): the force along the axis goes to the coordinate;
+        // the actuator's reaction (prismatic_joint.cpp:219-222) is a force on the base frame
+        const double tf = dot(tmp_force, axis);
+        LF = tmp_force - tf * axis;
+        LT = ET + cross(RKH_LD(L_::XE + 2 * j) * axis, tmp_force);
+        const double uj = RKH_LD(L_::U + j);
+        if (!h) RKH_LD(L_::F + j) = tf + uj;
+        LF = LF - uj * axis;
+        continue;
+      }
       const m33 Ra = pair_axis_angle_rotmat(RKH_LD(L_::CS + 2 * j), RKH_LD(L_::CS + 2 * j + 1),
                                             ldg3(J.axis_n));  // revolute_joint_3D::doForce (revolute_joint.cpp:170-181)
       const double ta = dot(ET, axis);
@@ -322,6 +377,7 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
   }
   RKH_STAMP(3)
 
+  pair_lds_handover();  // F
   // ---- the two lanes' rows meet in LDS (the link forces are no longer needed)
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -333,6 +389,7 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
       if (i < N && cn < N) RKH_LD(L_::MF + i * N + cn) = Mp[r][rr];
     }
   }
+  pair_lds_handover();  // MF
   // ---- mat<symmetric>(general): 0.5 * (M(j,i) + M(i,j)), j < i (mat_alg_symmetric.hpp:183-187), lower triangle
   double L[N][N], f[N];
 #pragma unroll
@@ -399,6 +456,13 @@ RKH_DI ShapeG pair_robot_pose(ScenePtr sc, PairLds<N>& lds, int e, int r) {
   const int js3 = j > 0 ? 3 * j - 3 : 0;
   d3 Epos = mk3(lds.v[L_::ECP + js3][e], lds.v[L_::ECP + js3 + 1][e], lds.v[L_::ECP + js3 + 2][e]);
   if (j == 0) Epos = ldg3(sc->base_pos);
+  if (kPrismatic) {
+    // a prismatic root: joint 0's end position is the base moved by R(base_quat) (q0 a).  The layout has no slot for
+    // it, so it is formed here, from the state in LDS and scene constants (uniform addresses: scalar loads).
+    const d3 root = ldg3(sc->base_pos) + mul(rotmat(ldg4(sc->base_quat)), lds.v[L_::XE][e] * ldg3(sc->joints[0].axis));
+    const bool moved = (j == 0) && (sc->prismatic_mask & 1u);
+    Epos = mk3(moved ? root.x : Epos.x, moved ? root.y : Epos.y, moved ? root.z : Epos.z);
+  }
   const d4 EQ = d4{lds.v[L_::ECQ + 4 * j][e], lds.v[L_::ECQ + 4 * j + 1][e], lds.v[L_::ECQ + 4 * j + 2][e],
                    lds.v[L_::ECQ + 4 * j + 3][e]};
   ShapeG A;
@@ -531,6 +595,7 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
         RKH_LD(L_::CS + 2 * jc + 1) = s2;
       }
     }
+    pair_lds_handover();  // CS
     d3 pos = ldg3(sc->base_pos);
     d4 Q = ldg4(sc->base_quat);
 #pragma unroll 1
@@ -539,7 +604,11 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
       const d3 axis_n = ldg3(J.axis_n);
       const double c2 = RKH_LD(L_::CS + 2 * j), s2 = RKH_LD(L_::CS + 2 * j + 1);
       const d4 tq = d4{c2, axis_n.x * s2, axis_n.y * s2, axis_n.z * s2};
-      const d4 EQ = qmul(Q, tq);
+      d4 EQ = qmul(Q, tq);
+      if (kPrismatic && ((sc->prismatic_mask >> j) & 1u)) {  // (uniform) prismatic_joint_3D: translate by R(Q) (q a), keep Q
+        pos = pos + mul(rotmat(Q), RKH_LD(L_::XE + 2 * j) * ldg3(J.axis));
+        EQ = Q;
+      }
       if (!h) {
         if (j > 0) {
           RKH_LD(L_::ECP + 3 * j - 3) = pos.x; RKH_LD(L_::ECP + 3 * j - 2) = pos.y; RKH_LD(L_::ECP + 3 * j - 1) = pos.z;
@@ -552,6 +621,7 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
       Q = qmul(EQ, ldg4(J.off_quat));
     }
   }
+  pair_lds_handover();  // ECP, ECQ
   RKH_STAMP(5)
 #pragma unroll 1
   for (int r0 = 0; r0 < n_robot; r0 += 2) {
@@ -850,6 +920,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
         }
       }
     }
+    pair_lds_handover();  // XE
     if (sing_now && alive) {
       singular = true;
       alive = false;
@@ -1104,6 +1175,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
           }
         }
       }
+      pair_lds_handover();  // XE
       if (sing_now && alive) {
         singular = true;
         alive = false;
@@ -1188,9 +1260,11 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   }
 }
 
+#ifndef RKH_PRISMATIC_FORMS  // (the workspace does not depend on the joint kinds)
 size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks) {
   return size_t(blocks) * size_t(6 * ((n_dof + 1) / 2)) * 64 * sizeof(double);
 }
+#endif
 
 // The steer launches of a round, one per step, over two ping-pong lists; d_cnt[k] = entries of the list launch k reads
 // (d_cnt[1 .. n_steps] must be zero when the first launch starts: round_begin_kernel clears them).  `blocks` bounds the
@@ -1200,6 +1274,10 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
                                        uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
                                        KernelGate gate, unsigned long long* d_steps_exec) {
   if (blocks == 0 || n_problems == 0) return RKH_OK;
+  if constexpr (!kPrismatic)
+    if (scene.host.has_prismatic)
+      return prismatic::launch_propagate_pair_steps(s, scene, dyn, tab_a, tab_b, n_problems, d_edge_base, d_list0, d_list1,
+                                                    d_cnt, d_ws, blocks, gate, d_steps_exec);
   PairStepArgs args;
   args.sc = scene.d_scene;
   args.dyn = dyn;
@@ -1225,6 +1303,7 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
   return RKH_OK;
 }
 
+#ifndef RKH_PRISMATIC_FORMS  // the cycle probe instruments the revolute form only
 // Diagnostic kernel (not on the product path): `iters` back-to-back f-evals + proximity tests of kPairEdges states per
 // wave with cycle counts per phase: [frames + sincos, jacobian columns, mass matrix, force sweep, assembly + cholesky,
 // proximity: joint frames, cull, exact routines]
@@ -1263,6 +1342,7 @@ __global__ __launch_bounds__(64, 2) void pair_cycles_kernel(const SceneDev* __re
     sink_out[blockIdx.x] = accv + (singular ? 1.0 : 0.0);
   }
 }
+#endif
 
 // Diagnostic kernel (not on the product path): the proximity test of B states, 32 per wave, counting what survives each
 // stage: out[0] += states tested, [1] += (robot shape, obstacle) pairs past the static reach + fp32 cull (the closed-form
@@ -1298,6 +1378,8 @@ __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __re
 
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out) {
+  if constexpr (!kPrismatic)
+    if (scene.host.has_prismatic) return prismatic::launch_pair_counts(s, scene, d_x, B, d_out);
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
   const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, B, d_out);
@@ -1307,8 +1389,13 @@ rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const doubl
   return RKH_OK;
 }
 
+#ifndef RKH_PRISMATIC_FORMS
 rkh_status launch_pair_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                               int iters, unsigned long long* d_out, double* d_sink) {
+  if (scene.host.has_prismatic) {
+    set_error("rkh_diag_feval_cycles: scenes with prismatic joints are not instrumented");
+    return RKH_ERR_UNSUPPORTED;
+  }
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
   const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((pair_cycles_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
@@ -1326,6 +1413,7 @@ size_t propagate_pairs_workspace_bytes(int n_dof, uint32_t edges_a, uint32_t edg
   const size_t slots = size_t(6 * ((n_dof + 1) / 2) + 4 * n_dof);
   return waves * slots * 64 * sizeof(double);
 }
+#endif
 
 rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
                                   uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
@@ -1336,6 +1424,9 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
     set_error("propagate (two lanes per edge): no workspace");
     return RKH_ERR_BAD_ARG;
   }
+  if constexpr (!kPrismatic)
+    if (scene.host.has_prismatic)
+      return prismatic::launch_propagate_pairs(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_ws, gate);
   const uint32_t ga = (grid_edges + kPairEdges - 1) / kPairEdges, gbk = (eb + kPairEdges - 1) / kPairEdges;
   PairArgs args;
   args.sc = scene.d_scene;
@@ -1355,10 +1446,14 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
   return RKH_OK;
 }
 
+#ifndef RKH_PRISMATIC_FORMS
 uint32_t pair_kernel_edges_per_wave() { return uint32_t(kPairEdges); }
+#endif
 
-// resident waves per CU of the kernel for this chain size
-uint32_t pair_kernel_waves_per_cu(int n_dof) {
+// resident waves per CU of the kernel for this chain size (and joint kinds: has_prismatic = the scene's)
+uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic) {
+  if constexpr (!kPrismatic)
+    if (has_prismatic) return prismatic::pair_kernel_waves_per_cu(n_dof, true);
   int blocks = 0;
   hipError_t e = hipErrorInvalidValue;
   with_n<1, 2, 3, 4, 6, 7>(n_dof, [&](auto c) {
@@ -1368,4 +1463,7 @@ uint32_t pair_kernel_waves_per_cu(int n_dof) {
 }
 
 #undef RKH_LD
+#ifdef RKH_PRISMATIC_FORMS
+}  // namespace prismatic
+#endif
 }  // namespace rkh

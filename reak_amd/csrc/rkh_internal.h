@@ -322,11 +322,12 @@ struct KernelGate {
 // ---- steer mapping ---------------------------------------------------------------------------------------------------
 // The kernel form that steers the edges of a dynamic-space launch.
 enum class SteerMapping : uint8_t {
-  Auto,       // batch planner rounds: Duo, Wave or Pair by the round's edge count, read on the device (launch_edges)
+  Auto,       // batch planner rounds: Duo, Wave or Pair by the round's edge count, read on the device (launch_edges);
+              // chains with prismatic joints: their one-wave form, then Pair (there is no Duo form for them)
   Duo,        // two waves per edge (state_derivative_duo)
   Wave,       // one wave per edge (the form with the support-map query for scenes with vertex-set shapes)
   Wave16,     // four edges per wave, 16 lanes each (the form with the support-map query)
-  Pair,       // two lanes per edge, 32 edges per wave (propagate_pair.hip)
+  Pair,       // two lanes per edge, 32 edges per wave (propagate_pair.hip; prismatic chains: propagate_pair_prismatic.hip)
   Planar,     // planar chains: one lane per edge (propagate_planar.hip)
   Prismatic,  // chains with prismatic joints: one wave per edge, no support-map query (propagate_prismatic.hip)
 };
@@ -345,10 +346,10 @@ inline SteerRequest steer_request() {
   return r;
 }
 
-// the two-lanes-per-edge kernel handles one serial chain of at most 7 joints, with at most a tip-to-world beam
+// the two-lanes-per-edge kernel handles one serial chain of at most 7 joints, revolute or prismatic (rkh::prismatic
+// forms), with at most a tip-to-world beam (a scene with prismatic joints has none)
 inline bool scene_fits_lane_kernel(const SceneDev& S) {
   if (S.has_meshes) return false;  // GJK pairs run in the wave-per-edge / quasi-static kernels
-  if (S.has_prismatic) return false;  // prismatic joints: the one-wave-per-edge kernel
   return S.n_dof <= 7 && S.n_branches == 0 && (!S.beam_on || (S.beam_j1 == S.n_dof - 1 && S.beam_j2 < 0));
 }
 
@@ -357,16 +358,19 @@ inline bool scene_fits_lane_kernel(const SceneDev& S) {
 //   Batch planner (rkh_planner_create*, dynamic space), at create: RKH_LANES_PER_EDGE 0 -> Auto, 2 -> Pair, 16 -> Wave16,
 //     any other value (128 included) -> Wave.  Unset: Auto if n_dof <= 6 and scene_fits_lane_kernel, else Wave16 if
 //     n_problems * 2 * b_max > 4096 (a round offers more waves than the chip has slots), else Wave.  Auto rounds run
-//     Duo below min(RKH_DUO_THRESHOLD, lane threshold) edges (compact rounds only; Auto never sees vertex-set shapes or
-//     prismatic joints), Wave below the lane threshold and Pair from there on.
+//     Duo below min(RKH_DUO_THRESHOLD, lane threshold) edges (compact rounds only; Auto never sees vertex-set shapes),
+//     Wave below the lane threshold and Pair from there on.  Chains with prismatic joints have no Duo form: their Auto
+//     rounds run the one-wave prismatic form below the lane threshold and Pair from there on.
 //   rkh_propagate, every call: unset -> Duo if edges <= 512, else Wave; 2 -> Pair, 16 -> Wave16, 128 -> Duo, any other
 //     value -> Wave.
 //   Graph planners (dynamic space), every launch: Duo if edges * n_problems <= RKH_DUO_THRESHOLD (read at create), else
 //     Wave; RKH_LANES_PER_EDGE does not apply.
 //   Then for these three: Pair or Auto on a scene the lane kernel does not fit -> Wave; Wave16 with 2 n_dof > 16 (a
-//     16-lane group holds at most 16 components) -> Wave; planar chains -> Planar; prismatic joints -> Prismatic; Duo on
-//     a scene with vertex-set shapes -> Wave (its support-map form).
-//   Cycle probe (rkh_diag_feval_cycles), every call: 2 -> Pair, 128 -> Duo, any other value -> Wave; no scene rule.
+//     16-lane group holds at most 16 components) -> Wave; planar chains -> Planar; prismatic joints: Pair stays Pair
+//     and the batch planner's Auto stays Auto (their rkh::prismatic forms), everything else -> Prismatic (one wave per
+//     edge; the graph planners always); Duo on a scene with vertex-set shapes -> Wave (its support-map form).
+//   Cycle probe (rkh_diag_feval_cycles), every call: 2 -> Pair, 128 -> Duo, any other value -> Wave; no scene rule (the
+//     probes refuse prismatic scenes themselves).
 //   rkh_diag_proximity_counts: scenes of scene_fits_lane_kernel only.
 inline SteerMapping steer_mapping(const SceneDev& S, SteerEntry entry, const SteerRequest& req, uint64_t edges,
                                   uint32_t n_problems, uint32_t b_max) {
@@ -391,10 +395,13 @@ inline SteerMapping steer_mapping(const SceneDev& S, SteerEntry entry, const Ste
   if ((m == M::Pair || m == M::Auto) && !scene_fits_lane_kernel(S)) m = M::Wave;
   if (m == M::Wave16 && 2 * S.n_dof > 16) m = M::Wave;
   if (S.planar) return M::Planar;
-  if (S.has_prismatic) return M::Prismatic;
+  if (S.has_prismatic) return (m == M::Pair || (m == M::Auto && entry == SteerEntry::BatchPlanner)) ? m : M::Prismatic;
   if (m == M::Duo && S.has_meshes) m = M::Wave;
   return m;
 }
+
+// rkh_steer_mapping_name(): the mapping this thread's last rkh_propagate / rkh_planner_create* (dynamic space) was given
+void note_steer_mapping(SteerMapping m);
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
 // They read the scene's kind (planar, vertex-set shapes, prismatic joints) from scene.host; the verdict kernels
@@ -422,6 +429,17 @@ rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const 
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems);
+// the two-lanes-per-edge forms (propagate_pair_prismatic.hip); the ones below hand these scenes on
+rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                  uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                  uint32_t n_problems, double* d_ws, KernelGate gate);
+rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
+                                       const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
+                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
+                                       KernelGate gate, unsigned long long* d_steps_exec);
+uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
+rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
+                              unsigned long long* d_out);
 }  // namespace prismatic
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink);
@@ -438,7 +456,7 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
                                        uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
                                        KernelGate gate, unsigned long long* d_steps_exec);
-uint32_t pair_kernel_waves_per_cu(int n_dof);
+uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
 uint32_t pair_kernel_edges_per_wave();
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out);

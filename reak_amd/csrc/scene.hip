@@ -155,6 +155,9 @@ __global__ void gjk_pairs_kernel(const rkh_shape* __restrict__ a, const rkh_shap
   out[i] = gjk_distance(to_gjk(conv(a[i]), pool), to_gjk(conv(b[i]), pool));
 }
 
+
+static thread_local SteerMapping g_steer_mapping = SteerMapping::Wave;
+void note_steer_mapping(SteerMapping m) { g_steer_mapping = m; }
 }  // namespace rkh
 
 static rkh_status upload_scene(rkh_ctx* ctx, rkh_scene* sc, const std::vector<PairDev>& pairs, rkh_scene** out) {
@@ -764,6 +767,7 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   // the mapping (identical results): by default a call of few edges -- the adaptors steer ONE edge per call -- takes the
   // lowest-latency one (steer_mapping)
   const SteerMapping m = steer_mapping(scene->host, SteerEntry::Propagate, steer_request(), B, 1, 0);
+  note_steer_mapping(m);
   DevBuf dws;
   if (m == SteerMapping::Pair) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
   st = launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, dws.as<double>());
@@ -807,6 +811,18 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
   RKH_HIP(hipMemcpyAsync(cycles, dout.p, size_t(B) * 8 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
+}
+
+const char* rkh_steer_mapping_name(void) {
+  switch (g_steer_mapping) {
+    case SteerMapping::Auto: return "auto";
+    case SteerMapping::Duo: return "duo";
+    case SteerMapping::Wave16: return "wave16";
+    case SteerMapping::Pair: return "pair";
+    case SteerMapping::Planar: return "planar";
+    case SteerMapping::Prismatic: return "prismatic";
+    default: return "wave";
+  }
 }
 
 rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t B, uint64_t counts[8]) {

@@ -77,6 +77,7 @@ EXPORTS = [
     "rkh_last_error", "rkh_version", "rkh_abi_version", "rkh_abi_check", "rkh_ctx_create", "rkh_ctx_destroy", "rkh_ctx_synchronize", "rkh_ctx_stream",
     "rkh_nn_create", "rkh_nn_destroy", "rkh_nn_clear", "rkh_nn_size", "rkh_nn_remove", "rkh_nn_live_size", "rkh_nn_append", "rkh_nn_query1",
     "rkh_nn_queryk", "rkh_nn_query1_async", "rkh_nn_queryk_async", "rkh_nn_fill_uniform", "rkh_nn_kernel_name",
+    "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
     "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
     "rkh_min_distance", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
@@ -88,7 +89,8 @@ EXPORTS = [
 
 
 def build(verbose=False):
-    """Compile every HIP source for gfx950 into reak_amd/librkh.so (hipcc cross-compiles without a GPU)."""
+    """Compile every HIP source for gfx950 into reak_amd/librkh.so and the library it loads from its own directory,
+    librkh_prismatic_pair.so (hipcc cross-compiles without a GPU)."""
     subprocess.run(["make", "-s", "-C", os.path.join(_HERE, "csrc")], check=True,
                    stdout=None if verbose else subprocess.DEVNULL, stderr=None if verbose else subprocess.DEVNULL)
     return _LIB_PATH
@@ -130,6 +132,7 @@ def load():
     lib.rkh_nn_set_coord_bound.argtypes = [vp, C.c_double]
     lib.rkh_nn_set_events.argtypes = [vp, vp, vp]
     lib.rkh_nn_kernel_name.restype = C.c_char_p
+    lib.rkh_steer_mapping_name.restype = C.c_char_p
     lib.rkh_scene_create.argtypes = [vp, C.POINTER(T.KteOp), C.c_int, C.POINTER(T.ChainBase), C.POINTER(T.Shape), C.c_int,
                                      C.POINTER(vp)]
     lib.rkh_scene_create_with_meshes.argtypes = [vp, C.POINTER(T.KteOp), C.c_int, C.POINTER(T.ChainBase), C.POINTER(T.Shape),
@@ -289,6 +292,12 @@ class HipNeighborSearch:
             self.close()
         except Exception:
             pass
+
+
+def steer_mapping_name():
+    """The mapping the steer plan chose at this thread's last Scene.steer_position_toward or RrtPlanner over a dynamic
+    space (rkh_steer_mapping_name): auto, duo, wave, wave16, pair, planar or prismatic."""
+    return load().rkh_steer_mapping_name().decode()
 
 
 def gjk_distance(ctx, a, b, mesh_vertices=None):

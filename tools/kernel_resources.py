@@ -7,7 +7,8 @@
     python tools/kernel_resources.py --out profiles/r03_kernel_resources.txt
 
 `kernel_resources(path)` returns {demangled kernel name: dict}; tests/test_kernel_resources.py asserts the figures the
-bench line and DESIGN.md quote against it."""
+bench line and DESIGN.md quote against it.  `PRISMATIC_PAIR_SO` is the library librkh.so takes the prismatic forms of the
+two-lanes steer kernels from; the table covers both libraries."""
 import argparse
 import os
 import re
@@ -19,6 +20,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+PRISMATIC_PAIR_SO = os.path.join(ROOT, "reak_amd", "librkh_prismatic_pair.so")
 FIELDS = ("vgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count",
           "private_segment_fixed_size", "group_segment_fixed_size", "max_flat_workgroup_size")
 
@@ -104,7 +106,10 @@ if __name__ == "__main__":
     ap.add_argument("--so", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    t = table(kernel_resources(a.so))
+    res = kernel_resources(a.so)
+    if a.so is None:
+        res.update(kernel_resources(PRISMATIC_PAIR_SO))
+    t = table(res)
     if a.out:
         open(a.out, "w").write(t)
     sys.stdout.write(t)
