@@ -58,7 +58,7 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps);
  * its stages ("collide"): counts[0] = states tested, [1] = (robot shape, obstacle) pairs that pass the
  * static reach and the bounding cull, [2] = closed forms evaluated, [3] = golden-section searches (capped cylinder /
  * box), [4] = states found in collision, [5] = proxy pairs of the scene (the tests per state before any culling),
- * [6] = those within the shapes' static reach.  Scenes of the two-lanes mapping only (serial chains of 3 or 6 joints,
+ * [6] = those within the shapes' static reach.  Scenes of the two-lanes mapping only (serial chains of 3, 6 or 7 joints,
  * revolute or prismatic). */
 rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t B, uint64_t counts[8]);
 

@@ -632,6 +632,7 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
     const int rc = (r < n_robot) ? r : r0;
     const ShapeG A = pair_robot_pose<N>(sc, lds, el, rc);
     const d3 ca = pose_to_parent(A.pos, A.q, mk3(0, 0, 0));
+    const d3 cull_org = ldg3(sc->base_pos);  // origin of the cull records (SceneDev::env_cull)
     const bool a_ccyl = (A.kind == RKH_SHAPE_CCYLINDER);
     // capped cylinder: its axis segment (for the cull below)
     const d3 a_ax = qrot(A.q, mk3(0.0, 0.0, 1.0));
@@ -650,16 +651,23 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
       // lower bound on its distance is positive -- the bounding-sphere test of proxy_query_model.cpp:384-389 or, for
       // a capped-cylinder robot shape, the distance from the obstacle's bounding sphere to the cylinder's axis segment --
       // so the verdict "some pair is closer than 0" is unchanged.  The cull runs in fp32 with fused multiply-adds (a
-      // conservative filter, not part of the reference's arithmetic): records and the shape's segment are rounded to
-      // fp32 and the reach carries a 1 mm margin, three orders of magnitude above the rounding of the fp32 evaluation at
-      // these magnitudes (coordinates of a few metres).
+      // conservative filter, not part of the reference's arithmetic) on coordinates RELATIVE TO THE CHAIN BASE: the
+      // records hold centre - base, subtracted in fp64 on the host (scene.hip), and the shape's centre loses the base in
+      // fp64 here, before anything is rounded to fp32.  What is rounded is then bounded by the chain's reach plus the
+      // obstacle's distance from the base, wherever the world sits: a few metres for every pair that can touch, so the
+      // 1 mm margin on the reach is three orders of magnitude above the rounding of the fp32 evaluation.  (Rounding
+      // absolute coordinates made the margin depend on the world's offset: an fp32 ulp at 1e5 m is 8 mm.)  An obstacle
+      // far from the base is rounded more coarsely -- relative to its own distance, 6e-8 of it.  Where its bounding
+      // radius is of the order of the reach it is far outside every reach by the same measure; the margin does not
+      // scale with the radius, so a very large obstacle centred far away (a slab of 100 m half-extent: centre and radius
+      // rounded at 1e-5 m) is covered only to that rounding, at any world offset.
       float ecx = e0x, ecy = e0y, ecz = e0z, ecr = e0r;
       if (o0 != 0) {  // further chunks of 64 obstacles (uniform branch)
         const int ol = (o0 + lane < n_env) ? o0 + lane : o0;
         ecx = float(sc->env_cull[ol][0]); ecy = float(sc->env_cull[ol][1]); ecz = float(sc->env_cull[ol][2]);
         ecr = float(sc->env_cull[ol][3]);
       }
-      const float cax = float(ca.x), cay = float(ca.y), caz = float(ca.z);
+      const float cax = float(ca.x - cull_org.x), cay = float(ca.y - cull_org.y), caz = float(ca.z - cull_org.z);
       const float aax = float(a_ax.x), aay = float(a_ax.y), aaz = float(a_ax.z);
       const float shl = float(seg_hl), srm = float(seg_rad_m) + 1e-3f;
       unsigned long long mask = 0ull;
@@ -1381,7 +1389,7 @@ rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const doubl
   if constexpr (!kPrismatic)
     if (scene.host.has_prismatic) return prismatic::launch_pair_counts(s, scene, d_x, B, d_out);
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
-  const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
+  const rkh_status st = with_n<6, 3, 7>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, B, d_out);
   });
   if (st != RKH_OK) return st;

@@ -166,8 +166,9 @@ struct SceneDev {
   JointDev joints[kMaxDof];
   ShapeDev robot[kMaxDof * 2];
   ShapeDev env[kMaxEnvShapes];
-  // cull table of the environment: global centre of the bounding sphere (pose.transformToGlobal(0) = the pose's
-  // position) and its radius; one bit per shape and kind (sphere, box, capped cylinder) in chunks of 64 shapes
+  // cull table of the environment: centre of the bounding sphere (pose.transformToGlobal(0) = the pose's position)
+  // RELATIVE TO base_pos -- the fp32 cull of the two-lanes steer kernels must not depend on where the world sits -- and
+  // its radius; one bit per shape and kind (sphere, box, capped cylinder) in chunks of 64 shapes
   double env_cull[kMaxEnvShapes][4];
   unsigned long long env_kind_mask[3][kMaxEnvShapes / 64];
   // Branching (quasi-static kernels only): joint j with branch_start[j] != 0 does not continue the previous link but

@@ -518,7 +518,7 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
         return RKH_ERR_CAPACITY;
       }
       d.link = -1;
-      for (int k = 0; k < 3; ++k) S.env_cull[S.n_env][k] = d.pos[k];
+      for (int k = 0; k < 3; ++k) S.env_cull[S.n_env][k] = d.pos[k] - S.base_pos[k];  // relative to the chain base
       S.env_cull[S.n_env][3] = d.brad;
       if (d.kind <= RKH_SHAPE_CCYLINDER)
         S.env_kind_mask[d.kind == RKH_SHAPE_SPHERE ? 0 : (d.kind == RKH_SHAPE_BOX ? 1 : 2)][S.n_env / 64] |= 1ull << (S.n_env % 64);

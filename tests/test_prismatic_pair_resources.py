@@ -42,7 +42,7 @@ def test_prismatic_pair_forms_add_no_lds(res):
     for n in (1, 2, 3, 4, 6, 7):
         for kernel in ("propagate_pair_kernel", "propagate_pair_step_kernel"):
             assert res[f"rkh::prismatic::{kernel}<{n}>"]["group_segment_fixed_size"] == res[f"rkh::{kernel}<{n}>"]["group_segment_fixed_size"]
-    for n in (3, 6):
+    for n in (3, 6, 7):
         assert res[f"rkh::prismatic::pair_counts_kernel<{n}>"]["group_segment_fixed_size"] == \
             res[f"rkh::pair_counts_kernel<{n}>"]["group_segment_fixed_size"]
 
@@ -53,7 +53,7 @@ def test_prismatic_pair_library_holds_the_pair_forms_only():
     import kernel_resources as kr
 
     own = kr.kernel_resources(kr.PRISMATIC_PAIR_SO)
-    assert len(own) == 14, sorted(own)
+    assert len(own) == 15, sorted(own)  # 6 + 6 steer kernels, the count probe for 3, 6 and 7 joints
     for k in own:
         assert k.split("<")[0] in ("rkh::prismatic::propagate_pair_kernel", "rkh::prismatic::propagate_pair_step_kernel",
                                    "rkh::prismatic::pair_counts_kernel"), k
