@@ -157,11 +157,11 @@ struct Heap4 {
 };
 
 struct GbProblem {
-  NnStore tree;
+  DeviceBuffer<double> pos;      // the vertex rows
+  NnStore tree;                  // ... as the launchers take them
   uint64_t n_dev = 0;            // rows on the device
-  void* d_knn_ws = nullptr;
-  uint32_t* d_src_idx = nullptr;
-  uint32_t* d_tgt_idx = nullptr;
+  DeviceBuffer<void> d_knn_ws;
+  DeviceBuffer<uint32_t> d_src_idx, d_tgt_idx;
 };
 
 struct GraphBatch {
@@ -176,7 +176,8 @@ struct GraphBatch {
   std::vector<GbProblem> prob;
   static constexpr size_t kKnnWsBytes = 128 * 1024;
   // command block: [KnnArgs x P][EdgeIO x P][EdgeIO (stage A) x P][GbAux x P], pinned host copy + device copy
-  unsigned char *h_cmd = nullptr, *d_cmd = nullptr;
+  PinnedBuffer<unsigned char> h_cmd;
+  DeviceBuffer<unsigned char> d_cmd;
   size_t cmd_bytes = 0;
   KnnArgs *h_knn = nullptr, *d_knn = nullptr;
   EdgeIO *h_io = nullptr, *d_io = nullptr;
@@ -184,9 +185,12 @@ struct GraphBatch {
   GbAux *h_aux = nullptr, *d_aux = nullptr;
   // result block per problem: {kcnt, overflow, n_edges, sel} kidx[kmax] kdist[kmax] nchk[emax] accept[emax] x_out[emax][D]
   //                           a_nchk[16] a_accept[16] a_xout[16][D]
-  unsigned char *h_res = nullptr, *d_res = nullptr;
+  PinnedBuffer<unsigned char> h_res;
+  DeviceBuffer<unsigned char> d_res;
   unsigned char* h_res_dev = nullptr;            // h_res as the device sees it
-  uint32_t *h_flag = nullptr, *h_flag_dev = nullptr, *d_arrivals = nullptr;
+  PinnedBuffer<uint32_t> h_flag;                 // the step word the host spins on (run())
+  uint32_t* h_flag_dev = nullptr;
+  DeviceBuffer<uint32_t> d_arrivals;
   uint32_t flag_seq = 0;
   size_t res_stride = 0, off_kidx = 0, off_kdist = 0, off_nchk = 0, off_accept = 0, off_xout = 0, off_anchk = 0,
          off_aaccept = 0, off_axout = 0;
@@ -203,10 +207,10 @@ struct GraphBatch {
   rkh_status init(rkh_scene* sc, const rkh_qs_space* space, uint32_t n_problems, const uint64_t* capacities,
                   uint32_t kmax_);
   rkh_status init_common(rkh_scene* sc, int D_, uint32_t n_problems, const uint64_t* capacities, uint32_t kmax_);
-  void destroy();
+  ~GraphBatch();  // waits for the stream and destroys it; the buffers then free themselves
 
-  unsigned char* dres(uint32_t i) const { return d_res + size_t(i) * res_stride; }
-  const unsigned char* hres(uint32_t i) const { return h_res + size_t(i) * res_stride; }
+  unsigned char* dres(uint32_t i) const { return d_res.get() + size_t(i) * res_stride; }
+  const unsigned char* hres(uint32_t i) const { return h_res.get() + size_t(i) * res_stride; }
   // ---- results of the last run()
   uint32_t kcnt(uint32_t i) const { return reinterpret_cast<const uint32_t*>(hres(i))[0]; }
   uint32_t overflow(uint32_t i) const { return reinterpret_cast<const uint32_t*>(hres(i))[1]; }

@@ -90,8 +90,7 @@ rkh_status GraphBatch::init_dynamic(rkh_scene* sc, const rkh_dyn_space* space, u
     set_error("graph batch: state dimension exceeds RKH_MAX_DOF");
     return RKH_ERR_UNSUPPORTED;
   }
-  rkh_status st = build_dyn_dev(*space, 1.0, &dyn);
-  if (st != RKH_OK) return st;
+  RKH_TRY(build_dyn_dev(*space, 1.0, &dyn));
   dynamic = true;
   steer_req = steer_request();
   std::memset(&qs, 0, sizeof(qs));
@@ -125,16 +124,16 @@ rkh_status GraphBatch::init_common(rkh_scene* sc, int D_, uint32_t n_problems, c
   RKH_HIP(hipSetDevice(sc->ctx->device));
   RKH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   cmd_bytes = size_t(P) * (sizeof(KnnArgs) + 2 * sizeof(EdgeIO) + sizeof(GbAux));
-  RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_cmd), cmd_bytes, hipHostMallocDefault));
-  RKH_HIP(hipMalloc(reinterpret_cast<void**>(&d_cmd), cmd_bytes));
+  RKH_TRY(h_cmd.alloc(cmd_bytes));
+  RKH_TRY(d_cmd.alloc(cmd_bytes));
   auto carve = [&](unsigned char* base, KnnArgs** k, EdgeIO** io, EdgeIO** ioa, GbAux** ax) {
     *k = reinterpret_cast<KnnArgs*>(base);
     *io = reinterpret_cast<EdgeIO*>(base + size_t(P) * sizeof(KnnArgs));
     *ioa = reinterpret_cast<EdgeIO*>(base + size_t(P) * (sizeof(KnnArgs) + sizeof(EdgeIO)));
     *ax = reinterpret_cast<GbAux*>(base + size_t(P) * (sizeof(KnnArgs) + 2 * sizeof(EdgeIO)));
   };
-  carve(h_cmd, &h_knn, &h_io, &h_ioa, &h_aux);
-  carve(d_cmd, &d_knn, &d_io, &d_ioa, &d_aux);
+  carve(h_cmd.get(), &h_knn, &h_io, &h_ioa, &h_aux);
+  carve(d_cmd.get(), &d_knn, &d_io, &d_ioa, &d_aux);
   auto up8 = [](size_t v) { return (v + 7) / 8 * 8; };
   off_kidx = 16;
   off_kdist = up8(off_kidx + size_t(kmax) * 4);
@@ -145,17 +144,15 @@ rkh_status GraphBatch::init_common(rkh_scene* sc, int D_, uint32_t n_problems, c
   off_aaccept = off_anchk + kGbStageA * 4;
   off_axout = up8(off_aaccept + kGbStageA);
   res_stride = (off_axout + size_t(kGbStageA) * D * 8 + 15) / 16 * 16;  // gb_download_kernel moves 16-byte words
-  RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_res), res_stride * P, hipHostMallocDefault));
-  RKH_HIP(hipMalloc(reinterpret_cast<void**>(&d_res), res_stride * P));
-  RKH_HIP(hipMemset(d_res, 0, res_stride * P));
-  std::memset(h_res, 0, res_stride * P);
+  RKH_TRY(h_res.alloc(res_stride * P));
+  RKH_TRY(d_res.alloc_zeroed(res_stride * P));
+  std::memset(h_res.get(), 0, res_stride * P);
   {  // results written to the host by the device + a flag word the host spins on (gb_download_kernel)
-    RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_flag), 64, hipHostMallocDefault));
-    *h_flag = 0u;
-    RKH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_flag_dev), h_flag, 0));
-    RKH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_res_dev), h_res, 0));
-    RKH_HIP(hipMalloc(reinterpret_cast<void**>(&d_arrivals), sizeof(uint32_t)));
-    RKH_HIP(hipMemset(d_arrivals, 0, sizeof(uint32_t)));
+    RKH_TRY(h_flag.alloc(16));  // (a cache line of its own)
+    *h_flag.get() = 0u;
+    RKH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_flag_dev), h_flag.get(), 0));
+    RKH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_res_dev), h_res.get(), 0));
+    RKH_TRY(d_arrivals.alloc_zeroed(1));
     flag_seq = 0;
   }
   prob.resize(P);
@@ -163,34 +160,20 @@ rkh_status GraphBatch::init_common(rkh_scene* sc, int D_, uint32_t n_problems, c
     GbProblem& q = prob[i];
     q.tree.D = D;
     q.tree.capacity = (capacities[i] + 255) / 256 * 256;
-    RKH_HIP(hipMalloc(&q.tree.d_pos, q.tree.capacity * DP * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_knn_ws, kKnnWsBytes));
-    RKH_HIP(hipMalloc(&q.d_src_idx, emax * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_tgt_idx, emax * sizeof(uint32_t)));
+    RKH_TRY(q.pos.alloc(q.tree.capacity * DP));
+    q.tree.d_pos = q.pos.get();
+    RKH_TRY(q.d_knn_ws.alloc(kKnnWsBytes));
+    RKH_TRY(q.d_src_idx.alloc(emax));
+    RKH_TRY(q.d_tgt_idx.alloc(emax));
   }
   begin();
   return RKH_OK;
 }
 
-void GraphBatch::destroy() {
-  if (stream) (void)hipStreamSynchronize(stream);
-  for (GbProblem& q : prob) {
-    (void)hipFree(q.tree.d_pos);
-    (void)hipFree(q.d_knn_ws);
-    (void)hipFree(q.d_src_idx);
-    (void)hipFree(q.d_tgt_idx);
-  }
-  prob.clear();
-  (void)hipHostFree(h_cmd);
-  (void)hipFree(d_cmd);
-  (void)hipHostFree(h_res);
-  if (h_flag) (void)hipHostFree(h_flag);
-  (void)hipFree(d_arrivals);
-  h_flag = nullptr;
-  d_arrivals = nullptr;
-  (void)hipFree(d_res);
-  if (stream) (void)hipStreamDestroy(stream);
-  stream = nullptr;
+GraphBatch::~GraphBatch() {
+  if (!stream) return;
+  (void)hipStreamSynchronize(stream);
+  (void)hipStreamDestroy(stream);
 }
 
 rkh_status GraphBatch::neighbours(uint32_t i, const double* host_pos, const double* query, Neighbours* out,
@@ -288,8 +271,8 @@ void GraphBatch::begin() {
     a.v = 0;
     a.kidx = reinterpret_cast<const uint32_t*>(dres(i) + off_kidx);
     a.kcnt = reinterpret_cast<const uint32_t*>(dres(i));
-    a.src_idx = prob[i].d_src_idx;
-    a.tgt_idx = prob[i].d_tgt_idx;
+    a.src_idx = prob[i].d_src_idx.get();
+    a.tgt_idx = prob[i].d_tgt_idx.get();
     a.n_edges = reinterpret_cast<uint32_t*>(dres(i)) + 2;
   }
   any_knn = any_edges = any_append = any_stage_a = false;
@@ -316,7 +299,7 @@ rkh_status GraphBatch::cmd_stage_a(uint32_t i, uint32_t select_mode, uint32_t co
   io.x_out = reinterpret_cast<double*>(dres(i) + off_axout);
   io.steps_free = reinterpret_cast<uint32_t*>(dres(i) + off_anchk);
   io.accept = dres(i) + off_aaccept;
-  io.err_flag = scene->d_err;
+  io.err_flag = scene->d_err.get();
   if (select_mode == GB_SELECT_POINT) {
     io.mode = EDGE_POINT;
   } else {
@@ -380,7 +363,7 @@ rkh_status GraphBatch::cmd_knn(uint32_t i, const double* query, uint64_t n, uint
     set_error("graph batch: k-NN workspace too small");
     return RKH_ERR_CAPACITY;
   }
-  knn_carve(q.d_knn_ws, 1, &a.ws);
+  knn_carve(q.d_knn_ws.get(), 1, &a.ws);
   a.ws.overflow = reinterpret_cast<uint32_t*>(dres(i)) + 1;
   a.pos = q.tree.d_pos;
   a.n = n;
@@ -404,14 +387,14 @@ void GraphBatch::cmd_edges(uint32_t i, uint32_t list_mode, uint32_t v, int mode,
   a.v = v;
   EdgeIO& io = h_io[i];
   io.src = q.tree.d_pos;
-  io.src_idx = q.d_src_idx;
+  io.src_idx = q.d_src_idx.get();
   io.src_stride = DP;
   if (list_mode == GB_LIST_KNN_TO_QUERY) {
     io.tgt = d_aux[i].query;
     io.tgt_stride = 0;
   } else {
     io.tgt = q.tree.d_pos;
-    io.tgt_idx = q.d_tgt_idx;
+    io.tgt_idx = q.d_tgt_idx.get();
     io.tgt_stride = DP;
   }
   io.B = 0;
@@ -421,7 +404,7 @@ void GraphBatch::cmd_edges(uint32_t i, uint32_t list_mode, uint32_t v, int mode,
   io.accept = dres(i) + off_accept;
   io.mode = mode;
   io.steer_tol = tol;
-  io.err_flag = scene->d_err;
+  io.err_flag = scene->d_err.get();
   any_edges = true;
 }
 
@@ -431,7 +414,7 @@ SteerMapping GraphBatch::steer(uint32_t edges) const {
 
 rkh_status GraphBatch::run() {
   hipStream_t s = stream;
-  RKH_HIP(hipMemcpyAsync(d_cmd, h_cmd, cmd_bytes, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(d_cmd.get(), h_cmd.get(), cmd_bytes, hipMemcpyHostToDevice, s));
   if (any_append) hipLaunchKernelGGL(gb_prep_kernel, dim3(P), dim3(64), 0, s, d_aux, DP);
   if (any_stage_a) {
     rkh_status st = dynamic ? launch_propagate(s, *scene, steer(kGbStageA), dyn, EdgeIO(), kGbStageA, 0, d_ioa, nullptr, P)
@@ -452,15 +435,15 @@ rkh_status GraphBatch::run() {
   }
   // the results land in pinned host memory; the acquire load of the step word orders the reads of h_res after it
   const uint32_t tag = ++flag_seq;
-  hipLaunchKernelGGL(gb_download_kernel, dim3(P), dim3(256), 0, s, reinterpret_cast<const uint4*>(d_res),
-                     reinterpret_cast<uint4*>(h_res_dev), uint32_t(res_stride / 16), d_arrivals, h_flag_dev, tag);
+  hipLaunchKernelGGL(gb_download_kernel, dim3(P), dim3(256), 0, s, reinterpret_cast<const uint4*>(d_res.get()),
+                     reinterpret_cast<uint4*>(h_res_dev), uint32_t(res_stride / 16), d_arrivals.get(), h_flag_dev, tag);
   RKH_HIP(hipGetLastError());
-  for (uint32_t spins = 0; __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != tag; ++spins) {
+  for (uint32_t spins = 0; __atomic_load_n(h_flag.get(), __ATOMIC_ACQUIRE) != tag; ++spins) {
     __builtin_ia32_pause();
     if ((spins & 0xFFFFu) == 0xFFFFu) {  // a failed launch or a device fault must not hang the host
       const hipError_t q = hipStreamQuery(s);
       if (q != hipSuccess && q != hipErrorNotReady) RKH_HIP(q);
-      if (q == hipSuccess && __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != tag) {
+      if (q == hipSuccess && __atomic_load_n(h_flag.get(), __ATOMIC_ACQUIRE) != tag) {
         set_error("graph batch: the step's results never arrived");
         return RKH_ERR_DEVICE;
       }

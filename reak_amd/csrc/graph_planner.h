@@ -71,7 +71,6 @@ struct GraphHandle {
   int D = 0;
   uint32_t P = 0;  // problems
   double lower[RKH_MAX_DOF], upper[RKH_MAX_DOF];
-  ~GraphHandle() { gb.destroy(); }
 
   // qs != nullptr: quasi-static free space (vertices = joint positions); dyn != nullptr: steerable dynamic free space
   // (vertices = states (q, qd), D = 2 n_dof; edges are RK4 propagations).  Every problem owns `slots` device trees

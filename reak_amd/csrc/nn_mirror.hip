@@ -435,62 +435,40 @@ extern "C" rkh_status rkh_diag_nn_mirror_query(rkh_ctx* ctx, const double* pts, 
   for (uint64_t i = 0; i < n; ++i)
     for (int d = 0; d < D; ++d) rows[i * DP + d] = pts[i * D + d];
   const uint32_t Bp = (B + 7u) / 8u * 8u;
-  double *d_pos = nullptr, *d_q = nullptr, *d_dist = nullptr;
-  void *d_mirror = nullptr, *d_scratch = nullptr;
-  uint32_t *d_idx = nullptr, *d_yb = nullptr, *d_dx = nullptr;
-  NnArgs* d_tab = nullptr;
-  auto cleanup = [&]() {
-    void* bufs[] = {d_pos, d_q, d_dist, d_mirror, d_idx, d_scratch, d_yb, d_tab, d_dx};
-    for (void* b : bufs) (void)hipFree(b);
-  };
-#define RKH_TRY(expr)                                               \
-  do {                                                              \
-    hipError_t _e = (expr);                                         \
-    if (_e != hipSuccess) {                                         \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-      cleanup();                                                    \
-      return RKH_ERR_DEVICE;                                        \
-    }                                                               \
-  } while (0)
+  DeviceBuffer<double> d_pos, d_q, d_dist;
+  DeviceBuffer<void> d_mirror, d_scratch;
+  DeviceBuffer<uint32_t> d_idx, d_yb, d_dx;
+  DeviceBuffer<NnArgs> d_tab;
   const size_t scratch_bytes = nn1_mirror_query_bytes() * Bp;
-  RKH_TRY(hipMalloc(&d_pos, rows.size() * sizeof(double)));
-  RKH_TRY(hipMalloc(&d_q, size_t(B) * D * sizeof(double)));
-  RKH_TRY(hipMalloc(&d_dist, size_t(B) * sizeof(double)));
-  RKH_TRY(hipMalloc(&d_idx, size_t(B) * sizeof(uint32_t)));
-  RKH_TRY(hipMalloc(&d_scratch, scratch_bytes));
-  RKH_TRY(hipMalloc(&d_yb, 2 * sizeof(uint32_t)));
-  RKH_TRY(hipMalloc(&d_dx, sizeof(uint32_t)));
-  RKH_TRY(hipMalloc(&d_tab, sizeof(NnArgs)));
-  RKH_TRY(hipMalloc(&d_mirror, nn1_mirror_bytes(n)));
-  RKH_TRY(hipMemcpy(d_pos, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-  RKH_TRY(hipMemcpy(d_q, q, size_t(B) * D * sizeof(double), hipMemcpyHostToDevice));
-  RKH_TRY(hipMemset(d_scratch, 0, scratch_bytes));
-  RKH_TRY(hipMemset(d_dx, 0, sizeof(uint32_t)));
+  RKH_TRY(d_pos.alloc(rows.size()));
+  RKH_TRY(d_q.alloc(size_t(B) * D));
+  RKH_TRY(d_dist.alloc(B));
+  RKH_TRY(d_idx.alloc(B));
+  RKH_TRY(d_scratch.alloc_zeroed(scratch_bytes));
+  RKH_TRY(d_yb.alloc(2));
+  RKH_TRY(d_dx.alloc_zeroed(1));
+  RKH_TRY(d_tab.alloc(1));
+  RKH_TRY(d_mirror.alloc(nn1_mirror_bytes(n)));
+  RKH_HIP(hipMemcpy(d_pos.get(), rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(d_q.get(), q, size_t(B) * D * sizeof(double), hipMemcpyHostToDevice));
   const uint32_t yb[2] = {0u, (B + nn1_mirror_queries() - 1) / nn1_mirror_queries()};
-  RKH_TRY(hipMemcpy(d_yb, yb, sizeof(yb), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(d_yb.get(), yb, sizeof(yb), hipMemcpyHostToDevice));
   NnArgs a;
-  a.pos = d_pos;
+  a.pos = d_pos.get();
   a.n = n;
-  a.q = d_q;
+  a.q = d_q.get();
   a.B = B;
-  a.idx = d_idx;
-  a.dist = d_dist;
-  a.mirror = d_mirror;
-  a.dx_max_bits = d_dx;
-  nn1_mirror_carve(d_scratch, Bp, &a);
-  RKH_TRY(hipMemcpy(d_tab, &a, sizeof(a), hipMemcpyHostToDevice));
-  rkh_status st = launch_mirror_fill(s, d_mirror, n);
-  if (st == RKH_OK) st = launch_mirror_build(s, d_mirror, d_pos, n, D, DP, d_dx);
-  if (st == RKH_OK)
-    st = launch_nn1_mirror(s, D, d_tab, 1, n, B, std::sqrt(double(D)) * coord_bound, d_yb, nullptr, nullptr);
-  if (st != RKH_OK) {
-    cleanup();
-    return st;
-  }
-  RKH_TRY(hipStreamSynchronize(s));
-  RKH_TRY(hipMemcpy(idx, d_idx, size_t(B) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  RKH_TRY(hipMemcpy(dist, d_dist, size_t(B) * sizeof(double), hipMemcpyDeviceToHost));
-#undef RKH_TRY
-  cleanup();
+  a.idx = d_idx.get();
+  a.dist = d_dist.get();
+  a.mirror = d_mirror.get();
+  a.dx_max_bits = d_dx.get();
+  nn1_mirror_carve(d_scratch.get(), Bp, &a);
+  RKH_HIP(hipMemcpy(d_tab.get(), &a, sizeof(a), hipMemcpyHostToDevice));
+  RKH_TRY(launch_mirror_fill(s, d_mirror.get(), n));
+  RKH_TRY(launch_mirror_build(s, d_mirror.get(), d_pos.get(), n, D, DP, d_dx.get()));
+  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, d_yb.get(), nullptr, nullptr));
+  RKH_HIP(hipStreamSynchronize(s));
+  RKH_HIP(hipMemcpy(idx, d_idx.get(), size_t(B) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(dist, d_dist.get(), size_t(B) * sizeof(double), hipMemcpyDeviceToHost));
   return RKH_OK;
 }

@@ -27,7 +27,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <random>
+#include <memory>
 
 #include "nn_device.h"
 #include "nn_mirror.h"
@@ -429,28 +429,20 @@ using namespace rkh;
 namespace {
 struct Problem {  // host view of one planning problem
   rkh_rrt_params prm;
-  uint32_t* d_mt = nullptr;  // the problem's mt19937 on the device: 624 state words + position
-  // device buffers
-  double* d_tree = nullptr;
-  uint32_t* d_parent = nullptr;
-  uint32_t* d_node_sample = nullptr;
-  double* d_goal_dist = nullptr;
-  double* d_samples = nullptr;
-  uint32_t* d_nn_seq = nullptr;
-  uint8_t* d_accept_log = nullptr;
-  uint32_t* d_nn_idx = nullptr;
-  double* d_nn_dist = nullptr;
-  double* d_x_out = nullptr;
-  uint32_t* d_steps = nullptr;
-  uint8_t* d_accept = nullptr;
-  double* d_probe_x = nullptr;
-  uint32_t* d_probe_steps = nullptr;
-  void* d_mirror = nullptr;        // half-precision mirror of d_tree (nn_mirror.h)
-  void* d_cand = nullptr;          // per-query scratch of the mirror sweep (nn1_mirror_carve), then one word: dx_max_bits
-  double* d_goal = nullptr;
-  double* d_part_dist = nullptr;
-  uint32_t* d_part_idx = nullptr;
-  uint32_t* d_round_n = nullptr;
+  DeviceBuffer<uint32_t> d_mt;  // the problem's mt19937 on the device: 624 state words + position
+  DeviceBuffer<double> d_tree, d_goal_dist, d_goal;              // [capacity] vertex rows and goal-probe results; the goal
+  DeviceBuffer<uint32_t> d_parent, d_node_sample;                // [capacity]
+  DeviceBuffer<double> d_samples;                                // [sample_cap] the sample stream ...
+  DeviceBuffer<uint32_t> d_nn_seq;                               // ... and the log of its iterations
+  DeviceBuffer<uint8_t> d_accept_log;
+  DeviceBuffer<uint32_t> d_nn_idx, d_steps, d_probe_steps;       // [b_max (+ kProbeGranule)] a round's candidates and probes
+  DeviceBuffer<double> d_nn_dist, d_x_out, d_probe_x;
+  DeviceBuffer<uint8_t> d_accept;
+  DeviceBuffer<double> d_part_dist;                              // partial minima of the NN sweep
+  DeviceBuffer<uint32_t> d_part_idx, d_round_n;
+  DeviceBuffer<void> d_mirror;       // half-precision mirror of d_tree (nn_mirror.h)
+  DeviceBuffer<void> d_cand;         // per-query scratch of the mirror sweep (nn1_mirror_carve), then one word:
+  uint32_t* dx_max_bits = nullptr;   // ... this one, the mirror's running maximum of |x - x_h| (null without a mirror)
   uint64_t capacity = 0, sample_cap = 0, samples_ready = 0;
   PlannerState h_state;
   // solution bookkeeping (register_basic_solution_path_impl, solution_path_factories.hpp:58-110)
@@ -461,13 +453,13 @@ struct Problem {  // host view of one planning problem
   bool truncated = false;
   uint64_t final_n = 0, final_iterations = 0;
 };
+static_assert(std::is_nothrow_move_constructible<Problem>::value, "std::vector<Problem> is resized");
 }  // namespace
 
 struct rkh_planner {
   rkh_scene* scene = nullptr;
   hipStream_t stream = nullptr;
-  double* h_gd = nullptr;     // pinned read-back buffer of the goal-probe results (rkh_planner_sync)
-  uint64_t h_gd_cap = 0;
+  PinnedBuffer<double> h_gd;  // pinned read-back buffer of the goal-probe results (rkh_planner_sync)
   hipStream_t copy_stream = nullptr;  // sample-stream uploads (beside the rounds enqueued on `stream`)
   bool quasi_static = false;  // false: steerable dynamic space (propagate kernel); true: manip_quasi_static_env (edge_check)
   double lower[RKH_MAX_STATE], upper[RKH_MAX_STATE];  // hyperbox the samples are drawn from
@@ -477,12 +469,15 @@ struct rkh_planner {
   uint32_t P = 0;
   std::vector<Problem> prob;
   uint32_t b_max = 1024;
+  uint32_t b_min = 8;          // RKH_BATCH_MIN
+  float batch_factor = 1.25f;  // candidates per round = batch_factor * sqrt(n) per problem (tune_planner)
+  uint64_t sample_cap_min = 0;  // RKH_SAMPLE_CAP: at least this many samples in a problem's first stream buffers
   SteerMapping steer = SteerMapping::Wave;  // the form of every round's steer launches (steer_mapping; dynamic space)
-  double* d_lane_ws = nullptr;  // workspace of the two-lanes-per-edge kernel
+  DeviceBuffer<double> d_lane_ws;  // workspace of the two-lanes-per-edge kernel
   double coord_bound = 0.0;     // max |coordinate| of vertices and samples (hyperbox bounds), 0 = unknown
-  uint32_t* d_sel = nullptr;    // [2] edges of the current round (by round parity), see round_begin_kernel
-  uint32_t* d_nn_base = nullptr;    // [P + 1] prefix of the NN sweep's query blocks per problem (matrix-core kernel)
-  uint32_t* d_wave_base = nullptr;  // [2 P + 1] prefix of the working waves per (problem, candidates | probes) segment
+  DeviceBuffer<uint32_t> d_sel;        // [2] edges of the current round (by round parity), see round_begin_kernel
+  DeviceBuffer<uint32_t> d_nn_base;    // [P + 1] prefix of the NN sweep's query blocks per problem (matrix-core kernel)
+  DeviceBuffer<uint32_t> d_wave_base;  // [2 P + 1] prefix of the working waves per (problem, candidates | probes) segment
   uint32_t round_parity = 0;
   // host-side upper bounds that size the launches of a round (the exact counts live on the device): n_ub[i] >= vertex
   // count of problem i (exact after every sync, + the round's batch bound per enqueued round)
@@ -496,18 +491,18 @@ struct rkh_planner {
   uint32_t part_blocks = 0;
   uint64_t max_capacity = 0;
   // device tables (P entries each)
-  PlannerState* d_states = nullptr;
-  ProblemDev* d_probs = nullptr;
-  NnArgs* d_nn_args = nullptr;
-  EdgeIO* d_io_steer = nullptr;
-  EdgeIO* d_io_probe = nullptr;
+  DeviceBuffer<PlannerState> d_states;
+  DeviceBuffer<ProblemDev> d_probs;
+  DeviceBuffer<NnArgs> d_nn_args;
+  DeviceBuffer<EdgeIO> d_io_steer;
+  DeviceBuffer<EdgeIO> d_io_probe;
   bool nn_mirror = false;  // the NN search of a round runs over the trees' half-precision mirrors (nn_mirror.hip)
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
   // Step-wise steer launches (propagate_pair_step_kernel): one launch per RK4 step over the live edges of all problems,
   // survivors handed on through two ping-pong lists.
-  uint2* d_step_list[2] = {nullptr, nullptr};  // (segment, edge) of the edges alive after step k (k odd / even)
-  uint32_t* d_step_cnt = nullptr;              // [kMaxSteps + 1] entries of the list launch k reads (cleared by round_begin_kernel)
-  unsigned long long* d_steps_exec = nullptr;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
+  DeviceBuffer<uint2> d_step_list[2];  // (segment, edge) of the edges alive after step k (k odd / even)
+  DeviceBuffer<uint32_t> d_step_cnt;   // [kMaxSteps + 1] entries of the list launch k reads (cleared by round_begin_kernel)
+  DeviceBuffer<unsigned long long> d_steps_exec;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
   uint32_t step_blocks_cap = 0;                // grid bound of a step launch (its blocks stride over the chunks beyond it)
   // rounds below this many edges keep the single whole-edge launch of the two-lanes mapping (RKH_STEER_SPLIT_MIN_EDGES;
   // default: what leaves every SIMD at most one 32-edge wave -- such a round gains nothing from shedding waves)
@@ -516,23 +511,41 @@ struct rkh_planner {
   uint64_t sum_batch_ub = 0, prev_sum_batch_ub = 0;  // host-side bounds on the candidates of this / the previous round, all problems
   // segment tables of the sample generator: [0] what the enqueued rounds need, [1] the next call's share, generated
   // while the GPU works on the rounds just enqueued
-  double* d_bounds = nullptr;  // lower[D], upper[D] of the sampled hyperbox
+  DeviceBuffer<double> d_bounds;  // lower[D], upper[D] of the sampled hyperbox
   struct Staging {
-    SampleSeg* h_tab = nullptr; // pinned segment table [P]
-    SampleSeg* d_tab = nullptr;
+    PinnedBuffer<SampleSeg> h_tab;  // pinned segment table [P]
+    DeviceBuffer<SampleSeg> d_tab;
     hipEvent_t done = nullptr;
     bool pending = false;
   } staging[2];
-  GoalSeg* h_gd_tab = nullptr;  // pinned [P]
-  GoalSeg* d_gd_tab = nullptr;
-  double* d_gd = nullptr;       // gathered goal-probe results (rkh_planner_sync)
-  uint64_t d_gd_cap = 0;
+  PinnedBuffer<GoalSeg> h_gd_tab;  // pinned [P]
+  DeviceBuffer<GoalSeg> d_gd_tab;
+  DeviceBuffer<double> d_gd;       // gathered goal-probe results (rkh_planner_sync)
   // optional HIP-event timing of the NN sweep kernel (RKH_PROFILE_NN=1)
   bool profile_nn = false;
   std::vector<hipEvent_t> ev;  // pairs
   std::vector<hipEvent_t> ev_steer;  // pairs around the steer launches of the same rounds
   uint32_t prof_rounds = 0;
   static constexpr uint32_t kProfMax = kProfRounds;
+
+  // the two-lanes steer kernel runs in this planner's rounds: its residency sizes the wave fit and the step-wise launches
+  bool lane_kernel() const { return steer == SteerMapping::Auto || steer == SteerMapping::Pair; }
+
+  // Both streams idle and the events gone first; the members then free their memory.
+  ~rkh_planner() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (Staging& sg : staging) {
+      if (sg.pending) (void)hipEventSynchronize(sg.done);
+      if (sg.done) (void)hipEventDestroy(sg.done);
+    }
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_steer) (void)hipEventDestroy(e);
+    if (copy_stream) {
+      (void)hipStreamSynchronize(copy_stream);
+      (void)hipStreamDestroy(copy_stream);
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -560,25 +573,25 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
     sg.pending = false;
   }
   if (!sg.done) RKH_HIP(hipEventCreateWithFlags(&sg.done, hipEventDisableTiming));
-  if (!sg.h_tab) {
-    RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&sg.h_tab), p->P * sizeof(SampleSeg), hipHostMallocDefault));
-    RKH_HIP(hipMalloc(&sg.d_tab, p->P * sizeof(SampleSeg)));
+  if (!sg.d_tab) {
+    RKH_TRY(sg.h_tab.alloc(p->P));
+    RKH_TRY(sg.d_tab.alloc(p->P));
   }
   uint32_t n_seg = 0;
   for (uint32_t i = 0; i < p->P; ++i) {
     if (!upto[i]) continue;
     Problem& q = p->prob[i];
-    SampleSeg& seg = sg.h_tab[n_seg++];
-    seg.dst = q.d_samples + q.samples_ready * D;
+    SampleSeg& seg = sg.h_tab.get()[n_seg++];
+    seg.dst = q.d_samples.get() + q.samples_ready * D;
     seg.count = (upto[i] - q.samples_ready) * D;
-    seg.mt = q.d_mt;
-    seg.ready_ptr = &p->d_states[i].samples_ready;
+    seg.mt = q.d_mt.get();
+    seg.ready_ptr = &p->d_states.get()[i].samples_ready;
     seg.ready_new = uint32_t(upto[i]);
     seg.pad = 0;
     q.samples_ready = upto[i];
   }
-  RKH_HIP(hipMemcpyAsync(sg.d_tab, sg.h_tab, n_seg * sizeof(SampleSeg), hipMemcpyHostToDevice, p->copy_stream));
-  hipLaunchKernelGGL(generate_samples_kernel, dim3(n_seg), dim3(256), 0, p->copy_stream, sg.d_tab, p->d_bounds, D);
+  RKH_HIP(hipMemcpyAsync(sg.d_tab.get(), sg.h_tab.get(), n_seg * sizeof(SampleSeg), hipMemcpyHostToDevice, p->copy_stream));
+  hipLaunchKernelGGL(generate_samples_kernel, dim3(n_seg), dim3(256), 0, p->copy_stream, sg.d_tab.get(), p->d_bounds.get(), D);
   RKH_HIP(hipGetLastError());
   // The generator runs on its own stream, beside the rounds already enqueued on the planner stream: it writes beyond every
   // problem's samples_ready (no round reads there) and then raises samples_ready.  Work enqueued on the planner stream
@@ -591,7 +604,7 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
 
 template <int DP>
 void launch_fixup(rkh_planner* p, uint32_t batch_ub) {
-  hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
+  hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs.get(), p->D);
 }
 
 // upper bound of the batch size round_begin_kernel will choose for a problem with at most n_ub vertices (same float
@@ -611,22 +624,22 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P);
   if (p->steer != SteerMapping::Auto) {
     KernelGate always;  // no gate; the executed steps are counted like Auto's (rkh_planner_steer_steps)
-    always.steps_exec = p->d_steps_exec;
+    always.steps_exec = p->d_steps_exec.get();
     return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
-                            p->d_lane_ws, always);
+                            p->d_lane_ws.get(), always);
   }
   // Auto: every form of the sequence is launched; on the device each compares the round's edge count with its gate and
   // the ones not chosen exit at once.  Small rounds -> Duo / Wave (latency), large -> Pair (32 edges per wave).
   auto run = [&](SteerMapping m, double* ws, const KernelGate& gate) {
     return launch_propagate(p->stream, *p->scene, m, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P, ws, gate);
   };
-  KernelGate gate_wave{p->d_sel + p->round_parity, 0u, p->lane_threshold};
-  KernelGate gate_lane{p->d_sel + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
-  gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec;
+  KernelGate gate_wave{p->d_sel.get() + p->round_parity, 0u, p->lane_threshold};
+  KernelGate gate_lane{p->d_sel.get() + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
+  gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec.get();
   if (compact && p->d_wave_base) {  // a regular round: (candidates, probes) segments as round_begin_kernel counted them
-    gate_lane.wave_base = p->d_wave_base;
+    gate_lane.wave_base = p->d_wave_base.get();
     gate_lane.n_segments = 2 * p->P;
-    gate_wave.wave_base = p->d_wave_base + (2 * p->P + 1);
+    gate_wave.wave_base = p->d_wave_base.get() + (2 * p->P + 1);
     gate_wave.n_segments = 2 * p->P;
   }
   rkh_status st = RKH_OK;
@@ -646,7 +659,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
   // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
   // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
-  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws, gate_lane);
+  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws.get(), gate_lane);
   // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
   // rounds take one whole-edge launch
   const uint32_t split_edges = p->split_min_edges;
@@ -657,7 +670,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate whole = gate_lane;
     whole.hi = split_edges;
     if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
-      st = run(SteerMapping::Pair, p->d_lane_ws, whole);
+      st = run(SteerMapping::Pair, p->d_lane_ws.get(), whole);
       if (st != RKH_OK) return st;
     }
     gate_lane.lo = split_edges;
@@ -666,17 +679,27 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   const uint32_t epw = pair_kernel_edges_per_wave();
   const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
   return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
-                                     p->d_wave_base + (2 * p->P + 1), p->d_step_list[0], p->d_step_list[1], p->d_step_cnt,
-                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec);
+                                     p->d_wave_base.get() + (2 * p->P + 1), p->d_step_list[0].get(),
+                                     p->d_step_list[1].get(), p->d_step_cnt.get(), p->d_lane_ws.get(), blocks, gate_lane,
+                                     p->d_steps_exec.get());
 }
 
 // goal probes still pending after the last enqueued round
 rkh_status flush_probes(rkh_planner* p) {
-  hipLaunchKernelGGL(probes_take_all_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
-  rkh_status st = launch_edges(p, p->b_max + kProbeGranule, 0, p->d_io_probe, nullptr);
-  if (st != RKH_OK) return st;
-  hipLaunchKernelGGL(probes_flushed_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
+  hipLaunchKernelGGL(probes_take_all_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs.get());
+  RKH_TRY(launch_edges(p, p->b_max + kProbeGranule, 0, p->d_io_probe.get(), nullptr));
+  hipLaunchKernelGGL(probes_flushed_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs.get());
   RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+// the timing events [2 slot] and [2 slot + 1] of a profiled round exist
+rkh_status ensure_event_pair(std::vector<hipEvent_t>& ev, uint32_t slot) {
+  while (ev.size() < 2 * size_t(slot + 1)) {
+    hipEvent_t e;
+    RKH_HIP(hipEventCreate(&e));
+    ev.push_back(e);
+  }
   return RKH_OK;
 }
 
@@ -686,22 +709,10 @@ rkh_status enqueue_round(rkh_planner* p) {
   uint32_t slot = 0;
   if (p->profile_nn && p->prof_rounds < rkh_planner::kProfMax) {
     slot = p->prof_rounds++;
-    if (p->ev.size() < 2 * size_t(slot + 1)) {
-      hipEvent_t a, b;
-      RKH_HIP(hipEventCreate(&a));
-      RKH_HIP(hipEventCreate(&b));
-      p->ev.push_back(a);
-      p->ev.push_back(b);
-    }
+    RKH_TRY(ensure_event_pair(p->ev, slot));
     ev0 = p->ev[2 * slot];
     ev1 = p->ev[2 * slot + 1];
-    if (p->ev_steer.size() < 2 * size_t(slot + 1)) {
-      hipEvent_t a, b;
-      RKH_HIP(hipEventCreate(&a));
-      RKH_HIP(hipEventCreate(&b));
-      p->ev_steer.push_back(a);
-      p->ev_steer.push_back(b);
-    }
+    RKH_TRY(ensure_event_pair(p->ev_steer, slot));
   }
   // the round's batch scale is chosen on the device (round_begin_kernel); the launches are sized for its upper end
   const bool fit = p->wave_fit && p->steer == SteerMapping::Auto;
@@ -722,21 +733,21 @@ rkh_status enqueue_round(rkh_planner* p) {
   const uint32_t probe_ub = p->prev_batch_ub ? p->prev_batch_ub : p->b_max;
   p->prev_batch_ub = batch_ub + kProbeGranule;  // next round's probes: this round's vertices + what was left over
   p->round_parity ^= 1u;
-  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs, p->P, slot, p->d_sel, p->round_parity,
-                     fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base, p->d_nn_base,
+  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs.get(), p->P, slot, p->d_sel.get(), p->round_parity,
+                     fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base.get(), p->d_nn_base.get(),
                      p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries(),
-                     p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
-                     p->d_step_cnt);
+                     p->d_wave_base.get() ? p->d_wave_base.get() + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
+                     p->d_step_cnt.get());
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
-                      ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
+                      ? launch_nn1_mirror(s, p->D, p->d_nn_args.get(), p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base.get(),
                                           ev0, ev1)
-                      : launch_nn1(s, p->D, NnArgs(), p->d_nn_args, p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
-                                   ev1, p->coord_bound, p->d_nn_base, true);
+                      : launch_nn1(s, p->D, NnArgs(), p->d_nn_args.get(), p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
+                                   ev1, p->coord_bound, p->d_nn_base.get(), true);
   if (st != RKH_OK) return st;
   // 2. speculative steer of all candidates + the goal probes of the vertices the previous round committed
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot], s);
-  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer, p->d_io_probe, true);
+  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer.get(), p->d_io_probe.get(), true);
   if (st != RKH_OK) return st;
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot + 1], s);
   // 3. fix-up against the vertices this round itself would add
@@ -752,53 +763,131 @@ rkh_status enqueue_round(rkh_planner* p) {
     default: set_error("planner: unsupported state dimension"); return RKH_ERR_UNSUPPORTED;
   }
   // 4. commit the valid prefix
-  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u);
+  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs.get(), p->D, p->DP, fit ? kProbeGranule : 1u);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
-void free_problem(Problem& q) {
-  void* bufs[] = {q.d_tree, q.d_parent, q.d_node_sample, q.d_goal_dist, q.d_samples, q.d_nn_seq, q.d_accept_log,
-                  q.d_nn_idx, q.d_nn_dist, q.d_x_out, q.d_steps, q.d_accept, q.d_probe_x, q.d_probe_steps, q.d_goal,
-                  q.d_part_dist, q.d_part_idx, q.d_round_n, q.d_mt, q.d_mirror, q.d_cand};
-  for (void* b : bufs) (void)hipFree(b);
+// ---- the device tables: entry i of each as a function of problem i ----------------------------------------------------
+ProblemDev problem_dev(const rkh_planner* p, uint32_t i) {
+  const Problem& q = p->prob[i];
+  ProblemDev pd;
+  pd.st = p->d_states.get() + i;
+  pd.tree = q.d_tree.get();
+  pd.parent = q.d_parent.get();
+  pd.node_sample = q.d_node_sample.get();
+  pd.samples = q.d_samples.get();
+  pd.nn_seq = q.d_nn_seq.get();
+  pd.accept_log = q.d_accept_log.get();
+  pd.nn_idx = q.d_nn_idx.get();
+  pd.nn_dist = q.d_nn_dist.get();
+  pd.x_out = q.d_x_out.get();
+  pd.accept = q.d_accept.get();
+  pd.round_n = q.d_round_n.get();
+  pd.mirror = static_cast<uint4*>(q.d_mirror.get());
+  pd.dx_max_bits = q.dx_max_bits;
+  return pd;
+}
+
+NnArgs nn_args(const rkh_planner* p, uint32_t i) {
+  const Problem& q = p->prob[i];
+  PlannerState* st = p->d_states.get() + i;
+  NnArgs na;
+  na.pos = q.d_tree.get();
+  na.d_n = &st->n;
+  na.q = q.d_samples.get();
+  na.d_qoff = &st->s0;
+  na.B = p->b_max;
+  na.d_B = &st->B;
+  na.part_dist = q.d_part_dist.get();
+  na.part_idx = q.d_part_idx.get();
+  na.seed = q.d_part_idx.get() + uint64_t(p->part_blocks) * p->b_max;
+  na.idx = q.d_nn_idx.get();
+  na.dist = q.d_nn_dist.get();
+  na.mirror = q.d_mirror.get();
+  if (q.d_cand) {
+    nn1_mirror_carve(q.d_cand.get(), p->b_max, &na);
+    na.dx_max_bits = q.dx_max_bits;
+  }
+  return na;
+}
+
+EdgeIO steer_io(const rkh_planner* p, uint32_t i) {
+  const Problem& q = p->prob[i];
+  PlannerState* st = p->d_states.get() + i;
+  EdgeIO io;
+  io.src = q.d_tree.get();
+  io.src_idx = q.d_nn_idx.get();
+  io.src_stride = p->DP;
+  io.tgt = q.d_samples.get();
+  io.d_tgt_off = &st->s0;
+  io.tgt_stride = p->D;
+  io.B = p->b_max;
+  io.d_B = &st->B;
+  io.x_out = q.d_x_out.get();
+  io.steps_free = q.d_steps.get();
+  io.mode = EDGE_STEER_ACCEPT;
+  io.best_case = q.d_nn_dist.get();
+  io.steer_tol = q.prm.steer_tol;
+  io.accept = q.d_accept.get();
+  io.err_flag = p->scene->d_err.get();
+  return io;
+}
+
+EdgeIO probe_io(const rkh_planner* p, uint32_t i) {
+  const Problem& q = p->prob[i];
+  PlannerState* st = p->d_states.get() + i;
+  EdgeIO gp;
+  gp.src = q.d_tree.get();
+  gp.d_src_first = &st->n_before;
+  gp.src_stride = p->DP;
+  gp.tgt = q.d_goal.get();
+  gp.tgt_stride = 0;
+  gp.B = p->b_max + kProbeGranule;
+  gp.d_B = &st->n_new;
+  gp.x_out = q.d_probe_x.get();
+  gp.steps_free = q.d_probe_steps.get();
+  gp.mode = EDGE_GOAL_PROBE;
+  gp.goal_dist = q.d_goal_dist.get();
+  gp.err_flag = p->scene->d_err.get();
+  return gp;
 }
 
 // generate_rrt has no iteration cap (rr_tree.hpp:192-196: keep_going() looks at the vertex count only), so the device-
 // resident sample stream and its per-iteration logs must not have one either: when a problem's cursor comes near the
-// end of its buffers they are re-allocated at twice the size.  Called with both streams idle (rkh_planner_sync).
+// end of its buffers they are re-allocated at twice the size.  Called with both streams idle (rkh_planner_sync).  A
+// failure before the swap leaves the problem as it was.
 rkh_status grow_sample_buffers(rkh_planner* p, uint32_t i, uint64_t new_cap) {
   Problem& q = p->prob[i];
   const int D = p->D;
-  double* ns = nullptr;
-  uint32_t* nq = nullptr;
-  uint8_t* na = nullptr;
-  RKH_HIP(hipMalloc(&ns, new_cap * D * sizeof(double)));
-  RKH_HIP(hipMalloc(&nq, new_cap * sizeof(uint32_t)));
-  RKH_HIP(hipMalloc(&na, new_cap));
-  RKH_HIP(hipMemcpy(ns, q.d_samples, q.samples_ready * D * sizeof(double), hipMemcpyDeviceToDevice));
-  RKH_HIP(hipMemcpy(nq, q.d_nn_seq, q.sample_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-  RKH_HIP(hipMemcpy(na, q.d_accept_log, q.sample_cap, hipMemcpyDeviceToDevice));
-  (void)hipFree(q.d_samples);
-  (void)hipFree(q.d_nn_seq);
-  (void)hipFree(q.d_accept_log);
-  q.d_samples = ns;
-  q.d_nn_seq = nq;
-  q.d_accept_log = na;
+  DeviceBuffer<double> ns;
+  DeviceBuffer<uint32_t> nq;
+  DeviceBuffer<uint8_t> na;
+  RKH_TRY(ns.alloc(new_cap * D));
+  RKH_TRY(nq.alloc(new_cap));
+  RKH_TRY(na.alloc(new_cap));
+  RKH_HIP(hipMemcpy(ns.get(), q.d_samples.get(), q.samples_ready * D * sizeof(double), hipMemcpyDeviceToDevice));
+  RKH_HIP(hipMemcpy(nq.get(), q.d_nn_seq.get(), q.sample_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  RKH_HIP(hipMemcpy(na.get(), q.d_accept_log.get(), q.sample_cap, hipMemcpyDeviceToDevice));
+  q.d_samples = std::move(ns);  // (frees the old one)
+  q.d_nn_seq = std::move(nq);
+  q.d_accept_log = std::move(na);
   q.sample_cap = new_cap;
   // the device tables that point into these buffers
-  const double* cs = ns;
-  RKH_HIP(hipMemcpy(&p->d_probs[i].samples, &cs, sizeof(cs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_probs[i].nn_seq, &nq, sizeof(nq), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_probs[i].accept_log, &na, sizeof(na), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_nn_args[i].q, &cs, sizeof(cs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_io_steer[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  const double* cs = q.d_samples.get();
+  uint32_t* cq = q.d_nn_seq.get();
+  uint8_t* ca = q.d_accept_log.get();
+  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].samples, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].nn_seq, &cq, sizeof(cq), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].accept_log, &ca, sizeof(ca), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_nn_args.get()[i].q, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_io_steer.get()[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
   return RKH_OK;
 }
 
 rkh_status read_states(rkh_planner* p) {
   std::vector<PlannerState> hs(p->P);
-  RKH_HIP(hipMemcpyAsync(hs.data(), p->d_states, p->P * sizeof(PlannerState), hipMemcpyDeviceToHost, p->stream));
+  RKH_HIP(hipMemcpyAsync(hs.data(), p->d_states.get(), p->P * sizeof(PlannerState), hipMemcpyDeviceToHost, p->stream));
   RKH_HIP(hipStreamSynchronize(p->stream));
   for (uint32_t i = 0; i < p->P; ++i) {
     p->prob[i].h_state = hs[i];
@@ -810,12 +899,11 @@ rkh_status read_states(rkh_planner* p) {
   return RKH_OK;
 }
 
-}  // namespace
+// ---- rkh_planner_create*: the phases, in the order they run -----------------------------------------------------------
 
-extern "C" {
-
-static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* space, const rkh_qs_space* qspace,
-                                        const rkh_rrt_params* prms, uint32_t n_problems, rkh_planner** out) {
+// 1. What the arguments alone decide; nothing exists yet.
+rkh_status check_create_args(const rkh_scene* scene, const rkh_dyn_space* space, const rkh_qs_space* qspace,
+                             const rkh_rrt_params* prms, uint32_t n_problems, rkh_planner** out) {
   if (!scene || (!space && !qspace) || !prms || !out || n_problems < 1) return RKH_ERR_BAD_ARG;
   const int space_dof = space ? space->n_dof : qspace->n_dof;
   if (space_dof != scene->host.n_dof) {
@@ -827,25 +915,24 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
       set_error("rkh_planner_create: max_vertices < 1");
       return RKH_ERR_BAD_ARG;
     }
-  rkh_planner* p = new rkh_planner();
-  p->scene = scene;
-  p->n_dof = space_dof;
-  p->P = n_problems;
-  rkh_status st = RKH_OK;
+  if (qspace && (!(qspace->min_interval > 0.0) || qspace->n_dof > kMaxDof)) {
+    set_error("rkh_qs_space: min_interval must be positive");
+    return RKH_ERR_BAD_ARG;
+  }
+  return RKH_OK;
+}
+
+// 2. The space: dimensions, the sampled hyperbox, the device form of the space, and the two bounds the NN sweeps take
+// from the largest |coordinate| per dimension.
+rkh_status setup_space(rkh_planner* p, const rkh_dyn_space* space, const rkh_qs_space* qspace, const rkh_rrt_params* prms) {
   if (space) {
     p->D = 2 * space->n_dof;
     for (int d = 0; d < p->D; ++d) {
       p->lower[d] = space->lower[d];
       p->upper[d] = space->upper[d];
     }
-    st = build_dyn_dev(*space, 1.0, &p->dyn);
-    if (st != RKH_OK) { delete p; return st; }
+    RKH_TRY(build_dyn_dev(*space, 1.0, &p->dyn));
   } else {
-    if (!(qspace->min_interval > 0.0) || qspace->n_dof > kMaxDof) {
-      delete p;
-      set_error("rkh_qs_space: min_interval must be positive");
-      return RKH_ERR_BAD_ARG;
-    }
     p->quasi_static = true;
     p->D = qspace->n_dof;
     std::memset(&p->qs, 0, sizeof(p->qs));
@@ -858,42 +945,38 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
     }
   }
   p->DP = nn_padded_dims(p->D);
-  // vertices and samples lie inside the hyperbox (is_free / random_point): bound for the NN sweep's float pre-filter
+  // vertices and samples lie inside the hyperbox (is_free / random_point), and the roots are vertices too: the bound of
+  // the NN sweep's float pre-filter, and the norm bound of the mirror sweep
   for (int d = 0; d < p->D; ++d) {
-    p->coord_bound = std::max(p->coord_bound, std::max(std::fabs(p->lower[d]), std::fabs(p->upper[d])));
-    for (uint32_t i = 0; i < n_problems; ++i)  // the root is a vertex too
-      p->coord_bound = std::max(p->coord_bound, std::fabs(prms[i].start[d]));
+    double m = std::max(std::fabs(p->lower[d]), std::fabs(p->upper[d]));
+    for (uint32_t i = 0; i < p->P; ++i) m = std::max(m, std::fabs(prms[i].start[d]));
+    p->coord_bound = std::max(p->coord_bound, m);
+    p->x_norm_bound += m * m;
   }
-  RKH_HIP(hipSetDevice(scene->ctx->device));
-  RKH_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  RKH_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-  {
-    std::vector<double> bounds(2 * p->D);
-    for (int d = 0; d < p->D; ++d) {
-      bounds[d] = p->lower[d];
-      bounds[p->D + d] = p->upper[d];
-    }
-    RKH_HIP(hipMalloc(&p->d_bounds, bounds.size() * sizeof(double)));
-    RKH_HIP(hipMemcpy(p->d_bounds, bounds.data(), bounds.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
+  p->x_norm_bound = std::sqrt(p->x_norm_bound) * (1.0 + 1e-9);
+  p->nn_mirror = nn1_mirror_applies(p->D, p->coord_bound);
+  return RKH_OK;
+}
+
+// 3. Tuning: every environment knob, the steer plan and the batch rule.  Writes into the planner, allocates nothing.
+void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
+  const rkh_scene* scene = p->scene;
   if (const char* e = getenv("RKH_WAVE_FIT")) p->wave_fit = atoi(e);
   if (const char* e = getenv("RKH_WAVE_FILL")) p->wave_fill = atof(e);
   // Many problems per planner: a round's candidates per problem stay within ONE query block of the mirror sweep (a
   // second block re-reads the whole tree for a handful of queries; 512 problems x 100 000: 7.45 -> 7.62 M expansions/s).
   // The batch rule only reaches the cap late in a run (1.25 sqrt(n) = 384 at n = 94 k) or through the wave fit's scale.
-  if (nn1_mirror_applies(p->D, p->coord_bound) && n_problems >= 64) p->b_max = std::min(p->b_max, nn1_mirror_queries());
+  if (p->nn_mirror && p->P >= 64) p->b_max = std::min(p->b_max, nn1_mirror_queries());
   if (const char* e = getenv("RKH_BATCH_MAX")) p->b_max = std::max(8, atoi(e));
   p->b_max = std::min<uint32_t>(p->b_max, 4096);
   if (const char* e = getenv("RKH_LANE_THRESHOLD")) p->lane_threshold = uint32_t(std::max(0, atoi(e)));
   if (!p->quasi_static) {
     const SteerRequest req = steer_request();
-    p->steer = steer_mapping(scene->host, SteerEntry::BatchPlanner, req, 0, n_problems, p->b_max);
+    p->steer = steer_mapping(scene->host, SteerEntry::BatchPlanner, req, 0, p->P, p->b_max);
     note_steer_mapping(p->steer);
     p->duo_threshold = req.duo_threshold;
   }
-  // the lane kernel's residency sizes the wave fit and the step-wise launches (the mappings that run it)
-  const bool lane_kernel = p->steer == SteerMapping::Auto || p->steer == SteerMapping::Pair;
-  if (lane_kernel) {
+  if (p->lane_kernel()) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, scene->ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
       p->wave_slots = uint32_t(prop.multiProcessorCount) * pair_kernel_waves_per_cu(scene->host.n_dof, scene->host.has_prismatic != 0);
@@ -902,6 +985,12 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   p->split_min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();
   if (const char* e = getenv("RKH_STEER_SPLIT_MIN_EDGES")) p->split_min_edges = uint32_t(std::max(0, atoi(e)));
   p->step_blocks_cap = 2 * p->wave_slots;
+  if (p->lane_kernel()) {
+    // the step kernel's blocks take their RK4 workspace out of the two-lanes workspace
+    const size_t lane_ws = propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, p->P);
+    if (propagate_pair_step_workspace_bytes(p->n_dof, p->step_blocks_cap) > lane_ws)
+      p->step_blocks_cap = uint32_t(lane_ws / propagate_pair_step_workspace_bytes(p->n_dof, 1));
+  }
   if (const char* e = getenv("RKH_PROFILE_NN")) p->profile_nn = atoi(e) != 0;
   // candidates per round = batch_factor * sqrt(n) per problem (results do not depend on it).  More candidates per
   // round mean fewer rounds but more discarded speculation (0.89 of the propagated edges are committed at 1.25, 0.72 at
@@ -912,199 +1001,277 @@ static rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* s
   // brings a mid-run round (n = max_vertices / 2) of all problems to ~32 k edges -- one 32-edge steer wave per SIMD --
   // within [1.25, 2], up to 4 for at most 16 problems.
   double mid_sqrt_sum = 0.0;
-  for (uint32_t i = 0; i < n_problems; ++i) mid_sqrt_sum += std::sqrt(0.5 * double(prms[i].max_vertices));
-  const double factor_cap = n_problems == 1 ? 2.0 : (n_problems <= 16 ? 4.0 : 2.0);
-  float batch_factor = float(std::min(factor_cap, std::max(1.25, 32768.0 / mid_sqrt_sum)));
-  uint32_t b_min = 8;
-  if (const char* e = getenv("RKH_BATCH_FACTOR")) batch_factor = float(atof(e));
-  if (const char* e = getenv("RKH_BATCH_MIN")) b_min = std::max(1, atoi(e));
-  p->nn_mirror = nn1_mirror_applies(p->D, p->coord_bound);
+  for (uint32_t i = 0; i < p->P; ++i) mid_sqrt_sum += std::sqrt(0.5 * double(prms[i].max_vertices));
+  const double factor_cap = p->P == 1 ? 2.0 : (p->P <= 16 ? 4.0 : 2.0);
+  p->batch_factor = float(std::min(factor_cap, std::max(1.25, 32768.0 / mid_sqrt_sum)));
+  if (const char* e = getenv("RKH_BATCH_FACTOR")) p->batch_factor = float(atof(e));
+  if (const char* e = getenv("RKH_BATCH_MIN")) p->b_min = std::max(1, atoi(e));
+  if (const char* e = getenv("RKH_SAMPLE_CAP")) p->sample_cap_min = strtoull(e, nullptr, 10);
+}
+
+// 4. The streams and what all problems share: the five tables, the sampled box, the counters and prefixes of a round.
+rkh_status alloc_planner_buffers(rkh_planner* p) {
+  const uint32_t P = p->P;
+  RKH_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  RKH_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
+  std::vector<double> bounds(2 * p->D);
   for (int d = 0; d < p->D; ++d) {
-    double m = std::max(std::fabs(p->lower[d]), std::fabs(p->upper[d]));
-    for (uint32_t i = 0; i < n_problems; ++i) m = std::max(m, std::fabs(prms[i].start[d]));
-    p->x_norm_bound += m * m;
+    bounds[d] = p->lower[d];
+    bounds[p->D + d] = p->upper[d];
   }
-  p->x_norm_bound = std::sqrt(p->x_norm_bound) * (1.0 + 1e-9);
-  const uint32_t P = n_problems;
-  p->prob.resize(P);
-  RKH_HIP(hipMalloc(&p->d_states, P * sizeof(PlannerState)));
-  RKH_HIP(hipMalloc(&p->d_probs, P * sizeof(ProblemDev)));
-  RKH_HIP(hipMalloc(&p->d_nn_args, P * sizeof(NnArgs)));
-  RKH_HIP(hipMalloc(&p->d_io_steer, P * sizeof(EdgeIO)));
-  RKH_HIP(hipMalloc(&p->d_io_probe, P * sizeof(EdgeIO)));
-  // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
-  // see prev_batch_ub and flush_probes)
-  if (lane_kernel)
-    RKH_HIP(hipMalloc(&p->d_lane_ws, propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max + kProbeGranule, P)));
-  if (p->d_lane_ws) {
+  RKH_TRY(p->d_bounds.alloc(bounds.size()));
+  RKH_HIP(hipMemcpy(p->d_bounds.get(), bounds.data(), bounds.size() * sizeof(double), hipMemcpyHostToDevice));
+  RKH_TRY(p->d_states.alloc(P));
+  RKH_TRY(p->d_probs.alloc(P));
+  RKH_TRY(p->d_nn_args.alloc(P));
+  RKH_TRY(p->d_io_steer.alloc(P));
+  RKH_TRY(p->d_io_probe.alloc(P));
+  if (p->lane_kernel()) {
+    // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
+    // see prev_batch_ub and flush_probes)
+    RKH_TRY(p->d_lane_ws.alloc(propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max + kProbeGranule, P) / sizeof(double)));
     // two prefix arrays of 2 P + 1 entries: waves of the two-lanes kernel, then single edges (one-wave-per-edge kernel)
-    RKH_HIP(hipMalloc(&p->d_wave_base, 2 * (2 * size_t(P) + 1) * sizeof(uint32_t)));
-    RKH_HIP(hipMemset(p->d_wave_base, 0, 2 * (2 * size_t(P) + 1) * sizeof(uint32_t)));
+    RKH_TRY(p->d_wave_base.alloc_zeroed(2 * (2 * size_t(P) + 1)));
     const size_t cap = size_t(P) * (2 * size_t(p->b_max) + kProbeGranule);
-    for (auto& l : p->d_step_list) RKH_HIP(hipMalloc(&l, cap * sizeof(uint2)));
-    RKH_HIP(hipMalloc(&p->d_step_cnt, (kMaxSteps + 1) * sizeof(uint32_t)));
-    RKH_HIP(hipMemset(p->d_step_cnt, 0, (kMaxSteps + 1) * sizeof(uint32_t)));
-    // the step kernel's blocks take their RK4 workspace out of the two-lanes workspace
-    if (propagate_pair_step_workspace_bytes(p->n_dof, p->step_blocks_cap) >
-        propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P))
-      p->step_blocks_cap = uint32_t(propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max, P) /
-                                    propagate_pair_step_workspace_bytes(p->n_dof, 1));
+    for (auto& l : p->d_step_list) RKH_TRY(l.alloc(cap));
+    RKH_TRY(p->d_step_cnt.alloc_zeroed(kMaxSteps + 1));
   }
-  RKH_HIP(hipMalloc(&p->d_nn_base, (size_t(P) + 1) * sizeof(uint32_t)));
-  RKH_HIP(hipMemset(p->d_nn_base, 0, (size_t(P) + 1) * sizeof(uint32_t)));
-  RKH_HIP(hipMalloc(&p->d_sel, 2 * sizeof(uint32_t)));
-  RKH_HIP(hipMemset(p->d_sel, 0, 2 * sizeof(uint32_t)));
-  RKH_HIP(hipMalloc(&p->d_steps_exec, sizeof(unsigned long long)));
-  RKH_HIP(hipMemset(p->d_steps_exec, 0, sizeof(unsigned long long)));
-  for (uint32_t i = 0; i < P; ++i) {
-    const uint64_t cap = (uint64_t(prms[i].max_vertices) + 1 + 255) / 256 * 256;
-    p->max_capacity = std::max(p->max_capacity, cap);
+  RKH_TRY(p->d_nn_base.alloc_zeroed(size_t(P) + 1));
+  RKH_TRY(p->d_sel.alloc_zeroed(2));
+  RKH_TRY(p->d_steps_exec.alloc_zeroed(1));
+  return RKH_OK;
+}
+
+// 5. One problem: its buffers, its mt19937, the root vertex with its mirror row, and its initial device state.
+rkh_status create_problem(rkh_planner* p, Problem& q) {
+  const int D = p->D, DP = p->DP;
+  const uint32_t b_max = p->b_max;
+  {  // get_global_rng().seed(s): std::mt19937 / boost::mt19937 seeding, position at the end of the state
+    std::vector<uint32_t> mt(kMtN + 1);
+    mt[0] = uint32_t(q.prm.seed);
+    for (int k = 1; k < kMtN; ++k) mt[k] = 1812433253u * (mt[k - 1] ^ (mt[k - 1] >> 30)) + uint32_t(k);
+    mt[kMtN] = uint32_t(kMtN);
+    RKH_TRY(q.d_mt.alloc(mt.size()));
+    RKH_HIP(hipMemcpy(q.d_mt.get(), mt.data(), mt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
-  p->part_blocks = nn1_partial_blocks(p->D, p->max_capacity, p->b_max, P, p->coord_bound);
-  p->n_ub.assign(P, 1);
+  const uint64_t max_total = uint64_t(q.prm.max_vertices) + 1;
+  RKH_TRY(q.d_tree.alloc(q.capacity * DP));
+  RKH_TRY(q.d_parent.alloc(q.capacity));
+  RKH_TRY(q.d_node_sample.alloc(q.capacity));
+  RKH_TRY(q.d_goal_dist.alloc(q.capacity));
+  q.sample_cap = std::max<uint64_t>(std::max<uint64_t>(4 * max_total + 4 * b_max, 1u << 14), p->sample_cap_min);
+  RKH_TRY(q.d_samples.alloc(q.sample_cap * D));
+  RKH_TRY(q.d_nn_seq.alloc(q.sample_cap));
+  RKH_TRY(q.d_accept_log.alloc(q.sample_cap));
+  RKH_TRY(q.d_nn_idx.alloc(b_max));
+  RKH_TRY(q.d_nn_dist.alloc(b_max));
+  RKH_TRY(q.d_x_out.alloc(uint64_t(b_max) * D));
+  RKH_TRY(q.d_steps.alloc(b_max));
+  RKH_TRY(q.d_accept.alloc(b_max));
+  RKH_TRY(q.d_probe_x.alloc(uint64_t(b_max + kProbeGranule) * D));
+  RKH_TRY(q.d_probe_steps.alloc(b_max + kProbeGranule));
+  RKH_TRY(q.d_goal.alloc(D));
+  RKH_TRY(q.d_part_dist.alloc(uint64_t(p->part_blocks) * b_max));
+  // one more row than the partials need: NnArgs::seed (sampled minima of the matrix-core sweep, "none" = all ones)
+  RKH_TRY(q.d_part_idx.alloc(uint64_t(p->part_blocks + 1) * b_max));
+  RKH_HIP(hipMemset(q.d_part_idx.get() + uint64_t(p->part_blocks) * b_max, 0xFF, uint64_t(b_max) * sizeof(uint32_t)));
+  if (p->profile_nn) RKH_TRY(q.d_round_n.alloc(2 * rkh_planner::kProfMax));
+  if (p->nn_mirror) {
+    RKH_TRY(q.d_mirror.alloc(nn1_mirror_bytes(q.capacity)));
+    RKH_TRY(launch_mirror_fill(p->stream, q.d_mirror.get(), q.capacity));
+    const size_t query_bytes = nn1_mirror_query_bytes() * b_max, cand_bytes = query_bytes + 256;
+    RKH_TRY(q.d_cand.alloc(cand_bytes));
+    RKH_HIP(hipMemsetAsync(q.d_cand.get(), 0, cand_bytes, p->stream));
+    q.dx_max_bits = reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand.get()) + query_bytes);
+  }
+  // root vertex = query start (create_root, rrt_path_planner.tpp:131-133)
+  std::vector<double> row(DP, 0.0);
+  for (int d = 0; d < D; ++d) row[d] = q.prm.start[d];
+  RKH_HIP(hipMemcpy(q.d_tree.get(), row.data(), DP * sizeof(double), hipMemcpyHostToDevice));
+  if (p->nn_mirror) RKH_TRY(launch_mirror_build(p->stream, q.d_mirror.get(), q.d_tree.get(), 1, D, DP, q.dx_max_bits));
+  const uint32_t no_parent = 0xFFFFFFFFu;
+  RKH_HIP(hipMemcpy(q.d_parent.get(), &no_parent, sizeof(uint32_t), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(q.d_goal.get(), q.prm.goal, D * sizeof(double), hipMemcpyHostToDevice));
+  PlannerState& s0 = q.h_state;
+  std::memset(&s0, 0, sizeof(s0));
+  s0.n = 1;
+  s0.n_before = 1;
+  s0.probed_n = 1;
+  s0.max_total = uint32_t(max_total);
+  s0.b_max = b_max;
+  s0.b_min = p->b_min;
+  s0.batch_factor = p->batch_factor;
+  return RKH_OK;
+}
+
+// 6. The five device tables, from the problems as they now stand.
+rkh_status upload_tables(rkh_planner* p) {
+  const uint32_t P = p->P;
   std::vector<PlannerState> hs(P);
   std::vector<ProblemDev> hp(P);
   std::vector<NnArgs> hn(P);
   std::vector<EdgeIO> hio(P), hgp(P);
-  const int D = p->D, DP = p->DP;
   for (uint32_t i = 0; i < P; ++i) {
-    Problem& q = p->prob[i];
-    q.prm = prms[i];
-    {  // get_global_rng().seed(s): std::mt19937 / boost::mt19937 seeding, position at the end of the state
-      std::vector<uint32_t> mt(kMtN + 1);
-      mt[0] = uint32_t(prms[i].seed);
-      for (int k = 1; k < kMtN; ++k) mt[k] = 1812433253u * (mt[k - 1] ^ (mt[k - 1] >> 30)) + uint32_t(k);
-      mt[kMtN] = uint32_t(kMtN);
-      RKH_HIP(hipMalloc(&q.d_mt, mt.size() * sizeof(uint32_t)));
-      RKH_HIP(hipMemcpy(q.d_mt, mt.data(), mt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    const uint64_t max_total = uint64_t(prms[i].max_vertices) + 1;
-    q.capacity = (max_total + 255) / 256 * 256;
-    RKH_HIP(hipMalloc(&q.d_tree, q.capacity * DP * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_parent, q.capacity * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_node_sample, q.capacity * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_goal_dist, q.capacity * sizeof(double)));
-    q.sample_cap = std::max<uint64_t>(4 * max_total + 4 * p->b_max, 1u << 14);
-    if (const char* e = getenv("RKH_SAMPLE_CAP")) q.sample_cap = std::max<uint64_t>(q.sample_cap, strtoull(e, nullptr, 10));
-    RKH_HIP(hipMalloc(&q.d_samples, q.sample_cap * D * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_nn_seq, q.sample_cap * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_accept_log, q.sample_cap));
-    RKH_HIP(hipMalloc(&q.d_nn_idx, p->b_max * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_nn_dist, p->b_max * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_x_out, uint64_t(p->b_max) * D * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_steps, p->b_max * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_accept, p->b_max));
-    RKH_HIP(hipMalloc(&q.d_probe_x, uint64_t(p->b_max + kProbeGranule) * D * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_probe_steps, (p->b_max + kProbeGranule) * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&q.d_goal, D * sizeof(double)));
-    RKH_HIP(hipMalloc(&q.d_part_dist, uint64_t(p->part_blocks) * p->b_max * sizeof(double)));
-    // one more row than the partials need: NnArgs::seed (sampled minima of the matrix-core sweep, "none" = all ones)
-    RKH_HIP(hipMalloc(&q.d_part_idx, uint64_t(p->part_blocks + 1) * p->b_max * sizeof(uint32_t)));
-    RKH_HIP(hipMemset(q.d_part_idx + uint64_t(p->part_blocks) * p->b_max, 0xFF, uint64_t(p->b_max) * sizeof(uint32_t)));
-    if (p->profile_nn) RKH_HIP(hipMalloc(&q.d_round_n, 2 * rkh_planner::kProfMax * sizeof(uint32_t)));
-    if (p->nn_mirror) {
-      RKH_HIP(hipMalloc(&q.d_mirror, nn1_mirror_bytes(q.capacity)));
-      rkh_status ms = launch_mirror_fill(p->stream, q.d_mirror, q.capacity);
-      if (ms != RKH_OK) return ms;
-      const size_t cand_bytes = nn1_mirror_query_bytes() * p->b_max + 256;
-      RKH_HIP(hipMalloc(&q.d_cand, cand_bytes));
-      RKH_HIP(hipMemsetAsync(q.d_cand, 0, cand_bytes, p->stream));
-    }
-    // root vertex = query start (create_root, rrt_path_planner.tpp:131-133)
-    std::vector<double> row(DP, 0.0);
-    for (int d = 0; d < D; ++d) row[d] = prms[i].start[d];
-    RKH_HIP(hipMemcpy(q.d_tree, row.data(), DP * sizeof(double), hipMemcpyHostToDevice));
-    if (p->nn_mirror) {
-      uint32_t* dxw = reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand) + nn1_mirror_query_bytes() * p->b_max);
-      rkh_status ms = launch_mirror_build(p->stream, q.d_mirror, q.d_tree, 1, D, DP, dxw);
-      if (ms != RKH_OK) return ms;
-    }
-    const uint32_t no_parent = 0xFFFFFFFFu;
-    RKH_HIP(hipMemcpy(q.d_parent, &no_parent, sizeof(uint32_t), hipMemcpyHostToDevice));
-    RKH_HIP(hipMemcpy(q.d_goal, prms[i].goal, D * sizeof(double), hipMemcpyHostToDevice));
-    PlannerState& s0 = hs[i];
-    std::memset(&s0, 0, sizeof(s0));
-    s0.n = 1;
-    s0.n_before = 1;
-    s0.probed_n = 1;
-    s0.max_total = uint32_t(max_total);
-    s0.b_max = p->b_max;
-    s0.b_min = b_min;
-    s0.batch_factor = batch_factor;
-    q.h_state = s0;
-    p->n_ub[i] = 1;
-    PlannerState* dst = p->d_states + i;
-    ProblemDev& pd = hp[i];
-    pd.st = dst;
-    pd.tree = q.d_tree;
-    pd.parent = q.d_parent;
-    pd.node_sample = q.d_node_sample;
-    pd.samples = q.d_samples;
-    pd.nn_seq = q.d_nn_seq;
-    pd.accept_log = q.d_accept_log;
-    pd.nn_idx = q.d_nn_idx;
-    pd.nn_dist = q.d_nn_dist;
-    pd.x_out = q.d_x_out;
-    pd.accept = q.d_accept;
-    pd.round_n = q.d_round_n;
-    pd.mirror = static_cast<uint4*>(q.d_mirror);
-    pd.dx_max_bits = q.d_cand ? reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand) + nn1_mirror_query_bytes() * p->b_max)
-                              : nullptr;
-    NnArgs& na = hn[i];
-    na.pos = q.d_tree;
-    na.d_n = &dst->n;
-    na.q = q.d_samples;
-    na.d_qoff = &dst->s0;
-    na.B = p->b_max;
-    na.d_B = &dst->B;
-    na.part_dist = q.d_part_dist;
-    na.part_idx = q.d_part_idx;
-    na.seed = q.d_part_idx + uint64_t(p->part_blocks) * p->b_max;
-    na.idx = q.d_nn_idx;
-    na.dist = q.d_nn_dist;
-    na.mirror = q.d_mirror;
-    if (q.d_cand) {
-      nn1_mirror_carve(q.d_cand, p->b_max, &na);
-      na.dx_max_bits = pd.dx_max_bits;
-    }
-    EdgeIO& io = hio[i];
-    io.src = q.d_tree;
-    io.src_idx = q.d_nn_idx;
-    io.src_stride = DP;
-    io.tgt = q.d_samples;
-    io.d_tgt_off = &dst->s0;
-    io.tgt_stride = D;
-    io.B = p->b_max;
-    io.d_B = &dst->B;
-    io.x_out = q.d_x_out;
-    io.steps_free = q.d_steps;
-    io.mode = EDGE_STEER_ACCEPT;
-    io.best_case = q.d_nn_dist;
-    io.steer_tol = prms[i].steer_tol;
-    io.accept = q.d_accept;
-    io.err_flag = scene->d_err;
-    EdgeIO& gp = hgp[i];
-    gp.src = q.d_tree;
-    gp.d_src_first = &dst->n_before;
-    gp.src_stride = DP;
-    gp.tgt = q.d_goal;
-    gp.tgt_stride = 0;
-    gp.B = p->b_max + kProbeGranule;
-    gp.d_B = &dst->n_new;
-    gp.x_out = q.d_probe_x;
-    gp.steps_free = q.d_probe_steps;
-    gp.mode = EDGE_GOAL_PROBE;
-    gp.goal_dist = q.d_goal_dist;
-    gp.err_flag = scene->d_err;
+    hs[i] = p->prob[i].h_state;
+    hp[i] = problem_dev(p, i);
+    hn[i] = nn_args(p, i);
+    hio[i] = steer_io(p, i);
+    hgp[i] = probe_io(p, i);
   }
-  RKH_HIP(hipMemcpy(p->d_states, hs.data(), P * sizeof(PlannerState), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_probs, hp.data(), P * sizeof(ProblemDev), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_nn_args, hn.data(), P * sizeof(NnArgs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_io_steer, hio.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_io_probe, hgp.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-  *out = p;
+  RKH_HIP(hipMemcpy(p->d_states.get(), hs.data(), P * sizeof(PlannerState), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(p->d_probs.get(), hp.data(), P * sizeof(ProblemDev), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(p->d_nn_args.get(), hn.data(), P * sizeof(NnArgs), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(p->d_io_steer.get(), hio.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(p->d_io_probe.get(), hgp.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
   return RKH_OK;
 }
+
+rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* space, const rkh_qs_space* qspace,
+                                 const rkh_rrt_params* prms, uint32_t n_problems, rkh_planner** out) {
+  RKH_TRY(check_create_args(scene, space, qspace, prms, n_problems, out));
+  std::unique_ptr<rkh_planner> p(new rkh_planner());  // the caller's only once the last step has succeeded
+  p->scene = scene;
+  p->n_dof = scene->host.n_dof;
+  p->P = n_problems;
+  RKH_TRY(setup_space(p.get(), space, qspace, prms));
+  RKH_HIP(hipSetDevice(scene->ctx->device));  // (before the tuning: its occupancy query acts on the current device)
+  tune_planner(p.get(), prms);
+  RKH_TRY(alloc_planner_buffers(p.get()));
+  p->prob.resize(n_problems);
+  for (uint32_t i = 0; i < n_problems; ++i) {
+    Problem& q = p->prob[i];
+    q.prm = prms[i];
+    q.capacity = (uint64_t(prms[i].max_vertices) + 1 + 255) / 256 * 256;  // whole 256-row tiles (the NN sweeps)
+    p->max_capacity = std::max(p->max_capacity, q.capacity);
+  }
+  p->part_blocks = nn1_partial_blocks(p->D, p->max_capacity, p->b_max, n_problems, p->coord_bound);
+  p->n_ub.assign(n_problems, 1);
+  for (Problem& q : p->prob) RKH_TRY(create_problem(p.get(), q));
+  RKH_TRY(upload_tables(p.get()));
+  *out = p.release();
+  return RKH_OK;
+}
+
+// ---- rkh_planner_sync: the three steps --------------------------------------------------------------------------------
+
+// 1. The states of all problems and the scene's error flag; a finished batch first runs the goal probes of its last
+// committed vertices.
+rkh_status read_round_results(rkh_planner* p) {
+  RKH_TRY(read_states(p));
+  int flag = 0;
+  int* const d_err = p->scene->d_err.get();
+  RKH_HIP(hipMemcpy(&flag, d_err, sizeof(int), hipMemcpyDeviceToHost));
+  if (flag != 0) {
+    RKH_HIP(hipMemset(d_err, 0, sizeof(int)));
+    set_error("planner: mass matrix is singular (Cholesky pivot < 1e-8)");
+    return rkh_status(flag);
+  }
+  bool all_done = true, pending = false;
+  for (Problem& q : p->prob) {
+    if (!(q.truncated || q.h_state.done == 1)) all_done = false;
+    if (q.h_state.probed_n < q.h_state.n) pending = true;
+  }
+  if (all_done && pending) {  // finished: run the goal probes of the last committed vertices
+    RKH_TRY(flush_probes(p));
+    RKH_TRY(read_states(p));
+  }
+  return RKH_OK;
+}
+
+// Goal-probe results of problem q that no sync has looked at yet: vertices [1, probed_n) have one, the first
+// goal_checked of them are done (a truncated problem takes no more).
+uint64_t new_goal_probes(const Problem& q) {
+  const uint64_t probed = q.h_state.probed_n < 1 ? 1 : q.h_state.probed_n;
+  return (!q.truncated && probed > 1 && q.goal_checked < probed - 1) ? probed - 1 - q.goal_checked : 0;
+}
+
+// 2. The new goal-probe results of all problems: gathered on the device, one copy into the pinned buffer, one wait.
+// Problem i's gd_cnt[i] results start at h_gd[gd_off[i]].
+rkh_status gather_goal_probes(rkh_planner* p, std::vector<uint64_t>& gd_off, std::vector<uint64_t>& gd_cnt) {
+  gd_off.assign(p->P, 0);
+  gd_cnt.assign(p->P, 0);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < p->P; ++i) {
+    gd_cnt[i] = new_goal_probes(p->prob[i]);
+    if (gd_cnt[i]) gd_off[i] = total;
+    total += gd_cnt[i];
+  }
+  if (total > p->h_gd.size()) RKH_TRY(p->h_gd.alloc(total + total / 2 + 1024));
+  if (!total) return RKH_OK;
+  if (!p->d_gd_tab) {
+    RKH_TRY(p->h_gd_tab.alloc(p->P));
+    RKH_TRY(p->d_gd_tab.alloc(p->P));
+  }
+  if (total > p->d_gd.size()) RKH_TRY(p->d_gd.alloc(total + total / 2 + 1024));
+  uint32_t n_seg = 0;
+  for (uint32_t i = 0; i < p->P; ++i)
+    if (gd_cnt[i]) {
+      GoalSeg& g = p->h_gd_tab.get()[n_seg++];
+      g.src = p->prob[i].d_goal_dist.get() + p->prob[i].goal_checked;
+      g.dst_off = gd_off[i];
+      g.count = gd_cnt[i];
+    }
+  RKH_HIP(hipMemcpyAsync(p->d_gd_tab.get(), p->h_gd_tab.get(), n_seg * sizeof(GoalSeg), hipMemcpyHostToDevice, p->stream));
+  hipLaunchKernelGGL(gather_goal_dist_kernel, dim3(n_seg), dim3(256), 0, p->stream, p->d_gd_tab.get(), p->d_gd.get());
+  RKH_HIP(hipGetLastError());
+  RKH_HIP(hipMemcpyAsync(p->h_gd.get(), p->d_gd.get(), total * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  RKH_HIP(hipStreamSynchronize(p->stream));
+  return RKH_OK;
+}
+
+// edge_added: a finite goal-probe distance registers a solution if it beats the best so far
+// (planning_visitors.hpp:194-200, solution_path_factories.hpp:58-110); keep_going() then also checks
+// max_num_results (p2p_planning_query.hpp:121-123).  gd[k], k < cnt: the goal-probe result of vertex goal_checked + 1 + k.
+rkh_status register_solutions(rkh_planner* p, uint32_t i, const double* gd, uint64_t cnt) {
+  Problem& q = p->prob[i];
+  const PlannerState& hs = q.h_state;
+  const uint64_t first = q.goal_checked;
+  std::vector<double> pos;
+  std::vector<uint32_t> par;
+  for (uint64_t k = 0; k < cnt; ++k) {
+    if (!(gd[k] < INFINITY)) continue;
+    if (pos.empty()) {
+      pos.resize(uint64_t(hs.n) * p->DP);
+      par.resize(hs.n);
+      RKH_HIP(hipMemcpy(pos.data(), q.d_tree.get(), pos.size() * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(par.data(), q.d_parent.get(), par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    double total = gd[k];
+    uint64_t v = first + k + 1;
+    while (par[v] != 0xFFFFFFFFu) {
+      const uint64_t pv = par[v];
+      double acc = 0.0;
+      for (int d = 0; d < p->D; ++d) {
+        const double df = pos[pv * p->DP + d] - pos[v * p->DP + d];
+        acc += df * df;
+      }
+      total += std::sqrt(acc);
+      v = pv;
+    }
+    if (q.num_solutions == 0 || total < q.best_cost) {
+      q.best_cost = total;
+      q.best_vertex = uint32_t(first + k + 1);
+      ++q.num_solutions;
+      if (q.num_solutions >= q.prm.max_results) {
+        // the sequential planner stops right after this vertex: drop what speculation added beyond it
+        q.truncated = true;
+        q.final_n = first + k + 2;
+        uint32_t smp = 0;
+        RKH_HIP(hipMemcpy(&smp, q.d_node_sample.get() + (first + k + 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
+        q.final_iterations = uint64_t(smp) + 1;
+        const uint32_t one = 1;  // freeze the problem on the device as well
+        RKH_HIP(hipMemcpy(&p->d_states.get()[i].done, &one, sizeof(uint32_t), hipMemcpyHostToDevice));
+        break;
+      }
+    }
+  }
+  q.goal_checked = first + cnt;
+  return RKH_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 rkh_status rkh_planner_create_batch(rkh_scene* scene, const rkh_dyn_space* space, const rkh_rrt_params* prms,
                                     uint32_t n_problems, rkh_planner** out) {
@@ -1130,39 +1297,7 @@ rkh_status rkh_planner_create(rkh_scene* scene, const rkh_dyn_space* space, cons
 uint32_t rkh_planner_num_problems(const rkh_planner* p) { return p ? p->P : 0; }
 
 rkh_status rkh_planner_destroy(rkh_planner* p) {
-  if (!p) return RKH_OK;
-  (void)hipStreamSynchronize(p->stream);
-  for (Problem& q : p->prob) free_problem(q);
-  (void)hipFree(p->d_states);
-  (void)hipFree(p->d_probs);
-  (void)hipFree(p->d_nn_args);
-  (void)hipFree(p->d_io_steer);
-  (void)hipFree(p->d_io_probe);
-  (void)hipFree(p->d_step_list[0]);
-  (void)hipFree(p->d_step_list[1]);
-  (void)hipFree(p->d_step_cnt);
-  (void)hipFree(p->d_steps_exec);
-  for (auto& sg : p->staging) {
-    if (sg.pending) (void)hipEventSynchronize(sg.done);
-    if (sg.h_tab) (void)hipHostFree(sg.h_tab);
-    if (sg.d_tab) (void)hipFree(sg.d_tab);
-    if (sg.done) (void)hipEventDestroy(sg.done);
-  }
-  (void)hipFree(p->d_lane_ws);
-  (void)hipFree(p->d_sel);
-  (void)hipFree(p->d_wave_base);
-  (void)hipFree(p->d_nn_base);
-  for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->ev_steer) (void)hipEventDestroy(e);
-  (void)hipStreamSynchronize(p->copy_stream);
-  (void)hipStreamDestroy(p->copy_stream);
-  if (p->d_bounds) (void)hipFree(p->d_bounds);
-  if (p->h_gd) (void)hipHostFree(p->h_gd);
-  if (p->h_gd_tab) (void)hipHostFree(p->h_gd_tab);
-  if (p->d_gd_tab) (void)hipFree(p->d_gd_tab);
-  if (p->d_gd) (void)hipFree(p->d_gd);
-  (void)hipStreamDestroy(p->stream);
-  delete p;
+  delete p;  // ~rkh_planner waits for both streams
   return RKH_OK;
 }
 
@@ -1178,7 +1313,7 @@ rkh_status rkh_planner_nn_profile(rkh_planner* p, double* total_ms, uint64_t* to
   std::vector<uint64_t> rows(p->prof_rounds, 0);
   std::vector<uint32_t> rn(p->prof_rounds);
   for (Problem& q : p->prob) {
-    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n, rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n.get(), rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < p->prof_rounds; ++r) rows[r] += rn[r];
   }
   for (uint32_t r = 0; r < p->prof_rounds; ++r) {
@@ -1199,8 +1334,8 @@ rkh_status rkh_planner_nn_pairs(rkh_planner* p, uint64_t* pairs) {
   RKH_HIP(hipStreamSynchronize(p->stream));
   std::vector<uint32_t> rn(p->prof_rounds), rb(p->prof_rounds);
   for (Problem& q : p->prob) {
-    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n, rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    RKH_HIP(hipMemcpy(rb.data(), q.d_round_n + rkh_planner::kProfMax, rb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n.get(), rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rb.data(), q.d_round_n.get() + rkh_planner::kProfMax, rb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < p->prof_rounds; ++r) *pairs += uint64_t(rn[r]) * rb[r];
   }
   return RKH_OK;
@@ -1227,7 +1362,7 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps) {
   if (!p->d_steps_exec) return RKH_OK;
   RKH_HIP(hipStreamSynchronize(p->stream));
   unsigned long long v = 0;
-  RKH_HIP(hipMemcpy(&v, p->d_steps_exec, sizeof(v), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(&v, p->d_steps_exec.get(), sizeof(v), hipMemcpyDeviceToHost));
   *executed_steps = v;
   return RKH_OK;
 }
@@ -1236,145 +1371,31 @@ rkh_status rkh_planner_enqueue(rkh_planner* p, uint32_t rounds) {
   if (!p) return RKH_ERR_BAD_ARG;
   // make sure the enqueued rounds cannot run out of samples (usually already there: see below)
   const uint64_t share = uint64_t(rounds ? rounds : 1) * p->b_max;
-  rkh_status st = upload_samples_all(p, share, 0);
-  if (st != RKH_OK) return st;
-  for (uint32_t r = 0; r < rounds; ++r) {
-    st = enqueue_round(p);
-    if (st != RKH_OK) return st;
-  }
+  RKH_TRY(upload_samples_all(p, share, 0));
+  for (uint32_t r = 0; r < rounds; ++r) RKH_TRY(enqueue_round(p));
   // while the GPU works on these rounds: the next call's share of the stream (generated on the host, copied behind the
   // rounds on the same stream)
-  if (rounds) st = upload_samples_all(p, 2 * share, 1);
-  return st;
+  return rounds ? upload_samples_all(p, 2 * share, 1) : RKH_OK;
 }
 
 rkh_status rkh_planner_sync(rkh_planner* p, rkh_planner_stats* stats) {
   if (!p) return RKH_ERR_BAD_ARG;
-  rkh_status st = read_states(p);
-  if (st != RKH_OK) return st;
-  int flag = 0;
-  RKH_HIP(hipMemcpy(&flag, p->scene->d_err, sizeof(int), hipMemcpyDeviceToHost));
-  if (flag != 0) {
-    RKH_HIP(hipMemset(p->scene->d_err, 0, sizeof(int)));
-    set_error("planner: mass matrix is singular (Cholesky pivot < 1e-8)");
-    return rkh_status(flag);
-  }
-  bool all_done = true, pending = false;
-  for (Problem& q : p->prob) {
-    if (!(q.truncated || q.h_state.done == 1)) all_done = false;
-    if (q.h_state.probed_n < q.h_state.n) pending = true;
-  }
-  if (all_done && pending) {  // finished: run the goal probes of the last committed vertices
-    st = flush_probes(p);
-    if (st != RKH_OK) return st;
-    st = read_states(p);
-    if (st != RKH_OK) return st;
-  }
-  // goal-probe results since the last call, all problems: asynchronous copies into one pinned buffer, one wait
-  std::vector<uint64_t> gd_off(p->P, 0), gd_cnt(p->P, 0);
-  {
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < p->P; ++i) {
-      Problem& q = p->prob[i];
-      const uint64_t probed = q.h_state.probed_n < 1 ? 1 : q.h_state.probed_n;
-      if (!q.truncated && probed > 1 && q.goal_checked < probed - 1) {
-        gd_off[i] = total;
-        gd_cnt[i] = probed - 1 - q.goal_checked;
-        total += gd_cnt[i];
-      }
-    }
-    if (total > p->h_gd_cap) {
-      if (p->h_gd) (void)hipHostFree(p->h_gd);
-      p->h_gd = nullptr;
-      p->h_gd_cap = total + total / 2 + 1024;
-      RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_gd), p->h_gd_cap * sizeof(double), hipHostMallocDefault));
-    }
-    if (total) {
-      if (!p->h_gd_tab) {
-        RKH_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_gd_tab), p->P * sizeof(GoalSeg), hipHostMallocDefault));
-        RKH_HIP(hipMalloc(&p->d_gd_tab, p->P * sizeof(GoalSeg)));
-      }
-      if (total > p->d_gd_cap) {
-        if (p->d_gd) (void)hipFree(p->d_gd);
-        p->d_gd = nullptr;
-        p->d_gd_cap = total + total / 2 + 1024;
-        RKH_HIP(hipMalloc(&p->d_gd, p->d_gd_cap * sizeof(double)));
-      }
-      uint32_t n_seg = 0;
-      for (uint32_t i = 0; i < p->P; ++i)
-        if (gd_cnt[i]) {
-          GoalSeg& g = p->h_gd_tab[n_seg++];
-          g.src = p->prob[i].d_goal_dist + p->prob[i].goal_checked;
-          g.dst_off = gd_off[i];
-          g.count = gd_cnt[i];
-        }
-      RKH_HIP(hipMemcpyAsync(p->d_gd_tab, p->h_gd_tab, n_seg * sizeof(GoalSeg), hipMemcpyHostToDevice, p->stream));
-      hipLaunchKernelGGL(gather_goal_dist_kernel, dim3(n_seg), dim3(256), 0, p->stream, p->d_gd_tab, p->d_gd);
-      RKH_HIP(hipGetLastError());
-      RKH_HIP(hipMemcpyAsync(p->h_gd, p->d_gd, total * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-      RKH_HIP(hipStreamSynchronize(p->stream));
-    }
-  }
+  RKH_TRY(read_round_results(p));
+  std::vector<uint64_t> gd_off, gd_cnt;
+  RKH_TRY(gather_goal_probes(p, gd_off, gd_cnt));
+  // per problem: grow the sample buffers, register solutions, fill the stats
   for (uint32_t i = 0; i < p->P; ++i) {
     Problem& q = p->prob[i];
     PlannerState& hs = q.h_state;
     if (!q.truncated && hs.done != 1 && uint64_t(hs.s0) + 64ull * p->b_max > q.sample_cap) {
       RKH_HIP(hipStreamSynchronize(p->copy_stream));
-      const rkh_status gs = grow_sample_buffers(p, i, std::max<uint64_t>(2 * q.sample_cap, uint64_t(hs.s0) + 256ull * p->b_max));
-      if (gs != RKH_OK) return gs;
+      RKH_TRY(grow_sample_buffers(p, i, std::max<uint64_t>(2 * q.sample_cap, uint64_t(hs.s0) + 256ull * p->b_max)));
     }
     if (hs.done == 2 && q.samples_ready < q.sample_cap) {  // sample stream ran dry mid-enqueue: refill and carry on
       hs.done = 0;
-      RKH_HIP(hipMemcpy(&p->d_states[i].done, &hs.done, sizeof(uint32_t), hipMemcpyHostToDevice));
+      RKH_HIP(hipMemcpy(&p->d_states.get()[i].done, &hs.done, sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    // edge_added: a finite goal-probe distance registers a solution if it beats the best so far
-    // (planning_visitors.hpp:194-200, solution_path_factories.hpp:58-110); keep_going() then also checks
-    // max_num_results (p2p_planning_query.hpp:121-123).
-    const uint64_t probed = hs.probed_n < 1 ? 1 : hs.probed_n;  // vertices [1, probed) have a goal-probe result
-    if (!q.truncated && probed > 1 && q.goal_checked < probed - 1) {
-      const uint64_t first = q.goal_checked, cnt = probed - 1 - first;
-      const double* gd = p->h_gd + gd_off[i];
-      std::vector<double> pos;
-      std::vector<uint32_t> par;
-      for (uint64_t k = 0; k < cnt; ++k) {
-        if (!(gd[k] < INFINITY)) continue;
-        if (pos.empty()) {
-          pos.resize(uint64_t(hs.n) * p->DP);
-          par.resize(hs.n);
-          RKH_HIP(hipMemcpy(pos.data(), q.d_tree, pos.size() * sizeof(double), hipMemcpyDeviceToHost));
-          RKH_HIP(hipMemcpy(par.data(), q.d_parent, par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        }
-        double total = gd[k];
-        uint64_t v = first + k + 1;
-        while (par[v] != 0xFFFFFFFFu) {
-          const uint64_t pv = par[v];
-          double acc = 0.0;
-          for (int d = 0; d < p->D; ++d) {
-            const double df = pos[pv * p->DP + d] - pos[v * p->DP + d];
-            acc += df * df;
-          }
-          total += std::sqrt(acc);
-          v = pv;
-        }
-        if (q.num_solutions == 0 || total < q.best_cost) {
-          q.best_cost = total;
-          q.best_vertex = uint32_t(first + k + 1);
-          ++q.num_solutions;
-          if (q.num_solutions >= q.prm.max_results) {
-            // the sequential planner stops right after this vertex: drop what speculation added beyond it
-            q.truncated = true;
-            q.final_n = first + k + 2;
-            uint32_t smp = 0;
-            RKH_HIP(hipMemcpy(&smp, q.d_node_sample + (first + k + 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
-            q.final_iterations = uint64_t(smp) + 1;
-            const uint32_t one = 1;  // freeze the problem on the device as well
-            RKH_HIP(hipMemcpy(&p->d_states[i].done, &one, sizeof(uint32_t), hipMemcpyHostToDevice));
-            break;
-          }
-        }
-      }
-      q.goal_checked = probed - 1;
-    }
+    if (gd_cnt[i]) RKH_TRY(register_solutions(p, i, p->h_gd.get() + gd_off[i], gd_cnt[i]));
     if (stats) {
       rkh_planner_stats& o = stats[i];
       std::memset(&o, 0, sizeof(o));
@@ -1402,7 +1423,7 @@ rkh_status rkh_planner_get_solution(rkh_planner* p, uint32_t problem, uint32_t* 
   if (q.best_vertex == 0xFFFFFFFFu) return RKH_OK;  // no solution registered
   RKH_HIP(hipStreamSynchronize(p->stream));
   std::vector<uint32_t> par(size_t(q.best_vertex) + 1);
-  RKH_HIP(hipMemcpy(par.data(), q.d_parent, par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(par.data(), q.d_parent.get(), par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<uint32_t> rev;
   for (uint32_t v = q.best_vertex; v != 0xFFFFFFFFu; v = par[v]) rev.push_back(v);
   *n_path = uint32_t(rev.size());
@@ -1442,27 +1463,24 @@ rkh_status rkh_planner_solve(rkh_planner* p, rkh_planner_stats* stats) {
 rkh_status rkh_planner_get_tree(rkh_planner* p, uint32_t problem, double* pos, uint32_t* parent, uint32_t* nn_seq,
                                 uint8_t* accept, double* goal_dist) {
   if (!p || problem >= p->P) return RKH_ERR_BAD_ARG;
-  if (goal_dist) {  // make sure no goal probe is pending
-    rkh_status fs = flush_probes(p);
-    if (fs != RKH_OK) return fs;
-  }
+  if (goal_dist) RKH_TRY(flush_probes(p));  // make sure no goal probe is pending
   RKH_HIP(hipStreamSynchronize(p->stream));
   Problem& q = p->prob[problem];
   const uint64_t n = q.truncated ? q.final_n : q.h_state.n;
   const uint64_t it = q.truncated ? q.final_iterations : q.h_state.s0;
   if (pos) {
     if (p->DP == p->D) {
-      RKH_HIP(hipMemcpy(pos, q.d_tree, n * p->D * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(pos, q.d_tree.get(), n * p->D * sizeof(double), hipMemcpyDeviceToHost));
     } else {
       std::vector<double> tmp(n * p->DP);
-      RKH_HIP(hipMemcpy(tmp.data(), q.d_tree, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(tmp.data(), q.d_tree.get(), tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
       for (uint64_t i = 0; i < n; ++i) std::memcpy(pos + i * p->D, &tmp[i * p->DP], p->D * sizeof(double));
     }
   }
-  if (parent) RKH_HIP(hipMemcpy(parent, q.d_parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (nn_seq && it) RKH_HIP(hipMemcpy(nn_seq, q.d_nn_seq, it * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (accept && it) RKH_HIP(hipMemcpy(accept, q.d_accept_log, it, hipMemcpyDeviceToHost));
-  if (goal_dist && n > 1) RKH_HIP(hipMemcpy(goal_dist, q.d_goal_dist, (n - 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (parent) RKH_HIP(hipMemcpy(parent, q.d_parent.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (nn_seq && it) RKH_HIP(hipMemcpy(nn_seq, q.d_nn_seq.get(), it * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (accept && it) RKH_HIP(hipMemcpy(accept, q.d_accept_log.get(), it, hipMemcpyDeviceToHost));
+  if (goal_dist && n > 1) RKH_HIP(hipMemcpy(goal_dist, q.d_goal_dist.get(), (n - 1) * sizeof(double), hipMemcpyDeviceToHost));
   return RKH_OK;
 }
 

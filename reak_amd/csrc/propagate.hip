@@ -2003,8 +2003,8 @@ static rkh_status launch_propagate_t(hipStream_t s, const rkh_scene& scene, cons
     grid = dim3(uint32_t(std::min<uint64_t>(all, gate.hi)), 1);
   }
   WaveArgs args;
-  args.sc = scene.d_scene;
-  args.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  args.sc = scene.d_scene.get();
+  args.pairs = scene.d_pairs.get();
   args.n_pairs = scene.n_pairs_verdict;
   args.dyn = dyn;
   args.io_a = io;
@@ -2063,7 +2063,7 @@ rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const 
     if (scene.host.has_prismatic) return prismatic::launch_state_derivative(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
   }
   const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
-    hipLaunchKernelGGL((state_derivative_kernel<decltype(c)::value>), dim3(B), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
+    hipLaunchKernelGGL((state_derivative_kernel<decltype(c)::value>), dim3(B), dim3(64), 0, s, scene.d_scene.get(), d_x, d_u, B,
                        d_pd, d_M, d_f, d_err);
   });
   if (st != RKH_OK) return st;
@@ -2148,8 +2148,8 @@ rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev&
     if (scene.host.has_prismatic)
       return prismatic::launch_edge_check(s, scene, qs, io, grid_edges, eb, tab_a, tab_b, n_problems);
   EdgeWalkArgs ka;
-  ka.sc = scene.d_scene;
-  ka.pairs = static_cast<const PairDev*>(scene.d_pairs);
+  ka.sc = scene.d_scene.get();
+  ka.pairs = scene.d_pairs.get();
   ka.n_pairs = scene.n_pairs_verdict;
   ka.qs = qs;
   ka.io_a = io;
@@ -2178,7 +2178,7 @@ rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const 
   const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((feval_cycles_duo_kernel<N>), dim3(B / 2), dim3(128), (SmemLayout<N, 64>::bytes(scene.host.n_env)), s,
-                       scene.d_scene, d_x, d_u, iters, d_out, d_sink);
+                       scene.d_scene.get(), d_x, d_u, iters, d_out, d_sink);
   });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
@@ -2194,7 +2194,7 @@ rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const doub
   const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((feval_cycles_kernel<N>), dim3(B), dim3(64), (SmemLayout<N, 64>::bytes(scene.host.n_env)), s,
-                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, d_u, iters, d_out,
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.n_pairs, d_x, d_u, iters, d_out,
                        d_sink);
   });
   if (st != RKH_OK) return st;
@@ -2210,7 +2210,7 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
   const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
-                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs, d_x, B, d_dist);
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.n_pairs, d_x, B, d_dist);
   });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());

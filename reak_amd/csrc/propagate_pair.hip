@@ -1287,7 +1287,7 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
       return prismatic::launch_propagate_pair_steps(s, scene, dyn, tab_a, tab_b, n_problems, d_edge_base, d_list0, d_list1,
                                                     d_cnt, d_ws, blocks, gate, d_steps_exec);
   PairStepArgs args;
-  args.sc = scene.d_scene;
+  args.sc = scene.d_scene.get();
   args.dyn = dyn;
   args.tab_a = tab_a;
   args.tab_b = tab_b;
@@ -1390,7 +1390,7 @@ rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const doubl
     if (scene.host.has_prismatic) return prismatic::launch_pair_counts(s, scene, d_x, B, d_out);
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
   const rkh_status st = with_n<6, 3, 7>(scene.host.n_dof, [&](auto c) {
-    hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, B, d_out);
+    hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene.get(), d_x, B, d_out);
   });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());
@@ -1406,7 +1406,7 @@ rkh_status launch_pair_cycles(hipStream_t s, const rkh_scene& scene, const doubl
   }
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
   const rkh_status st = with_n<6, 3>(scene.host.n_dof, [&](auto c) {
-    hipLaunchKernelGGL((pair_cycles_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene, d_x, d_u, B,
+    hipLaunchKernelGGL((pair_cycles_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene.get(), d_x, d_u, B,
                        iters, d_out, d_sink);
   });
   if (st != RKH_OK) return st;
@@ -1437,7 +1437,7 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
       return prismatic::launch_propagate_pairs(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, d_ws, gate);
   const uint32_t ga = (grid_edges + kPairEdges - 1) / kPairEdges, gbk = (eb + kPairEdges - 1) / kPairEdges;
   PairArgs args;
-  args.sc = scene.d_scene;
+  args.sc = scene.d_scene.get();
   args.dyn = dyn;
   args.io_a = io;
   args.io_b = EdgeIO();

@@ -422,7 +422,7 @@ rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const 
   gate.n_segments = 0;
   const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((planar_propagate_kernel<decltype(c)::value>), dim3(blocks_a + blocks_b, n_problems), dim3(64), 0, s,
-                       scene.d_scene, static_cast<const PairDev*>(scene.d_pairs), scene.n_pairs_verdict, dyn, io, EdgeIO(),
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.n_pairs_verdict, dyn, io, EdgeIO(),
                        tab_a, tab_b, blocks_a, gate);
   });
   if (st != RKH_OK) return st;
@@ -435,7 +435,7 @@ rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene,
   if (B == 0) return RKH_OK;
   const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((planar_state_derivative_kernel<decltype(c)::value>), dim3((B + 63) / 64), dim3(64), 0, s,
-                       scene.d_scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
+                       scene.d_scene.get(), d_x, d_u, B, d_pd, d_M, d_f, d_err);
   });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());

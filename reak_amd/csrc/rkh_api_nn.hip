@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 #include "rkh_internal.h"
@@ -77,28 +78,19 @@ rkh_status rkh_nn_create(rkh_ctx* ctx, int dims, uint64_t capacity, rkh_nn** out
     set_error("rkh_nn_create: dims > 32 unsupported");
     return RKH_ERR_BAD_ARG;
   }
-  rkh_nn* nn = new rkh_nn();
+  std::unique_ptr<rkh_nn> nn(new rkh_nn());
   nn->ctx = ctx;
   nn->st.D = dims;
   // round the capacity up to whole 256-row tiles so a sweep never reads past the allocation
   nn->st.capacity = (capacity + 255) / 256 * 256;
   RKH_HIP(hipSetDevice(ctx->device));
-  RKH_HIP(hipMalloc(&nn->st.d_pos, nn->st.capacity * DP * sizeof(double)));
-  *out = nn;
+  RKH_TRY(nn->pos.alloc(nn->st.capacity * DP));
+  nn->st.d_pos = nn->pos.get();
+  *out = nn.release();
   return RKH_OK;
 }
 rkh_status rkh_nn_destroy(rkh_nn* nn) {
-  if (!nn) return RKH_OK;
-  hipFree(nn->st.d_pos);
-  hipFree(nn->d_q);
-  hipFree(nn->d_idx);
-  hipFree(nn->d_dist);
-  hipFree(nn->d_count);
-  hipFree(nn->d_part_dist);
-  hipFree(nn->d_part_idx);
-  hipFree(nn->d_seed);
-  hipFree(nn->d_knn_ws);
-  delete nn;
+  delete nn;  // (its buffers free themselves; hipFree waits for the device)
   return RKH_OK;
 }
 rkh_status rkh_nn_clear(rkh_nn* nn) {
@@ -167,44 +159,29 @@ rkh_status rkh_nn_append(rkh_nn* nn, const double* pts, uint64_t n) {
 static rkh_status ensure_partials(rkh_nn* nn, uint32_t B) {
   const uint32_t blocks = nn1_partial_blocks(nn->st.D, nn->n, B, 1, nn->coord_bound);
   const uint64_t need = uint64_t(blocks) * B;
-  if (need > nn->part_cap) {
-    hipFree(nn->d_part_dist);
-    hipFree(nn->d_part_idx);
-    nn->d_part_dist = nullptr;
-    nn->d_part_idx = nullptr;
-    RKH_HIP(hipMalloc(&nn->d_part_dist, need * sizeof(double)));
-    RKH_HIP(hipMalloc(&nn->d_part_idx, need * sizeof(uint32_t)));
-    nn->part_cap = need;
+  if (need > nn->d_part_idx.size()) {
+    nn->d_part_dist.reset();  // both go before either comes back, as the peak of memory asks
+    nn->d_part_idx.reset();
+    RKH_TRY(nn->d_part_dist.alloc(need));
+    RKH_TRY(nn->d_part_idx.alloc(need));
   }
   nn->part_blocks = blocks;
-  if (B > nn->seed_cap) {
-    hipFree(nn->d_seed);
-    nn->d_seed = nullptr;
-    RKH_HIP(hipMalloc(&nn->d_seed, uint64_t(B) * sizeof(uint32_t)));
-    RKH_HIP(hipMemsetAsync(nn->d_seed, 0xFF, uint64_t(B) * sizeof(uint32_t), nn->ctx->stream));
-    nn->seed_cap = B;
+  if (B > nn->d_seed.size()) {
+    RKH_TRY(nn->d_seed.alloc(B));
+    RKH_HIP(hipMemsetAsync(nn->d_seed.get(), 0xFF, uint64_t(B) * sizeof(uint32_t), nn->ctx->stream));
   }
   return RKH_OK;
 }
 
 static rkh_status ensure_scratch(rkh_nn* nn, uint64_t q_elems, uint64_t res_elems) {
-  if (q_elems > nn->q_cap) {
-    hipFree(nn->d_q);
-    nn->d_q = nullptr;
-    RKH_HIP(hipMalloc(&nn->d_q, q_elems * sizeof(double)));
-    nn->q_cap = q_elems;
-  }
-  if (res_elems > nn->res_cap) {
-    hipFree(nn->d_idx);
-    hipFree(nn->d_dist);
-    hipFree(nn->d_count);
-    nn->d_idx = nullptr;
-    nn->d_dist = nullptr;
-    nn->d_count = nullptr;
-    RKH_HIP(hipMalloc(&nn->d_idx, res_elems * sizeof(uint32_t)));
-    RKH_HIP(hipMalloc(&nn->d_dist, res_elems * sizeof(double)));
-    RKH_HIP(hipMalloc(&nn->d_count, res_elems * sizeof(uint32_t)));
-    nn->res_cap = res_elems;
+  if (q_elems > nn->d_q.size()) RKH_TRY(nn->d_q.alloc(q_elems));
+  if (res_elems > nn->d_count.size()) {  // (the last of the three: a failure half-way leaves it behind the request)
+    nn->d_idx.reset();
+    nn->d_dist.reset();
+    nn->d_count.reset();
+    RKH_TRY(nn->d_idx.alloc(res_elems));
+    RKH_TRY(nn->d_dist.alloc(res_elems));
+    RKH_TRY(nn->d_count.alloc(res_elems));
   }
   return RKH_OK;
 }
@@ -222,18 +199,17 @@ rkh_status rkh_nn_set_coord_bound(rkh_nn* nn, double bound) {
 rkh_status rkh_nn_query1_async(rkh_nn* nn, const double* d_q, uint32_t B, uint32_t* d_idx, double* d_dist) {
   if (!nn || !d_q || !d_idx || !d_dist) return RKH_ERR_BAD_ARG;
   if (B == 0) return RKH_OK;
-  rkh_status st = ensure_partials(nn, B);
-  if (st != RKH_OK) return st;
+  RKH_TRY(ensure_partials(nn, B));
   NnArgs a;
   a.pos = nn->st.d_pos;
   a.n = nn->n;
   a.q = d_q;
   a.B = B;
-  a.part_dist = nn->d_part_dist;
-  a.part_idx = nn->d_part_idx;
+  a.part_dist = nn->d_part_dist.get();
+  a.part_idx = nn->d_part_idx.get();
   a.idx = d_idx;
   a.dist = d_dist;
-  a.seed = nn->d_seed;
+  a.seed = nn->d_seed.get();
   hipEvent_t e0 = nn->ev0, e1 = nn->ev1;
   nn->ev0 = nn->ev1 = nullptr;
   return launch_nn1(nn->ctx->stream, nn->st.D, a, nullptr, 1, nn->n, B, nn->part_blocks, e0, e1, nn->coord_bound);
@@ -249,14 +225,12 @@ rkh_status rkh_nn_query1(rkh_nn* nn, const double* q, uint32_t B, uint32_t* idx,
         return RKH_ERR_BAD_ARG;
       }
   }
-  rkh_status st = ensure_scratch(nn, uint64_t(B) * nn->st.D, B);
-  if (st != RKH_OK) return st;
+  RKH_TRY(ensure_scratch(nn, uint64_t(B) * nn->st.D, B));
   hipStream_t s = nn->ctx->stream;
-  RKH_HIP(hipMemcpyAsync(nn->d_q, q, uint64_t(B) * nn->st.D * sizeof(double), hipMemcpyHostToDevice, s));
-  st = rkh_nn_query1_async(nn, nn->d_q, B, nn->d_idx, nn->d_dist);
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(idx, nn->d_idx, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(dist, nn->d_dist, B * sizeof(double), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(nn->d_q.get(), q, uint64_t(B) * nn->st.D * sizeof(double), hipMemcpyHostToDevice, s));
+  RKH_TRY(rkh_nn_query1_async(nn, nn->d_q.get(), B, nn->d_idx.get(), nn->d_dist.get()));
+  RKH_HIP(hipMemcpyAsync(idx, nn->d_idx.get(), B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(dist, nn->d_dist.get(), B * sizeof(double), hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }
@@ -267,17 +241,10 @@ rkh_status rkh_nn_queryk_async(rkh_nn* nn, const double* d_q, uint32_t B, uint32
   if (B == 0) return RKH_OK;
   KnnWorkspace ws;
   size_t bytes = 0;
-  rkh_status st = knn_plan(nn->n, B, k, &ws, &bytes);
-  if (st != RKH_OK) return st;
-  if (bytes > nn->knn_ws_bytes) {
-    (void)hipFree(nn->d_knn_ws);
-    nn->d_knn_ws = nullptr;
-    RKH_HIP(hipMalloc(&nn->d_knn_ws, bytes));
-    nn->knn_ws_bytes = bytes;
-  }
-  knn_carve(nn->d_knn_ws, B, &ws);
-  st = launch_nnk(nn->ctx->stream, nn->st, nn->n, d_q, B, k, radius, d_idx, d_dist, d_count, ws);
-  if (st != RKH_OK) return st;
+  RKH_TRY(knn_plan(nn->n, B, k, &ws, &bytes));
+  if (bytes > nn->d_knn_ws.size()) RKH_TRY(nn->d_knn_ws.alloc(bytes));
+  knn_carve(nn->d_knn_ws.get(), B, &ws);
+  RKH_TRY(launch_nnk(nn->ctx->stream, nn->st, nn->n, d_q, B, k, radius, d_idx, d_dist, d_count, ws));
   return RKH_OK;
 }
 
@@ -285,17 +252,15 @@ rkh_status rkh_nn_queryk(rkh_nn* nn, const double* q, uint32_t B, uint32_t k, do
                          double* dist, uint32_t* count) {
   if (!nn || !q || !idx || !dist || !count || k == 0) return RKH_ERR_BAD_ARG;
   if (B == 0) return RKH_OK;
-  rkh_status st = ensure_scratch(nn, uint64_t(B) * nn->st.D, uint64_t(B) * k);
-  if (st != RKH_OK) return st;
+  RKH_TRY(ensure_scratch(nn, uint64_t(B) * nn->st.D, uint64_t(B) * k));
   hipStream_t s = nn->ctx->stream;
-  RKH_HIP(hipMemcpyAsync(nn->d_q, q, uint64_t(B) * nn->st.D * sizeof(double), hipMemcpyHostToDevice, s));
-  st = rkh_nn_queryk_async(nn, nn->d_q, B, k, radius, nn->d_idx, nn->d_dist, nn->d_count);
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(idx, nn->d_idx, uint64_t(B) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(dist, nn->d_dist, uint64_t(B) * k * sizeof(double), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(count, nn->d_count, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(nn->d_q.get(), q, uint64_t(B) * nn->st.D * sizeof(double), hipMemcpyHostToDevice, s));
+  RKH_TRY(rkh_nn_queryk_async(nn, nn->d_q.get(), B, k, radius, nn->d_idx.get(), nn->d_dist.get(), nn->d_count.get()));
+  RKH_HIP(hipMemcpyAsync(idx, nn->d_idx.get(), uint64_t(B) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(dist, nn->d_dist.get(), uint64_t(B) * k * sizeof(double), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(count, nn->d_count.get(), B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   uint32_t overflow = 0;  // first word of the k-NN workspace
-  RKH_HIP(hipMemcpyAsync(&overflow, nn->d_knn_ws, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(&overflow, nn->d_knn_ws.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   if (overflow) {
     set_error("rkh_nn_queryk: candidate capacity exceeded (too many vertices within the bound; shrink the radius)");

@@ -12,6 +12,7 @@
 
 #include "../../include/rkh.h"
 #include "../../include/rkh_diag.h"
+#include "device_buffer.h"
 
 namespace rkh {
 
@@ -24,6 +25,13 @@ void set_error(const std::string& msg);
       ::rkh::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                     \
       return (_e == hipErrorOutOfMemory) ? RKH_ERR_OOM : RKH_ERR_DEVICE;                       \
     }                                                                                          \
+  } while (0)
+
+// returns the status of a step that failed
+#define RKH_TRY(expr)                                                                          \
+  do {                                                                                         \
+    const rkh_status _st = (expr);                                                             \
+    if (_st != RKH_OK) return _st;                                                             \
   } while (0)
 
 // Calls f(std::integral_constant<int, N>()) for the N of Ns... equal to n: the chain sizes a launcher's kernels are
@@ -44,7 +52,7 @@ constexpr int kMaxSteps = 64;       // RK4 steps per edge
 // ---- NN sweep (nn_sweep.hip) -----------------------------------------------------------------
 // Vertex positions live row-major [n][D] in HBM (one contiguous 8*D-byte row per vertex): the sweep
 // streams them linearly through LDS tiles and the propagate kernel gathers a parent with one row read.
-struct NnStore {
+struct NnStore {  // a view: the handle that fills it in owns the rows
   double* d_pos = nullptr;  // [capacity][D]
   uint64_t capacity = 0;
   int D = 0;
@@ -202,6 +210,14 @@ struct SceneDev {
   int32_t has_prismatic;   // 1: prismatic_mask != 0 (the prismatic instantiations of the one-wave and quasi-static kernels)
 };
 
+struct PairDev {
+  uint8_t routine;      // PairRoutine (proximity_device.h)
+  uint8_t s1_is_robot;  // 1: (shape1, shape2) = (robot, env); 0: (env, robot)
+  uint16_t robot;
+  uint16_t env;
+  uint16_t pad;
+};
+
 }  // namespace rkh
 
 struct rkh_ctx {
@@ -211,49 +227,38 @@ struct rkh_ctx {
 
 struct rkh_nn {
   rkh_ctx* ctx = nullptr;
-  rkh::NnStore st;
+  rkh::DeviceBuffer<double> pos;  // the rows
+  rkh::NnStore st;                // ... as the launchers take them
   uint64_t n = 0;
-  // scratch for host-pointer queries
-  double* d_q = nullptr;
-  uint32_t* d_idx = nullptr;
-  double* d_dist = nullptr;
-  uint32_t* d_count = nullptr;
-  uint64_t q_cap = 0, res_cap = 0;
-  double* d_part_dist = nullptr;
-  uint32_t* d_part_idx = nullptr;
-  uint64_t part_cap = 0;
-  uint32_t* d_seed = nullptr;  // NnArgs::seed
-  uint32_t seed_cap = 0;
+  // scratch for host-pointer queries; each grows with the largest request (its size() is its capacity)
+  rkh::DeviceBuffer<double> d_q;
+  rkh::DeviceBuffer<uint32_t> d_idx;
+  rkh::DeviceBuffer<double> d_dist;
+  rkh::DeviceBuffer<uint32_t> d_count;
+  rkh::DeviceBuffer<double> d_part_dist;
+  rkh::DeviceBuffer<uint32_t> d_part_idx;
+  rkh::DeviceBuffer<uint32_t> d_seed;  // NnArgs::seed
   double max_abs_coord = 0.0;  // over the rows appended from the host (checked against coord_bound)
   std::vector<uint8_t> removed;  // tombstones (host copy; the device row of a removed vertex holds +inf)
   uint64_t n_removed = 0;
   uint32_t part_blocks = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // one-shot: bracket the next sweep kernel
-  void* d_knn_ws = nullptr;  // k-NN workspace
+  rkh::DeviceBuffer<void> d_knn_ws;  // k-NN workspace
   double coord_bound = 0.0;  // rkh_nn_set_coord_bound: |coordinate| bound enabling the single-precision pre-filters
-  size_t knn_ws_bytes = 0;
 };
 
 struct rkh_scene {
   rkh_ctx* ctx = nullptr;
   rkh::SceneDev host;
-  rkh::SceneDev* d_scene = nullptr;
-  void* d_pairs = nullptr;  // PairDev[n_pairs], sorted by routine
-  double* d_mesh_verts = nullptr;  // vertex pool of the mesh shapes
-  int* d_err = nullptr;
+  rkh::DeviceBuffer<rkh::SceneDev> d_scene;
+  rkh::DeviceBuffer<rkh::PairDev> d_pairs;   // [n_pairs], sorted by routine
+  rkh::DeviceBuffer<double> d_mesh_verts;    // vertex pool of the mesh shapes
+  rkh::DeviceBuffer<int> d_err;
   int n_pairs = 0;
   int n_pairs_verdict = -1;  // the first entries of d_pairs: pairs whose shapes can touch at all (verdict kernels scan these)
 };
 
 namespace rkh {
-
-struct PairDev {
-  uint8_t routine;      // PairRoutine (proximity_device.h)
-  uint8_t s1_is_robot;  // 1: (shape1, shape2) = (robot, env); 0: (env, robot)
-  uint16_t robot;
-  uint16_t env;
-  uint16_t pad;
-};
 
 struct DynDev {  // rkh_dyn_space on the device (passed by value)
   double dt, kp, kd, u_max, goal_tol;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #include "proximity_device.h"
 #include "rkh_internal.h"
@@ -160,23 +161,24 @@ static thread_local SteerMapping g_steer_mapping = SteerMapping::Wave;
 void note_steer_mapping(SteerMapping m) { g_steer_mapping = m; }
 }  // namespace rkh
 
-static rkh_status upload_scene(rkh_ctx* ctx, rkh_scene* sc, const std::vector<PairDev>& pairs, rkh_scene** out) {
+// the last step of both scene builders: the handle is the caller's only once everything is on the device
+static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, const std::vector<PairDev>& pairs,
+                               rkh_scene** out) {
   SceneDev& S = sc->host;
   sc->n_pairs = int(pairs.size());
   if (sc->n_pairs_verdict < 0 || sc->n_pairs_verdict > sc->n_pairs) sc->n_pairs_verdict = sc->n_pairs;
   RKH_HIP(hipSetDevice(ctx->device));
   if (S.has_meshes && g_n_mesh_vertices > 0) {
-    RKH_HIP(hipMalloc(&sc->d_mesh_verts, size_t(g_n_mesh_vertices) * 3 * sizeof(double)));
-    RKH_HIP(hipMemcpy(sc->d_mesh_verts, g_mesh_vertices, size_t(g_n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    S.mesh_verts = sc->d_mesh_verts;
+    RKH_TRY(sc->d_mesh_verts.alloc(size_t(g_n_mesh_vertices) * 3));
+    RKH_HIP(hipMemcpy(sc->d_mesh_verts.get(), g_mesh_vertices, size_t(g_n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
+    S.mesh_verts = sc->d_mesh_verts.get();
   }
-  RKH_HIP(hipMalloc(&sc->d_scene, sizeof(SceneDev)));
-  RKH_HIP(hipMemcpy(sc->d_scene, &S, sizeof(SceneDev), hipMemcpyHostToDevice));
-  RKH_HIP(hipMalloc(&sc->d_pairs, std::max<size_t>(1, pairs.size()) * sizeof(PairDev)));
-  if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs, pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
-  RKH_HIP(hipMalloc(&sc->d_err, sizeof(int)));
-  RKH_HIP(hipMemset(sc->d_err, 0, sizeof(int)));
-  *out = sc;
+  RKH_TRY(sc->d_scene.alloc(1));
+  RKH_HIP(hipMemcpy(sc->d_scene.get(), &S, sizeof(SceneDev), hipMemcpyHostToDevice));
+  RKH_TRY(sc->d_pairs.alloc(std::max<size_t>(1, pairs.size())));
+  if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs.get(), pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
+  RKH_TRY(sc->d_err.alloc_zeroed(1));
+  *out = sc.release();
   return RKH_OK;
 }
 
@@ -199,7 +201,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
               "{driving_actuator_gen, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D} groups");
     return RKH_ERR_UNSUPPORTED;
   }
-  rkh_scene* sc = new rkh_scene();
+  std::unique_ptr<rkh_scene> sc(new rkh_scene());
   sc->ctx = ctx;
   SceneDev& S = sc->host;
   std::memset(&S, 0, sizeof(S));
@@ -217,7 +219,6 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
     const rkh_kte_op& rev = prog[per * j + (dynamics ? 2 : 0)], &lnk = prog[per * j + (dynamics ? 3 : 1)];
     if (rev.kind != RKH_KTE_REVOLUTE_JOINT_2D || lnk.kind != RKH_KTE_RIGID_LINK_2D || rev.coord != j ||
         rev.base_frame != prev_end || lnk.base_frame != rev.end_frame) {
-      delete sc;
       set_error("rkh_scene_create: planar op group " + std::to_string(j) + " does not continue the serial chain");
       return RKH_ERR_UNSUPPORTED;
     }
@@ -227,7 +228,6 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       if (act.kind != RKH_KTE_DRIVING_ACTUATOR_GEN || act.coord != j || act.joint_op != per * j + 2 ||
           gen.kind != RKH_KTE_INERTIA_GEN || gen.coord != j || gen.upstream != (1u << j) ||
           in2.kind != RKH_KTE_INERTIA_2D || in2.end_frame != lnk.end_frame || in2.upstream != ((1u << (j + 1)) - 1u)) {
-        delete sc;
         set_error("rkh_scene_create: planar op group " + std::to_string(j) +
                   " is not {actuator, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D} of one serial joint");
         return RKH_ERR_UNSUPPORTED;
@@ -247,7 +247,6 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
   for (int i = 0; i < n_shapes; ++i) {
     const rkh_shape& s = shapes[i];
     if (s.kind < RKH_SHAPE_CIRCLE || s.kind > RKH_SHAPE_CRECT) {
-      delete sc;
       set_error("rkh_scene_create: a planar chain takes 2D shapes only (circle, rectangle, capped_rectangle)");
       return RKH_ERR_UNSUPPORTED;
     }
@@ -266,7 +265,6 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       for (int j = 0; j < n; ++j)
         if (joint_end_frame[j] == s.anchor) link = j;
       if (link < 0 || S.n_robot >= 2 * kMaxDof) {
-        delete sc;
         set_error("rkh_scene_create: robot shapes must be anchored on a revolute joint's end frame");
         return RKH_ERR_UNSUPPORTED;
       }
@@ -274,7 +272,6 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       S.robot[S.n_robot++] = d;
     } else {
       if (S.n_env >= kMaxEnvShapes) {
-        delete sc;
         set_error("rkh_scene_create: too many environment shapes");
         return RKH_ERR_CAPACITY;
       }
@@ -308,7 +305,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       }
       pairs.push_back(p);
     }
-  return upload_scene(ctx, sc, pairs, out);
+  return upload_scene(ctx, std::move(sc), pairs, out);
 }
 
 extern "C" {
@@ -356,7 +353,7 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     }
   }
   const int n = int(groups.size());
-  rkh_scene* sc = new rkh_scene();
+  std::unique_ptr<rkh_scene> sc(new rkh_scene());
   sc->ctx = ctx;
   SceneDev& S = sc->host;
   std::memset(&S, 0, sizeof(S));
@@ -403,7 +400,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
                     (first && groups[j].mount_op < 0 ? rev.base_frame == 0 : rev.base_frame == expect_base) &&
                     lnk.base_frame == rev.end_frame && ine.end_frame == lnk.end_frame && ine.upstream == branch_mask;
     if (!ok) {
-      delete sc;
       set_error("rkh_scene_create: op group " + std::to_string(j) + " does not match the chain pattern");
       return RKH_ERR_UNSUPPORTED;
     }
@@ -438,7 +434,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     for (int j = 1; j < n; ++j) branching = branching || S.branch_start[j] != 0;
     const char* why = branching ? "a branching chain" : (has_beam ? "a flexible_beam_3D" : nullptr);
     if (why) {
-      delete sc;
       set_error(std::string("rkh_scene_create: prismatic joints are supported in serial chains only, not with ") + why);
       return RKH_ERR_UNSUPPORTED;
     }
@@ -451,7 +446,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       if (bm.end_frame >= 0 && link_end_frame[j] == bm.end_frame) j2 = j;
     }
     if (j1 < 0 || (bm.end_frame >= 0 && j2 < 0) || j1 == j2) {
-      delete sc;
       set_error("rkh_scene_create: the flexible beam's anchors must be link end frames of the chain (anchor 2 may be a "
                 "world anchor, end_frame = -1)");
       return RKH_ERR_UNSUPPORTED;
@@ -488,7 +482,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     const bool kind_ok = (s.kind >= RKH_SHAPE_SPHERE && s.kind <= RKH_SHAPE_CCYLINDER) || s.kind == RKH_SHAPE_PLANE ||
                          s.kind == RKH_SHAPE_CYLINDER || (s.kind == RKH_SHAPE_MESH && mesh_range_ok(s));
     if (!kind_ok) {
-      delete sc;
       set_error("rkh_scene_create: unsupported shape kind");
       return RKH_ERR_UNSUPPORTED;
     }
@@ -504,7 +497,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       for (int j = 0; j < n; ++j)
         if (joint_end_frame[j] == s.anchor) link = j;
       if (link < 0 || S.n_robot >= 2 * kMaxDof) {
-        delete sc;
         set_error("rkh_scene_create: robot shapes must be anchored on a joint's end frame");
         return RKH_ERR_UNSUPPORTED;
       }
@@ -513,7 +505,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       robot_src.push_back(i);
     } else {
       if (S.n_env >= kMaxEnvShapes) {
-        delete sc;
         set_error("rkh_scene_create: too many environment shapes");
         return RKH_ERR_CAPACITY;
       }
@@ -534,7 +525,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     }
   }
   if (S.has_prismatic && S.has_meshes) {
-    delete sc;
     set_error("rkh_scene_create: prismatic joints are not supported together with mesh shapes");
     return RKH_ERR_UNSUPPORTED;
   }
@@ -585,7 +575,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       if (p.routine == 0) continue;  // no finder in the reference
       p.s1_is_robot = robot_first ? 1 : 0;
       if ((ki == RKH_SHAPE_PLANE || kj == RKH_SHAPE_PLANE) && on_prismatic(i)) {
-        delete sc;
         set_error("rkh_scene_create: a plane cannot be paired with a shape carried by a prismatic joint (the plane rule "
                   "below needs a finite reach)");
         return RKH_ERR_UNSUPPORTED;
@@ -599,7 +588,6 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
         double d2 = 0.0;
         for (int k = 0; k < 3; ++k) d2 += (S.env[j].pos[k] - S.base_pos[k]) * (S.env[j].pos[k] - S.base_pos[k]);
         if (std::sqrt(d2) + centre_reach[i] - S.env[j].brad - S.robot[i].brad > 0.0) {
-          delete sc;
           set_error("rkh_scene_create: a plane must be large enough that its bounding sphere (plane.cpp:31) always overlaps "
                     "the robot shapes' (otherwise the reference's result depends on the finder order)");
           return RKH_ERR_UNSUPPORTED;
@@ -619,7 +607,7 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
   int n_verdict = 0;
   for (const PairDev& q : pairs) n_verdict += unreachable(q) ? 0 : 1;
   sc->n_pairs_verdict = n_verdict;
-  return upload_scene(ctx, sc, pairs, out);
+  return upload_scene(ctx, std::move(sc), pairs, out);
 }
 
 rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n,
@@ -627,30 +615,25 @@ rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_sha
   if (!ctx || !a || !b || !dist) return RKH_ERR_BAD_ARG;
   if (n == 0) return RKH_OK;
   RKH_HIP(hipSetDevice(ctx->device));
-  rkh_shape *da = nullptr, *db = nullptr;
-  double *dv = nullptr, *dd = nullptr;
-  RKH_HIP(hipMalloc(&da, n * sizeof(rkh_shape)));
-  RKH_HIP(hipMalloc(&db, n * sizeof(rkh_shape)));
-  RKH_HIP(hipMalloc(&dd, n * sizeof(double)));
-  RKH_HIP(hipMalloc(&dv, std::max<size_t>(1, size_t(n_mesh_vertices) * 3) * sizeof(double)));
-  RKH_HIP(hipMemcpy(da, a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(db, b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv, mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(rkh::gjk_pairs_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, da, db, n, dv, dd);
+  DeviceBuffer<rkh_shape> da, db;
+  DeviceBuffer<double> dv, dd;
+  RKH_TRY(da.alloc(n));
+  RKH_TRY(db.alloc(n));
+  RKH_TRY(dd.alloc(n));
+  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
+  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(rkh::gjk_pairs_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, da.get(), db.get(), n, dv.get(),
+                     dd.get());
   RKH_HIP(hipGetLastError());
-  RKH_HIP(hipMemcpyAsync(dist, dd, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   RKH_HIP(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dv); (void)hipFree(dd);
   return RKH_OK;
 }
 
 rkh_status rkh_scene_destroy(rkh_scene* scene) {
-  if (!scene) return RKH_OK;
-  hipFree(scene->d_scene);
-  hipFree(scene->d_pairs);
-  if (scene->d_mesh_verts) hipFree(scene->d_mesh_verts);
-  hipFree(scene->d_err);
-  delete scene;
+  delete scene;  // (its buffers free themselves; hipFree waits for the device)
   return RKH_OK;
 }
 int rkh_scene_num_dof(const rkh_scene* scene) { return scene ? scene->host.n_dof : 0; }
@@ -659,11 +642,6 @@ int rkh_scene_num_pairs(const rkh_scene* scene) { return scene ? scene->n_pairs 
 }  // extern "C"
 
 namespace {
-struct DevBuf {  // scoped device scratch
-  void* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-};
 // dynamics entry points: branching chains are fine (wave-per-edge kernels); planar chains are position level only
 rkh_status reject_branches(const rkh_scene* scene) {
   if (scene->host.planar && !scene->host.planar_dynamics) {
@@ -674,9 +652,9 @@ rkh_status reject_branches(const rkh_scene* scene) {
 }
 rkh_status check_err_flag(rkh_scene* scene) {
   int flag = 0;
-  RKH_HIP(hipMemcpy(&flag, scene->d_err, sizeof(int), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(&flag, scene->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (flag != 0) {
-    RKH_HIP(hipMemset(scene->d_err, 0, sizeof(int)));
+    RKH_HIP(hipMemset(scene->d_err.get(), 0, sizeof(int)));
     set_error("mass matrix is singular (Cholesky pivot < 1e-8)");
     return rkh_status(flag);
   }
@@ -693,20 +671,18 @@ rkh_status rkh_state_derivative(rkh_scene* scene, const double* x, const double*
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DevBuf dx, du, dpd, dM, df;
-  RKH_HIP(hipMalloc(&dx.p, size_t(B) * 2 * n * 8));
-  RKH_HIP(hipMalloc(&du.p, size_t(B) * n * 8));
-  RKH_HIP(hipMalloc(&dpd.p, size_t(B) * 2 * n * 8));
-  RKH_HIP(hipMalloc(&dM.p, size_t(B) * n * n * 8));
-  RKH_HIP(hipMalloc(&df.p, size_t(B) * n * 8));
-  RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(du.p, u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  rkh_status st = launch_state_derivative(s, *scene, dx.as<double>(), du.as<double>(), B, dpd.as<double>(), dM.as<double>(),
-                                          df.as<double>(), scene->d_err);
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(pd, dpd.p, size_t(B) * 2 * n * 8, hipMemcpyDeviceToHost, s));
-  if (M) RKH_HIP(hipMemcpyAsync(M, dM.p, size_t(B) * n * n * 8, hipMemcpyDeviceToHost, s));
-  if (f) RKH_HIP(hipMemcpyAsync(f, df.p, size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
+  DeviceBuffer<double> dx, du, dpd, dM, df;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(du.alloc(size_t(B) * n));
+  RKH_TRY(dpd.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dM.alloc(size_t(B) * n * n));
+  RKH_TRY(df.alloc(size_t(B) * n));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(du.get(), u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
+  RKH_TRY(launch_state_derivative(s, *scene, dx.get(), du.get(), B, dpd.get(), dM.get(), df.get(), scene->d_err.get()));
+  RKH_HIP(hipMemcpyAsync(pd, dpd.get(), size_t(B) * 2 * n * 8, hipMemcpyDeviceToHost, s));
+  if (M) RKH_HIP(hipMemcpyAsync(M, dM.get(), size_t(B) * n * n * 8, hipMemcpyDeviceToHost, s));
+  if (f) RKH_HIP(hipMemcpyAsync(f, df.get(), size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return check_err_flag(scene);
 }
@@ -716,13 +692,12 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DevBuf dx, dd;
-  RKH_HIP(hipMalloc(&dx.p, size_t(B) * 2 * n * 8));
-  RKH_HIP(hipMalloc(&dd.p, size_t(B) * 8));
-  RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  rkh_status st = launch_min_distance(s, *scene, dx.as<double>(), B, dd.as<double>());
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(dist, dd.p, size_t(B) * 8, hipMemcpyDeviceToHost, s));
+  DeviceBuffer<double> dx, dd;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dd.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RKH_TRY(launch_min_distance(s, *scene, dx.get(), B, dd.get()));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }
@@ -737,44 +712,43 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   }
   if (B == 0) return RKH_OK;
   DynDev dyn;
-  rkh_status st = build_dyn_dev(*space, fraction, &dyn);
-  if (st != RKH_OK) return st;
+  RKH_TRY(build_dyn_dev(*space, fraction, &dyn));
   const int n = scene->host.n_dof, D = 2 * n;
   const int rec_stride = space->steps_per_edge + 1;
   hipStream_t s = scene->ctx->stream;
-  DevBuf da, db, dxo, dsf, drec;
-  RKH_HIP(hipMalloc(&da.p, size_t(B) * D * 8));
-  RKH_HIP(hipMalloc(&db.p, size_t(B) * D * 8));
-  RKH_HIP(hipMalloc(&dxo.p, size_t(B) * D * 8));
-  RKH_HIP(hipMalloc(&dsf.p, size_t(B) * 4));
+  DeviceBuffer<double> da, db, dxo, drec;
+  DeviceBuffer<uint32_t> dsf;
+  RKH_TRY(da.alloc(size_t(B) * D));
+  RKH_TRY(db.alloc(size_t(B) * D));
+  RKH_TRY(dxo.alloc(size_t(B) * D));
+  RKH_TRY(dsf.alloc(size_t(B)));
   if (record) {
-    RKH_HIP(hipMalloc(&drec.p, size_t(B) * rec_stride * D * 8));
-    RKH_HIP(hipMemsetAsync(drec.p, 0, size_t(B) * rec_stride * D * 8, s));
+    RKH_TRY(drec.alloc(size_t(B) * rec_stride * D));
+    RKH_HIP(hipMemsetAsync(drec.get(), 0, size_t(B) * rec_stride * D * 8, s));
   }
-  RKH_HIP(hipMemcpyAsync(da.p, a, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(db.p, b, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(da.get(), a, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(db.get(), b, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
   EdgeIO io;
-  io.src = da.as<double>();
+  io.src = da.get();
   io.src_stride = D;
-  io.tgt = db.as<double>();
+  io.tgt = db.get();
   io.tgt_stride = D;
   io.B = B;
-  io.x_out = dxo.as<double>();
-  io.steps_free = dsf.as<uint32_t>();
-  io.record = record ? drec.as<double>() : nullptr;
+  io.x_out = dxo.get();
+  io.steps_free = dsf.get();
+  io.record = record ? drec.get() : nullptr;
   io.record_stride = rec_stride;
-  io.err_flag = scene->d_err;
+  io.err_flag = scene->d_err.get();
   // the mapping (identical results): by default a call of few edges -- the adaptors steer ONE edge per call -- takes the
   // lowest-latency one (steer_mapping)
   const SteerMapping m = steer_mapping(scene->host, SteerEntry::Propagate, steer_request(), B, 1, 0);
   note_steer_mapping(m);
-  DevBuf dws;
-  if (m == SteerMapping::Pair) RKH_HIP(hipMalloc(&dws.p, propagate_pairs_workspace_bytes(n, B, 0, 1)));
-  st = launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, dws.as<double>());
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(x_out, dxo.p, size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(steps_free, dsf.p, size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  if (record) RKH_HIP(hipMemcpyAsync(record, drec.p, size_t(B) * rec_stride * D * 8, hipMemcpyDeviceToHost, s));
+  DeviceBuffer<void> dws;
+  if (m == SteerMapping::Pair) RKH_TRY(dws.alloc(propagate_pairs_workspace_bytes(n, B, 0, 1)));
+  RKH_TRY(launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, static_cast<double*>(dws.get())));
+  RKH_HIP(hipMemcpyAsync(x_out, dxo.get(), size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(steps_free, dsf.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  if (record) RKH_HIP(hipMemcpyAsync(record, drec.get(), size_t(B) * rec_stride * D * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return check_err_flag(scene);
 }
@@ -785,30 +759,28 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
   if (!scene || !x || !u || !cycles || B == 0) return RKH_ERR_BAD_ARG;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DevBuf dx, du, dout, dsink;
-  RKH_HIP(hipMalloc(&dx.p, size_t(B) * 2 * n * 8));
-  RKH_HIP(hipMalloc(&du.p, size_t(B) * n * 8));
-  RKH_HIP(hipMalloc(&dout.p, size_t(B) * 8 * 8));
-  RKH_HIP(hipMalloc(&dsink.p, size_t(B) * 8));
-  RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(du.p, u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
+  DeviceBuffer<double> dx, du, dsink;
+  DeviceBuffer<unsigned long long> dout;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(du.alloc(size_t(B) * n));
+  RKH_TRY(dout.alloc(size_t(B) * 8));
+  RKH_TRY(dsink.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(du.get(), u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
   rkh_status st;
   const SteerMapping m = steer_mapping(scene->host, SteerEntry::CycleProbe, steer_request(), B, 1, 0);
   if (m == SteerMapping::Pair) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
-    RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
-    st = launch_pair_cycles(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
-                            dsink.as<double>());
+    RKH_HIP(hipMemsetAsync(dout.get(), 0, size_t(B) * 8 * 8, s));
+    st = launch_pair_cycles(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get());
   } else if (m == SteerMapping::Duo) {  // two waves per edge: B / 2 states, rows 2 b / 2 b + 1 = the two waves' counters
-    RKH_HIP(hipMemsetAsync(dout.p, 0, size_t(B) * 8 * 8, s));
-    st = (B >= 2) ? launch_feval_cycles_duo(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
-                                            dsink.as<double>())
+    RKH_HIP(hipMemsetAsync(dout.get(), 0, size_t(B) * 8 * 8, s));
+    st = (B >= 2) ? launch_feval_cycles_duo(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get())
                   : RKH_ERR_BAD_ARG;
   } else {
-    st = launch_feval_cycles(s, *scene, dx.as<double>(), du.as<double>(), B, iters, dout.as<unsigned long long>(),
-                             dsink.as<double>());
+    st = launch_feval_cycles(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get());
   }
   if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(cycles, dout.p, size_t(B) * 8 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(cycles, dout.get(), size_t(B) * 8 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }
@@ -834,14 +806,14 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
     return RKH_ERR_UNSUPPORTED;
   }
   hipStream_t s = scene->ctx->stream;
-  DevBuf dx, dout;
-  RKH_HIP(hipMalloc(&dx.p, size_t(B) * 2 * n * 8));
-  RKH_HIP(hipMalloc(&dout.p, 8 * 8));
-  RKH_HIP(hipMemcpyAsync(dx.p, x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemsetAsync(dout.p, 0, 8 * 8, s));
-  const rkh_status st = launch_pair_counts(s, *scene, dx.as<double>(), B, dout.as<unsigned long long>());
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(counts, dout.p, 8 * 8, hipMemcpyDeviceToHost, s));
+  DeviceBuffer<double> dx;
+  DeviceBuffer<unsigned long long> dout;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dout.alloc(8));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemsetAsync(dout.get(), 0, 8 * 8, s));
+  RKH_TRY(launch_pair_counts(s, *scene, dx.get(), B, dout.get()));
+  RKH_HIP(hipMemcpyAsync(counts, dout.get(), 8 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   // what the host knows: proxy pairs of the scene, and the ones inside the shapes' static reach
   counts[5] = uint64_t(scene->n_pairs);
@@ -866,26 +838,26 @@ rkh_status rkh_edge_check(rkh_scene* scene, const double* lower, const double* u
     qs.upper[i] = upper[i];
   }
   hipStream_t s = scene->ctx->stream;
-  DevBuf da, db, dxo, dnc;
-  RKH_HIP(hipMalloc(&da.p, size_t(B) * n * 8));
-  RKH_HIP(hipMalloc(&db.p, size_t(B) * n * 8));
-  RKH_HIP(hipMalloc(&dxo.p, size_t(B) * n * 8));
-  RKH_HIP(hipMalloc(&dnc.p, size_t(B) * 4));
-  RKH_HIP(hipMemcpyAsync(da.p, a, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(db.p, b, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
+  DeviceBuffer<double> da, db, dxo;
+  DeviceBuffer<uint32_t> dnc;
+  RKH_TRY(da.alloc(size_t(B) * n));
+  RKH_TRY(db.alloc(size_t(B) * n));
+  RKH_TRY(dxo.alloc(size_t(B) * n));
+  RKH_TRY(dnc.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(da.get(), a, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemcpyAsync(db.get(), b, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
   EdgeIO io;
-  io.src = da.as<double>();
+  io.src = da.get();
   io.src_stride = n;
-  io.tgt = db.as<double>();
+  io.tgt = db.get();
   io.tgt_stride = n;
   io.B = B;
-  io.x_out = dxo.as<double>();
-  io.steps_free = dnc.as<uint32_t>();
-  io.err_flag = scene->d_err;
-  rkh_status st = launch_edge_check(s, *scene, qs, io, B);
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(out, dxo.p, size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(n_checked, dnc.p, size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  io.x_out = dxo.get();
+  io.steps_free = dnc.get();
+  io.err_flag = scene->d_err.get();
+  RKH_TRY(launch_edge_check(s, *scene, qs, io, B));
+  RKH_HIP(hipMemcpyAsync(out, dxo.get(), size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(n_checked, dnc.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }
