@@ -62,6 +62,17 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps);
  * revolute or prismatic). */
 rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t B, uint64_t counts[8]);
 
+/* The clearance bound the two-lanes steer kernels take out of that proximity test, per state (same device code): a
+ * lower bound on the distance of the closest (robot shape, obstacle) pair, <= 0 when some pair passes the bounding cull
+ * and in scenes the bound does not cover (branching or planar chains, prismatic joints, plane shapes), where the
+ * kernels test every step.  out[B]. */
+rkh_status rkh_diag_proximity_clearance(rkh_scene* scene, const double* x, uint32_t B, float* out);
+/* Always on: what the carried bound saved in the two-lanes steer launches on this scene so far (rkh_propagate and the
+ * planners created on it; planner launches are read after rkh_planner_sync).  counts[0] = edge-steps whose proximity
+ * test the bound settled, counts[1] = wave-steps (32 edges) that ran the test.  RKH_STEER_CLEARANCE=0 in the
+ * environment (read with the steer mapping's knobs) makes the kernels test every step. */
+rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2]);
+
 #ifdef __cplusplus
 }
 #endif

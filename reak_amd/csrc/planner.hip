@@ -88,7 +88,8 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
                                                            uint32_t* __restrict__ step_cnt) {
   __shared__ unsigned int s_waves;
   // live-edge counters of the step-wise steer launches of this round (launch_propagate_pair_steps)
-  if (step_cnt && threadIdx.x <= uint32_t(kMaxSteps)) step_cnt[threadIdx.x] = 0u;
+  // (two per step: the front and the back part of its list)
+  if (step_cnt && threadIdx.x < 2u * (uint32_t(kMaxSteps) + 1u)) step_cnt[threadIdx.x] = 0u;
   // per-problem inputs of the batch formula, cached once (the bisection below evaluates it ten times per problem) and the
   // three count arrays, scanned in LDS; problems beyond the cache capacity fall back to global memory
   constexpr uint32_t kCache = 1024;
@@ -500,8 +501,9 @@ struct rkh_planner {
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
   // Step-wise steer launches (propagate_pair_step_kernel): one launch per RK4 step over the live edges of all problems,
   // survivors handed on through two ping-pong lists.
-  DeviceBuffer<uint2> d_step_list[2];  // (segment, edge) of the edges alive after step k (k odd / even)
-  DeviceBuffer<uint32_t> d_step_cnt;   // [kMaxSteps + 1] entries of the list launch k reads (cleared by round_begin_kernel)
+  DeviceBuffer<uint4> d_step_list[2];  // (segment, edge, carried clearance) of the edges alive after step k (k odd / even)
+  DeviceBuffer<uint32_t> d_step_cnt;   // [2 (kMaxSteps + 1)] front, then back entries of the list launch k reads (cleared by round_begin_kernel)
+  bool steer_clearance = true;         // RKH_STEER_CLEARANCE
   DeviceBuffer<unsigned long long> d_steps_exec;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
   uint32_t step_blocks_cap = 0;                // grid bound of a step launch (its blocks stride over the chunks beyond it)
   // rounds below this many edges keep the single whole-edge launch of the two-lanes mapping (RKH_STEER_SPLIT_MIN_EDGES;
@@ -625,6 +627,8 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   if (p->steer != SteerMapping::Auto) {
     KernelGate always;  // no gate; the executed steps are counted like Auto's (rkh_planner_steer_steps)
     always.steps_exec = p->d_steps_exec.get();
+    always.clearance = p->steer_clearance;
+    always.clear_stats = p->scene->d_clear_stats.get();
     return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
                             p->d_lane_ws.get(), always);
   }
@@ -636,6 +640,8 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   KernelGate gate_wave{p->d_sel.get() + p->round_parity, 0u, p->lane_threshold};
   KernelGate gate_lane{p->d_sel.get() + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
   gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec.get();
+  gate_lane.clearance = p->steer_clearance;
+  gate_lane.clear_stats = p->scene->d_clear_stats.get();
   if (compact && p->d_wave_base) {  // a regular round: (candidates, probes) segments as round_begin_kernel counted them
     gate_lane.wave_base = p->d_wave_base.get();
     gate_lane.n_segments = 2 * p->P;
@@ -680,8 +686,8 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
   return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
                                      p->d_wave_base.get() + (2 * p->P + 1), p->d_step_list[0].get(),
-                                     p->d_step_list[1].get(), p->d_step_cnt.get(), p->d_lane_ws.get(), blocks, gate_lane,
-                                     p->d_steps_exec.get());
+                                     p->d_step_list[1].get(), uint32_t(p->d_step_list[0].size()), p->d_step_cnt.get(),
+                                     p->d_lane_ws.get(), blocks, gate_lane, p->d_steps_exec.get());
 }
 
 // goal probes still pending after the last enqueued round
@@ -975,6 +981,7 @@ void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
     p->steer = steer_mapping(scene->host, SteerEntry::BatchPlanner, req, 0, p->P, p->b_max);
     note_steer_mapping(p->steer);
     p->duo_threshold = req.duo_threshold;
+    p->steer_clearance = req.clearance;
   }
   if (p->lane_kernel()) {
     hipDeviceProp_t prop;
@@ -1034,7 +1041,7 @@ rkh_status alloc_planner_buffers(rkh_planner* p) {
     RKH_TRY(p->d_wave_base.alloc_zeroed(2 * (2 * size_t(P) + 1)));
     const size_t cap = size_t(P) * (2 * size_t(p->b_max) + kProbeGranule);
     for (auto& l : p->d_step_list) RKH_TRY(l.alloc(cap));
-    RKH_TRY(p->d_step_cnt.alloc_zeroed(kMaxSteps + 1));
+    RKH_TRY(p->d_step_cnt.alloc_zeroed(2 * (kMaxSteps + 1)));
   }
   RKH_TRY(p->d_nn_base.alloc_zeroed(size_t(P) + 1));
   RKH_TRY(p->d_sel.alloc_zeroed(2));

@@ -558,10 +558,24 @@ RKH_DI void pair_drain_q1(ScenePtr sc, PairLds<N>& lds, uint32_t* n_exact = null
   if (lane == 0) lds.qn[0] = 0u;
 }
 
+// Carried clearance (revolute forms; SceneDev::has_clearance scenes).  The cull below forms, for every pair it looks at,
+// a lower bound lb = |w| - reach on the pair's distance.  The smallest lb over the pairs with a finder up to kClearHorizon
+// beyond the static reach, and SceneDev::clear_static for all pairs further out, bound the clearance of the whole
+// configuration from below (the minimum distance over every pair the reference evaluates); a pair that passes the cull
+// has lb <= 0.  No point of the robot moves more than delta = sum_i clear_arm[i] |dq_i| between two
+// configurations, so a state within delta < clearance of a tested one is free without a test: the steer kernels carry
+// clearance - (the deltas of the steps since) per edge and run the test only when it is used up.  The test they skip
+// would have returned "free", so states, step counts and verdicts are unchanged.
+constexpr float kClearSlack = 1e-5f;   // for the rounding of the sqrt, the min and the carried subtractions
+constexpr float kClearMax = 4.0f;      // the carried value stays below this, so one of its roundings is below 2.4e-7
+constexpr float kClearStepPad = 2.4e-7f;  // added to every step's delta: the rounding of budget - delta
+
 // is the configuration in LD(XE..) (joint angles) collision-free?  (manip_dk_proxy_env_impl::is_free, proximity only)
+// clearance: a lower bound on the distance of the closest pair, <= 0 when some pair passed the cull (0 in the prismatic
+// forms, which do not form it)
 template <int N, bool DIAG = false>
 __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& lds, int el, int h,
-                                                    bool active, unsigned long long* stamps = nullptr) {
+                                                    bool active, float& clearance, unsigned long long* stamps = nullptr) {
   typedef PairLayout<N> L_;
   constexpr int R = L_::R;
   ScenePtr sc = sc_in;  // laundered, see pair_state_derivative
@@ -576,6 +590,7 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
   const int lane = threadIdx.x & 63;
   const int n_env = sc->n_env, n_robot = sc->n_robot;
   uint32_t c_q1 = 0, c_exact = 0, c_gold = 0;  // (diagnostic instantiation only)
+  float lb_min = INFINITY;  // smallest lower bound over this lane's pairs
   if (lane < 2) lds.qn[lane] = 0u;
   if (lane < kPairEdges) lds.hit[lane] = 0u;
   // this lane's cull record of the first obstacle chunk, fetched ahead of the kinematics
@@ -639,8 +654,11 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
     const double ra = sc->robot[rc].brad;
     const double seg_hl = a_ccyl ? 0.5 * A.d0 : 0.0, seg_rad_m = (a_ccyl ? A.d1 : ra) + 1e-9;
     // static reach (SceneDev::robot_n_reach): the obstacles this lane's shape can touch at all are a prefix of the table
+    // (the revolute forms scan on to robot_n_clear: obstacles that only the clearance bound looks at)
     const int my_reach = sc->robot_n_reach[rc];
-    const int reach0 = sc->robot_n_reach[r0], reach1 = (r0 + 1 < n_robot) ? sc->robot_n_reach[r0 + 1] : 0;
+    const int my_clear = kPrismatic ? my_reach : sc->robot_n_clear[rc];
+    const int reach0 = kPrismatic ? sc->robot_n_reach[r0] : sc->robot_n_clear[r0];
+    const int reach1 = (r0 + 1 < n_robot) ? (kPrismatic ? sc->robot_n_reach[r0 + 1] : sc->robot_n_clear[r0 + 1]) : 0;
     const int n_scan = reach0 > reach1 ? reach0 : reach1;  // uniform
 #pragma unroll 1
     for (int o0 = 0; o0 < n_scan; o0 += 64) {
@@ -671,6 +689,17 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
       const float aax = float(a_ax.x), aay = float(a_ax.y), aaz = float(a_ax.z);
       const float shl = float(seg_hl), srm = float(seg_rad_m) + 1e-3f;
       unsigned long long mask = 0ull;
+      // obstacles past this lane's own reach; pairs of kinds the reference has no finder for
+      const int mine = my_reach - o0;
+      unsigned long long mine_mask = (mine >= 64) ? ~0ull : (mine <= 0 ? 0ull : ((1ull << mine) - 1ull));
+      mine_mask &= has_finder;
+      if (!have) mine_mask = 0ull;
+      // the pairs the clearance bound is taken over
+      const int clr = my_clear - o0;
+      unsigned long long clear_mask = (clr >= 64) ? ~0ull : (clr <= 0 ? 0ull : ((1ull << clr) - 1ull));
+      clear_mask &= has_finder;
+      if (!have) clear_mask = 0ull;
+      unsigned mine_nib = 0u;  // bits i .. i + 3 of clear_mask
       auto cull_one = [&](int i) -> unsigned {  // 1 when the pair survives (branch-free: selects only)
         const float vx = readlane_f(ecx, i & 63) - cax, vy = readlane_f(ecy, i & 63) - cay, vz = readlane_f(ecz, i & 63) - caz;
         const float rb = readlane_f(ecr, i & 63);
@@ -680,18 +709,19 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
         const float wx = __builtin_fmaf(-t, aax, vx), wy = __builtin_fmaf(-t, aay, vy), wz = __builtin_fmaf(-t, aaz, vz);
         const float w2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
         const float reach = srm + rb;
+        if (!kPrismatic) {  // (v_sqrt_f32: 1 ulp, covered by kClearSlack)
+          const float lb = __builtin_amdgcn_sqrtf(w2) - reach;
+          lb_min = __builtin_fminf(lb_min, ((mine_nib >> (i & 3)) & 1u) ? lb : INFINITY);
+        }
         return (w2 > reach * reach) ? 0u : 1u;
       };
 #pragma unroll 1
       for (int i = 0; i < on; i += 4) {
+        if (!kPrismatic) mine_nib = unsigned(clear_mask >> i) & 0xFu;
         const unsigned nib = cull_one(i) | (cull_one(i + 1) << 1) | (cull_one(i + 2) << 2) | (cull_one(i + 3) << 3);
         mask |= (unsigned long long)nib << i;
       }
-      // obstacles past this lane's own reach; pairs of kinds the reference has no finder for
-      const int mine = my_reach - o0;
-      mask &= (mine >= 64) ? ~0ull : (mine <= 0 ? 0ull : ((1ull << mine) - 1ull));
-      mask &= has_finder;
-      if (!have) mask = 0ull;
+      mask &= mine_mask;
       // survivors -> first queue.  A lane whose entries do not all fit writes placeholders into the part of its range
       // that lies inside the queue and keeps its mask for the next turn.
       while (__any(mask != 0ull)) {
@@ -727,6 +757,12 @@ __device__ __forceinline__ bool pair_proximity_free(ScenePtr sc_in, PairLds<N>& 
     stamps[8] += v0;
     stamps[9] += v1;
     stamps[10] += v2;
+  }
+  if (!kPrismatic) {  // the edge's two lanes took the robot shapes in turn
+    const float other = __int_as_float(xchg_i(__float_as_int(lb_min)));
+    clearance = __builtin_fminf(__builtin_fminf(lb_min, other), __builtin_fminf(float(sc->clear_static), kClearMax)) - kClearSlack;
+  } else {
+    clearance = 0.0f;
   }
   const bool hit = (lds.hit[el] != 0u);
   return !(hit && active);
@@ -848,6 +884,9 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
   bool singular = false;
   bool alive = edge_valid;
   uint32_t n_exec = 0;  // steps integrated for this edge (KernelGate::steps_exec)
+  // carried clearance of the edge (see kClearSlack): what is left of the last test's bound; 0 = the first step tests
+  float budget = 0.0f;
+  uint32_t n_settled = 0, n_tested = 0;  // KernelGate::clear_stats: this edge's steps without a test, the wave's tests
   const int n_steps = pair_args()->dyn.n_steps;
 #pragma unroll 1
   for (int k = 0; k < n_steps; ++k) {
@@ -946,7 +985,25 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
       if (oob) alive = false;
     }
     if (!__any(alive)) break;
-    if (!pair_proximity_free<N>(sc, lds, el, h, alive)) alive = false;
+    bool test = true;
+    if (!kPrismatic) {
+      if (pair_args()->gate.clearance && sc->has_clearance) {
+        // delta of this step, from its start (the last free state) to the state to be tested, rounded up
+        double dl = 0.0;
+#pragma unroll 1
+        for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - ws_ld(ws, W_::X + 2 * j));
+        budget -= float(dl) * 1.000001f + kClearStepPad;
+        test = __any(alive && !(budget > 0.0f));
+      }
+    }
+    if (test) {  // (uniform) every live edge of the wave takes the fresh bound
+      float fresh;
+      if (!pair_proximity_free<N>(sc, lds, el, h, alive, fresh)) alive = false;
+      budget = fresh;
+      ++n_tested;
+    } else if (alive) {
+      ++n_settled;
+    }
     if (alive) {
       ++n_free;
       const EdgeIO* io = edge_io();
@@ -980,6 +1037,13 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
     if (lane == 0 && tot) atomicAdd(pair_args()->gate.steps_exec, (unsigned long long)tot);
+  }
+  if (pair_args()->gate.clear_stats) {
+    uint32_t tot = writer ? n_settled : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+    if (lane == 0 && tot) atomicAdd(pair_args()->gate.clear_stats, (unsigned long long)tot);
+    if (lane == 0 && n_tested) atomicAdd(pair_args()->gate.clear_stats + 1, (unsigned long long)n_tested);
   }
   if (io->mode != EDGE_PLAIN && writer) {
     const double n_ar = sqrt(s_ar), n_ab = sqrt(s_ab), n_rb = sqrt(s_rb);
@@ -1016,12 +1080,18 @@ struct PairStepArgs {
   const uint32_t* edge_base;  // [n_segments + 1] exclusive prefix of the edges per segment (segment 2p + g)
   uint32_t n_segments;
   uint32_t step;              // the step this launch integrates
-  const uint2* list_in;       // step > 0: (segment, edge) of the edges that are still alive
-  const uint32_t* cnt_in;     //           their number
-  uint2* list_out;            // survivors of this launch
+  // step > 0: (segment, edge, carried clearance as float bits, -) of the edges that are still alive, in two parts: the
+  // entries expected to need no proximity test in this launch from the front ([0, cnt_in[0])), the others from the back
+  // ([list_cap - cnt_in[kStepCntBack], list_cap)), so that whole waves can skip the test.  The sorting is a prediction
+  // only: every wave checks the real budgets of its edges.
+  const uint4* list_in;
+  const uint32_t* cnt_in;
+  uint4* list_out;            // survivors of this launch
   uint32_t* cnt_out;
+  uint32_t list_cap;          // entries of each list
   unsigned long long* steps_exec;  // optional: + the number of edge-steps this launch integrated
 };
+constexpr uint32_t kStepCntBack = uint32_t(kMaxSteps) + 1u;  // d_cnt[kStepCntBack + k]: back entries of the list launch k reads
 typedef const __attribute__((address_space(4))) PairStepArgs* PairStepArgP;
 RKH_DI PairStepArgP pair_step_args() {
   PairStepArgP a = (PairStepArgP)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1043,16 +1113,19 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   const int lane = threadIdx.x;
   const int h = lane & 1;
   const int el = lane >> 1;
-  uint32_t n_total;
+  uint32_t n_front, n_back;
   {
     PairStepArgP A = pair_step_args();
     if (A->gate.count) {
       const uint32_t c = *A->gate.count;
       if (c < A->gate.lo || c >= A->gate.hi) return;
     }
-    n_total = A->step == 0u ? A->edge_base[A->n_segments] : *A->cnt_in;
+    n_front = A->step == 0u ? A->edge_base[A->n_segments] : A->cnt_in[0];
+    n_back = A->step == 0u ? 0u : A->cnt_in[kStepCntBack];
   }
-  if (blockIdx.x * uint32_t(kPairEdges) >= n_total) return;
+  const uint32_t chunks_front = (n_front + uint32_t(kPairEdges) - 1u) / uint32_t(kPairEdges);
+  const uint32_t n_chunks = chunks_front + (n_back + uint32_t(kPairEdges) - 1u) / uint32_t(kPairEdges);
+  if (blockIdx.x >= n_chunks) return;
   const ScenePtr sc = (ScenePtr)pair_step_args()->sc;
   if (threadIdx.x < 3 * (N + 1)) {
     const int jj = threadIdx.x / 3;
@@ -1066,11 +1139,14 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   const int n_steps = pair_step_args()->dyn.n_steps;
   const int k = int(pair_step_args()->step);
 #pragma unroll 1
-  for (uint32_t i0 = blockIdx.x * uint32_t(kPairEdges); i0 < n_total; i0 += gridDim.x * uint32_t(kPairEdges)) {
-    const bool edge_valid = i0 + uint32_t(el) < n_total;
+  for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    const bool back = chunk >= chunks_front;  // (uniform)
+    const uint32_t i0 = (back ? chunk - chunks_front : chunk) * uint32_t(kPairEdges);
+    const bool edge_valid = i0 + uint32_t(el) < (back ? n_back : n_front);
     const uint32_t ic = edge_valid ? i0 + uint32_t(el) : i0;  // idle slots shadow the chunk's first edge
     // the lane pair's edge (both lanes of a pair hold the same values)
     uint32_t seg, ec;
+    float budget = 0.0f;  // carried clearance (launch 0 has none: it tests)
     if (k == 0) {  // entry ic of the round's implicit list: bisection in the prefix of the segments' edge counts
       const uint32_t* eb = pair_step_args()->edge_base;
       uint32_t lo = 0, hi = pair_step_args()->n_segments;  // eb[lo] <= ic < eb[hi]
@@ -1082,9 +1158,10 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
       seg = lo;
       ec = ic - eb[lo];
     } else {
-      const uint2 ent = pair_step_args()->list_in[ic];
+      const uint4 ent = pair_step_args()->list_in[back ? pair_step_args()->list_cap - 1u - ic : ic];
       seg = ent.x;
       ec = ent.y;
+      budget = __uint_as_float(ent.z);
     }
     const bool writer = edge_valid && h == 0;  // the lane that exports the edge's results
     auto edge_io = [&]() -> const EdgeIO* {
@@ -1120,6 +1197,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
       if (!(sqrt(s) > pair_step_args()->dyn.goal_tol)) alive = false;
     }
     bool singular = false;
+    float step_delta = 0.0f;  // this step's bound on the motion of the robot's points
     if (__any(alive)) {
       if (pair_step_args()->steps_exec) {
         const unsigned long long m = __ballot(alive && h == 0);
@@ -1201,7 +1279,31 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
         if (oob) alive = false;
       }
       if (__any(alive)) {
-        if (!pair_proximity_free<N>(sc, lds, el, h, alive)) alive = false;
+        bool test = true;
+        if (!kPrismatic) {
+          if (pair_step_args()->gate.clearance && sc->has_clearance) {
+            // delta of this step: from the state the launch read (still in the edge's row; with inner sub-steps the
+            // workspace holds only the last one's start) to the state to be tested, rounded up
+            const EdgeIO* io = edge_io();
+            const double* __restrict__ a_row = k ? io->x_out + uint64_t(ec) * D : io->src + uint64_t(source_row(io)) * io->src_stride;
+            double dl = 0.0;
+#pragma unroll 1
+            for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - a_row[2 * j]);
+            step_delta = float(dl) * 1.000001f + kClearStepPad;
+            budget -= step_delta;
+            test = __any(alive && !(budget > 0.0f));
+          }
+        }
+        unsigned long long* cs = pair_step_args()->gate.clear_stats;
+        if (test) {  // (uniform) every live edge of the wave takes the fresh bound
+          float fresh;
+          if (!pair_proximity_free<N>(sc, lds, el, h, alive, fresh)) alive = false;
+          budget = fresh;
+          if (cs && lane == 0) atomicAdd(cs + 1, 1ull);
+        } else if (cs) {
+          const unsigned long long m = __ballot(alive && h == 0);
+          if (lane == 0) atomicAdd(cs, (unsigned long long)__popcll(m));
+        }
       }
     }
     // ---- the step's outcome: alive = step k was free (the edge stands at the new state), else it stays where it was
@@ -1222,14 +1324,23 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
         }
       }
     }
-    {  // survivors -> the next launch's list
-      const unsigned long long m = __ballot(go_on && h == 0);
-      if (m) {
+    {  // survivors -> the next launch's list: from the front if the budget should last through the next step (it moves
+       // about as far as this one), else from the back
+      const bool quiet = budget > 2.0f * step_delta;  // (budgets are 0 where the clearance is off: all to the back)
+      const unsigned long long mf = __ballot(go_on && h == 0 && quiet), mb = __ballot(go_on && h == 0 && !quiet);
+      if (mf | mb) {
         PairStepArgP A = pair_step_args();
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(A->cnt_out, uint32_t(__popcll(m)));
-        base = uint32_t(__builtin_amdgcn_readfirstlane(int(base)));
-        if (go_on && h == 0) A->list_out[base + uint32_t(__popcll(m & ((1ull << lane) - 1ull)))] = make_uint2(seg, ec);
+        uint32_t base_f = 0, base_b = 0;
+        if (lane == 0 && mf) base_f = atomicAdd(A->cnt_out, uint32_t(__popcll(mf)));
+        if (lane == 0 && mb) base_b = atomicAdd(A->cnt_out + kStepCntBack, uint32_t(__popcll(mb)));
+        base_f = uint32_t(__builtin_amdgcn_readfirstlane(int(base_f)));
+        base_b = uint32_t(__builtin_amdgcn_readfirstlane(int(base_b)));
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (go_on && h == 0) {
+          const uint32_t at = quiet ? base_f + uint32_t(__popcll(mf & below))
+                                    : A->list_cap - 1u - (base_b + uint32_t(__popcll(mb & below)));
+          A->list_out[at] = make_uint4(seg, ec, __float_as_uint(budget), 0u);
+        }
       }
     }
     if (__any(finished)) {  // accept test / goal probe of the edges that end here
@@ -1274,18 +1385,19 @@ size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks) {
 }
 #endif
 
-// The steer launches of a round, one per step, over two ping-pong lists; d_cnt[k] = entries of the list launch k reads
-// (d_cnt[1 .. n_steps] must be zero when the first launch starts: round_begin_kernel clears them).  `blocks` bounds the
+// The steer launches of a round, one per step, over two ping-pong lists of list_cap entries; d_cnt[k] and
+// d_cnt[kStepCntBack + k] = front and back entries of the list launch k reads (d_cnt[0 .. 2 kMaxSteps + 1] must be zero
+// when the first launch starts: round_begin_kernel clears them).  `blocks` bounds the
 // grids; a launch with more chunks than blocks strides over them.
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
-                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
-                                       KernelGate gate, unsigned long long* d_steps_exec) {
+                                       uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec) {
   if (blocks == 0 || n_problems == 0) return RKH_OK;
   if constexpr (!kPrismatic)
     if (scene.host.has_prismatic)
       return prismatic::launch_propagate_pair_steps(s, scene, dyn, tab_a, tab_b, n_problems, d_edge_base, d_list0, d_list1,
-                                                    d_cnt, d_ws, blocks, gate, d_steps_exec);
+                                                    list_cap, d_cnt, d_ws, blocks, gate, d_steps_exec);
   PairStepArgs args;
   args.sc = scene.d_scene.get();
   args.dyn = dyn;
@@ -1296,6 +1408,7 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
   args.edge_base = d_edge_base;
   args.n_segments = 2 * n_problems;
   args.steps_exec = d_steps_exec;
+  args.list_cap = list_cap;
   const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
     for (int k = 0; k < dyn.n_steps; ++k) {
       args.step = uint32_t(k);
@@ -1343,7 +1456,8 @@ __global__ __launch_bounds__(64, 2) void pair_cycles_kernel(const SceneDev* __re
       accv += qdd[j];
       RKH_LD(L_::XE + 2 * j + 1) = RKH_LD(L_::XE + 2 * j + 1) + 1e-4 * qdd[j];
     }
-    accv += pair_proximity_free<N, true>((ScenePtr)sc, lds, el, h, true, st) ? 1.0 : 0.0;
+    float clearance;
+    accv += pair_proximity_free<N, true>((ScenePtr)sc, lds, el, h, true, clearance, st) ? 1.0 : 0.0;
   }
   if (lane == 0) {
     for (int i = 0; i < 8; ++i) out[blockIdx.x * 8 + i] = st[i];
@@ -1355,10 +1469,11 @@ __global__ __launch_bounds__(64, 2) void pair_cycles_kernel(const SceneDev* __re
 // Diagnostic kernel (not on the product path): the proximity test of B states, 32 per wave, counting what survives each
 // stage: out[0] += states tested, [1] += (robot shape, obstacle) pairs past the static reach + fp32 cull (the closed-form
 // stage's input), [2] += closed forms evaluated, [3] += golden-section searches (capped cylinder / box), [4] += states
-// found in collision.
+// found in collision.  clear_out (optional): the clearance bound of every state, as the steer kernels carry it.
 template <int N>
 __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __restrict__ sc, const double* __restrict__ x,
-                                                             uint32_t B, unsigned long long* __restrict__ out) {
+                                                             uint32_t B, unsigned long long* __restrict__ out,
+                                                             float* __restrict__ clear_out) {
   __shared__ PairLds<N> lds;
   if (threadIdx.x < 3 * (N + 1)) {
     const int jj = threadIdx.x / 3;
@@ -1372,7 +1487,9 @@ __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __re
   const uint32_t es = valid ? e : blockIdx.x * kPairEdges;
   for (int d = 0; d < 2 * N; ++d) RKH_LD(L_::XE + d) = x[uint64_t(es) * 2 * N + d];
   unsigned long long st[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const bool free_state = pair_proximity_free<N, true>((ScenePtr)sc, lds, el, h, true, st);
+  float clearance;
+  const bool free_state = pair_proximity_free<N, true>((ScenePtr)sc, lds, el, h, true, clearance, st);
+  if (clear_out && valid && h == 0) clear_out[e] = clearance;  // rkh_diag_proximity_clearance
   const unsigned long long hits = __ballot(!free_state && valid && h == 0);
   if (lane == 0) {
     const uint32_t n_here = (B - blockIdx.x * kPairEdges) < uint32_t(kPairEdges) ? (B - blockIdx.x * kPairEdges) : uint32_t(kPairEdges);
@@ -1385,12 +1502,13 @@ __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __re
 }
 
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
-                              unsigned long long* d_out) {
+                              unsigned long long* d_out, float* d_clear_out) {
   if constexpr (!kPrismatic)
-    if (scene.host.has_prismatic) return prismatic::launch_pair_counts(s, scene, d_x, B, d_out);
+    if (scene.host.has_prismatic) return prismatic::launch_pair_counts(s, scene, d_x, B, d_out, d_clear_out);
   const uint32_t waves = (B + kPairEdges - 1) / kPairEdges;
   const rkh_status st = with_n<6, 3, 7>(scene.host.n_dof, [&](auto c) {
-    hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene.get(), d_x, B, d_out);
+    hipLaunchKernelGGL((pair_counts_kernel<decltype(c)::value>), dim3(waves), dim3(64), 0, s, scene.d_scene.get(), d_x, B, d_out,
+                       d_clear_out);
   });
   if (st != RKH_OK) return st;
   RKH_HIP(hipGetLastError());

@@ -208,7 +208,20 @@ struct SceneDev {
   // prismatic_joint_3D groups (serial chains only): bit j = joint j translates along JointDev::axis (mAxis as given)
   uint32_t prismatic_mask;
   int32_t has_prismatic;   // 1: prismatic_mask != 0 (the prismatic instantiations of the one-wave and quasi-static kernels)
+  // Carried clearance of the two-lanes steer kernels (serial 3D revolute chains without vertex-set or plane shapes:
+  // has_clearance).  clear_arm[i] bounds the distance of every point of every robot shape on joint i or beyond from
+  // joint i's axis: max over the shapes r with link >= i of (link offsets i .. link - 1) + |local position| + bounding
+  // radius, the robot_n_reach sum started at joint i.  Turning joint i by d moves such a point by at most clear_arm[i] |d|,
+  // so between two configurations no point of the robot moves more than sum_i clear_arm[i] |dq_i|.
+  // The bound is a clearance over ALL pairs with a finder: robot shape r's cull also looks at the obstacles up to
+  // kClearHorizon beyond its static reach (the first robot_n_clear[r] >= robot_n_reach[r] of the table; they never
+  // reach the queues), and every pair further out is at least clear_static away in every configuration.
+  int32_t has_clearance;
+  double clear_arm[kMaxDof];
+  int32_t robot_n_clear[kMaxDof * 2];
+  double clear_static;
 };
+constexpr double kClearHorizon = 0.25;  // m; more than the 20 steps of a C2 edge can move the arm (20 x 6.3 mm)
 
 struct PairDev {
   uint8_t routine;      // PairRoutine (proximity_device.h)
@@ -254,6 +267,7 @@ struct rkh_scene {
   rkh::DeviceBuffer<rkh::PairDev> d_pairs;   // [n_pairs], sorted by routine
   rkh::DeviceBuffer<double> d_mesh_verts;    // vertex pool of the mesh shapes
   rkh::DeviceBuffer<int> d_err;
+  rkh::DeviceBuffer<unsigned long long> d_clear_stats;  // [2] KernelGate::clear_stats of every steer launch on this scene
   int n_pairs = 0;
   int n_pairs_verdict = -1;  // the first entries of d_pairs: pairs whose shapes can touch at all (verdict kernels scan these)
 };
@@ -324,6 +338,11 @@ struct KernelGate {
   // optional diagnostics: the kernel adds the edge-steps it integrated (steps that began with a live edge, the one that
   // ended it included) -- the executed work of a launch, as opposed to n_steps per launched edge
   unsigned long long* steps_exec = nullptr;
+  // two-lanes kernels: skip the proximity test of a step that a carried clearance bound settles (SceneDev::has_clearance
+  // scenes only; RKH_STEER_CLEARANCE=0 turns it off), and count [0] += edge-steps settled by the bound, [1] += wave-steps
+  // that ran the test (rkh_diag_steer_clearance_counts)
+  bool clearance = true;
+  unsigned long long* clear_stats = nullptr;
 };
 // ---- steer mapping ---------------------------------------------------------------------------------------------------
 // The kernel form that steers the edges of a dynamic-space launch.
@@ -344,11 +363,13 @@ struct SteerRequest {
   bool lanes_set = false;
   int lanes = 0;                 // RKH_LANES_PER_EDGE
   uint32_t duo_threshold = 512;  // RKH_DUO_THRESHOLD (0: never)
+  bool clearance = true;         // RKH_STEER_CLEARANCE (0: the two-lanes kernels test every step)
 };
 inline SteerRequest steer_request() {
   SteerRequest r;
   if (const char* e = getenv("RKH_LANES_PER_EDGE")) r.lanes_set = true, r.lanes = atoi(e);
   if (const char* e = getenv("RKH_DUO_THRESHOLD")) r.duo_threshold = uint32_t(std::max(0, atoi(e)));
+  if (const char* e = getenv("RKH_STEER_CLEARANCE")) r.clearance = atoi(e) != 0;
   return r;
 }
 
@@ -441,11 +462,11 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
                                   uint32_t n_problems, double* d_ws, KernelGate gate);
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
-                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
-                                       KernelGate gate, unsigned long long* d_steps_exec);
+                                       uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
 uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
-                              unsigned long long* d_out);
+                              unsigned long long* d_out, float* d_clear_out = nullptr);
 }  // namespace prismatic
 rkh_status launch_feval_cycles_duo(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                                    int iters, unsigned long long* d_out, double* d_sink);
@@ -460,12 +481,12 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
 size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks);
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
-                                       uint2* d_list0, uint2* d_list1, uint32_t* d_cnt, double* d_ws, uint32_t blocks,
-                                       KernelGate gate, unsigned long long* d_steps_exec);
+                                       uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
 uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
 uint32_t pair_kernel_edges_per_wave();
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
-                              unsigned long long* d_out);
+                              unsigned long long* d_out, float* d_clear_out = nullptr);
 rkh_status launch_pair_cycles(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u, uint32_t B,
                               int iters, unsigned long long* d_out, double* d_sink);
 // planar chains (propagate_planar.hip): one lane per edge

@@ -178,6 +178,7 @@ static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, cons
   RKH_TRY(sc->d_pairs.alloc(std::max<size_t>(1, pairs.size())));
   if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs.get(), pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
   RKH_TRY(sc->d_err.alloc_zeroed(1));
+  RKH_TRY(sc->d_clear_stats.alloc_zeroed(2));
   *out = sc.release();
   return RKH_OK;
 }
@@ -530,8 +531,9 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
   }
   // robot shape r rides on a prismatic joint (its travel has no bound in the scene: no static reach, no plane pairs)
   auto on_prismatic = [&](int r) { return (S.prismatic_mask & ((2u << S.robot[r].link) - 1u)) != 0u; };
+  S.clear_static = INFINITY;
   for (int r = 0; r < S.n_robot; ++r) {
-    S.robot_n_reach[r] = S.n_env;
+    S.robot_n_reach[r] = S.robot_n_clear[r] = S.n_env;
     if (S.n_branches != 0 || S.planar) continue;  // serial 3D chains only: every joint hangs off the previous link
     if (on_prismatic(r)) continue;
     double reach = 0.0;
@@ -545,6 +547,31 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
     int cnt = 0;
     while (cnt < S.n_env && env_key[cnt] <= reach + 1e-6) ++cnt;
     S.robot_n_reach[r] = cnt;
+    // carried clearance: the obstacles up to kClearHorizon beyond the reach are measured by the cull as well; the
+    // nearest one past that bounds every other pair of this shape in every configuration
+    while (cnt < S.n_env && env_key[cnt] <= reach + kClearHorizon) ++cnt;
+    S.robot_n_clear[r] = cnt;
+    if (cnt < S.n_env) S.clear_static = std::min(S.clear_static, env_key[cnt] - reach);
+  }
+  // Lever arms of the carried clearance (SceneDev::clear_arm): the static reach sum above, started at joint i.  The bound
+  // holds for serial 3D chains of revolute joints whose shapes all have a finite bounding radius about their position.
+  S.has_clearance = (S.n_branches == 0 && !S.planar && !S.has_meshes && !S.has_prismatic) ? 1 : 0;
+  for (int e = 0; e < S.n_env; ++e)
+    if (S.env[e].kind == RKH_SHAPE_PLANE || !std::isfinite(S.env[e].brad)) S.has_clearance = 0;
+  for (int i = 0; i < kMaxDof; ++i) S.clear_arm[i] = 0.0;
+  if (!S.has_clearance)  // nothing is carried: the cull scans the static reach only
+    for (int r = 0; r < S.n_robot; ++r) S.robot_n_clear[r] = S.robot_n_reach[r];
+  for (int r = 0; r < S.n_robot && S.has_clearance; ++r) {
+    if (S.robot[r].kind == RKH_SHAPE_PLANE || !std::isfinite(S.robot[r].brad)) S.has_clearance = 0;
+    const double* lp = S.robot[r].pos;
+    double arm = std::sqrt(lp[0] * lp[0] + lp[1] * lp[1] + lp[2] * lp[2]) + S.robot[r].brad;
+    for (int i = S.robot[r].link; i >= 0; --i) {  // arm = reach of shape r from joint i's origin
+      if (i < S.robot[r].link) {
+        const double* o = S.joints[i].off_pos;
+        arm += std::sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]);
+      }
+      S.clear_arm[i] = std::max(S.clear_arm[i], arm * (1.0 + 1e-9));  // the sums above are rounded
+    }
   }
   // proxy_query_pair_3D::createProxFinderList (proxy_query_model.cpp:215-374), then grouped by routine so
   // that the lanes of a wave run the same closed form (the verdict does not depend on the pair order)
@@ -745,7 +772,10 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   note_steer_mapping(m);
   DeviceBuffer<void> dws;
   if (m == SteerMapping::Pair) RKH_TRY(dws.alloc(propagate_pairs_workspace_bytes(n, B, 0, 1)));
-  RKH_TRY(launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, static_cast<double*>(dws.get())));
+  KernelGate gate;  // no gate; the two-lanes form carries its clearance bound unless RKH_STEER_CLEARANCE=0
+  gate.clearance = steer_request().clearance;
+  gate.clear_stats = scene->d_clear_stats.get();
+  RKH_TRY(launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, static_cast<double*>(dws.get()), gate));
   RKH_HIP(hipMemcpyAsync(x_out, dxo.get(), size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(steps_free, dsf.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
   if (record) RKH_HIP(hipMemcpyAsync(record, drec.get(), size_t(B) * rec_stride * D * 8, hipMemcpyDeviceToHost, s));
@@ -819,6 +849,42 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
   counts[5] = uint64_t(scene->n_pairs);
   counts[6] = uint64_t(scene->n_pairs_verdict);
   counts[7] = 0;
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_proximity_clearance(rkh_scene* scene, const double* x, uint32_t B, float* out) {
+  if (scene && reject_branches(scene) != RKH_OK) return RKH_ERR_UNSUPPORTED;
+  if (!scene || !x || !out || B == 0) return RKH_ERR_BAD_ARG;
+  const int n = scene->host.n_dof;
+  if (!scene_fits_lane_kernel(scene->host)) {
+    set_error("proximity clearance: a scene of the two-lanes steer mapping is needed");
+    return RKH_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx;
+  DeviceBuffer<unsigned long long> dcnt;
+  DeviceBuffer<float> dout;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dcnt.alloc(8));
+  RKH_TRY(dout.alloc(B));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RKH_HIP(hipMemsetAsync(dcnt.get(), 0, 8 * 8, s));
+  RKH_TRY(launch_pair_counts(s, *scene, dx.get(), B, dcnt.get(), dout.get()));
+  RKH_HIP(hipMemcpyAsync(out, dout.get(), size_t(B) * sizeof(float), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  if (!scene->host.has_clearance)  // the kernels carry nothing in such a scene
+    for (uint32_t i = 0; i < B; ++i) out[i] = 0.0f;
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2]) {
+  if (!scene || !counts) return RKH_ERR_BAD_ARG;
+  hipStream_t s = scene->ctx->stream;
+  unsigned long long v[2] = {0, 0};
+  RKH_HIP(hipStreamSynchronize(s));
+  RKH_HIP(hipMemcpy(v, scene->d_clear_stats.get(), sizeof(v), hipMemcpyDeviceToHost));
+  counts[0] = v[0];
+  counts[1] = v[1];
   return RKH_OK;
 }
 
