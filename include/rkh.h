@@ -66,6 +66,11 @@ rkh_status rkh_ctx_destroy(rkh_ctx* ctx);
 rkh_status rkh_ctx_synchronize(rkh_ctx* ctx);
 /* hipStream_t of the context as void* (bench.py brackets launches with HIP events on it). */
 void* rkh_ctx_stream(rkh_ctx* ctx);
+/* A context keeps the device memory of destroyed batch RRT planners for the next rkh_planner_create* on it (creating,
+ * solving and destroying planners over and over on one scene then maps memory once; RKH_ARENA_CACHE=0 in the environment
+ * at create turns that off).  This frees what is kept; so does rkh_ctx_destroy, and any allocation of the library that
+ * runs out of device memory before it gives up. */
+rkh_status rkh_ctx_release_cached_memory(rkh_ctx* ctx);
 
 /* ---- nearest neighbours -------------------------------------------------------------------
  * Replaces linear_neighbor_search<Graph> (ctrl/path_planning/topological_search.hpp:529-690):

@@ -53,6 +53,9 @@ rkh_status rkh_planner_steer_profile(rkh_planner* p, double* total_ms, uint64_t*
  * The executed work of the steer launches -- an edge is launched for n_steps but stops at its first state that is not
  * free (MEAQR_topology.hpp:550-559). */
 rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps);
+/* Samples the stream buffers of one problem hold at present (its sample stream and the two per-iteration logs): the
+ * first buffers are ranges of the planner's arena, rkh_planner_sync replaces them with larger ones of their own. */
+rkh_status rkh_diag_planner_sample_cap(rkh_planner* p, uint32_t problem, uint64_t* samples);
 
 /* The proximity test of the two-lanes steer kernels on B states (2 n_dof doubles each), counting what reaches each of
  * its stages ("collide"): counts[0] = states tested, [1] = (robot shape, obstacle) pairs that pass the

@@ -1,6 +1,7 @@
 // device_buffer.h -- the one owner of device and pinned host memory in librkh.so: every hipMalloc / hipHostMalloc and
 // its free happen here.  Handles and one-shot entry points hold their memory in these; device tables and launchers take
-// plain pointers from get().
+// plain pointers from get().  A batch RRT planner holds ONE allocation, a DeviceArena, and carves its buffers out of it
+// (arena_layout.h); a context keeps the arenas of destroyed planners for the next one (rkh_internal.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,10 +10,14 @@
 #include <type_traits>
 
 #include "../../include/rkh.h"
+#include "arena_layout.h"
 
 namespace rkh {
 
 void set_error(const std::string& msg);
+// Frees the arenas every live context keeps for reuse; returns the bytes freed (rkh_api_nn.hip).  A device allocation
+// that runs out of memory calls it and tries once more: nothing starves beside a parked slab.
+size_t release_cached_memory();
 
 // Move-only array of n elements of T (T = void: n bytes) in device memory, or in pinned host memory (Pinned).  The
 // destructor frees; a moved-from buffer is empty and frees nothing.
@@ -45,8 +50,12 @@ class Buffer {
   rkh_status alloc(size_t n) {
     reset();
     void* p = nullptr;
-    const rkh_status st = check(Pinned ? hipHostMalloc(&p, n * kElem, hipHostMallocDefault) : hipMalloc(&p, n * kElem),
-                                (Pinned ? "hipHostMalloc of " : "hipMalloc of ") + std::to_string(n * kElem) + " bytes");
+    hipError_t e = Pinned ? hipHostMalloc(&p, n * kElem, hipHostMallocDefault) : hipMalloc(&p, n * kElem);
+    if (!Pinned && e == hipErrorOutOfMemory && release_cached_memory() > 0) {
+      (void)hipGetLastError();  // the first attempt's error is dealt with
+      e = hipMalloc(&p, n * kElem);
+    }
+    const rkh_status st = check(e, (Pinned ? "hipHostMalloc of " : "hipMalloc of ") + std::to_string(n * kElem) + " bytes");
     if (st == RKH_OK) p_ = static_cast<T*>(p), n_ = n;
     return st;
   }
@@ -69,5 +78,24 @@ class Buffer {
 };
 template <class T> using DeviceBuffer = Buffer<T, false>;
 template <class T> using PinnedBuffer = Buffer<T, true>;
+
+// Move-only slab of device memory that its holder carves into ranges (arena_layout.h: 256-byte aligned offsets, a guard
+// tail behind the last range).  One hipMalloc however many ranges; the contents are whatever the memory held before.
+class DeviceArena {
+ public:
+  rkh_status alloc(size_t bytes) { return slab_.alloc(bytes); }
+  void reset() { slab_.reset(); }
+  size_t size() const { return slab_.size(); }
+  explicit operator bool() const { return bool(slab_); }
+  void* get() const { return slab_.get(); }
+  // the range as an array of T; null for a range of no bytes
+  template <class T>
+  T* at(const ArenaRange& r) const {
+    return r.bytes ? reinterpret_cast<T*>(static_cast<char*>(slab_.get()) + r.off) : nullptr;
+  }
+
+ private:
+  DeviceBuffer<void> slab_;
+};
 
 }  // namespace rkh

@@ -27,6 +27,12 @@ __device__ __forceinline__ float mirror_half_value(uint32_t bits) {
   return float(__builtin_bit_cast(_Float16, (unsigned short)(bits)));
 }
 
+// fragment i (16 bytes) of a mirror that holds pad rows only
+__device__ __forceinline__ uint4 mirror_pad_fragment(uint64_t i) {
+  const bool upper = ((i >> 5) & 1u) != 0u;  // lane half 1 holds slots 8..15: the pad norm sits in slot 12
+  return upper ? make_uint4(0u, 0u, mirror_half_bits(kMirrorPadNorm), 0u) : make_uint4(0u, 0u, 0u, 0u);
+}
+
 // the two 16-byte fragments (lane half 0: slots 0..7, lane half 1: slots 8..15) of one vertex row; *err = |x - x_h|
 // rounded up (0 for a removed vertex)
 __device__ __forceinline__ void mirror_row_fragments(const double* __restrict__ row, int D, uint4* f0, uint4* f1, float* err) {

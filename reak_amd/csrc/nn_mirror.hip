@@ -320,8 +320,7 @@ __global__ __launch_bounds__(256) void nn1_mirror_resolve_kernel(const NnArgs* _
 __global__ __launch_bounds__(256) void mirror_fill_kernel(uint4* __restrict__ mirror, uint64_t slabs) {
   const uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;  // one 16-byte fragment each
   if (i >= slabs * 64u) return;
-  const bool upper = ((i >> 5) & 1u) != 0u;  // lane half 1 holds slots 8..15: the pad norm sits in slot 12
-  mirror[i] = upper ? make_uint4(0u, 0u, mirror_half_bits(kMirrorPadNorm), 0u) : make_uint4(0u, 0u, 0u, 0u);
+  mirror[i] = mirror_pad_fragment(i);
 }
 
 __global__ __launch_bounds__(256) void mirror_build_kernel(uint4* __restrict__ mirror, const double* __restrict__ pos,

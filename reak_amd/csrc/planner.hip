@@ -29,6 +29,7 @@
 #include <cstring>
 #include <memory>
 
+#include "arena_layout.h"
 #include "nn_device.h"
 #include "nn_mirror.h"
 #include "rkh_internal.h"
@@ -423,6 +424,55 @@ __global__ void probes_flushed_kernel(const ProblemDev* __restrict__ probs) {
   st->n_new = 0;
 }
 
+
+// ---- create: one init pass over all problems ---------------------------------------------------------------------------
+// The planner's memory is a range of an arena that may have served another planner before: whatever a kernel reads before
+// a kernel writes it is written here.
+struct ProblemInit {  // one problem's row of the init table
+  uint32_t* mt;           // its generator: 624 state words + position
+  double* tree;           // row 0 = the start state, padded with zeroes to DP
+  uint32_t* parent;       // parent[0] = none
+  double* goal;
+  uint32_t* seed_row;     // [b_max] NnArgs::seed: all ones between sweeps
+  uint32_t* cand;         // scratch of the mirror sweep + the mirror's error word: zero (null without a mirror)
+  uint4* mirror;          // pad rows everywhere, then the root's row
+  uint32_t* dx_max_bits;
+  uint64_t mirror_frags;  // 16-byte fragments of the mirror
+  uint32_t seed, pad;
+  double start[RKH_MAX_STATE], goal_x[RKH_MAX_STATE];
+};
+
+// blockIdx.y = problem; the blocks of a problem stride over its mirror
+__global__ __launch_bounds__(256) void mirror_fill_all_kernel(const ProblemInit* __restrict__ tab) {
+  uint4* const mirror = tab[blockIdx.y].mirror;
+  const uint64_t frags = tab[blockIdx.y].mirror_frags;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < frags; i += gridDim.x * 256ull) mirror[i] = mirror_pad_fragment(i);
+}
+
+// One block per problem, after mirror_fill_all_kernel.  get_global_rng().seed(s): std::mt19937 / boost::mt19937 seeding
+// (32-bit integer recurrence), position at the end of the state.
+__global__ __launch_bounds__(256) void planner_init_kernel(const ProblemInit* __restrict__ tab, int D, int DP, uint32_t b_max,
+                                                            uint32_t cand_words) {
+  const ProblemInit& pi = tab[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t k = tid; k < b_max; k += 256) pi.seed_row[k] = 0xFFFFFFFFu;
+  for (uint32_t k = tid; k < cand_words; k += 256) pi.cand[k] = 0u;
+  if (tid < uint32_t(DP)) pi.tree[tid] = tid < uint32_t(D) ? pi.start[tid] : 0.0;
+  if (tid < uint32_t(D)) pi.goal[tid] = pi.goal_x[tid];
+  if (tid == 64) pi.parent[0] = 0xFFFFFFFFu;
+  if (tid == 128) {
+    uint32_t w = pi.seed;
+    pi.mt[0] = w;
+    for (uint32_t k = 1; k < uint32_t(kMtN); ++k) {
+      w = 1812433253u * (w ^ (w >> 30)) + k;
+      pi.mt[k] = w;
+    }
+    pi.mt[kMtN] = uint32_t(kMtN);
+  }
+  __syncthreads();  // the error word is zero before the root's row raises it
+  if (tid == 0 && pi.mirror) mirror_store_row(pi.mirror, 0, pi.start, D, pi.dx_max_bits);
+}
+
 }  // namespace rkh
 
 using namespace rkh;
@@ -430,20 +480,26 @@ using namespace rkh;
 namespace {
 struct Problem {  // host view of one planning problem
   rkh_rrt_params prm;
-  DeviceBuffer<uint32_t> d_mt;  // the problem's mt19937 on the device: 624 state words + position
-  DeviceBuffer<double> d_tree, d_goal_dist, d_goal;              // [capacity] vertex rows and goal-probe results; the goal
-  DeviceBuffer<uint32_t> d_parent, d_node_sample;                // [capacity]
-  DeviceBuffer<double> d_samples;                                // [sample_cap] the sample stream ...
-  DeviceBuffer<uint32_t> d_nn_seq;                               // ... and the log of its iterations
-  DeviceBuffer<uint8_t> d_accept_log;
-  DeviceBuffer<uint32_t> d_nn_idx, d_steps, d_probe_steps;       // [b_max (+ kProbeGranule)] a round's candidates and probes
-  DeviceBuffer<double> d_nn_dist, d_x_out, d_probe_x;
-  DeviceBuffer<uint8_t> d_accept;
-  DeviceBuffer<double> d_part_dist;                              // partial minima of the NN sweep
-  DeviceBuffer<uint32_t> d_part_idx, d_round_n;
-  DeviceBuffer<void> d_mirror;       // half-precision mirror of d_tree (nn_mirror.h)
-  DeviceBuffer<void> d_cand;         // per-query scratch of the mirror sweep (nn1_mirror_carve), then one word:
+  // ranges of the planner's arena (planner_arena_layout, ProblemRange), set by alloc_planner_buffers
+  uint32_t* d_mt = nullptr;  // the problem's mt19937 on the device: 624 state words + position
+  double *d_tree = nullptr, *d_goal_dist = nullptr, *d_goal = nullptr;  // [capacity] vertex rows and goal-probe results; the goal
+  uint32_t *d_parent = nullptr, *d_node_sample = nullptr;               // [capacity]
+  double* d_samples = nullptr;                                          // [sample_cap] the sample stream ...
+  uint32_t* d_nn_seq = nullptr;                                         // ... and the log of its iterations
+  uint8_t* d_accept_log = nullptr;
+  uint32_t *d_nn_idx = nullptr, *d_steps = nullptr, *d_probe_steps = nullptr;  // [b_max (+ kProbeGranule)] a round's candidates and probes
+  double *d_nn_dist = nullptr, *d_x_out = nullptr, *d_probe_x = nullptr;
+  uint8_t* d_accept = nullptr;
+  double* d_part_dist = nullptr;                                        // partial minima of the NN sweep
+  uint32_t *d_part_idx = nullptr, *d_round_n = nullptr;
+  void* d_mirror = nullptr;          // half-precision mirror of d_tree (nn_mirror.h)
+  void* d_cand = nullptr;            // per-query scratch of the mirror sweep (nn1_mirror_carve), then one word:
   uint32_t* dx_max_bits = nullptr;   // ... this one, the mirror's running maximum of |x - x_h| (null without a mirror)
+  // the three stream buffers once they have grown (grow_sample_buffers): d_samples, d_nn_seq and d_accept_log then point
+  // into these and the arena's ranges lie idle
+  DeviceBuffer<double> grown_samples;
+  DeviceBuffer<uint32_t> grown_nn_seq;
+  DeviceBuffer<uint8_t> grown_accept_log;
   uint64_t capacity = 0, sample_cap = 0, samples_ready = 0;
   PlannerState h_state;
   // solution bookkeeping (register_basic_solution_path_impl, solution_path_factories.hpp:58-110)
@@ -460,6 +516,18 @@ static_assert(std::is_nothrow_move_constructible<Problem>::value, "std::vector<P
 struct rkh_planner {
   rkh_scene* scene = nullptr;
   hipStream_t stream = nullptr;
+  // All device memory of the handle but the grown stream buffers and d_gd: one slab, carved by planner_arena_layout.  It
+  // comes from the scene's context and goes back to it (arena_cache: RKH_ARENA_CACHE=0 at create turns that off).
+  DeviceArena arena;
+  rkh_ctx* ctx = nullptr;  // the scene's, as it was at create: the arena goes back to it if it still exists
+  ArenaLayout layout;
+  bool arena_cache = true;    // RKH_ARENA_CACHE
+  bool arena_poison = false;  // RKH_ARENA_POISON: the slab is filled with 0xA5 bytes before anything is written
+  // One pinned block: the image of the arena's upload ranges [0, layout.upload_bytes) that create copies to the device
+  // (rkh_planner_sync then reads the states back into their place in it), the error flag's read-back slot, the two segment
+  // tables of the sample generator and the one of the goal-probe gather.
+  PinnedBuffer<char> h_block;
+  int* h_err = nullptr;
   PinnedBuffer<double> h_gd;  // pinned read-back buffer of the goal-probe results (rkh_planner_sync)
   hipStream_t copy_stream = nullptr;  // sample-stream uploads (beside the rounds enqueued on `stream`)
   bool quasi_static = false;  // false: steerable dynamic space (propagate kernel); true: manip_quasi_static_env (edge_check)
@@ -474,11 +542,11 @@ struct rkh_planner {
   float batch_factor = 1.25f;  // candidates per round = batch_factor * sqrt(n) per problem (tune_planner)
   uint64_t sample_cap_min = 0;  // RKH_SAMPLE_CAP: at least this many samples in a problem's first stream buffers
   SteerMapping steer = SteerMapping::Wave;  // the form of every round's steer launches (steer_mapping; dynamic space)
-  DeviceBuffer<double> d_lane_ws;  // workspace of the two-lanes-per-edge kernel
+  double* d_lane_ws = nullptr;  // workspace of the two-lanes-per-edge kernel
   double coord_bound = 0.0;     // max |coordinate| of vertices and samples (hyperbox bounds), 0 = unknown
-  DeviceBuffer<uint32_t> d_sel;        // [2] edges of the current round (by round parity), see round_begin_kernel
-  DeviceBuffer<uint32_t> d_nn_base;    // [P + 1] prefix of the NN sweep's query blocks per problem (matrix-core kernel)
-  DeviceBuffer<uint32_t> d_wave_base;  // [2 P + 1] prefix of the working waves per (problem, candidates | probes) segment
+  uint32_t* d_sel = nullptr;        // [2] edges of the current round (by round parity), see round_begin_kernel
+  uint32_t* d_nn_base = nullptr;    // [P + 1] prefix of the NN sweep's query blocks per problem (matrix-core kernel)
+  uint32_t* d_wave_base = nullptr;  // [2 P + 1] prefix of the working waves per (problem, candidates | probes) segment
   uint32_t round_parity = 0;
   // host-side upper bounds that size the launches of a round (the exact counts live on the device): n_ub[i] >= vertex
   // count of problem i (exact after every sync, + the round's batch bound per enqueued round)
@@ -492,19 +560,20 @@ struct rkh_planner {
   uint32_t part_blocks = 0;
   uint64_t max_capacity = 0;
   // device tables (P entries each)
-  DeviceBuffer<PlannerState> d_states;
-  DeviceBuffer<ProblemDev> d_probs;
-  DeviceBuffer<NnArgs> d_nn_args;
-  DeviceBuffer<EdgeIO> d_io_steer;
-  DeviceBuffer<EdgeIO> d_io_probe;
+  PlannerState* d_states = nullptr;
+  ProblemDev* d_probs = nullptr;
+  NnArgs* d_nn_args = nullptr;
+  EdgeIO* d_io_steer = nullptr;
+  EdgeIO* d_io_probe = nullptr;
   bool nn_mirror = false;  // the NN search of a round runs over the trees' half-precision mirrors (nn_mirror.hip)
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
   // Step-wise steer launches (propagate_pair_step_kernel): one launch per RK4 step over the live edges of all problems,
   // survivors handed on through two ping-pong lists.
-  DeviceBuffer<uint4> d_step_list[2];  // (segment, edge, carried clearance) of the edges alive after step k (k odd / even)
-  DeviceBuffer<uint32_t> d_step_cnt;   // [2 (kMaxSteps + 1)] front, then back entries of the list launch k reads (cleared by round_begin_kernel)
+  uint4* d_step_list[2] = {nullptr, nullptr};  // (segment, edge, carried clearance) of the edges alive after step k (k odd / even)
+  uint32_t step_list_cap = 0;          // entries of each list
+  uint32_t* d_step_cnt = nullptr;      // [2 (kMaxSteps + 1)] front, then back entries of the list launch k reads (cleared by round_begin_kernel)
   bool steer_clearance = true;         // RKH_STEER_CLEARANCE
-  DeviceBuffer<unsigned long long> d_steps_exec;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
+  unsigned long long* d_steps_exec = nullptr;  // edge-steps integrated by the steer kernels (diagnostics: rkh_planner_steer_steps)
   uint32_t step_blocks_cap = 0;                // grid bound of a step launch (its blocks stride over the chunks beyond it)
   // rounds below this many edges keep the single whole-edge launch of the two-lanes mapping (RKH_STEER_SPLIT_MIN_EDGES;
   // default: what leaves every SIMD at most one 32-edge wave -- such a round gains nothing from shedding waves)
@@ -513,15 +582,15 @@ struct rkh_planner {
   uint64_t sum_batch_ub = 0, prev_sum_batch_ub = 0;  // host-side bounds on the candidates of this / the previous round, all problems
   // segment tables of the sample generator: [0] what the enqueued rounds need, [1] the next call's share, generated
   // while the GPU works on the rounds just enqueued
-  DeviceBuffer<double> d_bounds;  // lower[D], upper[D] of the sampled hyperbox
+  double* d_bounds = nullptr;  // lower[D], upper[D] of the sampled hyperbox
   struct Staging {
-    PinnedBuffer<SampleSeg> h_tab;  // pinned segment table [P]
-    DeviceBuffer<SampleSeg> d_tab;
+    SampleSeg* h_tab = nullptr;  // pinned segment table [P] (h_block)
+    SampleSeg* d_tab = nullptr;
     hipEvent_t done = nullptr;
     bool pending = false;
   } staging[2];
-  PinnedBuffer<GoalSeg> h_gd_tab;  // pinned [P]
-  DeviceBuffer<GoalSeg> d_gd_tab;
+  GoalSeg* h_gd_tab = nullptr;  // pinned [P] (h_block)
+  GoalSeg* d_gd_tab = nullptr;
   DeviceBuffer<double> d_gd;       // gathered goal-probe results (rkh_planner_sync)
   // optional HIP-event timing of the NN sweep kernel (RKH_PROFILE_NN=1)
   bool profile_nn = false;
@@ -533,7 +602,7 @@ struct rkh_planner {
   // the two-lanes steer kernel runs in this planner's rounds: its residency sizes the wave fit and the step-wise launches
   bool lane_kernel() const { return steer == SteerMapping::Auto || steer == SteerMapping::Pair; }
 
-  // Both streams idle and the events gone first; the members then free their memory.
+  // Both streams idle and the events gone first; the arena then goes back to the context and the members free the rest.
   ~rkh_planner() {
     if (stream) (void)hipStreamSynchronize(stream);
     for (Staging& sg : staging) {
@@ -547,6 +616,7 @@ struct rkh_planner {
       (void)hipStreamDestroy(copy_stream);
     }
     if (stream) (void)hipStreamDestroy(stream);
+    if (arena_cache && ctx) ctx_give_arena(ctx, std::move(arena));
   }
 };
 
@@ -575,25 +645,21 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
     sg.pending = false;
   }
   if (!sg.done) RKH_HIP(hipEventCreateWithFlags(&sg.done, hipEventDisableTiming));
-  if (!sg.d_tab) {
-    RKH_TRY(sg.h_tab.alloc(p->P));
-    RKH_TRY(sg.d_tab.alloc(p->P));
-  }
   uint32_t n_seg = 0;
   for (uint32_t i = 0; i < p->P; ++i) {
     if (!upto[i]) continue;
     Problem& q = p->prob[i];
-    SampleSeg& seg = sg.h_tab.get()[n_seg++];
-    seg.dst = q.d_samples.get() + q.samples_ready * D;
+    SampleSeg& seg = sg.h_tab[n_seg++];
+    seg.dst = q.d_samples + q.samples_ready * D;
     seg.count = (upto[i] - q.samples_ready) * D;
-    seg.mt = q.d_mt.get();
-    seg.ready_ptr = &p->d_states.get()[i].samples_ready;
+    seg.mt = q.d_mt;
+    seg.ready_ptr = &p->d_states[i].samples_ready;
     seg.ready_new = uint32_t(upto[i]);
     seg.pad = 0;
     q.samples_ready = upto[i];
   }
-  RKH_HIP(hipMemcpyAsync(sg.d_tab.get(), sg.h_tab.get(), n_seg * sizeof(SampleSeg), hipMemcpyHostToDevice, p->copy_stream));
-  hipLaunchKernelGGL(generate_samples_kernel, dim3(n_seg), dim3(256), 0, p->copy_stream, sg.d_tab.get(), p->d_bounds.get(), D);
+  RKH_HIP(hipMemcpyAsync(sg.d_tab, sg.h_tab, n_seg * sizeof(SampleSeg), hipMemcpyHostToDevice, p->copy_stream));
+  hipLaunchKernelGGL(generate_samples_kernel, dim3(n_seg), dim3(256), 0, p->copy_stream, sg.d_tab, p->d_bounds, D);
   RKH_HIP(hipGetLastError());
   // The generator runs on its own stream, beside the rounds already enqueued on the planner stream: it writes beyond every
   // problem's samples_ready (no round reads there) and then raises samples_ready.  Work enqueued on the planner stream
@@ -606,7 +672,7 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
 
 template <int DP>
 void launch_fixup(rkh_planner* p, uint32_t batch_ub) {
-  hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs.get(), p->D);
+  hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
 }
 
 // upper bound of the batch size round_begin_kernel will choose for a problem with at most n_ub vertices (same float
@@ -626,26 +692,26 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P);
   if (p->steer != SteerMapping::Auto) {
     KernelGate always;  // no gate; the executed steps are counted like Auto's (rkh_planner_steer_steps)
-    always.steps_exec = p->d_steps_exec.get();
+    always.steps_exec = p->d_steps_exec;
     always.clearance = p->steer_clearance;
     always.clear_stats = p->scene->d_clear_stats.get();
     return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
-                            p->d_lane_ws.get(), always);
+                            p->d_lane_ws, always);
   }
   // Auto: every form of the sequence is launched; on the device each compares the round's edge count with its gate and
   // the ones not chosen exit at once.  Small rounds -> Duo / Wave (latency), large -> Pair (32 edges per wave).
   auto run = [&](SteerMapping m, double* ws, const KernelGate& gate) {
     return launch_propagate(p->stream, *p->scene, m, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P, ws, gate);
   };
-  KernelGate gate_wave{p->d_sel.get() + p->round_parity, 0u, p->lane_threshold};
-  KernelGate gate_lane{p->d_sel.get() + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
-  gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec.get();
+  KernelGate gate_wave{p->d_sel + p->round_parity, 0u, p->lane_threshold};
+  KernelGate gate_lane{p->d_sel + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
+  gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec;
   gate_lane.clearance = p->steer_clearance;
   gate_lane.clear_stats = p->scene->d_clear_stats.get();
   if (compact && p->d_wave_base) {  // a regular round: (candidates, probes) segments as round_begin_kernel counted them
-    gate_lane.wave_base = p->d_wave_base.get();
+    gate_lane.wave_base = p->d_wave_base;
     gate_lane.n_segments = 2 * p->P;
-    gate_wave.wave_base = p->d_wave_base.get() + (2 * p->P + 1);
+    gate_wave.wave_base = p->d_wave_base + (2 * p->P + 1);
     gate_wave.n_segments = 2 * p->P;
   }
   rkh_status st = RKH_OK;
@@ -665,7 +731,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
   // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
   // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
-  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws.get(), gate_lane);
+  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws, gate_lane);
   // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
   // rounds take one whole-edge launch
   const uint32_t split_edges = p->split_min_edges;
@@ -676,7 +742,7 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     KernelGate whole = gate_lane;
     whole.hi = split_edges;
     if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
-      st = run(SteerMapping::Pair, p->d_lane_ws.get(), whole);
+      st = run(SteerMapping::Pair, p->d_lane_ws, whole);
       if (st != RKH_OK) return st;
     }
     gate_lane.lo = split_edges;
@@ -685,16 +751,16 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   const uint32_t epw = pair_kernel_edges_per_wave();
   const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
   return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
-                                     p->d_wave_base.get() + (2 * p->P + 1), p->d_step_list[0].get(),
-                                     p->d_step_list[1].get(), uint32_t(p->d_step_list[0].size()), p->d_step_cnt.get(),
-                                     p->d_lane_ws.get(), blocks, gate_lane, p->d_steps_exec.get());
+                                     p->d_wave_base + (2 * p->P + 1), p->d_step_list[0],
+                                     p->d_step_list[1], p->step_list_cap, p->d_step_cnt,
+                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec);
 }
 
 // goal probes still pending after the last enqueued round
 rkh_status flush_probes(rkh_planner* p) {
-  hipLaunchKernelGGL(probes_take_all_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs.get());
-  RKH_TRY(launch_edges(p, p->b_max + kProbeGranule, 0, p->d_io_probe.get(), nullptr));
-  hipLaunchKernelGGL(probes_flushed_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs.get());
+  hipLaunchKernelGGL(probes_take_all_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
+  RKH_TRY(launch_edges(p, p->b_max + kProbeGranule, 0, p->d_io_probe, nullptr));
+  hipLaunchKernelGGL(probes_flushed_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -739,21 +805,21 @@ rkh_status enqueue_round(rkh_planner* p) {
   const uint32_t probe_ub = p->prev_batch_ub ? p->prev_batch_ub : p->b_max;
   p->prev_batch_ub = batch_ub + kProbeGranule;  // next round's probes: this round's vertices + what was left over
   p->round_parity ^= 1u;
-  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs.get(), p->P, slot, p->d_sel.get(), p->round_parity,
-                     fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base.get(), p->d_nn_base.get(),
+  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs, p->P, slot, p->d_sel, p->round_parity,
+                     fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base, p->d_nn_base,
                      p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries(),
-                     p->d_wave_base.get() ? p->d_wave_base.get() + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
-                     p->d_step_cnt.get());
+                     p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
+                     p->d_step_cnt);
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
-                      ? launch_nn1_mirror(s, p->D, p->d_nn_args.get(), p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base.get(),
+                      ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
                                           ev0, ev1)
-                      : launch_nn1(s, p->D, NnArgs(), p->d_nn_args.get(), p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
-                                   ev1, p->coord_bound, p->d_nn_base.get(), true);
+                      : launch_nn1(s, p->D, NnArgs(), p->d_nn_args, p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
+                                   ev1, p->coord_bound, p->d_nn_base, true);
   if (st != RKH_OK) return st;
   // 2. speculative steer of all candidates + the goal probes of the vertices the previous round committed
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot], s);
-  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer.get(), p->d_io_probe.get(), true);
+  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer, p->d_io_probe, true);
   if (st != RKH_OK) return st;
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot + 1], s);
   // 3. fix-up against the vertices this round itself would add
@@ -769,7 +835,7 @@ rkh_status enqueue_round(rkh_planner* p) {
     default: set_error("planner: unsupported state dimension"); return RKH_ERR_UNSUPPORTED;
   }
   // 4. commit the valid prefix
-  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs.get(), p->D, p->DP, fit ? kProbeGranule : 1u);
+  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -778,41 +844,41 @@ rkh_status enqueue_round(rkh_planner* p) {
 ProblemDev problem_dev(const rkh_planner* p, uint32_t i) {
   const Problem& q = p->prob[i];
   ProblemDev pd;
-  pd.st = p->d_states.get() + i;
-  pd.tree = q.d_tree.get();
-  pd.parent = q.d_parent.get();
-  pd.node_sample = q.d_node_sample.get();
-  pd.samples = q.d_samples.get();
-  pd.nn_seq = q.d_nn_seq.get();
-  pd.accept_log = q.d_accept_log.get();
-  pd.nn_idx = q.d_nn_idx.get();
-  pd.nn_dist = q.d_nn_dist.get();
-  pd.x_out = q.d_x_out.get();
-  pd.accept = q.d_accept.get();
-  pd.round_n = q.d_round_n.get();
-  pd.mirror = static_cast<uint4*>(q.d_mirror.get());
+  pd.st = p->d_states + i;
+  pd.tree = q.d_tree;
+  pd.parent = q.d_parent;
+  pd.node_sample = q.d_node_sample;
+  pd.samples = q.d_samples;
+  pd.nn_seq = q.d_nn_seq;
+  pd.accept_log = q.d_accept_log;
+  pd.nn_idx = q.d_nn_idx;
+  pd.nn_dist = q.d_nn_dist;
+  pd.x_out = q.d_x_out;
+  pd.accept = q.d_accept;
+  pd.round_n = q.d_round_n;
+  pd.mirror = static_cast<uint4*>(q.d_mirror);
   pd.dx_max_bits = q.dx_max_bits;
   return pd;
 }
 
 NnArgs nn_args(const rkh_planner* p, uint32_t i) {
   const Problem& q = p->prob[i];
-  PlannerState* st = p->d_states.get() + i;
+  PlannerState* st = p->d_states + i;
   NnArgs na;
-  na.pos = q.d_tree.get();
+  na.pos = q.d_tree;
   na.d_n = &st->n;
-  na.q = q.d_samples.get();
+  na.q = q.d_samples;
   na.d_qoff = &st->s0;
   na.B = p->b_max;
   na.d_B = &st->B;
-  na.part_dist = q.d_part_dist.get();
-  na.part_idx = q.d_part_idx.get();
-  na.seed = q.d_part_idx.get() + uint64_t(p->part_blocks) * p->b_max;
-  na.idx = q.d_nn_idx.get();
-  na.dist = q.d_nn_dist.get();
-  na.mirror = q.d_mirror.get();
+  na.part_dist = q.d_part_dist;
+  na.part_idx = q.d_part_idx;
+  na.seed = q.d_part_idx + uint64_t(p->part_blocks) * p->b_max;
+  na.idx = q.d_nn_idx;
+  na.dist = q.d_nn_dist;
+  na.mirror = q.d_mirror;
   if (q.d_cand) {
-    nn1_mirror_carve(q.d_cand.get(), p->b_max, &na);
+    nn1_mirror_carve(q.d_cand, p->b_max, &na);
     na.dx_max_bits = q.dx_max_bits;
   }
   return na;
@@ -820,49 +886,50 @@ NnArgs nn_args(const rkh_planner* p, uint32_t i) {
 
 EdgeIO steer_io(const rkh_planner* p, uint32_t i) {
   const Problem& q = p->prob[i];
-  PlannerState* st = p->d_states.get() + i;
+  PlannerState* st = p->d_states + i;
   EdgeIO io;
-  io.src = q.d_tree.get();
-  io.src_idx = q.d_nn_idx.get();
+  io.src = q.d_tree;
+  io.src_idx = q.d_nn_idx;
   io.src_stride = p->DP;
-  io.tgt = q.d_samples.get();
+  io.tgt = q.d_samples;
   io.d_tgt_off = &st->s0;
   io.tgt_stride = p->D;
   io.B = p->b_max;
   io.d_B = &st->B;
-  io.x_out = q.d_x_out.get();
-  io.steps_free = q.d_steps.get();
+  io.x_out = q.d_x_out;
+  io.steps_free = q.d_steps;
   io.mode = EDGE_STEER_ACCEPT;
-  io.best_case = q.d_nn_dist.get();
+  io.best_case = q.d_nn_dist;
   io.steer_tol = q.prm.steer_tol;
-  io.accept = q.d_accept.get();
+  io.accept = q.d_accept;
   io.err_flag = p->scene->d_err.get();
   return io;
 }
 
 EdgeIO probe_io(const rkh_planner* p, uint32_t i) {
   const Problem& q = p->prob[i];
-  PlannerState* st = p->d_states.get() + i;
+  PlannerState* st = p->d_states + i;
   EdgeIO gp;
-  gp.src = q.d_tree.get();
+  gp.src = q.d_tree;
   gp.d_src_first = &st->n_before;
   gp.src_stride = p->DP;
-  gp.tgt = q.d_goal.get();
+  gp.tgt = q.d_goal;
   gp.tgt_stride = 0;
   gp.B = p->b_max + kProbeGranule;
   gp.d_B = &st->n_new;
-  gp.x_out = q.d_probe_x.get();
-  gp.steps_free = q.d_probe_steps.get();
+  gp.x_out = q.d_probe_x;
+  gp.steps_free = q.d_probe_steps;
   gp.mode = EDGE_GOAL_PROBE;
-  gp.goal_dist = q.d_goal_dist.get();
+  gp.goal_dist = q.d_goal_dist;
   gp.err_flag = p->scene->d_err.get();
   return gp;
 }
 
 // generate_rrt has no iteration cap (rr_tree.hpp:192-196: keep_going() looks at the vertex count only), so the device-
 // resident sample stream and its per-iteration logs must not have one either: when a problem's cursor comes near the
-// end of its buffers they are re-allocated at twice the size.  Called with both streams idle (rkh_planner_sync).  A
-// failure before the swap leaves the problem as it was.
+// end of its buffers they are re-allocated at twice the size: buffers of their own, which supersede the ranges of the
+// arena the problem started in.  Called with both streams idle (rkh_planner_sync).  A failure before the swap leaves the
+// problem as it was.
 rkh_status grow_sample_buffers(rkh_planner* p, uint32_t i, uint64_t new_cap) {
   Problem& q = p->prob[i];
   const int D = p->D;
@@ -872,28 +939,34 @@ rkh_status grow_sample_buffers(rkh_planner* p, uint32_t i, uint64_t new_cap) {
   RKH_TRY(ns.alloc(new_cap * D));
   RKH_TRY(nq.alloc(new_cap));
   RKH_TRY(na.alloc(new_cap));
-  RKH_HIP(hipMemcpy(ns.get(), q.d_samples.get(), q.samples_ready * D * sizeof(double), hipMemcpyDeviceToDevice));
-  RKH_HIP(hipMemcpy(nq.get(), q.d_nn_seq.get(), q.sample_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-  RKH_HIP(hipMemcpy(na.get(), q.d_accept_log.get(), q.sample_cap, hipMemcpyDeviceToDevice));
-  q.d_samples = std::move(ns);  // (frees the old one)
-  q.d_nn_seq = std::move(nq);
-  q.d_accept_log = std::move(na);
+  RKH_HIP(hipMemcpy(ns.get(), q.d_samples, q.samples_ready * D * sizeof(double), hipMemcpyDeviceToDevice));
+  RKH_HIP(hipMemcpy(nq.get(), q.d_nn_seq, q.sample_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  RKH_HIP(hipMemcpy(na.get(), q.d_accept_log, q.sample_cap, hipMemcpyDeviceToDevice));
+  q.grown_samples = std::move(ns);  // (frees the ones of an earlier growth; the arena's first ranges just lie idle)
+  q.grown_nn_seq = std::move(nq);
+  q.grown_accept_log = std::move(na);
+  q.d_samples = q.grown_samples.get();
+  q.d_nn_seq = q.grown_nn_seq.get();
+  q.d_accept_log = q.grown_accept_log.get();
   q.sample_cap = new_cap;
   // the device tables that point into these buffers
-  const double* cs = q.d_samples.get();
-  uint32_t* cq = q.d_nn_seq.get();
-  uint8_t* ca = q.d_accept_log.get();
-  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].samples, &cs, sizeof(cs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].nn_seq, &cq, sizeof(cq), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_probs.get()[i].accept_log, &ca, sizeof(ca), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_nn_args.get()[i].q, &cs, sizeof(cs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(&p->d_io_steer.get()[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  const double* cs = q.d_samples;
+  uint32_t* cq = q.d_nn_seq;
+  uint8_t* ca = q.d_accept_log;
+  RKH_HIP(hipMemcpy(&p->d_probs[i].samples, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_probs[i].nn_seq, &cq, sizeof(cq), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_probs[i].accept_log, &ca, sizeof(ca), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_nn_args[i].q, &cs, sizeof(cs), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(&p->d_io_steer[i].tgt, &cs, sizeof(cs), hipMemcpyHostToDevice));
   return RKH_OK;
 }
 
+// The states of all problems and the scene's error flag (*p->h_err), read into the pinned block: two copies queued back
+// to back, one wait.
 rkh_status read_states(rkh_planner* p) {
-  std::vector<PlannerState> hs(p->P);
-  RKH_HIP(hipMemcpyAsync(hs.data(), p->d_states.get(), p->P * sizeof(PlannerState), hipMemcpyDeviceToHost, p->stream));
+  PlannerState* hs = reinterpret_cast<PlannerState*>(p->h_block.get() + p->layout.shared[SR_STATES].off);
+  RKH_HIP(hipMemcpyAsync(hs, p->d_states, p->P * sizeof(PlannerState), hipMemcpyDeviceToHost, p->stream));
+  RKH_HIP(hipMemcpyAsync(p->h_err, p->scene->d_err.get(), sizeof(int), hipMemcpyDeviceToHost, p->stream));
   RKH_HIP(hipStreamSynchronize(p->stream));
   for (uint32_t i = 0; i < p->P; ++i) {
     p->prob[i].h_state = hs[i];
@@ -1014,122 +1087,181 @@ void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
   if (const char* e = getenv("RKH_BATCH_FACTOR")) p->batch_factor = float(atof(e));
   if (const char* e = getenv("RKH_BATCH_MIN")) p->b_min = std::max(1, atoi(e));
   if (const char* e = getenv("RKH_SAMPLE_CAP")) p->sample_cap_min = strtoull(e, nullptr, 10);
+  if (const char* e = getenv("RKH_ARENA_CACHE")) p->arena_cache = atoi(e) != 0;
+  if (const char* e = getenv("RKH_ARENA_POISON")) p->arena_poison = atoi(e) != 0;
 }
 
-// 4. The streams and what all problems share: the five tables, the sampled box, the counters and prefixes of a round.
+// 4. The streams, then the memory: the arena's layout from the shape of the batch, the slab itself -- one the context
+// kept from an earlier planner, or a new one -- and every device pointer of the planner set to its range; the pinned
+// block beside it.
 rkh_status alloc_planner_buffers(rkh_planner* p) {
-  const uint32_t P = p->P;
+  const uint32_t P = p->P, b_max = p->b_max;
   RKH_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   RKH_HIP(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-  std::vector<double> bounds(2 * p->D);
+  std::vector<uint64_t> capacity(P), sample_cap(P), mirror_bytes(P);
+  for (uint32_t i = 0; i < P; ++i) {
+    Problem& q = p->prob[i];
+    q.sample_cap = planner_sample_cap(q.prm.max_vertices, b_max, p->sample_cap_min);
+    capacity[i] = q.capacity;
+    sample_cap[i] = q.sample_cap;
+    mirror_bytes[i] = nn1_mirror_bytes(q.capacity);
+  }
+  ArenaShape sh;
+  sh.P = P;
+  sh.capacity = capacity.data();
+  sh.sample_cap = sample_cap.data();
+  sh.mirror_bytes = mirror_bytes.data();
+  sh.b_max = b_max;
+  sh.probe_granule = kProbeGranule;
+  sh.part_blocks = p->part_blocks;
+  sh.prof_rounds = rkh_planner::kProfMax;
+  sh.D = p->D;
+  sh.DP = p->DP;
+  sh.mirror = p->nn_mirror;
+  sh.profile = p->profile_nn;
+  sh.lane = p->lane_kernel();
+  sh.cand_bytes = nn1_mirror_query_bytes() * b_max + 256;  // the per-query scratch, then the mirror's error word
+  if (sh.lane) {
+    // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
+    // see prev_batch_ub and flush_probes)
+    sh.lane_ws_bytes = propagate_pairs_workspace_bytes(p->n_dof, b_max, b_max + kProbeGranule, P);
+    p->step_list_cap = P * (2 * b_max + kProbeGranule);
+    sh.step_list_bytes = size_t(p->step_list_cap) * sizeof(uint4);
+  }
+  sh.state_bytes = sizeof(PlannerState);
+  sh.prob_bytes = sizeof(ProblemDev);
+  sh.nn_args_bytes = sizeof(NnArgs);
+  sh.edge_io_bytes = sizeof(EdgeIO);
+  sh.init_bytes = sizeof(ProblemInit);
+  sh.sample_seg_bytes = sizeof(SampleSeg);
+  sh.goal_seg_bytes = sizeof(GoalSeg);
+  sh.max_steps = kMaxSteps;
+  p->layout = planner_arena_layout(sh);
+  const ArenaLayout& L = p->layout;
+  RKH_TRY(ctx_take_arena(p->ctx, L.total, p->arena_cache, &p->arena));
+  const DeviceArena& A = p->arena;
+  // diagnostic: nothing may depend on what the memory held before, zeroes included
+  if (p->arena_poison) RKH_HIP(hipMemsetAsync(A.get(), 0xA5, A.size(), p->stream));
+  p->d_bounds = A.at<double>(L.shared[SR_BOUNDS]);
+  p->d_states = A.at<PlannerState>(L.shared[SR_STATES]);
+  p->d_probs = A.at<ProblemDev>(L.shared[SR_PROBS]);
+  p->d_nn_args = A.at<NnArgs>(L.shared[SR_NN_ARGS]);
+  p->d_io_steer = A.at<EdgeIO>(L.shared[SR_IO_STEER]);
+  p->d_io_probe = A.at<EdgeIO>(L.shared[SR_IO_PROBE]);
+  p->d_wave_base = A.at<uint32_t>(L.shared[SR_WAVE_BASE]);
+  p->d_step_cnt = A.at<uint32_t>(L.shared[SR_STEP_CNT]);
+  p->d_nn_base = A.at<uint32_t>(L.shared[SR_NN_BASE]);
+  p->d_sel = A.at<uint32_t>(L.shared[SR_SEL]);
+  p->d_steps_exec = A.at<unsigned long long>(L.shared[SR_STEPS_EXEC]);
+  p->staging[0].d_tab = A.at<SampleSeg>(L.shared[SR_SAMPLE_TAB0]);
+  p->staging[1].d_tab = A.at<SampleSeg>(L.shared[SR_SAMPLE_TAB1]);
+  p->d_gd_tab = A.at<GoalSeg>(L.shared[SR_GOAL_TAB]);
+  p->d_lane_ws = A.at<double>(L.shared[SR_LANE_WS]);
+  p->d_step_list[0] = A.at<uint4>(L.shared[SR_STEP_LIST0]);
+  p->d_step_list[1] = A.at<uint4>(L.shared[SR_STEP_LIST1]);
+  for (uint32_t i = 0; i < P; ++i) {
+    Problem& q = p->prob[i];
+    q.d_mt = A.at<uint32_t>(L.of(i, PR_MT));
+    q.d_tree = A.at<double>(L.of(i, PR_TREE));
+    q.d_parent = A.at<uint32_t>(L.of(i, PR_PARENT));
+    q.d_node_sample = A.at<uint32_t>(L.of(i, PR_NODE_SAMPLE));
+    q.d_goal_dist = A.at<double>(L.of(i, PR_GOAL_DIST));
+    q.d_samples = A.at<double>(L.of(i, PR_SAMPLES));
+    q.d_nn_seq = A.at<uint32_t>(L.of(i, PR_NN_SEQ));
+    q.d_accept_log = A.at<uint8_t>(L.of(i, PR_ACCEPT_LOG));
+    q.d_nn_idx = A.at<uint32_t>(L.of(i, PR_NN_IDX));
+    q.d_nn_dist = A.at<double>(L.of(i, PR_NN_DIST));
+    q.d_x_out = A.at<double>(L.of(i, PR_X_OUT));
+    q.d_steps = A.at<uint32_t>(L.of(i, PR_STEPS));
+    q.d_accept = A.at<uint8_t>(L.of(i, PR_ACCEPT));
+    q.d_probe_x = A.at<double>(L.of(i, PR_PROBE_X));
+    q.d_probe_steps = A.at<uint32_t>(L.of(i, PR_PROBE_STEPS));
+    q.d_goal = A.at<double>(L.of(i, PR_GOAL));
+    q.d_part_dist = A.at<double>(L.of(i, PR_PART_DIST));
+    q.d_part_idx = A.at<uint32_t>(L.of(i, PR_PART_IDX));
+    q.d_round_n = A.at<uint32_t>(L.of(i, PR_ROUND_N));
+    q.d_mirror = A.at<void>(L.of(i, PR_MIRROR));
+    q.d_cand = A.at<void>(L.of(i, PR_CAND));
+    q.dx_max_bits = q.d_cand ? reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand) + nn1_mirror_query_bytes() * b_max) : nullptr;
+  }
+  // the pinned block: image of the upload ranges | error flag | segment tables
+  const size_t seg_tab = arena_align_up(P * sizeof(SampleSeg)), gd_tab = arena_align_up(P * sizeof(GoalSeg));
+  RKH_TRY(p->h_block.alloc(L.upload_bytes + kArenaAlign + 2 * seg_tab + gd_tab));
+  char* h = p->h_block.get() + L.upload_bytes;
+  p->h_err = reinterpret_cast<int*>(h);
+  p->staging[0].h_tab = reinterpret_cast<SampleSeg*>(h + kArenaAlign);
+  p->staging[1].h_tab = reinterpret_cast<SampleSeg*>(h + kArenaAlign + seg_tab);
+  p->h_gd_tab = reinterpret_cast<GoalSeg*>(h + kArenaAlign + 2 * seg_tab);
+  return RKH_OK;
+}
+
+// 5. The image of the upload ranges, in the pinned block: the sampled box, every problem's initial device state and its
+// entry in the five tables, its row of the init table, and the zeroes of the round counters and prefixes.
+void fill_upload_image(rkh_planner* p) {
+  const ArenaLayout& L = p->layout;
+  char* h = p->h_block.get();
+  std::memset(h, 0, L.upload_bytes);
+  auto image = [&](SharedRange r) { return h + L.shared[r].off; };
+  double* bounds = reinterpret_cast<double*>(image(SR_BOUNDS));
   for (int d = 0; d < p->D; ++d) {
     bounds[d] = p->lower[d];
     bounds[p->D + d] = p->upper[d];
   }
-  RKH_TRY(p->d_bounds.alloc(bounds.size()));
-  RKH_HIP(hipMemcpy(p->d_bounds.get(), bounds.data(), bounds.size() * sizeof(double), hipMemcpyHostToDevice));
-  RKH_TRY(p->d_states.alloc(P));
-  RKH_TRY(p->d_probs.alloc(P));
-  RKH_TRY(p->d_nn_args.alloc(P));
-  RKH_TRY(p->d_io_steer.alloc(P));
-  RKH_TRY(p->d_io_probe.alloc(P));
-  if (p->lane_kernel()) {
-    // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
-    // see prev_batch_ub and flush_probes)
-    RKH_TRY(p->d_lane_ws.alloc(propagate_pairs_workspace_bytes(p->n_dof, p->b_max, p->b_max + kProbeGranule, P) / sizeof(double)));
-    // two prefix arrays of 2 P + 1 entries: waves of the two-lanes kernel, then single edges (one-wave-per-edge kernel)
-    RKH_TRY(p->d_wave_base.alloc_zeroed(2 * (2 * size_t(P) + 1)));
-    const size_t cap = size_t(P) * (2 * size_t(p->b_max) + kProbeGranule);
-    for (auto& l : p->d_step_list) RKH_TRY(l.alloc(cap));
-    RKH_TRY(p->d_step_cnt.alloc_zeroed(2 * (kMaxSteps + 1)));
-  }
-  RKH_TRY(p->d_nn_base.alloc_zeroed(size_t(P) + 1));
-  RKH_TRY(p->d_sel.alloc_zeroed(2));
-  RKH_TRY(p->d_steps_exec.alloc_zeroed(1));
-  return RKH_OK;
-}
-
-// 5. One problem: its buffers, its mt19937, the root vertex with its mirror row, and its initial device state.
-rkh_status create_problem(rkh_planner* p, Problem& q) {
-  const int D = p->D, DP = p->DP;
-  const uint32_t b_max = p->b_max;
-  {  // get_global_rng().seed(s): std::mt19937 / boost::mt19937 seeding, position at the end of the state
-    std::vector<uint32_t> mt(kMtN + 1);
-    mt[0] = uint32_t(q.prm.seed);
-    for (int k = 1; k < kMtN; ++k) mt[k] = 1812433253u * (mt[k - 1] ^ (mt[k - 1] >> 30)) + uint32_t(k);
-    mt[kMtN] = uint32_t(kMtN);
-    RKH_TRY(q.d_mt.alloc(mt.size()));
-    RKH_HIP(hipMemcpy(q.d_mt.get(), mt.data(), mt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  const uint64_t max_total = uint64_t(q.prm.max_vertices) + 1;
-  RKH_TRY(q.d_tree.alloc(q.capacity * DP));
-  RKH_TRY(q.d_parent.alloc(q.capacity));
-  RKH_TRY(q.d_node_sample.alloc(q.capacity));
-  RKH_TRY(q.d_goal_dist.alloc(q.capacity));
-  q.sample_cap = std::max<uint64_t>(std::max<uint64_t>(4 * max_total + 4 * b_max, 1u << 14), p->sample_cap_min);
-  RKH_TRY(q.d_samples.alloc(q.sample_cap * D));
-  RKH_TRY(q.d_nn_seq.alloc(q.sample_cap));
-  RKH_TRY(q.d_accept_log.alloc(q.sample_cap));
-  RKH_TRY(q.d_nn_idx.alloc(b_max));
-  RKH_TRY(q.d_nn_dist.alloc(b_max));
-  RKH_TRY(q.d_x_out.alloc(uint64_t(b_max) * D));
-  RKH_TRY(q.d_steps.alloc(b_max));
-  RKH_TRY(q.d_accept.alloc(b_max));
-  RKH_TRY(q.d_probe_x.alloc(uint64_t(b_max + kProbeGranule) * D));
-  RKH_TRY(q.d_probe_steps.alloc(b_max + kProbeGranule));
-  RKH_TRY(q.d_goal.alloc(D));
-  RKH_TRY(q.d_part_dist.alloc(uint64_t(p->part_blocks) * b_max));
-  // one more row than the partials need: NnArgs::seed (sampled minima of the matrix-core sweep, "none" = all ones)
-  RKH_TRY(q.d_part_idx.alloc(uint64_t(p->part_blocks + 1) * b_max));
-  RKH_HIP(hipMemset(q.d_part_idx.get() + uint64_t(p->part_blocks) * b_max, 0xFF, uint64_t(b_max) * sizeof(uint32_t)));
-  if (p->profile_nn) RKH_TRY(q.d_round_n.alloc(2 * rkh_planner::kProfMax));
-  if (p->nn_mirror) {
-    RKH_TRY(q.d_mirror.alloc(nn1_mirror_bytes(q.capacity)));
-    RKH_TRY(launch_mirror_fill(p->stream, q.d_mirror.get(), q.capacity));
-    const size_t query_bytes = nn1_mirror_query_bytes() * b_max, cand_bytes = query_bytes + 256;
-    RKH_TRY(q.d_cand.alloc(cand_bytes));
-    RKH_HIP(hipMemsetAsync(q.d_cand.get(), 0, cand_bytes, p->stream));
-    q.dx_max_bits = reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand.get()) + query_bytes);
-  }
-  // root vertex = query start (create_root, rrt_path_planner.tpp:131-133)
-  std::vector<double> row(DP, 0.0);
-  for (int d = 0; d < D; ++d) row[d] = q.prm.start[d];
-  RKH_HIP(hipMemcpy(q.d_tree.get(), row.data(), DP * sizeof(double), hipMemcpyHostToDevice));
-  if (p->nn_mirror) RKH_TRY(launch_mirror_build(p->stream, q.d_mirror.get(), q.d_tree.get(), 1, D, DP, q.dx_max_bits));
-  const uint32_t no_parent = 0xFFFFFFFFu;
-  RKH_HIP(hipMemcpy(q.d_parent.get(), &no_parent, sizeof(uint32_t), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(q.d_goal.get(), q.prm.goal, D * sizeof(double), hipMemcpyHostToDevice));
-  PlannerState& s0 = q.h_state;
-  std::memset(&s0, 0, sizeof(s0));
-  s0.n = 1;
-  s0.n_before = 1;
-  s0.probed_n = 1;
-  s0.max_total = uint32_t(max_total);
-  s0.b_max = b_max;
-  s0.b_min = p->b_min;
-  s0.batch_factor = p->batch_factor;
-  return RKH_OK;
-}
-
-// 6. The five device tables, from the problems as they now stand.
-rkh_status upload_tables(rkh_planner* p) {
-  const uint32_t P = p->P;
-  std::vector<PlannerState> hs(P);
-  std::vector<ProblemDev> hp(P);
-  std::vector<NnArgs> hn(P);
-  std::vector<EdgeIO> hio(P), hgp(P);
-  for (uint32_t i = 0; i < P; ++i) {
-    hs[i] = p->prob[i].h_state;
+  PlannerState* hs = reinterpret_cast<PlannerState*>(image(SR_STATES));
+  ProblemDev* hp = reinterpret_cast<ProblemDev*>(image(SR_PROBS));
+  NnArgs* hn = reinterpret_cast<NnArgs*>(image(SR_NN_ARGS));
+  EdgeIO* hio = reinterpret_cast<EdgeIO*>(image(SR_IO_STEER));
+  EdgeIO* hgp = reinterpret_cast<EdgeIO*>(image(SR_IO_PROBE));
+  ProblemInit* hi = reinterpret_cast<ProblemInit*>(image(SR_INIT_TAB));
+  for (uint32_t i = 0; i < p->P; ++i) {
+    Problem& q = p->prob[i];
+    PlannerState& s0 = q.h_state;
+    std::memset(&s0, 0, sizeof(s0));
+    s0.n = 1;  // root vertex = query start (create_root, rrt_path_planner.tpp:131-133)
+    s0.n_before = 1;
+    s0.probed_n = 1;
+    s0.max_total = uint32_t(q.prm.max_vertices) + 1;
+    s0.b_max = p->b_max;
+    s0.b_min = p->b_min;
+    s0.batch_factor = p->batch_factor;
+    hs[i] = s0;
     hp[i] = problem_dev(p, i);
     hn[i] = nn_args(p, i);
     hio[i] = steer_io(p, i);
     hgp[i] = probe_io(p, i);
+    ProblemInit& pi = hi[i];
+    pi.mt = q.d_mt;
+    pi.tree = q.d_tree;
+    pi.parent = q.d_parent;
+    pi.goal = q.d_goal;
+    pi.seed_row = q.d_part_idx + uint64_t(p->part_blocks) * p->b_max;
+    pi.cand = static_cast<uint32_t*>(q.d_cand);
+    pi.mirror = static_cast<uint4*>(q.d_mirror);
+    pi.dx_max_bits = q.dx_max_bits;
+    pi.mirror_frags = q.d_mirror ? nn1_mirror_bytes(q.capacity) / sizeof(uint4) : 0;
+    pi.seed = uint32_t(q.prm.seed);
+    for (int d = 0; d < p->D; ++d) {
+      pi.start[d] = q.prm.start[d];
+      pi.goal_x[d] = q.prm.goal[d];
+    }
   }
-  RKH_HIP(hipMemcpy(p->d_states.get(), hs.data(), P * sizeof(PlannerState), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_probs.get(), hp.data(), P * sizeof(ProblemDev), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_nn_args.get(), hn.data(), P * sizeof(NnArgs), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_io_steer.get(), hio.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(p->d_io_probe.get(), hgp.data(), P * sizeof(EdgeIO), hipMemcpyHostToDevice));
+}
+
+// 6. One copy for the upload ranges, then the init pass over all problems (mirror_fill_all_kernel, planner_init_kernel).
+// Returns with the stream idle: an error of the pass is create's error.
+rkh_status init_device(rkh_planner* p) {
+  const ArenaLayout& L = p->layout;
+  RKH_HIP(hipMemcpyAsync(p->arena.get(), p->h_block.get(), L.upload_bytes, hipMemcpyHostToDevice, p->stream));
+  const ProblemInit* d_init = p->arena.at<ProblemInit>(L.shared[SR_INIT_TAB]);
+  if (p->nn_mirror) {
+    const uint64_t max_frags = nn1_mirror_bytes(p->max_capacity) / sizeof(uint4);
+    const uint32_t gx = uint32_t(std::min<uint64_t>(std::max<uint64_t>((max_frags + 1023) / 1024, 1), 65535));
+    hipLaunchKernelGGL(mirror_fill_all_kernel, dim3(gx, p->P), dim3(256), 0, p->stream, d_init);
+  }
+  const uint32_t cand_words = p->nn_mirror ? uint32_t((nn1_mirror_query_bytes() * p->b_max + 256) / sizeof(uint32_t)) : 0u;
+  hipLaunchKernelGGL(planner_init_kernel, dim3(p->P), dim3(256), 0, p->stream, d_init, p->D, p->DP, p->b_max, cand_words);
+  RKH_HIP(hipGetLastError());
+  RKH_HIP(hipStreamSynchronize(p->stream));
   return RKH_OK;
 }
 
@@ -1138,23 +1270,24 @@ rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* space, c
   RKH_TRY(check_create_args(scene, space, qspace, prms, n_problems, out));
   std::unique_ptr<rkh_planner> p(new rkh_planner());  // the caller's only once the last step has succeeded
   p->scene = scene;
+  p->ctx = scene->ctx;
   p->n_dof = scene->host.n_dof;
   p->P = n_problems;
   RKH_TRY(setup_space(p.get(), space, qspace, prms));
   RKH_HIP(hipSetDevice(scene->ctx->device));  // (before the tuning: its occupancy query acts on the current device)
   tune_planner(p.get(), prms);
-  RKH_TRY(alloc_planner_buffers(p.get()));
   p->prob.resize(n_problems);
   for (uint32_t i = 0; i < n_problems; ++i) {
     Problem& q = p->prob[i];
     q.prm = prms[i];
-    q.capacity = (uint64_t(prms[i].max_vertices) + 1 + 255) / 256 * 256;  // whole 256-row tiles (the NN sweeps)
+    q.capacity = planner_capacity_rows(prms[i].max_vertices);
     p->max_capacity = std::max(p->max_capacity, q.capacity);
   }
   p->part_blocks = nn1_partial_blocks(p->D, p->max_capacity, p->b_max, n_problems, p->coord_bound);
   p->n_ub.assign(n_problems, 1);
-  for (Problem& q : p->prob) RKH_TRY(create_problem(p.get(), q));
-  RKH_TRY(upload_tables(p.get()));
+  RKH_TRY(alloc_planner_buffers(p.get()));
+  fill_upload_image(p.get());
+  RKH_TRY(init_device(p.get()));
   *out = p.release();
   return RKH_OK;
 }
@@ -1165,11 +1298,9 @@ rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* space, c
 // committed vertices.
 rkh_status read_round_results(rkh_planner* p) {
   RKH_TRY(read_states(p));
-  int flag = 0;
-  int* const d_err = p->scene->d_err.get();
-  RKH_HIP(hipMemcpy(&flag, d_err, sizeof(int), hipMemcpyDeviceToHost));
+  const int flag = *p->h_err;
   if (flag != 0) {
-    RKH_HIP(hipMemset(d_err, 0, sizeof(int)));
+    RKH_HIP(hipMemset(p->scene->d_err.get(), 0, sizeof(int)));
     set_error("planner: mass matrix is singular (Cholesky pivot < 1e-8)");
     return rkh_status(flag);
   }
@@ -1205,21 +1336,17 @@ rkh_status gather_goal_probes(rkh_planner* p, std::vector<uint64_t>& gd_off, std
   }
   if (total > p->h_gd.size()) RKH_TRY(p->h_gd.alloc(total + total / 2 + 1024));
   if (!total) return RKH_OK;
-  if (!p->d_gd_tab) {
-    RKH_TRY(p->h_gd_tab.alloc(p->P));
-    RKH_TRY(p->d_gd_tab.alloc(p->P));
-  }
   if (total > p->d_gd.size()) RKH_TRY(p->d_gd.alloc(total + total / 2 + 1024));
   uint32_t n_seg = 0;
   for (uint32_t i = 0; i < p->P; ++i)
     if (gd_cnt[i]) {
-      GoalSeg& g = p->h_gd_tab.get()[n_seg++];
-      g.src = p->prob[i].d_goal_dist.get() + p->prob[i].goal_checked;
+      GoalSeg& g = p->h_gd_tab[n_seg++];
+      g.src = p->prob[i].d_goal_dist + p->prob[i].goal_checked;
       g.dst_off = gd_off[i];
       g.count = gd_cnt[i];
     }
-  RKH_HIP(hipMemcpyAsync(p->d_gd_tab.get(), p->h_gd_tab.get(), n_seg * sizeof(GoalSeg), hipMemcpyHostToDevice, p->stream));
-  hipLaunchKernelGGL(gather_goal_dist_kernel, dim3(n_seg), dim3(256), 0, p->stream, p->d_gd_tab.get(), p->d_gd.get());
+  RKH_HIP(hipMemcpyAsync(p->d_gd_tab, p->h_gd_tab, n_seg * sizeof(GoalSeg), hipMemcpyHostToDevice, p->stream));
+  hipLaunchKernelGGL(gather_goal_dist_kernel, dim3(n_seg), dim3(256), 0, p->stream, p->d_gd_tab, p->d_gd.get());
   RKH_HIP(hipGetLastError());
   RKH_HIP(hipMemcpyAsync(p->h_gd.get(), p->d_gd.get(), total * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   RKH_HIP(hipStreamSynchronize(p->stream));
@@ -1240,8 +1367,8 @@ rkh_status register_solutions(rkh_planner* p, uint32_t i, const double* gd, uint
     if (pos.empty()) {
       pos.resize(uint64_t(hs.n) * p->DP);
       par.resize(hs.n);
-      RKH_HIP(hipMemcpy(pos.data(), q.d_tree.get(), pos.size() * sizeof(double), hipMemcpyDeviceToHost));
-      RKH_HIP(hipMemcpy(par.data(), q.d_parent.get(), par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(pos.data(), q.d_tree, pos.size() * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(par.data(), q.d_parent, par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     double total = gd[k];
     uint64_t v = first + k + 1;
@@ -1264,10 +1391,10 @@ rkh_status register_solutions(rkh_planner* p, uint32_t i, const double* gd, uint
         q.truncated = true;
         q.final_n = first + k + 2;
         uint32_t smp = 0;
-        RKH_HIP(hipMemcpy(&smp, q.d_node_sample.get() + (first + k + 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
+        RKH_HIP(hipMemcpy(&smp, q.d_node_sample + (first + k + 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
         q.final_iterations = uint64_t(smp) + 1;
         const uint32_t one = 1;  // freeze the problem on the device as well
-        RKH_HIP(hipMemcpy(&p->d_states.get()[i].done, &one, sizeof(uint32_t), hipMemcpyHostToDevice));
+        RKH_HIP(hipMemcpy(&p->d_states[i].done, &one, sizeof(uint32_t), hipMemcpyHostToDevice));
         break;
       }
     }
@@ -1320,7 +1447,7 @@ rkh_status rkh_planner_nn_profile(rkh_planner* p, double* total_ms, uint64_t* to
   std::vector<uint64_t> rows(p->prof_rounds, 0);
   std::vector<uint32_t> rn(p->prof_rounds);
   for (Problem& q : p->prob) {
-    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n.get(), rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n, rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < p->prof_rounds; ++r) rows[r] += rn[r];
   }
   for (uint32_t r = 0; r < p->prof_rounds; ++r) {
@@ -1341,8 +1468,8 @@ rkh_status rkh_planner_nn_pairs(rkh_planner* p, uint64_t* pairs) {
   RKH_HIP(hipStreamSynchronize(p->stream));
   std::vector<uint32_t> rn(p->prof_rounds), rb(p->prof_rounds);
   for (Problem& q : p->prob) {
-    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n.get(), rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    RKH_HIP(hipMemcpy(rb.data(), q.d_round_n.get() + rkh_planner::kProfMax, rb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rn.data(), q.d_round_n, rn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RKH_HIP(hipMemcpy(rb.data(), q.d_round_n + rkh_planner::kProfMax, rb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < p->prof_rounds; ++r) *pairs += uint64_t(rn[r]) * rb[r];
   }
   return RKH_OK;
@@ -1369,8 +1496,14 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps) {
   if (!p->d_steps_exec) return RKH_OK;
   RKH_HIP(hipStreamSynchronize(p->stream));
   unsigned long long v = 0;
-  RKH_HIP(hipMemcpy(&v, p->d_steps_exec.get(), sizeof(v), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(&v, p->d_steps_exec, sizeof(v), hipMemcpyDeviceToHost));
   *executed_steps = v;
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_planner_sample_cap(rkh_planner* p, uint32_t problem, uint64_t* samples) {
+  if (!p || problem >= p->P || !samples) return RKH_ERR_BAD_ARG;
+  *samples = p->prob[problem].sample_cap;
   return RKH_OK;
 }
 
@@ -1400,7 +1533,7 @@ rkh_status rkh_planner_sync(rkh_planner* p, rkh_planner_stats* stats) {
     }
     if (hs.done == 2 && q.samples_ready < q.sample_cap) {  // sample stream ran dry mid-enqueue: refill and carry on
       hs.done = 0;
-      RKH_HIP(hipMemcpy(&p->d_states.get()[i].done, &hs.done, sizeof(uint32_t), hipMemcpyHostToDevice));
+      RKH_HIP(hipMemcpy(&p->d_states[i].done, &hs.done, sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (gd_cnt[i]) RKH_TRY(register_solutions(p, i, p->h_gd.get() + gd_off[i], gd_cnt[i]));
     if (stats) {
@@ -1430,7 +1563,7 @@ rkh_status rkh_planner_get_solution(rkh_planner* p, uint32_t problem, uint32_t* 
   if (q.best_vertex == 0xFFFFFFFFu) return RKH_OK;  // no solution registered
   RKH_HIP(hipStreamSynchronize(p->stream));
   std::vector<uint32_t> par(size_t(q.best_vertex) + 1);
-  RKH_HIP(hipMemcpy(par.data(), q.d_parent.get(), par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  RKH_HIP(hipMemcpy(par.data(), q.d_parent, par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<uint32_t> rev;
   for (uint32_t v = q.best_vertex; v != 0xFFFFFFFFu; v = par[v]) rev.push_back(v);
   *n_path = uint32_t(rev.size());
@@ -1477,17 +1610,17 @@ rkh_status rkh_planner_get_tree(rkh_planner* p, uint32_t problem, double* pos, u
   const uint64_t it = q.truncated ? q.final_iterations : q.h_state.s0;
   if (pos) {
     if (p->DP == p->D) {
-      RKH_HIP(hipMemcpy(pos, q.d_tree.get(), n * p->D * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(pos, q.d_tree, n * p->D * sizeof(double), hipMemcpyDeviceToHost));
     } else {
       std::vector<double> tmp(n * p->DP);
-      RKH_HIP(hipMemcpy(tmp.data(), q.d_tree.get(), tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+      RKH_HIP(hipMemcpy(tmp.data(), q.d_tree, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
       for (uint64_t i = 0; i < n; ++i) std::memcpy(pos + i * p->D, &tmp[i * p->DP], p->D * sizeof(double));
     }
   }
-  if (parent) RKH_HIP(hipMemcpy(parent, q.d_parent.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (nn_seq && it) RKH_HIP(hipMemcpy(nn_seq, q.d_nn_seq.get(), it * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (accept && it) RKH_HIP(hipMemcpy(accept, q.d_accept_log.get(), it, hipMemcpyDeviceToHost));
-  if (goal_dist && n > 1) RKH_HIP(hipMemcpy(goal_dist, q.d_goal_dist.get(), (n - 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (parent) RKH_HIP(hipMemcpy(parent, q.d_parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (nn_seq && it) RKH_HIP(hipMemcpy(nn_seq, q.d_nn_seq, it * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (accept && it) RKH_HIP(hipMemcpy(accept, q.d_accept_log, it, hipMemcpyDeviceToHost));
+  if (goal_dist && n > 1) RKH_HIP(hipMemcpy(goal_dist, q.d_goal_dist, (n - 1) * sizeof(double), hipMemcpyDeviceToHost));
   return RKH_OK;
 }
 

@@ -13,6 +13,70 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 int nn_padded_dims(int D);
 const char* nn_last_kernel_name();
+
+// ---- the arenas a context keeps (rkh_internal.h) ------------------------------------------------------------------------
+// The live contexts: a planner that outlives its context must not hand memory to it, and an allocation that runs out of
+// memory anywhere in the library frees what every context has parked.
+static std::mutex g_ctx_mutex;
+static std::vector<rkh_ctx*> g_ctx_live;
+static bool ctx_is_live(const rkh_ctx* ctx) { return std::find(g_ctx_live.begin(), g_ctx_live.end(), ctx) != g_ctx_live.end(); }
+
+// (the arenas are freed outside the lock: hipFree waits for the device)
+static size_t free_arenas(std::vector<DeviceArena>& arenas) {
+  size_t bytes = 0;
+  for (DeviceArena& a : arenas) bytes += a.size();
+  arenas.clear();
+  return bytes;
+}
+
+size_t release_cached_memory() {
+  std::vector<DeviceArena> gone;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    for (rkh_ctx* c : g_ctx_live) {
+      for (DeviceArena& a : c->arena_cache) gone.push_back(std::move(a));
+      c->arena_cache.clear();
+    }
+  }
+  return free_arenas(gone);
+}
+
+rkh_status ctx_take_arena(rkh_ctx* ctx, size_t bytes, bool cached, DeviceArena* out) {
+  if (cached) {
+    std::vector<DeviceArena> gone;
+    {
+      std::lock_guard<std::mutex> lock(g_ctx_mutex);
+      std::vector<DeviceArena>& cache = ctx->arena_cache;
+      size_t best = cache.size();
+      for (size_t k = 0; k < cache.size(); ++k)
+        if (cache[k].size() >= bytes && (best == cache.size() || cache[k].size() < cache[best].size())) best = k;
+      if (best < cache.size()) {
+        *out = std::move(cache[best]);
+        cache.erase(cache.begin() + best);
+        return RKH_OK;
+      }
+      gone.swap(cache);
+    }
+    free_arenas(gone);
+  }
+  return out->alloc(bytes);
+}
+
+void ctx_give_arena(rkh_ctx* ctx, DeviceArena&& arena) {
+  DeviceArena drop = std::move(arena);  // freed at the end of this call unless the cache takes it
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  if (!drop || !ctx_is_live(ctx)) return;
+  std::vector<DeviceArena>& cache = ctx->arena_cache;
+  if (cache.size() >= kArenaCacheSlots) {  // full: the smallest one goes
+    size_t least = 0;
+    for (size_t k = 1; k < cache.size(); ++k)
+      if (cache[k].size() < cache[least].size()) least = k;
+    if (cache[least].size() >= drop.size()) return;
+    std::swap(cache[least], drop);
+    return;
+  }
+  cache.push_back(std::move(drop));
+}
 }  // namespace rkh
 
 using namespace rkh;
@@ -55,13 +119,31 @@ rkh_status rkh_ctx_create(int device, rkh_ctx** out) {
   rkh_ctx* c = new rkh_ctx();
   c->device = device;
   RKH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    g_ctx_live.push_back(c);
+  }
   *out = c;
   return RKH_OK;
 }
 rkh_status rkh_ctx_destroy(rkh_ctx* ctx) {
   if (!ctx) return RKH_OK;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    g_ctx_live.erase(std::remove(g_ctx_live.begin(), g_ctx_live.end(), ctx), g_ctx_live.end());
+  }
   hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // (frees the arenas it kept)
+  return RKH_OK;
+}
+rkh_status rkh_ctx_release_cached_memory(rkh_ctx* ctx) {
+  if (!ctx) return RKH_ERR_BAD_ARG;
+  std::vector<DeviceArena> gone;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    gone.swap(ctx->arena_cache);
+  }
+  free_arenas(gone);
   return RKH_OK;
 }
 rkh_status rkh_ctx_synchronize(rkh_ctx* ctx) {

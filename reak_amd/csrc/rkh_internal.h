@@ -236,7 +236,20 @@ struct PairDev {
 struct rkh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  // Arenas of destroyed batch RRT planners, kept for the next one: creating, solving and destroying a planner over and
+  // over on one scene then maps its memory once (at 512 problems x 100 000 vertices a planner holds 26 GB).  At most
+  // kArenaCacheSlots; rkh_ctx_release_cached_memory, an allocation that runs out of memory and rkh_ctx_destroy free them.
+  std::vector<rkh::DeviceArena> arena_cache;
 };
+
+namespace rkh {
+constexpr size_t kArenaCacheSlots = 4;
+// An arena of at least `bytes`: the smallest cached one that fits, else a new one -- after the cached ones are freed, so
+// that nothing is hoarded beside a larger live slab.  cached = false: a new one, the cache untouched (RKH_ARENA_CACHE=0).
+rkh_status ctx_take_arena(rkh_ctx* ctx, size_t bytes, bool cached, DeviceArena* out);
+// The arena of a planner whose streams are idle goes back to its context, or is freed if the context is gone (or full).
+void ctx_give_arena(rkh_ctx* ctx, DeviceArena&& arena);
+}  // namespace rkh
 
 struct rkh_nn {
   rkh_ctx* ctx = nullptr;

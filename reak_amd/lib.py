@@ -75,6 +75,7 @@ def abi_sizes():
 
 EXPORTS = [
     "rkh_last_error", "rkh_version", "rkh_abi_version", "rkh_abi_check", "rkh_ctx_create", "rkh_ctx_destroy", "rkh_ctx_synchronize", "rkh_ctx_stream",
+    "rkh_ctx_release_cached_memory", "rkh_diag_planner_sample_cap",
     "rkh_nn_create", "rkh_nn_destroy", "rkh_nn_clear", "rkh_nn_size", "rkh_nn_remove", "rkh_nn_live_size", "rkh_nn_append", "rkh_nn_query1",
     "rkh_nn_queryk", "rkh_nn_query1_async", "rkh_nn_queryk_async", "rkh_nn_fill_uniform", "rkh_nn_kernel_name",
     "rkh_steer_mapping_name",
@@ -115,6 +116,7 @@ def load():
     lib.rkh_ctx_synchronize.argtypes = [vp]
     lib.rkh_ctx_stream.restype = vp
     lib.rkh_ctx_stream.argtypes = [vp]
+    lib.rkh_ctx_release_cached_memory.argtypes = [vp]
     lib.rkh_nn_create.argtypes = [vp, C.c_int, u64, C.POINTER(vp)]
     lib.rkh_nn_destroy.argtypes = [vp]
     lib.rkh_nn_clear.argtypes = [vp]
@@ -184,6 +186,7 @@ def load():
     lib.rkh_planner_nn_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.rkh_planner_steer_profile.argtypes = [vp, dp, C.POINTER(C.c_uint64)]
     lib.rkh_planner_steer_steps.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.rkh_diag_planner_sample_cap.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
     lib.rkh_diag_nn_mirror_query.argtypes = [vp, dp, C.c_uint64, C.c_int, dp, C.c_uint32, C.c_double, C.POINTER(C.c_uint32), dp]
     lib.rkh_abi_version.restype = C.c_uint32
     lib.rkh_abi_check.argtypes = [C.c_uint32] + [C.c_size_t] * 10
@@ -216,6 +219,10 @@ class Context:
     @property
     def stream(self):
         return self.lib.rkh_ctx_stream(self.h)
+
+    def release_cached_memory(self):
+        """Free the device memory of closed batch planners that the context keeps for the next one."""
+        _check(self.lib.rkh_ctx_release_cached_memory(self.h))
 
     def close(self):
         if self.h:
@@ -508,6 +515,12 @@ class RrtPlanner:
         """RK4 steps the steer kernels integrated so far (executed work, not n_steps per launched edge)."""
         n = C.c_uint64()
         _check(self.lib.rkh_planner_steer_steps(self.h, C.byref(n)))
+        return n.value
+
+    def sample_cap(self, problem=0):
+        """Samples the problem's stream buffers hold at present (they grow at a sync)."""
+        n = C.c_uint64()
+        _check(self.lib.rkh_diag_planner_sample_cap(self.h, problem, C.byref(n)))
         return n.value
 
     def tree(self, problem=0):
