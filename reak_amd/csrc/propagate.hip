@@ -181,6 +181,143 @@ __device__ __forceinline__ void stage_env(const SceneDev* __restrict__ sc, Shape
   for (int i = lane; i < n_words; i += 64) dst[i] = src[i];
 }
 
+// ---- the phases of x' = f(x,u) that its one-wave form (state_derivative) and its two-waves form (state_derivative_duo)
+// share.  `sync` orders the LDS traffic of the lanes that run the phase: a block barrier where the whole block does, a
+// wave-local fence where one wave of two does (wave_sync).
+
+// Jacobian columns, one lane per (body b, coord c <= b): get_jac_relative_to (motion_jacobians.hpp:238-251) with
+// f2 = (~F_c) * F_b (frame_3D.hpp:184-189,222-238,368-382)
+template <int N, int GL, bool PRISM>
+__device__ __forceinline__ void feval_jacobian_columns(const SceneDev* __restrict__ sc_beam, const JointLds* __restrict__ jl,
+                                                       GroupWs<N>& ws, int gl) {
+  for (int p = gl; p < N * (N + 1) / 2; p += GL) {
+    int b = 0, c = p;  // unrank p -> (b, c), c <= b
+    while (c > b) {
+      c -= b + 1;
+      ++b;
+    }
+    if (c < sc_beam->branch_first[b]) continue;  // joint c is not upstream of body b (another branch)
+    const d3 cp = ld3(ws.Epos[c]);
+    const d4 cq = ld4(ws.Equat[c]);
+    const d3 bp = ld3(ws.Lpos[b]);
+    const d4 bq = ld4(ws.Lquat[b]);
+    const m33 R = rotmat(cq);
+    const d4 iq = qinv(cq);
+    const d3 ipos = mulT(-cp, R);
+    const m33 Ri = rotmat(iq);
+    const d3 f2pos = ipos + mul(Ri, bp);
+    const d4 f2q = qmul(iq, bq);
+    const m33 Rf = rotmat(f2q);
+    const d3 axis = ld3(jl[c].axis);
+    d3 wt = mulT(axis, Rf);
+    d3 vt = mulT(cross(axis, f2pos), Rf);
+    if (PRISM && ((sc_beam->prismatic_mask >> c) & 1u)) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0
+      vt = mulT(axis, Rf);
+      wt = mk3(0, 0, 0);
+    }
+    st3(ws.Tcm[b][c], vt);
+    st3(ws.Tcm[b][c] + 3, wt);
+  }
+}
+
+// Mf = Tcm^T (Mcm Tcm), one lane per entry (i,j), summation order of mat_alg_symmetric.hpp:551-566 (Mcm*Tcm) and
+// mat_operators.hpp:104-114 (dense product); then M = mat<symmetric>(Mf).
+// (the loop is uniform -- lanes without an entry in the last pass recompute the last entry and do not store -- and the
+// v_readlane reads of the chain parameters sit outside the per-lane condition: a readlane must not pick a lane that
+// was masked off when a run-time-indexed copy of the parameter registers was made)
+template <int N, int GL, class Sync>
+__device__ __forceinline__ void feval_mass_matrix(const SceneDev* __restrict__ sc_beam, const CPack<N>& cp,
+                                                  const JointLds* __restrict__ jl, GroupWs<N>& ws, int gl, Sync sync) {
+  for (int e0 = 0; e0 < N * N; e0 += GL) {
+    const bool e_valid = e0 + gl < N * N;
+    const int e = e_valid ? e0 + gl : N * N - 1;
+    const int i = e / N, jx = e % N;
+    double s = 0.0;
+    if (i == jx) s = s + jl[i].joint_inertia;  // inertia_gen rows: Tcm = 1, Mcm = rotor inertia
+#pragma unroll
+    for (int b = 0; b < N; ++b) {
+      const int bb = b * 32;
+      const double mass = cget(cp, bb + JC_MASS);
+      const double inertia[6] = {cget(cp, bb + JC_INER), cget(cp, bb + JC_INER + 1), cget(cp, bb + JC_INER + 2),
+                                 cget(cp, bb + JC_INER + 3), cget(cp, bb + JC_INER + 4), cget(cp, bb + JC_INER + 5)};
+      const int first_b = sc_beam->branch_first[b];
+      if (b >= i && b >= jx && i >= first_b && jx >= first_b) {
+        const double* Ti = ws.Tcm[b][i];
+        const double* Tj = ws.Tcm[b][jx];
+        s = s + Ti[0] * (mass * Tj[0]);
+        s = s + Ti[1] * (mass * Tj[1]);
+        s = s + Ti[2] * (mass * Tj[2]);
+        const d3 P = sym_mul(inertia, mk3(Tj[3], Tj[4], Tj[5]));
+        s = s + Ti[3] * P.x;
+        s = s + Ti[4] * P.y;
+        s = s + Ti[5] * P.z;
+      }
+    }
+    if (e_valid) ws.Mf[i][jx] = s;
+  }
+  sync();
+  // mat<symmetric>(general): 0.5 * (M(j,i) + M(i,j)), j < i  (mat_alg_symmetric.hpp:183-187)
+  for (int e = gl; e < N * N; e += GL) {
+    const int i = e / N, jx = e % N;
+    const int lo = i < jx ? i : jx, hi = i < jx ? jx : i;
+    ws.M[i][jx] = (i == jx) ? ws.Mf[i][i] : 0.5 * (ws.Mf[lo][hi] + ws.Mf[hi][lo]);
+  }
+  sync();
+}
+
+// linsolve_Cholesky (mat_cholesky.hpp:546-554): lane i owns row i (Lrow); every L(i,j) is formed by the reference's
+// operation sequence (A(i,j), minus L(i,k) L(j,k) for k ascending, divided by L(j,j)).  The factor overwrites ws.M.
+// Returns whether a pivot was below 1e-8.
+template <int N, class Sync>
+__device__ __forceinline__ bool feval_cholesky_factor(GroupWs<N>& ws, int gl, double (&Lrow)[N], Sync sync) {
+  const int row = gl < N ? gl : N - 1;
+  bool sing = false;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    // pivot of column j, computed by every lane from row j (already final in LDS for k < j)
+    double dgl = ws.M[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) {
+      const double ljk = ws.M[j][k];
+      dgl = dgl - ljk * ljk;
+    }
+    if (dgl < 1e-8) sing = true;
+    const double ljj = sqrt(dgl);
+    double v = ws.M[row][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) v = v - Lrow[k] * ws.M[j][k];
+    v = v / ljj;
+    Lrow[j] = (row == j) ? ljj : v;
+    if (gl < N && row >= j) ws.M[row][j] = Lrow[j];
+    sync();
+  }
+  return sing;
+}
+
+// backsub_Cholesky_impl (mat_cholesky.hpp:160-178): L y = f, then L^T x = y.  f: this lane's row of the right-hand side;
+// returns its row of the solution (the rows of an edge sit in the lanes gb .. gb + N - 1 of the wave)
+template <int N>
+__device__ __forceinline__ double feval_backsub(const GroupWs<N>& ws, int gl, int gb, const double (&Lrow)[N], double f) {
+  const int row = gl < N ? gl : N - 1;
+  double diag = 1.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) diag = (row == k) ? Lrow[k] : diag;
+  double accv = f;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double yk = __shfl(accv / diag, gb + k, 64);
+    if (row == k) accv = yk;
+    else if (row > k) accv = accv - Lrow[k] * yk;
+  }
+#pragma unroll
+  for (int k = N - 1; k >= 0; --k) {
+    const double xk = __shfl(accv / diag, gb + k, 64);
+    if (row == k) accv = xk;
+    else if (row < k) accv = accv - ws.M[k][row] * xk;
+  }
+  return accv;
+}
+
 // x' = f(x,u) for the lane group's edge.  ws.x / ws.u hold the state and the input (already staged).
 // Returns dp for lane gl (< 2N); sets *singular if a Cholesky pivot is < 1e-8.
 // PRISM: the scene may hold prismatic joints (SceneDev::prismatic_mask; serial chains without a beam); false compiles the
@@ -303,36 +440,8 @@ __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const C
   __syncthreads();
   RKH_STAMP(1)
 
-  // ---- jacobian columns, one lane per (body b, coord c <= b): get_jac_relative_to
-  //      (motion_jacobians.hpp:238-251) with f2 = (~F_c) * F_b (frame_3D.hpp:184-189,222-238,368-382)
-  for (int p = gl; p < N * (N + 1) / 2; p += GL) {
-    int b = 0, c = p;  // unrank p -> (b, c), c <= b
-    while (c > b) {
-      c -= b + 1;
-      ++b;
-    }
-    if (c < sc_beam->branch_first[b]) continue;  // joint c is not upstream of body b (another branch)
-    const d3 cp = ld3(ws.Epos[c]);
-    const d4 cq = ld4(ws.Equat[c]);
-    const d3 bp = ld3(ws.Lpos[b]);
-    const d4 bq = ld4(ws.Lquat[b]);
-    const m33 R = rotmat(cq);
-    const d4 iq = qinv(cq);
-    const d3 ipos = mulT(-cp, R);
-    const m33 Ri = rotmat(iq);
-    const d3 f2pos = ipos + mul(Ri, bp);
-    const d4 f2q = qmul(iq, bq);
-    const m33 Rf = rotmat(f2q);
-    const d3 axis = ld3(jl[c].axis);
-    d3 wt = mulT(axis, Rf);
-    d3 vt = mulT(cross(axis, f2pos), Rf);
-    if (PRISM && ((sc_beam->prismatic_mask >> c) & 1u)) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0
-      vt = mulT(axis, Rf);
-      wt = mk3(0, 0, 0);
-    }
-    st3(ws.Tcm[b][c], vt);
-    st3(ws.Tcm[b][c] + 3, wt);
-  }
+  // ---- jacobian columns
+  feval_jacobian_columns<N, GL, PRISM>(sc_beam, jl, ws, gl);
 
   RKH_STAMP(2)
   // ---- tip -> base sweep (kte_map_chain::doForce in reverse op order), group-uniform
@@ -395,91 +504,16 @@ __device__ double state_derivative(const SceneDev* __restrict__ sc_beam, const C
   __syncthreads();
   RKH_STAMP(3)
 
-  // ---- Mf = Tcm^T (Mcm Tcm), one lane per entry (i,j), summation order of
-  //      mat_alg_symmetric.hpp:551-566 (Mcm*Tcm) and mat_operators.hpp:104-114 (dense product)
-  // (the loop is uniform -- lanes without an entry in the last pass recompute the last entry and do not store -- and the
-  // v_readlane reads of the chain parameters sit outside the per-lane condition: a readlane must not pick a lane that
-  // was masked off when a run-time-indexed copy of the parameter registers was made)
-  for (int e0 = 0; e0 < N * N; e0 += GL) {
-    const bool e_valid = e0 + gl < N * N;
-    const int e = e_valid ? e0 + gl : N * N - 1;
-    const int i = e / N, jx = e % N;
-    double s = 0.0;
-    if (i == jx) s = s + jl[i].joint_inertia;  // inertia_gen rows: Tcm = 1, Mcm = rotor inertia
-#pragma unroll
-    for (int b = 0; b < N; ++b) {
-      const int bb = b * 32;
-      const double mass = cget(cp, bb + JC_MASS);
-      const double inertia[6] = {cget(cp, bb + JC_INER), cget(cp, bb + JC_INER + 1), cget(cp, bb + JC_INER + 2),
-                                 cget(cp, bb + JC_INER + 3), cget(cp, bb + JC_INER + 4), cget(cp, bb + JC_INER + 5)};
-      const int first_b = sc_beam->branch_first[b];
-      if (b >= i && b >= jx && i >= first_b && jx >= first_b) {
-        const double* Ti = ws.Tcm[b][i];
-        const double* Tj = ws.Tcm[b][jx];
-        s = s + Ti[0] * (mass * Tj[0]);
-        s = s + Ti[1] * (mass * Tj[1]);
-        s = s + Ti[2] * (mass * Tj[2]);
-        const d3 P = sym_mul(inertia, mk3(Tj[3], Tj[4], Tj[5]));
-        s = s + Ti[3] * P.x;
-        s = s + Ti[4] * P.y;
-        s = s + Ti[5] * P.z;
-      }
-    }
-    if (e_valid) ws.Mf[i][jx] = s;
-  }
-  __syncthreads();
-  // mat<symmetric>(general): 0.5 * (M(j,i) + M(i,j)), j < i  (mat_alg_symmetric.hpp:183-187)
-  for (int e = gl; e < N * N; e += GL) {
-    const int i = e / N, jx = e % N;
-    const int lo = i < jx ? i : jx, hi = i < jx ? jx : i;
-    ws.M[i][jx] = (i == jx) ? ws.Mf[i][i] : 0.5 * (ws.Mf[lo][hi] + ws.Mf[hi][lo]);
-  }
-  __syncthreads();
+  // ---- Mf = Tcm^T (Mcm Tcm), M
+  feval_mass_matrix<N, GL>(sc_beam, cp, jl, ws, gl, [] { __syncthreads(); });
 
   RKH_STAMP(4)
-  // ---- linsolve_Cholesky (mat_cholesky.hpp:546-554): lane i owns row i; every L(i,j) is formed by the
-  //      reference's operation sequence (A(i,j), minus L(i,k) L(j,k) for k ascending, divided by L(j,j))
-  const int row = gl < N ? gl : N - 1;
+  // ---- linsolve_Cholesky (mat_cholesky.hpp:546-554), then backsub_Cholesky_impl (mat_cholesky.hpp:160-178)
   double Lrow[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) Lrow[k] = 0.0;
-  bool sing = false;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    // pivot of column j, computed by every lane from row j (already final in LDS for k < j)
-    double dgl = ws.M[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) {
-      const double ljk = ws.M[j][k];
-      dgl = dgl - ljk * ljk;
-    }
-    if (dgl < 1e-8) sing = true;
-    const double ljj = sqrt(dgl);
-    double v = ws.M[row][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) v = v - Lrow[k] * ws.M[j][k];
-    v = v / ljj;
-    Lrow[j] = (row == j) ? ljj : v;
-    if (gl < N && row >= j) ws.M[row][j] = Lrow[j];
-    __syncthreads();
-  }
-  // backsub_Cholesky_impl (mat_cholesky.hpp:160-178): L y = f, then L^T x = y
-  double diag = 1.0;
-#pragma unroll
-  for (int k = 0; k < N; ++k) diag = (row == k) ? Lrow[k] : diag;
-  double accv = f_mine;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const double yk = __shfl(accv / diag, gb + k, 64);
-    if (row == k) accv = yk;
-    else if (row > k) accv = accv - Lrow[k] * yk;
-  }
-#pragma unroll
-  for (int k = N - 1; k >= 0; --k) {
-    const double xk = __shfl(accv / diag, gb + k, 64);
-    if (row == k) accv = xk;
-    else if (row < k) accv = accv - ws.M[k][row] * xk;
-  }
+  const bool sing = feval_cholesky_factor<N>(ws, gl, Lrow, [] { __syncthreads(); });
+  const double accv = feval_backsub<N>(ws, gl, gb, Lrow, f_mine);
   if (sing) *singular = true;
 
   // pd[2j] = q_dot_j ; pd[2j+1] = qdd_j  (kte_nl_system.hpp:276-279)
@@ -539,7 +573,6 @@ __device__ double state_derivative_duo(const SceneDev* __restrict__ sc_beam, con
   double Lrow[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) Lrow[k] = 0.0;
-  const int row = gl < N ? gl : N - 1;
   bool sing = false;
   if (wave == 0) {
     {  // ---- pose half of the base -> tip sweep; every joint's end frames are published as soon as they are stored
@@ -571,87 +604,14 @@ __device__ double state_derivative_duo(const SceneDev* __restrict__ sc_beam, con
       }
     }
     RKH_STAMP(1)
-    // ---- jacobian columns (as in state_derivative)
-    for (int p = gl; p < N * (N + 1) / 2; p += GL) {
-      int b = 0, c = p;
-      while (c > b) {
-        c -= b + 1;
-        ++b;
-      }
-      if (c < sc_beam->branch_first[b]) continue;
-      const d3 cpos = ld3(ws.Epos[c]);
-      const d4 cq = ld4(ws.Equat[c]);
-      const d3 bp = ld3(ws.Lpos[b]);
-      const d4 bq = ld4(ws.Lquat[b]);
-      const m33 R = rotmat(cq);
-      const d4 iq = qinv(cq);
-      const d3 ipos = mulT(-cpos, R);
-      const m33 Ri = rotmat(iq);
-      const d3 f2pos = ipos + mul(Ri, bp);
-      const d4 f2q = qmul(iq, bq);
-      const m33 Rf = rotmat(f2q);
-      const d3 axis = ld3(jl[c].axis);
-      const d3 wt = mulT(axis, Rf);
-      const d3 vt = mulT(cross(axis, f2pos), Rf);
-      st3(ws.Tcm[b][c], vt);
-      st3(ws.Tcm[b][c] + 3, wt);
-    }
+    // ---- jacobian columns
+    feval_jacobian_columns<N, GL, false>(sc_beam, jl, ws, gl);
     wave_sync();
     RKH_STAMP(2)
-    // ---- Mf = Tcm^T (Mcm Tcm), M, Cholesky factor (as in state_derivative; wave-local ordering instead of barriers)
-    for (int e0 = 0; e0 < N * N; e0 += GL) {
-      const bool e_valid = e0 + gl < N * N;
-      const int e = e_valid ? e0 + gl : N * N - 1;
-      const int i = e / N, jx = e % N;
-      double sacc = 0.0;
-      if (i == jx) sacc = sacc + jl[i].joint_inertia;
-#pragma unroll
-      for (int b = 0; b < N; ++b) {
-        const int bb = b * 32;
-        const double mass = cget(cp, bb + JC_MASS);
-        const double inertia[6] = {cget(cp, bb + JC_INER), cget(cp, bb + JC_INER + 1), cget(cp, bb + JC_INER + 2),
-                                   cget(cp, bb + JC_INER + 3), cget(cp, bb + JC_INER + 4), cget(cp, bb + JC_INER + 5)};
-        const int first_b = sc_beam->branch_first[b];
-        if (b >= i && b >= jx && i >= first_b && jx >= first_b) {
-          const double* Ti = ws.Tcm[b][i];
-          const double* Tj = ws.Tcm[b][jx];
-          sacc = sacc + Ti[0] * (mass * Tj[0]);
-          sacc = sacc + Ti[1] * (mass * Tj[1]);
-          sacc = sacc + Ti[2] * (mass * Tj[2]);
-          const d3 P = sym_mul(inertia, mk3(Tj[3], Tj[4], Tj[5]));
-          sacc = sacc + Ti[3] * P.x;
-          sacc = sacc + Ti[4] * P.y;
-          sacc = sacc + Ti[5] * P.z;
-        }
-      }
-      if (e_valid) ws.Mf[i][jx] = sacc;
-    }
-    wave_sync();
-    for (int e = gl; e < N * N; e += GL) {
-      const int i = e / N, jx = e % N;
-      const int lo = i < jx ? i : jx, hi = i < jx ? jx : i;
-      ws.M[i][jx] = (i == jx) ? ws.Mf[i][i] : 0.5 * (ws.Mf[lo][hi] + ws.Mf[hi][lo]);
-    }
-    wave_sync();
+    // ---- Mf = Tcm^T (Mcm Tcm), M, Cholesky factor (wave-local ordering instead of barriers)
+    feval_mass_matrix<N, GL>(sc_beam, cp, jl, ws, gl, [] { wave_sync(); });
     RKH_STAMP(3)
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      double dgl = ws.M[j][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) {
-        const double ljk = ws.M[j][k];
-        dgl = dgl - ljk * ljk;
-      }
-      if (dgl < 1e-8) sing = true;
-      const double ljj = sqrt(dgl);
-      double v = ws.M[row][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v = v - Lrow[k] * ws.M[j][k];
-      v = v / ljj;
-      Lrow[j] = (row == j) ? ljj : v;
-      if (gl < N && row >= j) ws.M[row][j] = Lrow[j];
-      wave_sync();
-    }
+    sing = feval_cholesky_factor<N>(ws, gl, Lrow, [] { wave_sync(); });
     RKH_STAMP(4)
   } else {
     // ---- velocity / acceleration half of the base -> tip sweep.  Only the recurrences w, alpha, acc are serial: the
@@ -777,22 +737,7 @@ __device__ double state_derivative_duo(const SceneDev* __restrict__ sc_beam, con
   __syncthreads();
   RKH_STAMP(5)
   if (wave == 0) {  // backsub_Cholesky_impl (mat_cholesky.hpp:160-178): L y = f, then L^T x = y
-    double diag = 1.0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) diag = (row == k) ? Lrow[k] : diag;
-    double accv = (gl < N) ? ws.tmp[gl] : 0.0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      const double yk = __shfl(accv / diag, k, 64);
-      if (row == k) accv = yk;
-      else if (row > k) accv = accv - Lrow[k] * yk;
-    }
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-      const double xk = __shfl(accv / diag, k, 64);
-      if (row == k) accv = xk;
-      else if (row < k) accv = accv - ws.M[k][row] * xk;
-    }
+    const double accv = feval_backsub<N>(ws, gl, 0, Lrow, (gl < N) ? ws.tmp[gl] : 0.0);
     const double qdd = __shfl(accv, gl >> 1, 64);
     if (gl < D) ws.dpx[gl] = (gl & 1) ? qdd : ws.x[gl + 1];
     if (sing && lead) ws.duo_sing = 1u;
@@ -1060,10 +1005,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
   const int n_pairs = wave_args()->n_pairs;
   const uint32_t grid_a = wave_args()->grid_a;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  if (wave_args()->gate.count) {  // the planner's per-round choice between the kernel mappings
-    const uint32_t c = *wave_args()->gate.count;
-    if (c < wave_args()->gate.lo || c >= wave_args()->gate.hi) return;
-  }
+  if (steer_gate_closed(&wave_args()->gate)) return;  // the planner's per-round choice between the kernel mappings
   constexpr int G = 64 / GL;
   BlockLds<N, GL>& lds = *reinterpret_cast<BlockLds<N, GL>*>(smem_raw);
   ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayout<N, GL>::block_bytes);
@@ -1074,15 +1016,10 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
   if (wave_args()->gate.wave_base) {  // compact mapping (one edge per wave): block L of a 1-D grid takes working edge L
     const uint32_t L = blockIdx.x;
     if (L >= wave_args()->gate.wave_base[wave_args()->gate.n_segments]) return;
-    uint32_t lo = 0, hi = wave_args()->gate.n_segments;
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (wave_args()->gate.wave_base[mid] <= L) lo = mid;
-      else hi = mid;
-    }
-    problem = lo >> 1;
-    group_b = (lo & 1u) != 0u;
-    blk = L - wave_args()->gate.wave_base[lo];
+    const uint32_t seg = segment_of(wave_args()->gate.wave_base, wave_args()->gate.n_segments, L);
+    problem = seg >> 1;
+    group_b = (seg & 1u) != 0u;
+    blk = L - wave_args()->gate.wave_base[seg];
   }
   auto edge_io = [&]() -> const EdgeIO* {
     WaveArgP A = wave_args();
@@ -1104,8 +1041,8 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
   stage_chain<N>(sc, lds.joints, lds.base, lane);
   stage_env(sc, env_lds, lane);
   GroupWs<N>& ws = lds.g[g];
-  const uint32_t si = edge_io()->src_idx ? edge_io()->src_idx[ec] : ((edge_io()->d_src_first ? *edge_io()->d_src_first : 0u) + ec);
-  const uint64_t trow = edge_io()->tgt_idx ? uint64_t(edge_io()->tgt_idx[ec]) : (edge_io()->d_tgt_off ? uint64_t(*edge_io()->d_tgt_off) : 0ull) + ec;
+  const uint32_t si = edge_source_row(*edge_io(), ec);
+  const uint64_t trow = edge_target_row(*edge_io(), ec);
   const double a_d = (gl < D) ? edge_io()->src[uint64_t(si) * edge_io()->src_stride + gl] : 0.0;
   const double b_d = (gl < D) ? edge_io()->tgt[trow * edge_io()->tgt_stride + gl] : 0.0;
   const double lo = (gl < D) ? wave_args()->dyn.lower[gl] : 0.0;
@@ -1123,26 +1060,13 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
   uint32_t n_exec = 0;     // steps integrated for this edge (KernelGate::steps_exec)
   if (record && gl < D) record[(uint64_t(e) * record_stride + 0) * D + gl] = x;
 
-  // steps of this edge: the launch's schedule, or (EdgeIO::frac) the edge's own travel fraction cut with the comparison
-  // of the steer loop, current_time < fraction * (steps_per_edge * dt), current_time accumulated step by step
+  // steps of this edge: the launch's schedule, or (EdgeIO::frac) those of the edge's own travel fraction
   int n_steps = wave_args()->dyn.n_steps;
-  if (edge_io()->frac) {
-    const double T_goal = edge_io()->frac[ec] * wave_args()->dyn.full_time;
-    double current_time = 0.0;
-    n_steps = 0;
-    while (current_time < T_goal && n_steps < kMaxSteps) {
-      current_time += wave_args()->dyn.dt;
-      ++n_steps;
-    }
-  }
+  if (edge_io()->frac) n_steps = edge_step_count(edge_io()->frac[ec], wave_args()->dyn.full_time, wave_args()->dyn.dt);
   if (edge_io()->mode == EDGE_POINT) {  // is_free(target): bounds, then proximity; no propagation
     n_steps = 0;
     x = b_d;
-    bool oob = false;
-    if (gl < D) {
-      if (lo < hi) oob = (x < lo) || (x > hi);
-      else oob = (x > lo) || (x < hi);
-    }
+    const bool oob = (gl < D) && hyperbox_out(lo, hi, x);
     const unsigned long long m = __ballot(oob);
     const unsigned long long gm = (GL == 64) ? m : ((m >> gb) & ((1ull << (GL & 63)) - 1ull));
     bool free_pt = gm == 0ull;
@@ -1162,17 +1086,11 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
     // PD law, zero-order hold over the step
     if (gl < D) ws.x[gl] = x;
     __syncthreads();
-    if (gl < N) {
-      double v = wave_args()->dyn.kp * (ws.b[2 * gl] - ws.x[2 * gl]) + wave_args()->dyn.kd * (ws.b[2 * gl + 1] - ws.x[2 * gl + 1]);
-      if (v > wave_args()->dyn.u_max) v = wave_args()->dyn.u_max;
-      else if (v < -wave_args()->dyn.u_max) v = -wave_args()->dyn.u_max;
-      ws.u[gl] = v;
-    }
-    // runge_kutta4_integrate_impl (runge_kutta4_integrator_sys.hpp:53-97), time_step = dt.
-    // One call site for f(x,u): each loop iteration of the reference evaluates f four times that
-    // matter (the prime of :69 or the re-prime of :95, then :82, :86, :92); they are the stages of
-    // a rolled loop here, which keeps a single copy of the dynamics in the instruction stream.
-    // The re-prime after the last iteration is dead in the reference and is not evaluated.
+    if (gl < N)
+      ws.u[gl] = pd_input(wave_args()->dyn.kp, wave_args()->dyn.kd, wave_args()->dyn.u_max, ws.b[2 * gl], ws.x[2 * gl],
+                          ws.b[2 * gl + 1], ws.x[2 * gl + 1]);
+    // runge_kutta4_integrate_impl, time_step = dt: one call site for f(x,u), the stages of rk4_stage (steer_edge.h) in a
+    // rolled loop.  The re-prime after the last iteration is dead in the reference and is not evaluated.
     const double h = wave_args()->dyn.dt;
     double xe = x;  // end_point
     {
@@ -1185,32 +1103,15 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
         __syncthreads();
         const double dp = DUO ? state_derivative_duo<N>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], gl, wave, &sing_now)
                               : state_derivative<N, GL, kPrismatic>(sc, cp, lds.joints, lds.base, ws, lds.sink[lane], gl, gb, &sing_now);
-        const int stage = ev & 3;
-        if (stage == 0) {
-          w = xe;
-          k1 = h * dp;
-          xe = xe + 0.5 * k1;
-        } else if (stage == 1) {
-          k2 = h * dp;
-          xe = w + 0.5 * k2;
-        } else if (stage == 2) {
-          k3 = h * dp;
-          xe = w + k3;
-        } else {
-          xe = xe + ((((1.0 / 6.0) * k1 + (2.0 / 6.0) * k2) + (h / 6.0) * dp) - (2.0 / 3.0) * k3);
-        }
+        rk4_stage(ev & 3, h, dp, xe, w, k1, k2, k3);
       }
       if (sing_now && alive) {
         singular = true;
         alive = false;
       }
     }
-    // is_free(x_next): hyperbox bounds (hyperbox_topology.hpp:178-189), then proximity
-    bool oob = false;
-    if (gl < D) {
-      if (lo < hi) oob = (xe < lo) || (xe > hi);
-      else oob = (xe > lo) || (xe < hi);
-    }
+    // is_free(x_next): hyperbox bounds, then proximity
+    const bool oob = (gl < D) && hyperbox_out(lo, hi, xe);
     {
       const unsigned long long m = __ballot(oob);
       const unsigned long long gm = (GL == 64) ? m : ((m >> gb) & ((1ull << (GL & 63)) - 1ull));
@@ -1236,23 +1137,10 @@ __global__ __launch_bounds__(DUO ? 128 : 64, GL == 64 ? 1 : 2) void propagate_ke
     const double n_ar = group_norm<N>(ws, a_d - x, gl);
     const double n_ab = group_norm<N>(ws, a_d - b_d, gl);
     const double n_rb = group_norm<N>(ws, x - b_d, gl);
-    if (edge_io()->mode == EDGE_STEER_ACCEPT) {
-      // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-      const double traveled = n_ar;
-      const double best_case = edge_io()->best_case ? edge_io()->best_case[ec] : n_ab;
-      const bool ok = (!isinf(traveled)) && (traveled < 2.0 * best_case) && (traveled > edge_io()->steer_tol * best_case);
-      if (edge_valid && gl == 0 && writer) edge_io()->accept[e] = ok ? 1 : 0;
-    } else if (edge_io()->mode == EDGE_CONNECT) {
-      // planning_visitor_base::can_be_connected (planning_visitors.hpp:385-395); steer_tol carries the connection tolerance
-      const bool ok = (!isinf(n_ar)) && (n_rb < edge_io()->steer_tol * n_ar);
-      if (edge_valid && gl == 0 && writer) edge_io()->accept[e] = ok ? 1 : 0;
-    } else if (edge_io()->mode == EDGE_WALK_ACCEPT) {
-      // planning_visitor_base::random_walk (planning_visitors.hpp:418-421)
-      const bool ok = (!isinf(n_ar)) && (n_ar > edge_io()->steer_tol * edge_io()->best_case[ec]);
-      if (edge_valid && gl == 0 && writer) edge_io()->accept[e] = ok ? 1 : 0;
-    } else if (edge_io()->mode == EDGE_GOAL_PROBE) {
-      // C_free distance used by the goal probe (MEAQR_topology.hpp:995-1003)
-      if (edge_valid && gl == 0 && writer) edge_io()->goal_dist[si - 1] = (n_ab * 0.05 > n_rb) ? n_ab : INFINITY;
+    const int acc = edge_accept(edge_io()->mode, n_ar, n_ab, n_rb, edge_io()->best_case, ec, edge_io()->steer_tol, kNoWalk);
+    if (edge_valid && gl == 0 && writer) {
+      if (acc != kNoAccept) edge_io()->accept[e] = uint8_t(acc);
+      else if (edge_io()->mode == EDGE_GOAL_PROBE) edge_io()->goal_dist[si - 1] = goal_probe_steerable(n_ab, n_rb);
     }
   }
 }
@@ -1346,8 +1234,8 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
   const int lane = tid & 63, wave = tid >> 6;
   const int g = tid / GL, gl = lane % GL, gb = (lane / GL) * GL;  // group of the block, lane of the group, its base lane in the wave
   GroupWsQs<N>& ws = lds.g[g];
-  const uint32_t si = io.src_idx ? io.src_idx[e] : ((io.d_src_first ? *io.d_src_first : 0u) + e);
-  const uint64_t trow = io.tgt_idx ? uint64_t(io.tgt_idx[e]) : ((io.d_tgt_off ? uint64_t(*io.d_tgt_off) : 0ull) + e);
+  const uint32_t si = edge_source_row(io, e);
+  const uint64_t trow = edge_target_row(io, e);
   const double a_d = (gl < N) ? io.src[uint64_t(si) * io.src_stride + gl] : 0.0;
   const double b_d = (gl < N) ? io.tgt[trow * io.tgt_stride + gl] : 0.0;
   const double lo = (gl < N) ? qs.lower[gl] : 0.0;
@@ -1370,11 +1258,7 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
   if (io.mode == EDGE_POINT) {
     // is_free(target): hyperbox bounds, then proximity (manip_free_workspace.hpp:79-99,154-156); group 0 tests it
     if (gl < N) ws.x[2 * gl] = b_d * speed;
-    bool oob = false;
-    if (gl < N) {
-      if (lo < hi) oob = (b_d < lo) || (b_d > hi);
-      else oob = (b_d > lo) || (b_d < hi);
-    }
+    const bool oob = (gl < N) && hyperbox_out(lo, hi, b_d);
     const unsigned long long mo = __ballot(oob);
     const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
     __syncthreads();
@@ -1416,11 +1300,7 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
         ws.x[2 * gl] = pt * speed;
         lds.pts[g][gl] = pt;
       }
-      bool oob = false;
-      if (gl < N) {
-        if (lo < hi) oob = (pt < lo) || (pt > hi);
-        else oob = (pt > lo) || (pt < hi);
-      }
+      const bool oob = (gl < N) && hyperbox_out(lo, hi, pt);
       const unsigned long long mo = __ballot(oob);
       const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
       __syncthreads();
@@ -1468,29 +1348,13 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
     const double n_ar = norm_n(a_d - result);
     const double n_ab = dist_tot;
     const double n_rb = norm_n(result - b_d);
-    if (io.mode == EDGE_STEER_ACCEPT || io.mode == EDGE_STEER_BOTH) {
-      // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-      const double best_case = io.best_case ? io.best_case[e] : n_ab;
-      const bool ok = (!isinf(n_ar)) && (n_ar < 2.0 * best_case) && (n_ar > io.steer_tol * best_case);
-      // EDGE_STEER_BOTH: bit 1 = the walk completed.  steer_back_to_position(target, source) walks the same points
-      // (move_position_back_to, interpolated_topologies.hpp:165-191) and returns the same point unless the walk
-      // completes, where it returns the source itself (:185-186): its verdict is bit 0 && !bit 1.
-      if (tid == 0) io.accept[e] = (ok ? 1 : 0) | ((io.mode == EDGE_STEER_BOTH && completed_walk) ? 2 : 0);
-    } else if (io.mode == EDGE_GOAL_PROBE) {
-      // interp_topo_get_distance_pred (interpolated_topologies.hpp:193-199)
-      if (tid == 0) io.goal_dist[si - 1] = (n_rb < DBL_EPSILON) ? n_ab : INFINITY;
-    } else if (io.mode == EDGE_CONNECT) {
-      // planning_visitor_base::can_be_connected (planning_visitors.hpp:385-395)
-      const bool ok = (!isinf(n_ar)) && (n_rb < io.steer_tol * n_ar);  // steer_tol carries the connection tolerance
-      if (tid == 0) io.accept[e] = ok ? 1 : 0;
-    } else if (io.mode == EDGE_WALK_ACCEPT) {
-      // planning_visitor_base::random_walk (planning_visitors.hpp:418-421)
-      const bool ok = (!isinf(n_ar)) && (n_ar > io.steer_tol * io.best_case[e]);
-      if (tid == 0) io.accept[e] = ok ? 1 : 0;
+    const int acc = edge_accept(io.mode, n_ar, n_ab, n_rb, io.best_case, e, io.steer_tol, completed_walk ? 1 : 0);
+    if (tid == 0) {
+      if (acc != kNoAccept) io.accept[e] = uint8_t(acc);
+      else if (io.mode == EDGE_GOAL_PROBE) io.goal_dist[si - 1] = goal_probe_interpolated(n_ab, n_rb);
     }
   }
 }
-
 
 template <int N, int W>
 __device__ __forceinline__ const PairDev* edge_check_stage(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
@@ -1606,12 +1470,8 @@ __global__ __launch_bounds__(256) void edge_points_kernel(EdgeWalkArgs) {
   }
   const int mode = RKH_IO(mode);
   if (tid < N) {
-    const uint32_t* src_idx = RKH_IO(src_idx);
-    const uint32_t* d_src_first = RKH_IO(d_src_first);
-    const uint32_t* tgt_idx = RKH_IO(tgt_idx);
-    const uint32_t* d_tgt_off = RKH_IO(d_tgt_off);
-    const uint32_t si = src_idx ? src_idx[e] : ((d_src_first ? *d_src_first : 0u) + e);
-    const uint64_t trow = tgt_idx ? uint64_t(tgt_idx[e]) : ((d_tgt_off ? uint64_t(*d_tgt_off) : 0ull) + e);
+    const uint32_t si = edge_source_row(RKH_IO(src_idx), RKH_IO(d_src_first), e);
+    const uint64_t trow = edge_target_row(RKH_IO(tgt_idx), RKH_IO(d_tgt_off), e);
     lds.a[tid] = RKH_IO(src)[uint64_t(si) * RKH_IO(src_stride) + tid];
     lds.b[tid] = RKH_IO(tgt)[trow * RKH_IO(tgt_stride) + tid];
   }
@@ -1761,11 +1621,7 @@ __global__ __launch_bounds__(256) void edge_points_kernel(EdgeWalkArgs) {
   auto out_of_bounds = [&](int t) {
     bool oob = false;
 #pragma unroll
-    for (int d = 0; d < N; ++d) {
-      const double pt = lds.pts[d][t], lo = qs.lower[d], hi = qs.upper[d];
-      if (lo < hi) oob = oob || (pt < lo) || (pt > hi);
-      else oob = oob || (pt > lo) || (pt < hi);
-    }
+    for (int d = 0; d < N; ++d) oob |= hyperbox_out(qs.lower[d], qs.upper[d], lds.pts[d][t]);
     return oob;
   };
 
@@ -1854,29 +1710,11 @@ __global__ __launch_bounds__(256) void edge_points_kernel(EdgeWalkArgs) {
     const double n_ar = norm_n(a_d - result);
     const double n_ab = dist_tot;
     const double n_rb = norm_n(result - b_d);
-    const double steer_tol = RKH_IO(steer_tol);
-    if (mode == EDGE_STEER_ACCEPT || mode == EDGE_STEER_BOTH) {
-      // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-      const double best_case = RKH_IO(best_case) ? RKH_IO(best_case)[e] : n_ab;
-      const bool ok = (!isinf(n_ar)) && (n_ar < 2.0 * best_case) && (n_ar > steer_tol * best_case);
-      // EDGE_STEER_BOTH: bit 1 = the walk completed (see edge_check_kernel)
-      if (tid == 0) RKH_IO(accept)[e] = (ok ? 1 : 0) | ((mode == EDGE_STEER_BOTH && completed_walk) ? 2 : 0);
-    } else if (mode == EDGE_GOAL_PROBE) {
-      // interp_topo_get_distance_pred (interpolated_topologies.hpp:193-199)
-      if (tid == 0) {
-        const uint32_t* src_idx = RKH_IO(src_idx);
-        const uint32_t* d_src_first = RKH_IO(d_src_first);
-        const uint32_t si = src_idx ? src_idx[e] : ((d_src_first ? *d_src_first : 0u) + e);
-        RKH_IO(goal_dist)[si - 1] = (n_rb < DBL_EPSILON) ? n_ab : INFINITY;
-      }
-    } else if (mode == EDGE_CONNECT) {
-      // planning_visitor_base::can_be_connected (planning_visitors.hpp:385-395); steer_tol carries the connection tolerance
-      const bool ok = (!isinf(n_ar)) && (n_rb < steer_tol * n_ar);
-      if (tid == 0) RKH_IO(accept)[e] = ok ? 1 : 0;
-    } else if (mode == EDGE_WALK_ACCEPT) {
-      // planning_visitor_base::random_walk (planning_visitors.hpp:418-421)
-      const bool ok = (!isinf(n_ar)) && (n_ar > steer_tol * RKH_IO(best_case)[e]);
-      if (tid == 0) RKH_IO(accept)[e] = ok ? 1 : 0;
+    const int acc = edge_accept(mode, n_ar, n_ab, n_rb, RKH_IO(best_case), e, RKH_IO(steer_tol), completed_walk ? 1 : 0);
+    if (tid == 0) {
+      if (acc != kNoAccept) RKH_IO(accept)[e] = uint8_t(acc);
+      else if (mode == EDGE_GOAL_PROBE)
+        RKH_IO(goal_dist)[edge_source_row(RKH_IO(src_idx), RKH_IO(d_src_first), e) - 1] = goal_probe_interpolated(n_ab, n_rb);
     }
   }
 #undef RKH_IO

@@ -792,6 +792,16 @@ RKH_DI PairArgP pair_args() {
   return a;
 }
 
+// The joint axes of the chain in LDS (PairLds::axis), for the Jacobian columns; ends on a block barrier
+template <int N>
+RKH_DI void pair_stage_axes(ScenePtr sc, PairLds<N>& lds) {
+  if (threadIdx.x < 3 * (N + 1)) {
+    const int jj = threadIdx.x / 3;
+    lds.axis[jj][threadIdx.x % 3] = sc->joints[jj < N ? jj : N - 1].axis[threadIdx.x % 3];
+  }
+  __syncthreads();
+}
+
 template <int N>
 __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
   __shared__ PairLds<N> lds;
@@ -831,11 +841,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     }
   }
   const ScenePtr sc = (ScenePtr)pair_args()->sc;
-  if (threadIdx.x < 3 * (N + 1)) {
-    const int jj = threadIdx.x / 3;
-    lds.axis[jj][threadIdx.x % 3] = sc->joints[jj < N ? jj : N - 1].axis[threadIdx.x % 3];
-  }
-  __syncthreads();
+  pair_stage_axes<N>((ScenePtr)sc, lds);
   // the launch's EdgeIO record: an entry of a device table, or one of the two by-value copies in the kernarg segment
   auto edge_io = [&]() -> const EdgeIO* {
     PairArgP A = pair_args();
@@ -1049,12 +1055,10 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     const double n_ar = sqrt(s_ar), n_ab = sqrt(s_ab), n_rb = sqrt(s_rb);
     if (io->mode == EDGE_STEER_ACCEPT) {
       // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-      const double best_case = io->best_case ? io->best_case[ec] : n_ab;
-      const bool ok = (!isinf(n_ar)) && (n_ar < 2.0 * best_case) && (n_ar > io->steer_tol * best_case);
-      io->accept[ec] = ok ? 1 : 0;
+      io->accept[ec] = uint8_t(edge_accept(EDGE_STEER_ACCEPT, n_ar, n_ab, n_rb, io->best_case, ec, io->steer_tol, kNoWalk));
     } else {
       // C_free distance used by the goal probe (MEAQR_topology.hpp:995-1003)
-      io->goal_dist[si - 1] = (n_ab * 0.05 > n_rb) ? n_ab : INFINITY;
+      io->goal_dist[si - 1] = goal_probe_steerable(n_ab, n_rb);
     }
   }
 }
@@ -1127,11 +1131,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   const uint32_t n_chunks = chunks_front + (n_back + uint32_t(kPairEdges) - 1u) / uint32_t(kPairEdges);
   if (blockIdx.x >= n_chunks) return;
   const ScenePtr sc = (ScenePtr)pair_step_args()->sc;
-  if (threadIdx.x < 3 * (N + 1)) {
-    const int jj = threadIdx.x / 3;
-    lds.axis[jj][threadIdx.x % 3] = sc->joints[jj < N ? jj : N - 1].axis[threadIdx.x % 3];
-  }
-  __syncthreads();
+  pair_stage_axes<N>((ScenePtr)sc, lds);
   PairWsRef ws;
   ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(pair_step_args()->ws_all + uint64_t(blockIdx.x) * uint64_t(W_::SLOTS * 64), 0,
                                               W_::SLOTS * 512, 0x00020000);
@@ -1366,12 +1366,10 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
           const double n_ar = sqrt(s_ar), n_ab = sqrt(s_ab), n_rb = sqrt(s_rb);
           if (io->mode == EDGE_STEER_ACCEPT) {
             // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-            const double best_case = io->best_case ? io->best_case[ec] : n_ab;
-            const bool ok = (!isinf(n_ar)) && (n_ar < 2.0 * best_case) && (n_ar > io->steer_tol * best_case);
-            io->accept[ec] = ok ? 1 : 0;
+            io->accept[ec] = uint8_t(edge_accept(EDGE_STEER_ACCEPT, n_ar, n_ab, n_rb, io->best_case, ec, io->steer_tol, kNoWalk));
           } else {
             // C_free distance used by the goal probe (MEAQR_topology.hpp:995-1003)
-            io->goal_dist[si - 1] = (n_ab * 0.05 > n_rb) ? n_ab : INFINITY;
+            io->goal_dist[si - 1] = goal_probe_steerable(n_ab, n_rb);
           }
         }
       }
@@ -1434,11 +1432,7 @@ __global__ __launch_bounds__(64, 2) void pair_cycles_kernel(const SceneDev* __re
                                                              unsigned long long* __restrict__ out,
                                                              double* __restrict__ sink_out) {
   __shared__ PairLds<N> lds;
-  if (threadIdx.x < 3 * (N + 1)) {
-    const int jj = threadIdx.x / 3;
-    lds.axis[jj][threadIdx.x % 3] = sc->joints[jj < N ? jj : N - 1].axis[threadIdx.x % 3];
-  }
-  __syncthreads();
+  pair_stage_axes<N>((ScenePtr)sc, lds);
   typedef PairLayout<N> L_;
   const int lane = threadIdx.x, h = lane & 1, el = lane >> 1;
   uint32_t e = blockIdx.x * kPairEdges + el;
@@ -1475,11 +1469,7 @@ __global__ __launch_bounds__(64, 2) void pair_counts_kernel(const SceneDev* __re
                                                              uint32_t B, unsigned long long* __restrict__ out,
                                                              float* __restrict__ clear_out) {
   __shared__ PairLds<N> lds;
-  if (threadIdx.x < 3 * (N + 1)) {
-    const int jj = threadIdx.x / 3;
-    lds.axis[jj][threadIdx.x % 3] = sc->joints[jj < N ? jj : N - 1].axis[threadIdx.x % 3];
-  }
-  __syncthreads();
+  pair_stage_axes<N>((ScenePtr)sc, lds);
   typedef PairLayout<N> L_;
   const int lane = threadIdx.x, h = lane & 1, el = lane >> 1;
   const uint32_t e = blockIdx.x * kPairEdges + el;

@@ -196,14 +196,8 @@ template <int N>
 RKH_DI bool planar_is_free(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs, int n_pairs,
                            const DynDev& dyn, const double* __restrict__ x) {
 #pragma unroll
-  for (int d = 0; d < 2 * N; ++d) {
-    const double lo = dyn.lower[d], hi = dyn.upper[d];
-    if (lo < hi) {
-      if ((x[d] < lo) || (x[d] > hi)) return false;
-    } else if ((x[d] > lo) || (x[d] < hi)) {
-      return false;
-    }
-  }
+  for (int d = 0; d < 2 * N; ++d)
+    if (hyperbox_out(dyn.lower[d], dyn.upper[d], x[d])) return false;
   d2 Epos[N], Erot[N];
   {
     d2 pos = mk2(sc->base_pos[0], sc->base_pos[1]);
@@ -275,18 +269,15 @@ __global__ __launch_bounds__(64) void planar_propagate_kernel(const SceneDev* __
                                                               const EdgeIO* __restrict__ tab_a,
                                                               const EdgeIO* __restrict__ tab_b, uint32_t blocks_a,
                                                               KernelGate gate) {
-  if (gate.count) {
-    const uint32_t c = *gate.count;
-    if (c < gate.lo || c >= gate.hi) return;
-  }
+  if (steer_gate_closed(&gate)) return;
   constexpr int D = 2 * N;
   const bool group_b = blockIdx.x >= blocks_a;
   const EdgeIO io = tab_a ? (group_b ? tab_b[blockIdx.y] : tab_a[blockIdx.y]) : (group_b ? io_b : io_a);
   const uint32_t B = io.d_B ? *io.d_B : io.B;
   const uint32_t e = (group_b ? blockIdx.x - blocks_a : blockIdx.x) * 64u + threadIdx.x;
   if (e >= B) return;
-  const uint32_t si = io.src_idx ? io.src_idx[e] : ((io.d_src_first ? *io.d_src_first : 0u) + e);
-  const uint64_t trow = io.tgt_idx ? uint64_t(io.tgt_idx[e]) : (io.d_tgt_off ? uint64_t(*io.d_tgt_off) : 0ull) + e;
+  const uint32_t si = edge_source_row(io, e);
+  const uint64_t trow = edge_target_row(io, e);
   double a[D], b[D], x[D];
 #pragma unroll
   for (int d = 0; d < D; ++d) {
@@ -299,15 +290,7 @@ __global__ __launch_bounds__(64) void planar_propagate_kernel(const SceneDev* __
   if (record)
     for (int d = 0; d < D; ++d) record[(uint64_t(e) * record_stride + 0) * D + d] = x[d];
   int n_steps = dyn.n_steps;
-  if (io.frac) {  // the edge's own travel fraction, cut with the steer loop's comparison
-    const double T_goal = io.frac[e] * dyn.full_time;
-    double current_time = 0.0;
-    n_steps = 0;
-    while (current_time < T_goal && n_steps < kMaxSteps) {
-      current_time += dyn.dt;
-      ++n_steps;
-    }
-  }
+  if (io.frac) n_steps = edge_step_count(io.frac[e], dyn.full_time, dyn.dt);  // the edge's own travel fraction
   uint32_t n_free = 0;
   bool singular = false;
   if (io.mode == EDGE_POINT) {
@@ -320,12 +303,7 @@ __global__ __launch_bounds__(64) void planar_propagate_kernel(const SceneDev* __
     if (!(planar_norm<N>(x, b) > dyn.goal_tol)) break;
     double u[N];
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-      double v = dyn.kp * (b[2 * j] - x[2 * j]) + dyn.kd * (b[2 * j + 1] - x[2 * j + 1]);
-      if (v > dyn.u_max) v = dyn.u_max;
-      else if (v < -dyn.u_max) v = -dyn.u_max;
-      u[j] = v;
-    }
+    for (int j = 0; j < N; ++j) u[j] = pd_input(dyn.kp, dyn.kd, dyn.u_max, b[2 * j], x[2 * j], b[2 * j + 1], x[2 * j + 1]);
     // runge_kutta4_integrate_impl (runge_kutta4_integrator_sys.hpp:53-97), stages rolled like in propagate.hip
     const double h = dyn.dt;
     double xe[D], w[D], k1[D], k2[D], k3[D], dp[D];
@@ -342,21 +320,7 @@ __global__ __launch_bounds__(64) void planar_propagate_kernel(const SceneDev* __
       if (!planar_state_derivative<N>(sc, xe, u, dp)) sing_now = true;
       const int stage = ev & 3;
 #pragma unroll
-      for (int d = 0; d < D; ++d) {
-        if (stage == 0) {
-          w[d] = xe[d];
-          k1[d] = h * dp[d];
-          xe[d] = xe[d] + 0.5 * k1[d];
-        } else if (stage == 1) {
-          k2[d] = h * dp[d];
-          xe[d] = w[d] + 0.5 * k2[d];
-        } else if (stage == 2) {
-          k3[d] = h * dp[d];
-          xe[d] = w[d] + k3[d];
-        } else {
-          xe[d] = xe[d] + ((((1.0 / 6.0) * k1[d] + (2.0 / 6.0) * k2[d]) + (h / 6.0) * dp[d]) - (2.0 / 3.0) * k3[d]);
-        }
-      }
+      for (int d = 0; d < D; ++d) rk4_stage(stage, h, dp[d], xe[d], w[d], k1[d], k2[d], k3[d]);
     }
     if (sing_now) {
       singular = true;
@@ -377,16 +341,9 @@ __global__ __launch_bounds__(64) void planar_propagate_kernel(const SceneDev* __
     const double n_ar = planar_norm<N>(a, x);
     const double n_ab = planar_norm<N>(a, b);
     const double n_rb = planar_norm<N>(x, b);
-    if (io.mode == EDGE_STEER_ACCEPT) {
-      const double best_case = io.best_case ? io.best_case[e] : n_ab;
-      io.accept[e] = ((!isinf(n_ar)) && (n_ar < 2.0 * best_case) && (n_ar > io.steer_tol * best_case)) ? 1 : 0;
-    } else if (io.mode == EDGE_CONNECT) {
-      io.accept[e] = ((!isinf(n_ar)) && (n_rb < io.steer_tol * n_ar)) ? 1 : 0;
-    } else if (io.mode == EDGE_WALK_ACCEPT) {
-      io.accept[e] = ((!isinf(n_ar)) && (n_ar > io.steer_tol * io.best_case[e])) ? 1 : 0;
-    } else if (io.mode == EDGE_GOAL_PROBE) {
-      io.goal_dist[si - 1] = (n_ab * 0.05 > n_rb) ? n_ab : INFINITY;
-    }
+    const int acc = edge_accept(io.mode, n_ar, n_ab, n_rb, io.best_case, e, io.steer_tol, kNoWalk);
+    if (acc != kNoAccept) io.accept[e] = uint8_t(acc);
+    else if (io.mode == EDGE_GOAL_PROBE) io.goal_dist[si - 1] = goal_probe_steerable(n_ab, n_rb);
   }
 }
 

@@ -13,6 +13,7 @@
 #include "../../include/rkh.h"
 #include "../../include/rkh_diag.h"
 #include "device_buffer.h"
+#include "steer_edge.h"  // EdgeMode, EdgeIO, KernelGate, kMaxSteps
 
 namespace rkh {
 
@@ -47,7 +48,6 @@ rkh_status with_n(int n, F&& f) {
 
 constexpr int kMaxDof = 12;         // joints of a scene (dynamics kernels: 1, 2, 3, 6; quasi-static kernels also 12)
 constexpr int kMaxEnvShapes = 256;  // environment shapes resident in LDS
-constexpr int kMaxSteps = 64;       // RK4 steps per edge
 
 // ---- NN sweep (nn_sweep.hip) -----------------------------------------------------------------
 // Vertex positions live row-major [n][D] in HBM (one contiguous 8*D-byte row per vertex): the sweep
@@ -295,16 +295,6 @@ struct DynDev {  // rkh_dyn_space on the device (passed by value)
   int8_t inner[kMaxSteps];  // runge_kutta4_integrate_impl loop iterations of step k (normally 1), whole step budget
 };
 
-enum EdgeMode : int {
-  EDGE_PLAIN = 0,
-  EDGE_STEER_ACCEPT = 1,
-  EDGE_GOAL_PROBE = 2,
-  EDGE_CONNECT = 3,
-  EDGE_WALK_ACCEPT = 4,  // random_walk: traveled > steer_tol * best_case[e] (best_case carries the target distance)
-  EDGE_STEER_BOTH = 6,   // quasi-static kernel: EDGE_STEER_ACCEPT in bit 0 of accept, bit 1 = the walk ran to its end
-  EDGE_POINT = 5,        // accept = is_free(target point), no walk (quasi-static kernel, one-wave-per-edge dynamics kernel)
-};
-
 struct QsDev {  // manip_quasi_static_env on the device (passed by value)
   double min_interval, fraction;
   double lower[kMaxDof], upper[kMaxDof];
@@ -314,49 +304,6 @@ inline void qs_set_speed(QsDev& qs, const double* speed_limits, int n) {
   for (int i = 0; i < kMaxDof; ++i) qs.speed[i] = (speed_limits && i < n && speed_limits[i] != 0.0) ? speed_limits[i] : 1.0;
 }
 
-struct EdgeIO {  // inputs / outputs of one propagate launch (all device pointers)
-  const double* src = nullptr;         // source rows
-  const uint32_t* src_idx = nullptr;   // row of edge e (null: *d_src_first + e, or e)
-  const uint32_t* d_src_first = nullptr;
-  uint32_t src_stride = 0;
-  const double* tgt = nullptr;         // target rows
-  const uint32_t* d_tgt_off = nullptr; // row offset read on the device
-  const uint32_t* tgt_idx = nullptr;   // optional: target row of edge e (quasi-static edge kernel)
-  uint32_t tgt_stride = 0;             // 0: one target for all edges
-  const double* frac = nullptr;        // optional per-edge travel fraction (quasi-static kernel; null: QsDev::fraction)
-  uint32_t B = 0;
-  const uint32_t* d_B = nullptr;
-  double* x_out = nullptr;
-  uint32_t* steps_free = nullptr;
-  double* record = nullptr;
-  int record_stride = 0;
-  int mode = EDGE_PLAIN;
-  const double* best_case = nullptr;
-  double steer_tol = 0.1;
-  uint8_t* accept = nullptr;
-  double* goal_dist = nullptr;         // indexed by source row - 1
-  int* err_flag = nullptr;
-};
-
-// A steer kernel with a gate runs only if lo <= *count < hi (read on the device); count == nullptr: always.
-struct KernelGate {
-  const uint32_t* count = nullptr;
-  uint32_t lo = 0, hi = 0xFFFFFFFFu;
-  // two-lanes kernel, table launches: exclusive prefix of the working waves per segment (segment 2p = candidates of
-  // problem p, 2p+1 = its goal probes; wave_base[n_segments] = total).  The blocks of the grid, in dispatch order, then
-  // take the working waves one after the other, so the round-robin of blocks over the 8 XCDs spreads the work evenly
-  // whatever the per-problem counts are (a (wave, problem) grid leaves holes that land unevenly on the XCDs).
-  const uint32_t* wave_base = nullptr;
-  uint32_t n_segments = 0;
-  // optional diagnostics: the kernel adds the edge-steps it integrated (steps that began with a live edge, the one that
-  // ended it included) -- the executed work of a launch, as opposed to n_steps per launched edge
-  unsigned long long* steps_exec = nullptr;
-  // two-lanes kernels: skip the proximity test of a step that a carried clearance bound settles (SceneDev::has_clearance
-  // scenes only; RKH_STEER_CLEARANCE=0 turns it off), and count [0] += edge-steps settled by the bound, [1] += wave-steps
-  // that ran the test (rkh_diag_steer_clearance_counts)
-  bool clearance = true;
-  unsigned long long* clear_stats = nullptr;
-};
 // ---- steer mapping ---------------------------------------------------------------------------------------------------
 // The kernel form that steers the edges of a dynamic-space launch.
 enum class SteerMapping : uint8_t {
