@@ -75,6 +75,14 @@ rkh_status rkh_diag_proximity_clearance(rkh_scene* scene, const double* x, uint3
  * test the bound settled, counts[1] = wave-steps (32 edges) that ran the test.  RKH_STEER_CLEARANCE=0 in the
  * environment (read with the steer mapping's knobs) makes the kernels test every step. */
 rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2]);
+/* Always on: what the rounds of this planner did with the candidates they did not consume, summed over its problems
+ * (waits for the planner's stream).  counts[0] = candidates discarded (a round of B candidates that consumes `cut` of
+ * them discards B - cut; their samples come up again in the next round), counts[1] = candidates that took the stashed
+ * result of such a discarded candidate instead of being steered again, because their nearest neighbour was still the
+ * vertex the stashed edge started from (reak_amd/csrc/round_carry.h).  Only rounds that take the step-wise steer launch
+ * with at least RKH_STEER_CARRY_MIN_EDGES edges (default: the built-in step-wise threshold) reuse; RKH_STEER_CARRY=0 in
+ * the environment at rkh_planner_create* switches the reuse off. */
+rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@
 // GPU (tests/cpp/arena_layout_test.cpp).  planner_arena_layout is a pure function of the shape of the batch: it hands
 // out byte ranges at kArenaAlign, one after the other, and leaves kArenaGuardBytes behind the last one -- buffers that
 // ended an allocation of their own had page slack behind them, and a padded-tile read a little past the last range must
-// stay inside the slab.  Ranges that a shape does not need (no mirror, no profile, no two-lanes workspace) have 0 bytes
+// stay inside the slab.  Ranges that a shape does not need (no mirror, no profile, no two-lanes workspace, no carry) have 0 bytes
 // and take no room.
 #pragma once
 #include <algorithm>
@@ -32,11 +32,11 @@ enum SharedRange : int {
   SR_SAMPLE_TAB0 = SR_UPLOAD_END, SR_SAMPLE_TAB1, SR_GOAL_TAB, SR_LANE_WS, SR_STEP_LIST0, SR_STEP_LIST1,
   SR_COUNT
 };
-// The 21 buffers of one problem.
+// The 25 buffers of one problem.  PR_STASH_*: what a round's discarded candidates leave for the next one (round_carry.h).
 enum ProblemRange : int {
   PR_MT, PR_TREE, PR_PARENT, PR_NODE_SAMPLE, PR_GOAL_DIST, PR_SAMPLES, PR_NN_SEQ, PR_ACCEPT_LOG, PR_NN_IDX, PR_NN_DIST,
   PR_X_OUT, PR_STEPS, PR_ACCEPT, PR_PROBE_X, PR_PROBE_STEPS, PR_GOAL, PR_PART_DIST, PR_PART_IDX, PR_ROUND_N, PR_MIRROR,
-  PR_CAND,
+  PR_CAND, PR_STASH_X, PR_STASH_NN, PR_STASH_STEPS, PR_STASH_ACCEPT,
   PR_COUNT
 };
 
@@ -55,6 +55,7 @@ struct ArenaShape {
   uint32_t b_max = 0, probe_granule = 0, part_blocks = 0, prof_rounds = 0;
   int D = 0, DP = 0;
   bool mirror = false, profile = false, lane = false;
+  bool carry = false;          // rounds may reuse the discarded candidates of the round before (needs lane)
   size_t cand_bytes = 0;       // per-query scratch of the mirror sweep + the mirror's error word (mirror only)
   size_t lane_ws_bytes = 0;    // workspace of the two-lanes steer kernels (lane only)
   size_t step_list_bytes = 0;  // one of the two lists of the step-wise steer launches (lane only)
@@ -129,6 +130,12 @@ inline ArenaLayout planner_arena_layout(const ArenaShape& s) {
     r[PR_ROUND_N] = take(s.profile ? 2 * size_t(s.prof_rounds) * sizeof(uint32_t) : 0);
     r[PR_MIRROR] = take(s.mirror ? size_t(s.mirror_bytes[i]) : 0);
     r[PR_CAND] = take(s.mirror ? s.cand_bytes : 0);
+    // rows [cut, B) of x_out, nn_idx, steps and accept, packed from slot 0
+    const size_t stash = (s.lane && s.carry) ? b : 0;
+    r[PR_STASH_X] = take(stash * D * sizeof(double));
+    r[PR_STASH_NN] = take(stash * sizeof(uint32_t));
+    r[PR_STASH_STEPS] = take(stash * sizeof(uint32_t));
+    r[PR_STASH_ACCEPT] = take(stash);
   }
   L.total = cur + kArenaGuardBytes;
   return L;

@@ -33,6 +33,7 @@
 #include "nn_device.h"
 #include "nn_mirror.h"
 #include "rkh_internal.h"
+#include "round_carry.h"
 
 namespace rkh {
 
@@ -50,8 +51,9 @@ struct PlannerState {  // device-resident, one per problem
   uint32_t b_max;
   float batch_factor;
   uint32_t b_min;
-  uint32_t pad;
+  uint32_t carried;      // candidates the last commit left in the stash (round_carry.h); 0 wherever the stash is not valid
   unsigned long long rounds, edges_speculated, fixup_cut;
+  unsigned long long cand_discarded, cand_reused;  // candidates [cut, B) of all rounds; those a later round did not steer again
 };
 
 struct ProblemDev {  // device pointers of one problem
@@ -66,6 +68,12 @@ struct ProblemDev {  // device pointers of one problem
   double* nn_dist;
   double* x_out;
   uint8_t* accept;
+  uint32_t* steps;
+  // what the discarded candidates of the last round left (round_carry.h); null: this planner's rounds never carry
+  double* stash_x;
+  uint32_t* stash_nn;
+  uint32_t* stash_steps;
+  uint8_t* stash_accept;
   uint32_t* round_n;  // profiling: vertex count at the start of each round (may be null)
   uint4* mirror;      // half-precision mirror of the tree rows (nn_mirror.h), or null
   uint32_t* dx_max_bits;  // its running maximum of |x - x_h|
@@ -86,8 +94,8 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
                                                            float fit_fill, uint32_t slots, uint32_t* __restrict__ wave_base,
                                                            uint32_t* __restrict__ nn_base, uint32_t nn_queries,
                                                            uint32_t* __restrict__ edge_base, uint32_t epw,
-                                                           uint32_t* __restrict__ step_cnt) {
-  __shared__ unsigned int s_waves;
+                                                           uint32_t* __restrict__ step_cnt, uint32_t carry_fit_lo) {
+  __shared__ unsigned int s_waves, s_edges, s_steered;
   // live-edge counters of the step-wise steer launches of this round (launch_propagate_pair_steps)
   // (two per step: the front and the back part of its list)
   if (step_cnt && threadIdx.x < 2u * (uint32_t(kMaxSteps) + 1u)) step_cnt[threadIdx.x] = 0u;
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
   // three count arrays, scanned in LDS; problems beyond the cache capacity fall back to global memory
   constexpr uint32_t kCache = 1024;
   __shared__ float s_bf[kCache], s_sq[kCache];
-  __shared__ uint32_t s_bmin[kCache], s_bcap[kCache], s_probe_waves[kCache];
+  __shared__ uint32_t s_bmin[kCache], s_bcap[kCache], s_probe_waves[kCache], s_probes[kCache], s_carried[kCache];
   __shared__ uint32_t s_scan[3][2 * kCache + 1];
   const bool cached = P <= kCache;
   const uint32_t tid = threadIdx.x;
@@ -123,6 +131,8 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
       s_bmin[i] = done ? 0u : st->b_min;
       s_bcap[i] = done ? 0u : (st->b_max < avail ? st->b_max : avail);  // min(b_max, avail): the two upper clamps
       s_probe_waves[i] = (st->n_new + epw - 1u) / epw;
+      s_probes[i] = st->n_new;
+      s_carried[i] = st->carried;
     }
     __syncthreads();
   }
@@ -134,21 +144,38 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
     if (B > s_bcap[i]) B = s_bcap[i];
     return B;
   };
+  // A round that carries (round_carry.h; carry_fit_lo = the fewest edges of such a round, kCarryOff: the fit does not
+  // look) runs launch 0 over one compact list of the edges it steers: its waves are that total over epw, rounded up, with
+  // the expected reuse taken off every problem's candidates.
   auto waves_at = [&](float sc) -> uint32_t {  // block-wide sum, same value in every thread
-    uint32_t w = 0;
+    uint32_t w = 0, e = 0, steered = 0;
     for (uint32_t i = tid; i < P; i += blockDim.x) {
+      uint32_t B, n_new, carried;
       if (cached) {
-        w += (batch_cached(i, sc) + epw - 1u) / epw + s_probe_waves[i];
+        B = batch_cached(i, sc);
+        n_new = s_probes[i];
+        carried = s_carried[i];
+        w += (B + epw - 1u) / epw + s_probe_waves[i];
       } else {
         const PlannerState* st = probs[i].st;
-        w += (batch_of(st, sc) + epw - 1u) / epw + (st->n_new + epw - 1u) / epw;
+        B = batch_of(st, sc);
+        n_new = st->n_new;
+        carried = st->carried;
+        w += (B + epw - 1u) / epw + (n_new + epw - 1u) / epw;
       }
+      e += B + n_new;
+      steered += B - carry_expected_reuse(carried, B) + n_new;
     }
     __syncthreads();
-    if (tid == 0) s_waves = 0u;
+    if (tid == 0) s_waves = s_edges = s_steered = 0u;
     __syncthreads();
     if (w) atomicAdd(&s_waves, w);
+    if (carry_fit_lo != kCarryOff && e) {
+      atomicAdd(&s_edges, e);
+      atomicAdd(&s_steered, steered);
+    }
     __syncthreads();
+    if (carry_fit_lo != kCarryOff && s_edges >= carry_fit_lo) return (s_steered + epw - 1u) / epw;
     return s_waves;
   };
   float scale = 1.0f;
@@ -260,8 +287,9 @@ __global__ __launch_bounds__(256) void fixup_kernel(const ProblemDev* __restrict
 // probe_granule: goal probes ride in the next steer launch in whole groups of this many (32 = one steer wave of the
 // two-lanes mapping: a (problem, probes) segment of the grid then has no half-empty last wave; what is left over waits
 // for the vertices of the next round, the last ones for flush_probes; 1 = every pending probe rides along).
+// stash: the candidates this round throws away, [cut, B), leave their results for the next round (round_carry.h).
 __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restrict__ probs, int D, int DP,
-                                                      uint32_t probe_granule) {
+                                                      uint32_t probe_granule, bool stash) {
   __shared__ uint32_t scan[256];
   __shared__ uint32_t carry;
   __shared__ uint32_t cut;  // number of candidates actually consumed
@@ -271,6 +299,8 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
   const uint32_t n0 = st->n;
   const uint32_t s0 = st->s0;
   const uint32_t budget = st->max_total - n0;  // vertices that may still be added
+  const uint32_t B = st->B;
+  const bool was_done = st->done != 0u;  // (read by every thread before thread 0 may change it below)
   if (threadIdx.x == 0) {
     carry = 0;
     cut = F;
@@ -320,9 +350,63 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
     const uint32_t pending = n0 + added - first_pending;
     st->n_new = pending - pending % probe_granule;
     st->s0 = s0 + cut;
-    st->fixup_cut += (st->B - F);
+    st->fixup_cut += (B - F);
+    st->cand_discarded += (B - cut);
     if (st->n >= st->max_total) st->done = 1;
   }
+  // rows [cut, B) of the round's results -> the stash, packed from slot 0.  Every candidate of the round was steered (or
+  // took a stashed result itself), whichever mapping ran, so every row is the result of (nn_idx[b], sample s0 + b).
+  const uint32_t added_all = carry < budget ? carry : budget;
+  const bool live = !was_done && n0 + added_all < st->max_total;
+  const uint32_t carried = carry_count(B, cut, stash && pr.stash_x && live);
+  if (threadIdx.x == 0) st->carried = carried;
+  for (uint32_t j = threadIdx.x; j < carried; j += 256) {
+    const uint32_t b = carry_old_slot(j, cut);
+    pr.stash_nn[j] = pr.nn_idx[b];
+    pr.stash_steps[j] = pr.steps[b];
+    pr.stash_accept[j] = pr.accept[b];
+  }
+  const double* __restrict__ x_from = pr.x_out + uint64_t(carry_old_slot(0u, cut)) * D;
+  for (uint32_t k = threadIdx.x; k < carried * uint32_t(D); k += 256) pr.stash_x[k] = x_from[k];
+}
+
+// One block per problem, between the NN resolve and the steer launches of a round that carries (carry_round of the round's
+// edge count: the same decision launch 0 of propagate_pair_step_kernel takes).  Candidates the reuse predicate marks take
+// their stashed end state, accept bit and step count; every other candidate and every goal probe of the problem is
+// appended to the list launch 0 reads, as (segment, edge, no carried clearance, 0): one ballot, one prefix and one atomic
+// per wave.  A reused edge is in no list: no steer launch sees it.
+__global__ __launch_bounds__(256) void carry_restore_kernel(const ProblemDev* __restrict__ probs, int D,
+                                                             const uint32_t* __restrict__ edge_count, uint32_t lo, uint32_t hi,
+                                                             uint32_t carry_min_edges, uint4* __restrict__ list,
+                                                             uint32_t* __restrict__ list_cnt, uint32_t list_cap) {
+  if (!carry_round(*edge_count, lo, hi, carry_min_edges)) return;
+  const ProblemDev pr = probs[blockIdx.x];
+  PlannerState* st = pr.st;
+  const uint32_t B = st->B, n_new = st->n_new, carried = st->carried;
+  const uint32_t total = B + n_new;
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t n_reused = 0;  // (lane 0 of each wave counts its wave's)
+  for (uint32_t base = 0; base < total; base += 256) {  // (uniform trip count)
+    const uint32_t i = base + threadIdx.x;
+    const bool cand = i < B;
+    const bool reuse = cand && carry_reuses(i, carried, B, pr.nn_idx[i], pr.stash_nn);
+    if (reuse) {
+      for (int d = 0; d < D; ++d) pr.x_out[uint64_t(i) * D + d] = pr.stash_x[uint64_t(i) * D + d];
+      pr.accept[i] = pr.stash_accept[i];
+      pr.steps[i] = pr.stash_steps[i];
+    }
+    const bool steered = i < total && !reuse;
+    const unsigned long long m = __ballot(steered);
+    n_reused += uint32_t(__popcll(__ballot(reuse)));
+    if (m) {
+      uint32_t at = 0;
+      if (lane == 0) at = atomicAdd(list_cnt, uint32_t(__popcll(m)));
+      at = uint32_t(__builtin_amdgcn_readfirstlane(int(at))) + uint32_t(__popcll(m & below));
+      if (steered && at < list_cap) list[at] = make_uint4(2u * blockIdx.x + (cand ? 0u : 1u), cand ? i : i - B, 0u, 0u);
+    }
+  }
+  if (lane == 0 && n_reused) atomicAdd(&st->cand_reused, (unsigned long long)n_reused);
 }
 
 // after a probe-only flush launch: nothing is pending any more
@@ -490,6 +574,9 @@ struct Problem {  // host view of one planning problem
   uint32_t *d_nn_idx = nullptr, *d_steps = nullptr, *d_probe_steps = nullptr;  // [b_max (+ kProbeGranule)] a round's candidates and probes
   double *d_nn_dist = nullptr, *d_x_out = nullptr, *d_probe_x = nullptr;
   uint8_t* d_accept = nullptr;
+  double* d_stash_x = nullptr;  // [b_max] the last round's discarded candidates (round_carry.h); null: no carry
+  uint32_t *d_stash_nn = nullptr, *d_stash_steps = nullptr;
+  uint8_t* d_stash_accept = nullptr;
   double* d_part_dist = nullptr;                                        // partial minima of the NN sweep
   uint32_t *d_part_idx = nullptr, *d_round_n = nullptr;
   void* d_mirror = nullptr;          // half-precision mirror of d_tree (nn_mirror.h)
@@ -578,6 +665,15 @@ struct rkh_planner {
   // rounds below this many edges keep the single whole-edge launch of the two-lanes mapping (RKH_STEER_SPLIT_MIN_EDGES;
   // default: what leaves every SIMD at most one 32-edge wave -- such a round gains nothing from shedding waves)
   uint32_t split_min_edges = 0;
+  // Rounds that take the step-wise launch with at least carry_min_edges edges reuse the steered edges of the candidates
+  // the round before discarded (round_carry.h; RKH_STEER_CARRY=0: never, RKH_STEER_CARRY_MIN_EDGES).  The default is the
+  // built-in step-wise threshold whatever split_min_edges says: only the step-wise launches honour the mark, and the
+  // executed-step counter stays comparable across the mappings below it.
+  bool carry = false;
+  uint32_t carry_min_edges = 0;
+  // the wave fit takes the expected reuse off a carrying round's work: measured 0.5 % slower than counting the candidates
+  // (DESIGN 5), so off unless RKH_STEER_CARRY_FIT=1 asks for it
+  bool carry_fit = false;
   uint64_t max_n_ub = 1;  // largest vertex-count bound over the problems (sizes the mirror sweep's row slices)
   uint64_t sum_batch_ub = 0, prev_sum_batch_ub = 0;  // host-side bounds on the candidates of this / the previous round, all problems
   // segment tables of the sample generator: [0] what the enqueued rounds need, [1] the next call's share, generated
@@ -750,10 +846,16 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
   if (edges_ub < gate_lane.lo) return RKH_OK;
   const uint32_t epw = pair_kernel_edges_per_wave();
   const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
+  // a round that carries: the stashed results go to their slots and launch 0 gets the list of the edges left to steer
+  const uint32_t carry_min = p->carry ? p->carry_min_edges : kCarryOff;
+  if (p->carry && edges_ub >= carry_min) {
+    hipLaunchKernelGGL(carry_restore_kernel, dim3(p->P), dim3(256), 0, p->stream, p->d_probs, p->D, gate_lane.count,
+                       gate_lane.lo, gate_lane.hi, carry_min, p->d_step_list[0], p->d_step_cnt, p->step_list_cap);
+  }
   return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
                                      p->d_wave_base + (2 * p->P + 1), p->d_step_list[0],
                                      p->d_step_list[1], p->step_list_cap, p->d_step_cnt,
-                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec);
+                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec, carry_min);
 }
 
 // goal probes still pending after the last enqueued round
@@ -809,7 +911,9 @@ rkh_status enqueue_round(rkh_planner* p) {
                      fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base, p->d_nn_base,
                      p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries(),
                      p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
-                     p->d_step_cnt);
+                     p->d_step_cnt,
+                     (p->carry && p->carry_fit) ? std::max(p->carry_min_edges, std::max(p->lane_threshold, p->split_min_edges))
+                                                : kCarryOff);
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
                       ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
@@ -835,7 +939,8 @@ rkh_status enqueue_round(rkh_planner* p) {
     default: set_error("planner: unsupported state dimension"); return RKH_ERR_UNSUPPORTED;
   }
   // 4. commit the valid prefix
-  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u);
+  hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u,
+                     p->carry);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -855,6 +960,11 @@ ProblemDev problem_dev(const rkh_planner* p, uint32_t i) {
   pd.nn_dist = q.d_nn_dist;
   pd.x_out = q.d_x_out;
   pd.accept = q.d_accept;
+  pd.steps = q.d_steps;
+  pd.stash_x = q.d_stash_x;
+  pd.stash_nn = q.d_stash_nn;
+  pd.stash_steps = q.d_stash_steps;
+  pd.stash_accept = q.d_stash_accept;
   pd.round_n = q.d_round_n;
   pd.mirror = static_cast<uint4*>(q.d_mirror);
   pd.dx_max_bits = q.dx_max_bits;
@@ -1071,6 +1181,11 @@ void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
     if (propagate_pair_step_workspace_bytes(p->n_dof, p->step_blocks_cap) > lane_ws)
       p->step_blocks_cap = uint32_t(lane_ws / propagate_pair_step_workspace_bytes(p->n_dof, 1));
   }
+  p->carry = !p->quasi_static && p->steer == SteerMapping::Auto && p->dyn.n_steps > 1;
+  if (const char* e = getenv("RKH_STEER_CARRY")) p->carry = p->carry && atoi(e) != 0;
+  p->carry_min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();
+  if (const char* e = getenv("RKH_STEER_CARRY_MIN_EDGES")) p->carry_min_edges = uint32_t(std::max(0, atoi(e)));
+  if (const char* e = getenv("RKH_STEER_CARRY_FIT")) p->carry_fit = atoi(e) != 0;
   if (const char* e = getenv("RKH_PROFILE_NN")) p->profile_nn = atoi(e) != 0;
   // candidates per round = batch_factor * sqrt(n) per problem (results do not depend on it).  More candidates per
   // round mean fewer rounds but more discarded speculation (0.89 of the propagated edges are committed at 1.25, 0.72 at
@@ -1120,6 +1235,7 @@ rkh_status alloc_planner_buffers(rkh_planner* p) {
   sh.mirror = p->nn_mirror;
   sh.profile = p->profile_nn;
   sh.lane = p->lane_kernel();
+  sh.carry = p->carry;
   sh.cand_bytes = nn1_mirror_query_bytes() * b_max + 256;  // the per-query scratch, then the mirror's error word
   if (sh.lane) {
     // (sized for the largest grid of a launch: b_max candidates and up to b_max + kProbeGranule goal probes per problem,
@@ -1182,6 +1298,10 @@ rkh_status alloc_planner_buffers(rkh_planner* p) {
     q.d_round_n = A.at<uint32_t>(L.of(i, PR_ROUND_N));
     q.d_mirror = A.at<void>(L.of(i, PR_MIRROR));
     q.d_cand = A.at<void>(L.of(i, PR_CAND));
+    q.d_stash_x = A.at<double>(L.of(i, PR_STASH_X));
+    q.d_stash_nn = A.at<uint32_t>(L.of(i, PR_STASH_NN));
+    q.d_stash_steps = A.at<uint32_t>(L.of(i, PR_STASH_STEPS));
+    q.d_stash_accept = A.at<uint8_t>(L.of(i, PR_STASH_ACCEPT));
     q.dx_max_bits = q.d_cand ? reinterpret_cast<uint32_t*>(static_cast<char*>(q.d_cand) + nn1_mirror_query_bytes() * b_max) : nullptr;
   }
   // the pinned block: image of the upload ranges | error flag | segment tables
@@ -1498,6 +1618,17 @@ rkh_status rkh_planner_steer_steps(rkh_planner* p, uint64_t* executed_steps) {
   unsigned long long v = 0;
   RKH_HIP(hipMemcpy(&v, p->d_steps_exec, sizeof(v), hipMemcpyDeviceToHost));
   *executed_steps = v;
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]) {
+  if (!p || !counts) return RKH_ERR_BAD_ARG;
+  RKH_TRY(read_states(p));
+  counts[0] = counts[1] = 0;
+  for (const Problem& q : p->prob) {
+    counts[0] += q.h_state.cand_discarded;
+    counts[1] += q.h_state.cand_reused;
+  }
   return RKH_OK;
 }
 

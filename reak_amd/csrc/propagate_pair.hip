@@ -34,6 +34,7 @@
 #include "device_math.h"
 #include "proximity_device.h"
 #include "rkh_internal.h"
+#include "round_carry.h"
 
 namespace rkh {
 #ifdef RKH_PRISMATIC_FORMS
@@ -1094,6 +1095,10 @@ struct PairStepArgs {
   uint32_t* cnt_out;
   uint32_t list_cap;          // entries of each list
   unsigned long long* steps_exec;  // optional: + the number of edge-steps this launch integrated
+  // A round that carries (carry_round of the gate's count, round_carry.h; kCarryOff: none does): launch 0 reads list_in
+  // too -- the edges carry_restore_kernel left to steer, all with clearance 0 in the front part -- instead of the
+  // implicit list of edge_base.  What launch 0 does because it integrates step 0 stays keyed on the step.
+  uint32_t carry_min_edges;
 };
 constexpr uint32_t kStepCntBack = uint32_t(kMaxSteps) + 1u;  // d_cnt[kStepCntBack + k]: back entries of the list launch k reads
 typedef const __attribute__((address_space(4))) PairStepArgs* PairStepArgP;
@@ -1118,14 +1123,17 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
   const int h = lane & 1;
   const int el = lane >> 1;
   uint32_t n_front, n_back;
+  bool listed;  // (uniform) this launch takes its edges from list_in
   {
     PairStepArgP A = pair_step_args();
+    listed = A->step != 0u;
     if (A->gate.count) {
       const uint32_t c = *A->gate.count;
       if (c < A->gate.lo || c >= A->gate.hi) return;
+      listed = listed || carry_round(c, A->gate.lo, A->gate.hi, A->carry_min_edges);
     }
-    n_front = A->step == 0u ? A->edge_base[A->n_segments] : A->cnt_in[0];
-    n_back = A->step == 0u ? 0u : A->cnt_in[kStepCntBack];
+    n_front = listed ? A->cnt_in[0] : A->edge_base[A->n_segments];
+    n_back = listed ? A->cnt_in[kStepCntBack] : 0u;
   }
   const uint32_t chunks_front = (n_front + uint32_t(kPairEdges) - 1u) / uint32_t(kPairEdges);
   const uint32_t n_chunks = chunks_front + (n_back + uint32_t(kPairEdges) - 1u) / uint32_t(kPairEdges);
@@ -1147,7 +1155,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
     // the lane pair's edge (both lanes of a pair hold the same values)
     uint32_t seg, ec;
     float budget = 0.0f;  // carried clearance (launch 0 has none: it tests)
-    if (k == 0) {  // entry ic of the round's implicit list: bisection in the prefix of the segments' edge counts
+    if (!listed) {  // entry ic of the round's implicit list: bisection in the prefix of the segments' edge counts
       const uint32_t* eb = pair_step_args()->edge_base;
       uint32_t lo = 0, hi = pair_step_args()->n_segments;  // eb[lo] <= ic < eb[hi]
       while (hi - lo > 1) {
@@ -1390,12 +1398,13 @@ size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks) {
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
                                        uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
-                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec) {
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec,
+                                       uint32_t carry_min_edges) {
   if (blocks == 0 || n_problems == 0) return RKH_OK;
   if constexpr (!kPrismatic)
     if (scene.host.has_prismatic)
       return prismatic::launch_propagate_pair_steps(s, scene, dyn, tab_a, tab_b, n_problems, d_edge_base, d_list0, d_list1,
-                                                    list_cap, d_cnt, d_ws, blocks, gate, d_steps_exec);
+                                                    list_cap, d_cnt, d_ws, blocks, gate, d_steps_exec, carry_min_edges);
   PairStepArgs args;
   args.sc = scene.d_scene.get();
   args.dyn = dyn;
@@ -1407,6 +1416,7 @@ rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, co
   args.n_segments = 2 * n_problems;
   args.steps_exec = d_steps_exec;
   args.list_cap = list_cap;
+  args.carry_min_edges = carry_min_edges;
   const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
     for (int k = 0; k < dyn.n_steps; ++k) {
       args.step = uint32_t(k);

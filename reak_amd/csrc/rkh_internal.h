@@ -423,7 +423,8 @@ rkh_status launch_propagate_pairs(hipStream_t s, const rkh_scene& scene, const D
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
                                        uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
-                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec,
+                                       uint32_t carry_min_edges);
 uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
                               unsigned long long* d_out, float* d_clear_out = nullptr);
@@ -442,7 +443,8 @@ size_t propagate_pair_step_workspace_bytes(int n_dof, uint32_t blocks);
 rkh_status launch_propagate_pair_steps(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO* tab_a,
                                        const EdgeIO* tab_b, uint32_t n_problems, const uint32_t* d_edge_base,
                                        uint4* d_list0, uint4* d_list1, uint32_t list_cap, uint32_t* d_cnt, double* d_ws,
-                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec);
+                                       uint32_t blocks, KernelGate gate, unsigned long long* d_steps_exec,
+                                       uint32_t carry_min_edges);
 uint32_t pair_kernel_waves_per_cu(int n_dof, bool has_prismatic);
 uint32_t pair_kernel_edges_per_wave();
 rkh_status launch_pair_counts(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B,
