@@ -153,6 +153,34 @@ rkh_status rkh_state_derivative(rkh_scene* scene, const double* x, const double*
 /* manip_dk_proxy_env_impl::is_free's distance (ctrl/topologies/manip_free_workspace.hpp:79-99):
  * minimum proxy-pair distance for B states (apply_to_model + findMinimumDistance). */
 rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, double* dist);
+/* The records behind that distance: what proxy_query_pair_3D::findMinimumDistance()->getLastResult() and
+ * gatherCollisionPoints hold (geometry/proximity/proxy_query_model.cpp:376-400 and :402-421; proximity_record_3D.hpp:47-56).
+ *   point1 / point2   mPoint1 on the finder's shape1, mPoint2 on its shape2, world frame.
+ *   shape1 / shape2   the two shapes as indices into the shapes array given to rkh_scene_create, in the FINDER's order
+ *                     (createProxFinderList, :225-370: the plane first, else the sphere, else the capped cylinder; equal
+ *                     kinds: the robot's shape), not robot-then-environment.
+ *   Finder order      i-major over the robot shapes, j-minor over the environment shapes, each in the caller's order.
+ * rkh_min_distance_records, for B states: the winning finder's record.  The loop of :384-397 takes a new minimum only on
+ * a strictly smaller distance and its bounding-sphere skip cannot drop a finder that would win (the shapes are bounded;
+ * rkh_scene_create enforces the plane rule), so the winner is the first finder in finder order among those at the
+ * minimum distance.  dist[b] is bit-identical to rkh_min_distance's.  A scene without finders: dist = +inf, shape ids
+ * 0xFFFFFFFF, points 0.
+ * rkh_collision_records, for B states: every finder whose bounding spheres are not apart (:409-411, "> 0.0" skips) and
+ * whose distance is < 0.0 (:414), in finder order.  n_found[b] counts them all and may exceed cap; the first cap of
+ * them are written to row b of the [B][cap] arrays; the slots behind them read dist +inf, shape ids 0xFFFFFFFF, points 0.
+ * No pointer may be NULL (RKH_ERR_BAD_ARG); B == 0 is RKH_OK.  RKH_ERR_UNSUPPORTED, with an error text: scenes with
+ * RKH_SHAPE_MESH shapes (the support-map query yields a distance and no points) and planar (2D) scenes
+ * (proxy_query_pair_2D's records are not built). */
+rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t B,
+                                    double* dist,      /* [B]    */
+                                    double* point1,    /* [B][3] */
+                                    double* point2,    /* [B][3] */
+                                    uint32_t* shape1,  /* [B]    */
+                                    uint32_t* shape2); /* [B]    */
+rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap,
+                                 uint32_t* n_found,                             /* [B] */
+                                 double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
+                                 uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
 /* steer_position_toward of the steerable dynamic free space (rkh_dyn_space) for B (a,b) pairs:
  * x_out [B][2n] last collision-free state, steps_free[B] accepted RK4 steps, record (optional)
  * [B][steps_per_edge+1][2n] the steer record. RK4 = runge_kutta4_integrate_impl

@@ -420,20 +420,33 @@ struct is_steerable_space_tag<kte_dynamic_free_space<P> > {
   static const bool value = true;
 };
 
-// ---- proximity socket: proxy_query_pair_3D::findMinimumDistance ----------------------------------------------------
+// ---- proximity socket: proxy_query_pair_3D::findMinimumDistance / gatherCollisionPoints ---------------------------
 // manip_dk_proxy_env_impl::is_free reads `findMinimumDistance()->getLastResult().mDistance`
 // (manip_free_workspace.hpp:85-95; proximity_finder_3D.hpp:49-82).  The device applies the state to the chain
-// (manip_direct_kin_map::apply_to_model) and evaluates every finder of the pair list in one call.
-struct proximity_record {  // proximity_record_3D (proximity_record_3D.hpp:47-56); points are not produced
+// (manip_direct_kin_map::apply_to_model), evaluates every finder of the pair list in one call and returns the winning
+// finder's whole record (rkh_min_distance_records), or the records of all colliding finders (rkh_collision_records).
+// Scenes whose records are not built (mesh shapes, planar chains: RKH_ERR_UNSUPPORTED from those entries) still answer
+// with the distance; their points are NaN and their shape indices no_shape.
+struct proximity_record {  // proximity_record_3D (proximity_record_3D.hpp:47-56)
+  double mPoint1[3] = {0.0, 0.0, 0.0};  // on the finder's shape1, world frame
+  double mPoint2[3] = {0.0, 0.0, 0.0};  // on its shape2
   double mDistance = std::numeric_limits<double>::infinity();
 };
 class hip_proximity_finder {
  public:
+  static const uint32_t no_shape = 0xFFFFFFFFu;
   explicit hip_proximity_finder(double d) { m_last.mDistance = d; }
+  hip_proximity_finder(const proximity_record& r, uint32_t shape1, uint32_t shape2)
+      : m_last(r), m_shape1(shape1), m_shape2(shape2) {}
   const proximity_record& getLastResult() const { return m_last; }
+  // proximity_finder_3D::getShape1 / getShape2 as indices into the shapes array the scene was created from, in the
+  // finder's own order (the plane first, else the sphere, else the capped cylinder)
+  uint32_t getShape1Index() const { return m_shape1; }
+  uint32_t getShape2Index() const { return m_shape2; }
 
  private:
   proximity_record m_last;
+  uint32_t m_shape1 = no_shape, m_shape2 = no_shape;
 };
 class hip_proxy_query_pair {
  public:
@@ -445,9 +458,44 @@ class hip_proxy_query_pair {
   }
   std::shared_ptr<hip_proximity_finder> findMinimumDistance() const {
     if (rkh_scene_num_pairs(m_scene.get()) == 0) return std::shared_ptr<hip_proximity_finder>();  // empty finder list
-    double d = 0.0;
-    check(rkh_min_distance(m_scene.get(), m_state.data(), 1, &d));
-    return std::make_shared<hip_proximity_finder>(d);
+    proximity_record r;
+    uint32_t s1 = hip_proximity_finder::no_shape, s2 = hip_proximity_finder::no_shape;
+    const rkh_status st =
+        rkh_min_distance_records(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
+    if (st == RKH_ERR_UNSUPPORTED) {  // no records for this kind of scene: the distance alone
+      check(rkh_min_distance(m_scene.get(), m_state.data(), 1, &r.mDistance));
+      for (int k = 0; k < 3; ++k) r.mPoint1[k] = r.mPoint2[k] = std::numeric_limits<double>::quiet_NaN();
+    } else {
+      check(st);
+    }
+    return std::make_shared<hip_proximity_finder>(r, s1, s2);
+  }
+  // proxy_query_pair_3D::gatherCollisionPoints (proxy_query_model.cpp:402-421): appends the records of all colliding
+  // finders in finder order, returns whether there is one.  shapes (optional) receives their (shape1, shape2) indices.
+  bool gatherCollisionPoints(std::vector<proximity_record>& aOutput,
+                             std::vector<std::pair<uint32_t, uint32_t> >* shapes = nullptr) const {
+    uint32_t cap = 8, n_found = 0;
+    std::vector<double> d, p1, p2;
+    std::vector<uint32_t> s1, s2;
+    for (;;) {  // grow until every colliding finder fits
+      d.resize(cap); p1.resize(3 * std::size_t(cap)); p2.resize(3 * std::size_t(cap));
+      s1.resize(cap); s2.resize(cap);
+      check(rkh_collision_records(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(), s1.data(),
+                                  s2.data()));
+      if (n_found <= cap) break;
+      cap = n_found;
+    }
+    for (uint32_t i = 0; i < n_found; ++i) {
+      proximity_record r;
+      for (int k = 0; k < 3; ++k) {
+        r.mPoint1[k] = p1[3 * std::size_t(i) + k];
+        r.mPoint2[k] = p2[3 * std::size_t(i) + k];
+      }
+      r.mDistance = d[i];
+      aOutput.push_back(r);
+      if (shapes) shapes->push_back(std::make_pair(s1[i], s2[i]));
+    }
+    return n_found > 0;
   }
 
  private:

@@ -84,6 +84,11 @@ rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2])
  * the environment at rkh_planner_create* switches the reuse off. */
 rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]);
 
+/* Kernel time of the distance query on B states: `runs` launches of rkh_min_distance's kernel (records == 0) or of
+ * rkh_min_distance_records' (records != 0) over the same device copy of x, each between two events on the context's
+ * stream; ms[runs] = the elapsed times.  No copies are timed (tools/measure_record_query.py). */
+rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

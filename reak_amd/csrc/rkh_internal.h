@@ -230,6 +230,15 @@ struct PairDev {
   uint16_t env;
   uint16_t pad;
 };
+// What the record queries report about pair p of d_pairs (same order): its place in the reference's finder list and the
+// caller's indices of the finder's (shape1, shape2).  rank = (robot shape) * n_env + (environment shape), both counted in
+// the order the caller gave them: i-major / j-minor like createProxFinderList (proxy_query_model.cpp:215-374), so ranks
+// order the finders as mProxFinders does (pairs without a finder leave gaps).
+struct PairIdDev {
+  uint32_t rank;
+  uint32_t shape1, shape2;
+};
+constexpr int kMaxRecordPairs = 128 * 64;  // collision_records_kernel keeps one bit per pair in two 64-bit masks per lane
 
 }  // namespace rkh
 
@@ -278,6 +287,7 @@ struct rkh_scene {
   rkh::SceneDev host;
   rkh::DeviceBuffer<rkh::SceneDev> d_scene;
   rkh::DeviceBuffer<rkh::PairDev> d_pairs;   // [n_pairs], sorted by routine
+  rkh::DeviceBuffer<rkh::PairIdDev> d_pair_ids;  // [n_pairs] (3D scenes): finder rank and the caller's shape indices
   rkh::DeviceBuffer<double> d_mesh_verts;    // vertex pool of the mesh shapes
   rkh::DeviceBuffer<int> d_err;
   rkh::DeviceBuffer<unsigned long long> d_clear_stats;  // [2] KernelGate::clear_stats of every steer launch on this scene
@@ -406,6 +416,19 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              uint32_t grid_b = 0, const EdgeIO* tab_a = nullptr, const EdgeIO* tab_b = nullptr,
                              uint32_t n_problems = 1);
+// The record queries (3D scenes without vertex-set shapes; chains with prismatic joints included): one launch each over
+// all n_pairs.  Outputs as in rkh.h, on the device.
+struct RecordOut {
+  uint32_t* n_found = nullptr;  // collision records only
+  double* dist = nullptr;
+  double* point1 = nullptr;
+  double* point2 = nullptr;
+  uint32_t* shape1 = nullptr;
+  uint32_t* shape2 = nullptr;
+};
+rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
+rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                    RecordOut out);
 // The same four compiled for chains with prismatic joints (propagate_prismatic.hip); the ones above hand these scenes on.
 namespace prismatic {
 rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,

@@ -163,7 +163,7 @@ void note_steer_mapping(SteerMapping m) { g_steer_mapping = m; }
 
 // the last step of both scene builders: the handle is the caller's only once everything is on the device
 static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, const std::vector<PairDev>& pairs,
-                               rkh_scene** out) {
+                               rkh_scene** out, const std::vector<PairIdDev>& pair_ids = std::vector<PairIdDev>()) {
   SceneDev& S = sc->host;
   sc->n_pairs = int(pairs.size());
   if (sc->n_pairs_verdict < 0 || sc->n_pairs_verdict > sc->n_pairs) sc->n_pairs_verdict = sc->n_pairs;
@@ -177,6 +177,11 @@ static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, cons
   RKH_HIP(hipMemcpy(sc->d_scene.get(), &S, sizeof(SceneDev), hipMemcpyHostToDevice));
   RKH_TRY(sc->d_pairs.alloc(std::max<size_t>(1, pairs.size())));
   if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs.get(), pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
+  if (pair_ids.size() == pairs.size() && !S.planar) {  // the record queries' table (3D scenes)
+    RKH_TRY(sc->d_pair_ids.alloc(std::max<size_t>(1, pair_ids.size())));
+    if (!pair_ids.empty())
+      RKH_HIP(hipMemcpy(sc->d_pair_ids.get(), pair_ids.data(), pair_ids.size() * sizeof(PairIdDev), hipMemcpyHostToDevice));
+  }
   RKH_TRY(sc->d_err.alloc_zeroed(1));
   RKH_TRY(sc->d_clear_stats.alloc_zeroed(2));
   *out = sc.release();
@@ -634,7 +639,20 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
   int n_verdict = 0;
   for (const PairDev& q : pairs) n_verdict += unreachable(q) ? 0 : 1;
   sc->n_pairs_verdict = n_verdict;
-  return upload_scene(ctx, std::move(sc), pairs, out);
+  // The record queries name a pair by the caller's shape indices and order the pairs as the reference's finder list
+  // does: the robot shapes kept the caller's order above, the environment shapes were sorted by closeness.
+  std::vector<uint32_t> env_rank(S.n_env, 0u);  // place of scene environment shape j among the caller's environment shapes
+  for (int j = 0; j < S.n_env; ++j)
+    for (int k = 0; k < S.n_env; ++k) env_rank[j] += env_src[k] < env_src[j] ? 1u : 0u;
+  std::vector<PairIdDev> pair_ids(pairs.size());
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    const PairDev& q = pairs[k];
+    const uint32_t rid = uint32_t(robot_src[q.robot]), eid = uint32_t(env_src[q.env]);
+    pair_ids[k].rank = uint32_t(q.robot) * uint32_t(S.n_env) + env_rank[q.env];
+    pair_ids[k].shape1 = q.s1_is_robot ? rid : eid;
+    pair_ids[k].shape2 = q.s1_is_robot ? eid : rid;
+  }
+  return upload_scene(ctx, std::move(sc), pairs, out, pair_ids);
 }
 
 rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n,
@@ -687,6 +705,16 @@ rkh_status check_err_flag(rkh_scene* scene) {
   }
   return RKH_OK;
 }
+// the record queries serve 3D scenes whose pairs all have a closed form
+rkh_status records_supported(const rkh_scene* scene, const char* entry) {
+  const char* why = scene->host.planar      ? "planar (2D) scenes: the records of proxy_query_pair_2D are not built"
+                    : scene->host.has_meshes ? "scenes with mesh shapes: the support-map (GJK) query yields a distance and no points"
+                    : scene->n_pairs > kMaxRecordPairs ? "more proxy pairs than the record kernels keep track of"
+                                                       : nullptr;
+  if (!why) return RKH_OK;
+  set_error(std::string(entry) + ": not supported for " + why);
+  return RKH_ERR_UNSUPPORTED;
+}
 }  // namespace
 
 extern "C" {
@@ -725,6 +753,116 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
   RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
   RKH_TRY(launch_min_distance(s, *scene, dx.get(), B, dd.get()));
   RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
+}
+
+rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
+                                    double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_supported(scene, "rkh_min_distance_records"));
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dd.alloc(size_t(B)));
+  RKH_TRY(dp1.alloc(size_t(B) * 3));
+  RKH_TRY(dp2.alloc(size_t(B) * 3));
+  RKH_TRY(ds1.alloc(size_t(B)));
+  RKH_TRY(ds2.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch_min_distance_records(s, *scene, dx.get(), B, out));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms) {
+  if (!scene || !x || !ms || B == 0) return RKH_ERR_BAD_ARG;
+  if (records) RKH_TRY(records_supported(scene, "rkh_diag_distance_query_ms"));
+  const int n = scene->host.n_dof;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dd.alloc(size_t(B)));
+  RKH_TRY(dp1.alloc(size_t(B) * 3));
+  RKH_TRY(dp2.alloc(size_t(B) * 3));
+  RKH_TRY(ds1.alloc(size_t(B)));
+  RKH_TRY(ds2.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  RKH_HIP(hipEventCreate(&e0));
+  RKH_HIP(hipEventCreate(&e1));
+  rkh_status st = RKH_OK;
+  for (uint32_t r = 0; r < runs && st == RKH_OK; ++r) {
+    hipError_t err = hipEventRecord(e0, s);
+    st = records ? launch_min_distance_records(s, *scene, dx.get(), B, out) : launch_min_distance(s, *scene, dx.get(), B, dd.get());
+    if (err == hipSuccess) err = hipEventRecord(e1, s);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms[r], e0, e1);
+    if (err != hipSuccess && st == RKH_OK) {
+      set_error(std::string("rkh_diag_distance_query_ms: ") + hipGetErrorString(err));
+      st = RKH_ERR_DEVICE;
+    }
+  }
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  return st;
+}
+
+rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found, double* dist,
+                                 double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_supported(scene, "rkh_collision_records"));
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  const size_t slots = size_t(B) * cap;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> dn, ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dn.alloc(size_t(B)));
+  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 3)));
+  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 3)));
+  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.n_found = dn.get();
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch_collision_records(s, *scene, dx.get(), B, cap, out));
+  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  if (slots) {
+    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
+  }
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }

@@ -81,9 +81,9 @@ EXPORTS = [
     "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
     "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
-    "rkh_min_distance", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
+    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
-    "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
+    "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
     "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
 ]
@@ -145,6 +145,9 @@ def load():
     lib.rkh_scene_num_pairs.argtypes = [vp]
     lib.rkh_state_derivative.argtypes = [vp, dp, dp, u32, dp, dp, dp]
     lib.rkh_min_distance.argtypes = [vp, dp, u32, dp]
+    lib.rkh_min_distance_records.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
+    lib.rkh_collision_records.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
+    lib.rkh_diag_distance_query_ms.argtypes = [vp, dp, u32, C.c_int, u32, C.POINTER(C.c_float)]
     lib.rkh_propagate.argtypes = [vp, C.POINTER(T.DynSpace), dp, dp, u32, d, dp, u32p, dp]
     lib.rkh_diag_feval_cycles.argtypes = [vp, dp, dp, u32, C.c_int, C.POINTER(C.c_uint64)]
     lib.rkh_diag_proximity_counts.argtypes = [vp, dp, u32, C.POINTER(C.c_uint64)]
@@ -398,6 +401,40 @@ class Scene:
         d = np.zeros(x.shape[0])
         _check(self.lib.rkh_min_distance(self.h, T.dptr(x), x.shape[0], T.dptr(d)))
         return d
+
+    def min_distance_records(self, x):
+        """proxy_query_pair_3D::findMinimumDistance()->getLastResult() per state (rkh_min_distance_records): dist [B],
+        point1 / point2 [B][3] (world frame, on the finder's shape1 / shape2), shape1 / shape2 [B] (indices into the
+        scenario's shapes, in the finder's order; 0xFFFFFFFF without finders)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B = x.shape[0]
+        d, p1, p2 = np.zeros(B), np.zeros((B, 3)), np.zeros((B, 3))
+        s1, s2 = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        _check(self.lib.rkh_min_distance_records(self.h, T.dptr(x), B, T.dptr(d), T.dptr(p1), T.dptr(p2), T.u32ptr(s1),
+                                                 T.u32ptr(s2)))
+        return {"dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def distance_query_ms(self, x, records, runs):
+        """Kernel times [runs] in ms of the distance query (records=False) or the record query (True) on the states x,
+        events around each launch (rkh_diag_distance_query_ms)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        ms = np.zeros(int(runs), dtype=np.float32)
+        _check(self.lib.rkh_diag_distance_query_ms(self.h, T.dptr(x), x.shape[0], 1 if records else 0, int(runs),
+                                                   ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
+
+    def collision_records(self, x, cap):
+        """proxy_query_pair_3D::gatherCollisionPoints per state (rkh_collision_records): n_found [B] (all colliding
+        finders, may exceed cap) and the first cap records in finder order: dist [B][cap], point1 / point2 [B][cap][3],
+        shape1 / shape2 [B][cap]; unused slots hold +inf, zeros and 0xFFFFFFFF."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B, cap = x.shape[0], int(cap)
+        n = np.zeros(B, dtype=np.uint32)
+        d, p1, p2 = np.zeros((B, cap)), np.zeros((B, cap, 3)), np.zeros((B, cap, 3))
+        s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
+        _check(self.lib.rkh_collision_records(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1), T.dptr(p2),
+                                              T.u32ptr(s1), T.u32ptr(s2)))
+        return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
 
     def move_position_toward(self, lower, upper, min_interval, a, b, fraction=1.0):
         """manip_quasi_static_env::move_position_toward for B (a,b) joint-position pairs (rkh_edge_check)."""
