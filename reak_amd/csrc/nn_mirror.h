@@ -9,10 +9,58 @@
 // a sweep reads 32 bytes per vertex where the fp64 rows are 8 Dp.  The mirror is written where rows are written
 // (commit_kernel, planner.hip); rows past the end of a tree and removed vertices are PAD rows (coordinates 0, n0 =
 // 60000): their estimate is 60000, above every real one while Dp (2 M)^2 < 60000.
+//
+// The OPEN LISTS of the sweep's second pass and the arithmetic of its work items are stated here once, for the device
+// and for a host compiler (tests/cpp/nn_open_plan_test.cpp reads this header without HIP: everything below the plan is
+// device code and only visible to hipcc).
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
+
+#ifndef RKH_HD
+#ifdef __HIPCC__
+#define RKH_HD __host__ __device__ __forceinline__
+#else
+#define RKH_HD inline
+#endif
+#endif
+
+namespace rkh {
+
+// ---- pass 2 of the sweep (nn_mirror.hip): which (row slice, query) pairs it visits, and how a block takes its share
+constexpr uint32_t kMirrorGroups = 12;                   // query groups of 32 a block keeps in registers
+constexpr uint32_t kMirrorQueries = 32 * kMirrorGroups;  // 384
+
+// Pass 1 leaves est = the smallest estimate of a row slice for a query, the thr kernel the query's threshold thr
+// (smallest estimate over all slices + band; +inf for an empty tree).  Pass 2 recomputes the SAME estimates, so a slice
+// holds a row with c <= thr iff est <= thr: only then is the query OPEN in the slice.  thr = +inf opens every slice
+// (est = +inf included); thr = -inf (a pad slot) opens none; a NaN on either side opens none, as c <= thr records none.
+RKH_HD bool mirror_open(float est, float thr) { return est <= thr; }
+
+// Block `block` of a row slice takes the entries [first, first + count) of that slice's query list (of `listed`
+// entries: the open list, or the whole batch when the lists are off) as `groups` groups of 32; the last group's `pad`
+// slots repeat the block's last entry as an operand and never record (threshold -inf).  count == 0: no work, the block
+// leaves.
+struct MirrorOpenItem {
+  uint32_t first, count, groups, pad;
+};
+RKH_HD MirrorOpenItem mirror_open_item(uint32_t listed, uint32_t block) {
+  MirrorOpenItem it;
+  it.first = block * kMirrorQueries;
+  it.count = it.first < listed ? (listed - it.first < kMirrorQueries ? listed - it.first : kMirrorQueries) : 0u;
+  it.groups = (it.count + 31u) >> 5;
+  it.pad = 32u * it.groups - it.count;
+  return it;
+}
+// the list entry slot `slot` (< 32 * groups) of an item reads, and whether the slot may record
+RKH_HD uint32_t mirror_open_entry(const MirrorOpenItem& it, uint32_t slot) {
+  return it.first + (slot < it.count ? slot : it.count - 1u);
+}
+RKH_HD bool mirror_open_slot_live(const MirrorOpenItem& it, uint32_t slot) { return slot < it.count; }
+
+}  // namespace rkh
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 
 namespace rkh {
 
@@ -81,3 +129,4 @@ __device__ __forceinline__ void mirror_store_row(uint4* __restrict__ mirror, uin
 }
 
 }  // namespace rkh
+#endif  // __HIPCC__

@@ -22,7 +22,21 @@
 //     ordered-integer atomicMin per lane and spent most of its time there); nn1_mirror_thr_kernel turns the minimum over
 //     the slices into the query's threshold; PASS 2 repeats the sweep -- same operands, same instruction, bit-identical
 //     estimates -- against that FIXED threshold and appends the rows below it to the query's list;
-//     nn1_mirror_resolve_kernel evaluates those exactly.
+//     nn1_mirror_resolve_kernel evaluates those exactly;
+//   * pass 2 only where a query is OPEN: its estimates are pass 1's, so a slice whose minimum est[slice][q] lies above
+//     thr[q] holds no row for q's list (mirror_open, nn_mirror.h).  The thr kernel, which reads every est anyway, writes
+//     per (tree, slice) the list of the open queries and its length; a pass-2 block takes its queries from the list of
+//     its slice (mirror_open_item) and leaves when the list has no block for it.  On planner trees a query is open in
+//     one slice, rarely two: a block's 12 groups become one or two, and pass 2 approaches one read of the mirror.
+//     The order of a list influences no result: lists of rows are filled by atomics and the resolve kernel decides by
+//     (distance, index).  RKH_NN_MIRROR_OPEN=0 keeps the pass over all queries (the lists are then not built).
+//   * where the lists live: in rows of their own behind est (nn1_mirror_query_bytes() grows by 2 bytes per slice and
+//     query slot for the entries, 16-bit query numbers, and 16 per slot for the 32 lengths), not in the est rows they
+//     would fit into once the thresholds are known.  Reuse in place needs every read of a tree's est to precede every
+//     write -- a whole tree's est in one block's registers or LDS, 128 KB at 4096 queries x 32 slices -- and saves 80
+//     bytes per query slot of an arena that holds megabytes per tree.  One block per tree builds the lists (ballot,
+//     prefix over its four waves, plain stores), so the lengths need no zeroing between rounds and the lists come out
+//     in query order.
 //
 // Error bound.  x_h, q_h = half(float(x)), half(float(q)) per coordinate.  The rounding errors are MEASURED, not bounded:
 //   dx = max over the rows of a tree of |x - x_h| (kept per tree: mirror_store_row's callers raise it, ordered-integer
@@ -42,6 +56,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -58,8 +73,8 @@ namespace {
 typedef float mir_f16v __attribute__((ext_vector_type(16)));
 typedef _Float16 mir_h8 __attribute__((ext_vector_type(8)));
 
-constexpr int kMirG = 12;                  // query groups of 32 per block
-constexpr int kMirQueries = 32 * kMirG;    // 384
+constexpr int kMirG = int(kMirrorGroups);     // query groups of 32 per block
+constexpr int kMirQueries = int(kMirrorQueries);  // 384
 constexpr int kMirThreads = 256;           // four waves: the same queries, every fourth slab of the block's slice each
 constexpr uint32_t kMirCandCap = 32;       // candidate rows kept per query (more: the exact scan of the resolve kernel)
 constexpr uint32_t kMirMaxSlices = 32;     // row slices per tree (rows of NnArgs::est)
@@ -97,35 +112,78 @@ __global__ __launch_bounds__(256) void nn1_mirror_prep_kernel(const NnArgs* __re
   qi3[2] = sqrt(qn2) * (1.0 + 1e-12);
 }
 
-// ---- between the passes: threshold of a query = (minimum over the row slices) + band
+// ---- between the passes: threshold of a query = (minimum over the row slices) + band; with open_lists, the list of the
+// open queries of every slice (NnArgs::open_list, open_cnt).  Lists: grid (1, trees), the block walks its tree's queries
+// 256 at a time and appends each slice's open ones in query order -- ballot per wave, prefix over the four waves in
+// LDS, plain stores, so nothing needs to be zero when the kernel starts.  Without: grid (ceil(B / 256), trees).
 __global__ __launch_bounds__(256) void nn1_mirror_thr_kernel(const NnArgs* __restrict__ table, uint32_t gx,
-                                                             double x_norm_bound) {
+                                                             double x_norm_bound, uint32_t open_lists) {
+  __shared__ uint32_t s_cnt[4][kMirMaxSlices];  // open queries of the current 256 per (wave, slice)
+  __shared__ uint32_t s_len[kMirMaxSlices];     // list lengths so far (entry sl is thread sl's alone)
   const NnArgs a = table[blockIdx.y];
   const uint32_t B = a.d_B ? *a.d_B : a.B;
-  const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
-  if (qi >= B) return;
-  float cmin = INFINITY;
-  for (uint32_t sl = 0; sl < gx; ++sl) cmin = __builtin_fminf(cmin, a.est[uint64_t(sl) * a.est_stride + qi]);
-  const double* __restrict__ qi3 = a.qinfo + uint64_t(qi) * 3;
-  const double qh2 = qi3[0], dq = qi3[1], qn = qi3[2];
-  const double dx = double(__uint_as_float(*a.dx_max_bits)) * (1.0 + 1e-6);
-  const double delta = dx + dq;
-  const double X = x_norm_bound * (1.0 + 1e-3);  // |x_h| <= |x| (1 + 2^-11)
-  const double eps = 1.9073486328125e-06 * (X * X + 2.0 * X * qn) + 1e-9;
-  const double base = fmax(0.0, double(cmin) + qh2) + 2.0 * delta * delta + eps;
-  const double d_up = delta + sqrt(base) * (1.0 + 1e-12);
-  const double E = 2.0 * d_up * delta + delta * delta + eps;
-  const double band = 2.0 * E * (1.0 + 1e-9);
-  // (+inf, an empty tree, stays +inf: every row is a candidate and the resolve kernel sorts it out)
-  a.thr[qi] = cmin < INFINITY ? __double2float_ru(double(cmin) + band) : INFINITY;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid < kMirMaxSlices) s_len[tid] = 0u;
+  for (uint32_t qb = blockIdx.x * 256u; qb < B; qb += gridDim.x * 256u) {  // (B is uniform: whole blocks iterate)
+    const uint32_t qi = qb + tid;
+    const bool live = qi < B;
+    float thr = -INFINITY;
+    float est[kMirMaxSlices];  // the query's minima, read once (slices past gx: +inf, open nowhere but in an empty tree's
+                               // lists, which the loops below do not visit)
+#pragma unroll
+    for (uint32_t sl = 0; sl < kMirMaxSlices; ++sl)
+      est[sl] = (live && sl < gx) ? a.est[uint64_t(sl) * a.est_stride + qi] : INFINITY;
+    if (live) {
+      float cmin = INFINITY;
+#pragma unroll
+      for (uint32_t sl = 0; sl < kMirMaxSlices; ++sl) cmin = __builtin_fminf(cmin, est[sl]);
+      const double* __restrict__ qi3 = a.qinfo + uint64_t(qi) * 3;
+      const double qh2 = qi3[0], dq = qi3[1], qn = qi3[2];
+      const double dx = double(__uint_as_float(*a.dx_max_bits)) * (1.0 + 1e-6);
+      const double delta = dx + dq;
+      const double X = x_norm_bound * (1.0 + 1e-3);  // |x_h| <= |x| (1 + 2^-11)
+      const double eps = 1.9073486328125e-06 * (X * X + 2.0 * X * qn) + 1e-9;
+      const double base = fmax(0.0, double(cmin) + qh2) + 2.0 * delta * delta + eps;
+      const double d_up = delta + sqrt(base) * (1.0 + 1e-12);
+      const double E = 2.0 * d_up * delta + delta * delta + eps;
+      const double band = 2.0 * E * (1.0 + 1e-9);
+      // (+inf, an empty tree, stays +inf: every row is a candidate and the resolve kernel sorts it out)
+      thr = cmin < INFINITY ? __double2float_ru(double(cmin) + band) : INFINITY;
+      a.thr[qi] = thr;
+    }
+    if (!open_lists) continue;
+    // the slices the query is open in, one bit each; a query slot past the batch is never open
+    uint32_t open_mask = 0u;
+#pragma unroll
+    for (uint32_t sl = 0; sl < kMirMaxSlices; ++sl) open_mask |= (live && mirror_open(est[sl], thr)) ? (1u << sl) : 0u;
+    for (uint32_t sl = 0; sl < gx; ++sl) {
+      const unsigned long long m = __ballot(((open_mask >> sl) & 1u) != 0u);
+      if (lane == 0) s_cnt[wave][sl] = uint32_t(__builtin_popcountll(m));
+    }
+    __syncthreads();
+    for (uint32_t sl = 0; sl < gx; ++sl) {
+      const bool o = ((open_mask >> sl) & 1u) != 0u;
+      const unsigned long long m = __ballot(o);
+      uint32_t pos = s_len[sl] + uint32_t(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
+      for (uint32_t w = 0; w < wave; ++w) pos += s_cnt[w][sl];
+      if (o) a.open_list[uint64_t(sl) * a.est_stride + pos] = uint16_t(qi);  // pos < B: at most one entry per query
+    }
+    __syncthreads();
+    if (tid < gx) s_len[tid] += s_cnt[0][tid] + s_cnt[1][tid] + s_cnt[2][tid] + s_cnt[3][tid];
+    __syncthreads();
+  }
+  if (open_lists && tid < gx) a.open_cnt[tid] = s_len[tid];  // (also for a tree without queries: no stale list is read)
 }
 
 // PASS 1: minimum of the estimates per (slice, query) -> NnArgs::est.  PASS 2: rows at or below NnArgs::thr -> lists.
-// Work items as in the bf16 sweep (nn_xcd_item), always with a query-block prefix.
+// Work items as in the bf16 sweep (nn_xcd_item), always with a query-block prefix.  PASS 2 with open_lists: item (bx, by)
+// is block by of the open list of slice bx (mirror_open_item); the grid is still the host's bound of one block per 384
+// queries of the batch and slice, a block past its slice's list leaves.
 template <int PASS>
 __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_kernel(const NnArgs* __restrict__ table,
                                                                     const uint32_t* __restrict__ yblock_base,
-                                                                    uint32_t n_problems, uint32_t gx) {
+                                                                    uint32_t n_problems, uint32_t gx,
+                                                                    uint32_t open_lists) {
   __shared__ float wave_min[PASS == 1 ? kMirThreads / 64 : 1][PASS == 1 ? kMirQueries : 1];
   uint32_t bx, by, bz;
   __builtin_assume(yblock_base != nullptr);
@@ -135,12 +193,21 @@ __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_ker
   const uint4* __restrict__ qfrag = nn_uniform(a.qfrag);
   const uint32_t n = nn_uniform(a.d_n ? *a.d_n : uint32_t(a.n));
   const uint32_t B = nn_queries(a);
-  const uint32_t q0 = by * uint32_t(kMirQueries);
-  if (q0 >= B) return;
+  // the block's queries: entries [q0, q0 + it.count) of the batch, or of the open list of its slice (uniform)
+  const uint16_t* __restrict__ olist = nullptr;
+  uint32_t listed = B;
+  if (PASS == 2 && open_lists) {
+    olist = nn_uniform(a.open_list) + uint64_t(bx) * a.est_stride;
+    listed = nn_uniform(a.open_cnt[bx]);
+  }
+  const MirrorOpenItem it = mirror_open_item(listed, by);
+  if (it.count == 0u) return;
+  const uint32_t q0 = it.first;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, hi = lane >> 5;
-  const int ng = int(((B - q0 < uint32_t(kMirQueries) ? B - q0 : uint32_t(kMirQueries)) + 31u) >> 5);  // uniform
+  const int ng = int(it.groups);  // uniform
+  const uint32_t qcol = q0 + uint32_t(col);  // the lane's entry of group 0
 
   // B operands: lane (col, hi) holds slots 8 hi .. 8 hi + 7 of query q0 + 32 g + col
   uint4 bop[kMirG];
@@ -150,10 +217,11 @@ __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_ker
     bop[g] = make_uint4(0u, 0u, 0u, 0u);
     thr[g] = PASS == 1 ? INFINITY : -INFINITY;
     if (g < ng) {
-      const uint32_t qi = q0 + 32u * uint32_t(g) + uint32_t(col);
-      const uint32_t qsrc = qi < B ? qi : (B - 1u);
+      const uint32_t slot = 32u * uint32_t(g) + uint32_t(col);
+      const uint32_t e = mirror_open_entry(it, slot);
+      const uint32_t qsrc = (PASS == 2 && olist) ? uint32_t(olist[e]) : e;
       bop[g] = qfrag[uint64_t(qsrc) * 2 + uint32_t(hi)];
-      if (PASS == 2) thr[g] = qi < B ? a.thr[qsrc] : -INFINITY;  // a query slot past the batch never records
+      if (PASS == 2) thr[g] = mirror_open_slot_live(it, slot) ? a.thr[qsrc] : -INFINITY;  // a pad slot never records
     }
   }
 
@@ -189,7 +257,12 @@ __global__ __launch_bounds__(kMirThreads, PASS == 1 ? 4 : 3) void nn1_mirror_ker
       // through one untaken scalar branch (a per-lane `if` compiles to a TAKEN exec-mask branch around the inlined
       // slow path in every block: pass 2 then ran at 0.4 of pass 1's speed)
       if (__builtin_expect(__any(m <= thr[g]), 0) && m <= thr[g]) {
-        const uint32_t qi = q0 + 32u * uint32_t(g) + uint32_t(col);
+        // the real query, read again from the list.  (The empty asm keeps this path's address arithmetic inside it:
+        // hoisted out of the slab loop it holds two registers per group through the sweep, and the kernel spills.)
+        uint32_t e = qcol;
+        asm volatile("" : "+v"(e));
+        e += 32u * uint32_t(g);
+        const uint32_t qi = olist ? uint32_t(olist[e]) : e;
         const uint32_t row0 = slab * 32u + 4u * uint32_t(hi);
         uint32_t mask = 0u;
 #pragma unroll
@@ -337,8 +410,12 @@ uint32_t nn1_mirror_cand_cap() { return kMirCandCap; }
 uint32_t nn1_mirror_max_slices() { return kMirMaxSlices; }
 size_t nn1_mirror_bytes(uint64_t capacity_rows) { return size_t((capacity_rows + 31) / 32) * 1024; }
 // per-query scratch of a tree's sweeps, in bytes per query slot: B operand (32) + qinfo (24) + threshold (4) +
-// candidate count (4) + candidate rows + the per-slice minima
-size_t nn1_mirror_query_bytes() { return 32 + 24 + 4 + 4 + 4 * size_t(kMirCandCap) + 4 * size_t(kMirMaxSlices); }
+// candidate count (4) + candidate rows + the per-slice minima + the per-slice open lists (16-bit entries) + 16 for the
+// lists' lengths (4 * kMirMaxSlices bytes per tree, and b_max >= 8)
+static_assert(kMirMaxSlices * sizeof(uint32_t) <= 8 * 16, "the open lists' lengths take 16 bytes of 8 query slots");
+size_t nn1_mirror_query_bytes() {
+  return 32 + 24 + 4 + 4 + 4 * size_t(kMirCandCap) + 4 * size_t(kMirMaxSlices) + 2 * size_t(kMirMaxSlices) + 16;
+}
 // carve a block of nn1_mirror_query_bytes() * b_max bytes (b_max a multiple of 8, base 256-byte aligned) into the
 // per-query arrays of `a`
 void nn1_mirror_carve(void* base, uint32_t b_max, NnArgs* a) {
@@ -355,6 +432,19 @@ void nn1_mirror_carve(void* base, uint32_t b_max, NnArgs* a) {
   p += size_t(b_max) * 4 * kMirCandCap;
   a->est = reinterpret_cast<float*>(p);
   a->est_stride = b_max;
+  p += size_t(b_max) * 4 * kMirMaxSlices;
+  a->open_list = reinterpret_cast<uint16_t*>(p);  // rows of est_stride entries, like est
+  p += size_t(b_max) * 2 * kMirMaxSlices;
+  a->open_cnt = reinterpret_cast<uint32_t*>(p);
+}
+
+// RKH_NN_MIRROR_OPEN=0: pass 2 over all queries of the batch, as before the open lists (results are the same).  A
+// planner reads the switch once, when it is created (tune_planner).  rkh_diag_nn_mirror_query has no handle to keep
+// it in and reads it again at every call, on purpose: tests/test_nn_mirror_open_gpu.py compares the two forms in one
+// process.
+bool nn1_mirror_open_lists() {
+  const char* e = getenv("RKH_NN_MIRROR_OPEN");
+  return !e || atoi(e) != 0;
 }
 
 // does the mirror sweep take this problem shape?
@@ -383,9 +473,10 @@ rkh_status launch_mirror_build(hipStream_t s, void* d_mirror, const double* d_po
 // d_yblock_base: [n_problems + 1] exclusive prefix of ceil(B_p / nn1_mirror_queries()); n_upper / B_upper (host bounds)
 // only size the grids; x_norm_bound >= |x| for every vertex.  ev0 / ev1 bracket all five launches.
 rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32_t n_problems, uint64_t n_upper,
-                             uint32_t B_upper, double x_norm_bound, const uint32_t* d_yblock_base, hipEvent_t ev0,
-                             hipEvent_t ev1) {
+                             uint32_t B_upper, double x_norm_bound, const uint32_t* d_yblock_base, bool open_lists,
+                             hipEvent_t ev0, hipEvent_t ev1) {
   if (B_upper == 0 || n_problems == 0) return RKH_OK;
+  if (B_upper > 0xFFFFu) open_lists = false;  // (list entries are 16-bit query numbers; a planner's batch is <= 4096)
   const uint32_t gy = (B_upper + kMirQueries - 1) / kMirQueries;
   const uint64_t slabs = (n_upper + 31) / 32;
   // row slices per tree: ~8 k blocks over the whole grid, at least 32 slabs (8 per wave) per block
@@ -398,9 +489,12 @@ rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32
   nn_set_last_kernel_name("nn1_mirror_kernel");
   if (ev0) (void)hipEventRecord(ev0, s);
   hipLaunchKernelGGL(nn1_mirror_prep_kernel, qgrid, dim3(256), 0, s, d_table, D);
-  hipLaunchKernelGGL((nn1_mirror_kernel<1>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx));
-  hipLaunchKernelGGL(nn1_mirror_thr_kernel, qgrid, dim3(256), 0, s, d_table, uint32_t(gx), x_norm_bound);
-  hipLaunchKernelGGL((nn1_mirror_kernel<2>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx));
+  hipLaunchKernelGGL((nn1_mirror_kernel<1>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx),
+                     0u);
+  hipLaunchKernelGGL(nn1_mirror_thr_kernel, open_lists ? dim3(1, n_problems) : qgrid, dim3(256), 0, s, d_table, uint32_t(gx),
+                     x_norm_bound, open_lists ? 1u : 0u);
+  hipLaunchKernelGGL((nn1_mirror_kernel<2>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx),
+                     open_lists ? 1u : 0u);
   const dim3 rgrid((B_upper + 15) / 16, n_problems);
   switch (nn_padded_dims(D)) {
     case 2: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<2>), rgrid, dim3(256), 0, s, d_table, D); break;
@@ -465,7 +559,8 @@ extern "C" rkh_status rkh_diag_nn_mirror_query(rkh_ctx* ctx, const double* pts, 
   RKH_HIP(hipMemcpy(d_tab.get(), &a, sizeof(a), hipMemcpyHostToDevice));
   RKH_TRY(launch_mirror_fill(s, d_mirror.get(), n));
   RKH_TRY(launch_mirror_build(s, d_mirror.get(), d_pos.get(), n, D, DP, d_dx.get()));
-  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, d_yb.get(), nullptr, nullptr));
+  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, d_yb.get(),
+                            nn1_mirror_open_lists(), nullptr, nullptr));
   RKH_HIP(hipStreamSynchronize(s));
   RKH_HIP(hipMemcpy(idx, d_idx.get(), size_t(B) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   RKH_HIP(hipMemcpy(dist, d_dist.get(), size_t(B) * sizeof(double), hipMemcpyDeviceToHost));

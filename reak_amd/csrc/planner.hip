@@ -282,6 +282,86 @@ __global__ __launch_bounds__(256) void fixup_kernel(const ProblemDev* __restrict
   if (lane == 0 && sqrt(smin) < pr.nn_dist[b]) atomicMin(&st->F, b);
 }
 
+// The same verdict with every accepted end state read from global memory once per block and row tile instead of once per
+// candidate: a block takes kFixCands consecutive candidates of one problem, lane l of each of its four waves candidate
+// b0 + l, and walks the rows below them in tiles of fix_rows<DP>().  Of a tile only the ACCEPTED rows are staged in LDS,
+// packed in row order (ballot per wave, prefix over the waves), with their row numbers; wave w then takes the staged
+// rows w, w + 4, ... -- all lanes read the same row, an LDS broadcast -- and a lane keeps a row's distance if the row
+// lies below its candidate.  The four waves' minima meet in LDS.  A minimum does not depend on the order, every distance
+// is nn_exact_sq of the same operands: F is what fixup_kernel finds.
+constexpr uint32_t kFixCands = 64;
+template <int DP>
+constexpr uint32_t fix_rows() { return DP <= 16 ? 256u : 128u; }  // 24 .. 32 KB of rows per block
+
+template <int DP>
+__global__ __launch_bounds__(256) void fixup_tiled_kernel(const ProblemDev* __restrict__ probs, int D) {
+  constexpr uint32_t TR = fix_rows<DP>();
+  __shared__ __attribute__((aligned(16))) double s_row[TR][DP];
+  __shared__ uint32_t s_j[TR];
+  __shared__ uint32_t s_cnt[4];
+  __shared__ double s_min[4][kFixCands];
+  __shared__ uint32_t s_F;
+  const ProblemDev pr = probs[blockIdx.y];
+  PlannerState* st = pr.st;
+  const uint32_t B = st->B;
+  const uint32_t b0 = blockIdx.x * kFixCands;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (b0 >= B) return;  // (uniform: B and b0 are the block's)
+  // F only ever decreases (atomicMin), down to the smallest candidate whose test succeeds.  If the value read here is
+  // at or below b0, the final F is too, and no candidate of this tile can lower it: the tile is not needed.  A stale
+  // (larger) value only means the tile is evaluated although it could have been skipped.  Other blocks of the problem
+  // lower F while this one starts, so ONE thread reads it and the whole block decides on that word: the exit is
+  // block-uniform, no wave meets a barrier the others have left.
+  if (tid == 0) s_F = st->F;
+  __syncthreads();
+  if (b0 >= s_F) return;
+  const uint32_t b = b0 + lane;  // (b >= B, b == 0: no row lies below, or the result is not used)
+  const uint32_t b_end = b0 + kFixCands < B ? b0 + kFixCands : B;
+  const uint32_t j_end = b_end - 1u;  // rows [0, j_end) lie below some candidate of the tile
+  const double* q = pr.samples + (uint64_t(st->s0) + (b < B ? b : b0)) * D;
+  double qv[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) qv[d] = d < D ? q[d] : 0.0;
+  double smin = INFINITY;
+  for (uint32_t r0 = 0; r0 < j_end; r0 += TR) {
+    const uint32_t j = r0 + tid;
+    const bool acc = tid < TR && j < j_end && pr.accept[j] != 0;
+    const unsigned long long m = __ballot(acc);
+    if (lane == 0) s_cnt[wave] = uint32_t(__builtin_popcountll(m));
+    __syncthreads();
+    uint32_t slot = uint32_t(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
+    for (uint32_t w = 0; w < wave; ++w) slot += s_cnt[w];
+    const uint32_t staged = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (acc) {
+      const double* p = pr.x_out + uint64_t(j) * D;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) s_row[slot][d] = nn_qcoord(p, d, D);
+      s_j[slot] = j;
+    }
+    __syncthreads();
+    for (uint32_t k = wave; k < staged; k += 4) {
+      const double* __restrict__ x = s_row[k];
+      const double s = nn_exact_sq<DP>([&](int d) { return qv[d] - x[d]; });
+      if (s_j[k] < b && s < smin) smin = s;
+    }
+    __syncthreads();  // (the next tile overwrites the staged rows and counts)
+  }
+  s_min[wave][lane] = smin;
+  __syncthreads();
+  if (wave == 0) {
+    smin = s_min[0][lane];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const double o = s_min[w][lane];
+      if (o < smin) smin = o;
+    }
+    const bool hit = b < B && sqrt(smin) < pr.nn_dist[b < B ? b : 0u];
+    // lanes are candidates in order: the first hit is the tile's smallest
+    const unsigned long long hits = __ballot(hit);
+    if (hits && lane == uint32_t(__builtin_ctzll(hits))) atomicMin(&st->F, b);
+  }
+}
+
 // One 256-thread block per problem: commit candidates [0, F) in order (prefix scan of the accept flags),
 // honouring the vertex budget of keep_going() (motion_planner_base.hpp:355-374).
 // probe_granule: goal probes ride in the next steer launch in whole groups of this many (32 = one steer wave of the
@@ -653,6 +733,8 @@ struct rkh_planner {
   EdgeIO* d_io_steer = nullptr;
   EdgeIO* d_io_probe = nullptr;
   bool nn_mirror = false;  // the NN search of a round runs over the trees' half-precision mirrors (nn_mirror.hip)
+  bool nn_open = true;     // ... its second pass only where a query is open (RKH_NN_MIRROR_OPEN)
+  bool fixup_tiled = true; // the fix-up stages accepted end states in LDS (RKH_FIXUP_TILED; 0: one wave per candidate)
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
   // Step-wise steer launches (propagate_pair_step_kernel): one launch per RK4 step over the live edges of all problems,
   // survivors handed on through two ping-pong lists.
@@ -768,7 +850,11 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
 
 template <int DP>
 void launch_fixup(rkh_planner* p, uint32_t batch_ub) {
-  hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
+  if (p->fixup_tiled)
+    hipLaunchKernelGGL((fixup_tiled_kernel<DP>), dim3((batch_ub + kFixCands - 1) / kFixCands, p->P), dim3(256), 0, p->stream,
+                       p->d_probs, p->D);
+  else
+    hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
 }
 
 // upper bound of the batch size round_begin_kernel will choose for a problem with at most n_ub vertices (same float
@@ -917,7 +1003,7 @@ rkh_status enqueue_round(rkh_planner* p) {
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
                       ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
-                                          ev0, ev1)
+                                          p->nn_open, ev0, ev1)
                       : launch_nn1(s, p->D, NnArgs(), p->d_nn_args, p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
                                    ev1, p->coord_bound, p->d_nn_base, true);
   if (st != RKH_OK) return st;
@@ -1187,6 +1273,8 @@ void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
   if (const char* e = getenv("RKH_STEER_CARRY_MIN_EDGES")) p->carry_min_edges = uint32_t(std::max(0, atoi(e)));
   if (const char* e = getenv("RKH_STEER_CARRY_FIT")) p->carry_fit = atoi(e) != 0;
   if (const char* e = getenv("RKH_PROFILE_NN")) p->profile_nn = atoi(e) != 0;
+  p->nn_open = nn1_mirror_open_lists();
+  if (const char* e = getenv("RKH_FIXUP_TILED")) p->fixup_tiled = atoi(e) != 0;
   // candidates per round = batch_factor * sqrt(n) per problem (results do not depend on it).  More candidates per
   // round mean fewer rounds but more discarded speculation (0.89 of the propagated edges are committed at 1.25, 0.72 at
   // 2, 0.55 at 3, 0.45 at 4), and a round is only cheap to enlarge while the chip is not full.  Measured optimum
