@@ -289,19 +289,12 @@ static void launch_nnk_dp(hipStream_t s, const KnnArgs& single, const KnnArgs* d
 
 static rkh_status launch_nnk_any(hipStream_t s, int D, const KnnArgs& single, const KnnArgs* d_tab, uint32_t gx,
                                  uint32_t gy, uint32_t b_max, uint32_t m_pow2, uint32_t cmax, uint32_t n_jobs) {
-  switch (nn_padded_dims(D)) {
-#define RKH_CASE(DP) \
-  case DP: launch_nnk_dp<DP>(s, single, d_tab, gx, gy, b_max, m_pow2, cmax, n_jobs); break
-    RKH_CASE(2);
-    RKH_CASE(4);
-    RKH_CASE(6);
-    RKH_CASE(8);
-    RKH_CASE(12);
-    RKH_CASE(16);
-    RKH_CASE(24);
-    RKH_CASE(32);
-#undef RKH_CASE
-    default: set_error("k-NN: unsupported dimension"); return RKH_ERR_BAD_ARG;
+  const bool dims_ok = with_padded_dims(D, [&](auto dp) {
+    launch_nnk_dp<decltype(dp)::value>(s, single, d_tab, gx, gy, b_max, m_pow2, cmax, n_jobs);
+  });
+  if (!dims_ok) {
+    set_error("k-NN: unsupported dimension");
+    return RKH_ERR_BAD_ARG;
   }
   RKH_HIP(hipGetLastError());
   return RKH_OK;

@@ -3,12 +3,30 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "rkh_internal.h"
 
 namespace rkh {
 
 typedef float rkh_f16v __attribute__((ext_vector_type(16)));  // accumulator of a 32x32 matrix instruction
+
+// The one dispatch over the padded row widths (nn_padded_dims): f(std::integral_constant<int, DP>()) for the width DP of
+// D coordinates -- a padded width maps to itself --; false if D has none.  Host code.
+template <class F>
+bool with_padded_dims(int D, F&& f) {
+  switch (nn_padded_dims(D)) {
+    case 2: f(std::integral_constant<int, 2>()); return true;
+    case 4: f(std::integral_constant<int, 4>()); return true;
+    case 6: f(std::integral_constant<int, 6>()); return true;
+    case 8: f(std::integral_constant<int, 8>()); return true;
+    case 12: f(std::integral_constant<int, 12>()); return true;
+    case 16: f(std::integral_constant<int, 16>()); return true;
+    case 24: f(std::integral_constant<int, 24>()); return true;
+    case 32: f(std::integral_constant<int, 32>()); return true;
+  }
+  return false;
+}
 
 // The parity contract of every NN form (1-NN and k-NN): the squared distance is the reference's left-to-right sum
 //   s = df(0) * df(0),  then  s = s + df(d) * df(d)  for d = 1 .. DP - 1

@@ -496,13 +496,17 @@ rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32
   hipLaunchKernelGGL((nn1_mirror_kernel<2>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx),
                      open_lists ? 1u : 0u);
   const dim3 rgrid((B_upper + 15) / 16, n_problems);
-  switch (nn_padded_dims(D)) {
-    case 2: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<2>), rgrid, dim3(256), 0, s, d_table, D); break;
-    case 4: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<4>), rgrid, dim3(256), 0, s, d_table, D); break;
-    case 6: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<6>), rgrid, dim3(256), 0, s, d_table, D); break;
-    case 8: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<8>), rgrid, dim3(256), 0, s, d_table, D); break;
-    case 12: hipLaunchKernelGGL((nn1_mirror_resolve_kernel<12>), rgrid, dim3(256), 0, s, d_table, D); break;
-    default: set_error("nn mirror: unsupported dimension"); return RKH_ERR_BAD_ARG;
+  bool resolved = false;  // (the resolve kernel exists for the widths a mirror fragment holds)
+  with_padded_dims(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if constexpr (DP <= kMirrorMaxDims) {
+      hipLaunchKernelGGL((nn1_mirror_resolve_kernel<DP>), rgrid, dim3(256), 0, s, d_table, D);
+      resolved = true;
+    }
+  });
+  if (!resolved) {
+    set_error("nn mirror: unsupported dimension");
+    return RKH_ERR_BAD_ARG;
   }
   if (ev1) (void)hipEventRecord(ev1, s);
   RKH_HIP(hipGetLastError());

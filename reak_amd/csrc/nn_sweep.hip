@@ -1178,21 +1178,6 @@ static int padded_dims(int D) {
 }
 int nn_padded_dims(int D) { return padded_dims(D); }
 
-// f(std::integral_constant<int, DP>()) for the padded width DP of D; false if D has none
-template <class F>
-static bool with_padded_dims(int D, F&& f) {
-  switch (padded_dims(D)) {
-    case 2: f(std::integral_constant<int, 2>()); return true;
-    case 4: f(std::integral_constant<int, 4>()); return true;
-    case 6: f(std::integral_constant<int, 6>()); return true;
-    case 8: f(std::integral_constant<int, 8>()); return true;
-    case 12: f(std::integral_constant<int, 12>()); return true;
-    case 16: f(std::integral_constant<int, 16>()); return true;
-    case 24: f(std::integral_constant<int, 24>()); return true;
-    case 32: f(std::integral_constant<int, 32>()); return true;
-  }
-  return false;
-}
 // f(std::integral_constant<int, QB>()) for the QB of Q... equal to qb; false if none is, or if f returns false
 template <int... Q, class F>
 static bool with_qb(uint32_t qb, F&& f) {

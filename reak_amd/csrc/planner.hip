@@ -34,6 +34,7 @@
 #include "nn_mirror.h"
 #include "rkh_internal.h"
 #include "round_carry.h"
+#include "round_plan.h"
 
 namespace rkh {
 
@@ -79,28 +80,62 @@ struct ProblemDev {  // device pointers of one problem
   uint32_t* dx_max_bits;  // its running maximum of |x - x_h|
 };
 
-// sel: {edge counter of even rounds, of odd rounds}.  Every problem adds its candidates + pending goal probes to the
-// counter of this round's parity and block 0 clears the other one for the next round; the two steer kernels of the
-// round compare the sum with their threshold (see launch_edges).
+// round_begin_kernel's arguments (round_begin_args builds them from the planner)
+struct RoundBeginArgs {
+  const ProblemDev* probs;
+  uint32_t P;
+  uint32_t round_slot;  // profiling: this round's slot of ProblemDev::round_n
+  // sel: {edge counter of even rounds, of odd rounds}.  Every problem adds its candidates + pending goal probes to the
+  // counter of this round's parity and block 0 clears the other one for the next round; the steer kernels of the round
+  // compare the sum with their gates (steer_plan).
+  uint32_t* sel;
+  uint32_t parity;
+  float fit_fill;   // the wave fit's target fill of the last pass of steer waves; 0: no fit, scale 1
+  uint32_t slots;   // concurrent waves of the two-lanes steer kernel
+  // exclusive prefixes over the problems, written for the round's compact launch mappings (null: not needed): steer waves
+  // per (candidates | probes) segment of the two-lanes kernel, single edges per segment of the one-wave-per-edge kernel,
+  // query blocks of nn_queries queries of the NN sweep
+  uint32_t* wave_base;  // [2 P + 1]
+  uint32_t* edge_base;  // [2 P + 1]
+  uint32_t* nn_base;    // [P + 1]
+  uint32_t nn_queries;
+  uint32_t epw;         // edges per steer wave (pair_kernel_edges_per_wave)
+  uint32_t* step_cnt;   // live-edge counters of the step-wise steer launches (two per step: front and back of its list)
+  uint32_t carry_fit_lo;  // the fewest edges of a round that carries (SteerPlan::carry_lo); kCarryOff: the fit does not look
+};
+
 constexpr uint32_t kProfRounds = 8192;  // profiled rounds per planner (RKH_PROFILE_NN)
 constexpr uint32_t kProbeGranule = 32;  // goal probes ride in whole steer waves when the wave fit is on (commit_kernel)
-// One block for all problems.  Batch sizes: B = scale * batch_factor * sqrt(n) (results do not depend on them).  With
-// fit_fill > 0 the scale of the round is chosen here, from the exact counts: the two-lanes steer kernel runs one wave of
-// 32 edges per SIMD (`slots` waves at a time), so the steer time of a round is its number of waves divided by `slots`,
-// rounded UP; the scale (0.75 .. 1.4) is bisected so that the round's waves -- candidates plus the pending goal probes
-// of every problem -- fill fit_fill of a whole number of such passes.
-__global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __restrict__ probs, uint32_t P,
-                                                           uint32_t round_slot, uint32_t* __restrict__ sel, uint32_t parity,
-                                                           float fit_fill, uint32_t slots, uint32_t* __restrict__ wave_base,
-                                                           uint32_t* __restrict__ nn_base, uint32_t nn_queries,
-                                                           uint32_t* __restrict__ edge_base, uint32_t epw,
-                                                           uint32_t* __restrict__ step_cnt, uint32_t carry_fit_lo) {
+
+// the batch rule's inputs of a problem as its state stands
+__device__ __forceinline__ BatchInputs batch_inputs(const PlannerState* st) {
+  const bool done = st->done != 0u;
+  const uint32_t avail = st->samples_ready - st->s0;
+  BatchInputs in;
+  in.batch_factor = st->batch_factor;
+  in.sqrt_n = sqrtf(float(st->n));
+  in.b_min = done ? 0u : st->b_min;
+  in.b_cap = done ? 0u : (st->b_max < avail ? st->b_max : avail);  // the two upper clamps
+  return in;
+}
+
+// One block for all problems: the batch of every problem (round_plan.h: the batch rule, and with fit_fill > 0 the wave fit
+// over the exact counts -- candidates plus the pending goal probes of every problem), the round's edge count, the
+// prefixes of the compact launch mappings.
+__global__ __launch_bounds__(256) void round_begin_kernel(const RoundBeginArgs args) {
+  const ProblemDev* __restrict__ const probs = args.probs;
+  uint32_t* __restrict__ const sel = args.sel;
+  uint32_t* __restrict__ const wave_base = args.wave_base;
+  uint32_t* __restrict__ const edge_base = args.edge_base;
+  uint32_t* __restrict__ const nn_base = args.nn_base;
+  uint32_t* __restrict__ const step_cnt = args.step_cnt;
+  const uint32_t P = args.P, round_slot = args.round_slot, parity = args.parity, slots = args.slots;
+  const uint32_t nn_queries = args.nn_queries, epw = args.epw, carry_fit_lo = args.carry_fit_lo;
+  const float fit_fill = args.fit_fill;
   __shared__ unsigned int s_waves, s_edges, s_steered;
-  // live-edge counters of the step-wise steer launches of this round (launch_propagate_pair_steps)
-  // (two per step: the front and the back part of its list)
   if (step_cnt && threadIdx.x < 2u * (uint32_t(kMaxSteps) + 1u)) step_cnt[threadIdx.x] = 0u;
-  // per-problem inputs of the batch formula, cached once (the bisection below evaluates it ten times per problem) and the
-  // three count arrays, scanned in LDS; problems beyond the cache capacity fall back to global memory
+  // per-problem inputs of the batch rule, cached once (the fit evaluates it eleven times per problem) and the three count
+  // arrays, scanned in LDS; problems beyond the cache capacity fall back to global memory
   constexpr uint32_t kCache = 1024;
   __shared__ float s_bf[kCache], s_sq[kCache];
   __shared__ uint32_t s_bmin[kCache], s_bcap[kCache], s_probe_waves[kCache], s_probes[kCache], s_carried[kCache];
@@ -109,59 +144,38 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
   const uint32_t tid = threadIdx.x;
   // With the wave fit on, a problem's candidates are a whole number of 32-edge steer waves: every (problem, candidates)
   // segment of the steer grid otherwise ends in a wave that is half empty on average (256 such waves per round of ~2700).
-  const bool wave_round = fit_fill > 0.0f && epw > 1u;
-  auto batch_of = [&](const PlannerState* st, float sc) -> uint32_t {
-    if (st->done) return 0u;
-    const float want = sc * st->batch_factor * sqrtf(float(st->n));
-    uint32_t B = uint32_t(want);
-    if (wave_round && B >= epw) B -= B % epw;  // whole steer waves: no half-empty last wave per problem
-    if (B < st->b_min) B = st->b_min;
-    if (B > st->b_max) B = st->b_max;
-    const uint32_t avail = st->samples_ready - st->s0;
-    if (B > avail) B = avail;
-    return B;
-  };
+  const uint32_t granule = fit_fill > 0.0f ? epw : 1u;
   if (cached) {
     for (uint32_t i = tid; i < P; i += blockDim.x) {
       const PlannerState* st = probs[i].st;
-      const bool done = st->done != 0u;
-      const uint32_t avail = st->samples_ready - st->s0;
-      s_bf[i] = st->batch_factor;
-      s_sq[i] = sqrtf(float(st->n));
-      s_bmin[i] = done ? 0u : st->b_min;
-      s_bcap[i] = done ? 0u : (st->b_max < avail ? st->b_max : avail);  // min(b_max, avail): the two upper clamps
-      s_probe_waves[i] = (st->n_new + epw - 1u) / epw;
+      const BatchInputs in = batch_inputs(st);
+      s_bf[i] = in.batch_factor;
+      s_sq[i] = in.sqrt_n;
+      s_bmin[i] = in.b_min;
+      s_bcap[i] = in.b_cap;
+      s_probe_waves[i] = round_waves(st->n_new, epw);
       s_probes[i] = st->n_new;
       s_carried[i] = st->carried;
     }
     __syncthreads();
   }
-  auto batch_cached = [&](uint32_t i, float sc) -> uint32_t {  // same value as batch_of(probs[i].st, sc)
-    const float want = sc * s_bf[i] * s_sq[i];
-    uint32_t B = uint32_t(want);
-    if (wave_round && B >= epw) B -= B % epw;
-    if (B < s_bmin[i]) B = s_bmin[i];
-    if (B > s_bcap[i]) B = s_bcap[i];
-    return B;
-  };
-  // A round that carries (round_carry.h; carry_fit_lo = the fewest edges of such a round, kCarryOff: the fit does not
-  // look) runs launch 0 over one compact list of the edges it steers: its waves are that total over epw, rounded up, with
-  // the expected reuse taken off every problem's candidates.
+  // A round that carries (round_carry.h) runs launch 0 over one compact list of the edges it steers: its waves are that
+  // total over epw, rounded up, with the expected reuse taken off every problem's candidates.
   auto waves_at = [&](float sc) -> uint32_t {  // block-wide sum, same value in every thread
     uint32_t w = 0, e = 0, steered = 0;
     for (uint32_t i = tid; i < P; i += blockDim.x) {
       uint32_t B, n_new, carried;
       if (cached) {
-        B = batch_cached(i, sc);
+        B = round_batch(BatchInputs{s_bf[i], s_sq[i], s_bmin[i], s_bcap[i]}, sc, granule);
         n_new = s_probes[i];
         carried = s_carried[i];
-        w += (B + epw - 1u) / epw + s_probe_waves[i];
+        w += round_waves(B, epw) + s_probe_waves[i];
       } else {
         const PlannerState* st = probs[i].st;
-        B = batch_of(st, sc);
+        B = round_batch(batch_inputs(st), sc, granule);
         n_new = st->n_new;
         carried = st->carried;
-        w += (B + epw - 1u) / epw + (n_new + epw - 1u) / epw;
+        w += round_waves(B, epw) + round_waves(n_new, epw);
       }
       e += B + n_new;
       steered += B - carry_expected_reuse(carried, B) + n_new;
@@ -175,31 +189,17 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
       atomicAdd(&s_steered, steered);
     }
     __syncthreads();
-    if (carry_fit_lo != kCarryOff && s_edges >= carry_fit_lo) return (s_steered + epw - 1u) / epw;
+    if (carry_fit_lo != kCarryOff && s_edges >= carry_fit_lo) return round_waves(s_steered, epw);
     return s_waves;
   };
-  float scale = 1.0f;
-  if (fit_fill > 0.0f) {
-    const float w1 = float(waves_at(1.0f));
-    if (w1 > 0.75f * float(slots)) {
-      const float passes = ceilf(w1 / float(slots) - 0.15f);
-      const float target = passes * float(slots) * fit_fill;
-      float lo = 0.75f, hi = 1.4f;
-      for (int it = 0; it < 10; ++it) {
-        const float mid = 0.5f * (lo + hi);
-        if (float(waves_at(mid)) > target) hi = mid;
-        else lo = mid;
-      }
-      scale = lo;
-    }
-  }
+  const float scale = fit_fill > 0.0f ? fit_batch_scale(waves_at, slots, fit_fill) : 1.0f;
   if (tid == 0) sel[parity ^ 1u] = 0u;
   uint32_t edges = 0;
   for (uint32_t i = tid; i < P; i += blockDim.x) {
     const ProblemDev pr = probs[i];
     PlannerState* st = pr.st;
     if (pr.round_n) pr.round_n[round_slot] = st->done ? 0u : st->n;
-    const uint32_t B = batch_of(st, scale);
+    const uint32_t B = round_batch(batch_inputs(st), scale, granule);
     if (!st->done && B == 0) st->done = 2;  // sample stream exhausted: host must upload more
     st->B = B;
     st->F = B;
@@ -215,10 +215,10 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const ProblemDev* __re
     uint32_t* eb = cached ? s_scan[1] : edge_base;
     uint32_t* nb = cached ? s_scan[2] : nn_base;
     if (wave_base) {
-      wb[2 * i + 1] = (B + epw - 1u) / epw;
-      wb[2 * i + 2] = (st->n_new + epw - 1u) / epw;
+      wb[2 * i + 1] = round_waves(B, epw);
+      wb[2 * i + 2] = round_waves(st->n_new, epw);
     }
-    if (nn_base) nb[i + 1] = (B + nn_queries - 1u) / nn_queries;
+    if (nn_base) nb[i + 1] = round_waves(B, nn_queries);
     if (edge_base) {
       eb[2 * i + 1] = B;
       eb[2 * i + 2] = st->n_new;
@@ -714,6 +714,7 @@ struct rkh_planner {
   uint32_t* d_sel = nullptr;        // [2] edges of the current round (by round parity), see round_begin_kernel
   uint32_t* d_nn_base = nullptr;    // [P + 1] prefix of the NN sweep's query blocks per problem (matrix-core kernel)
   uint32_t* d_wave_base = nullptr;  // [2 P + 1] prefix of the working waves per (problem, candidates | probes) segment
+  uint32_t* d_edge_base = nullptr;  // [2 P + 1] ... of the single edges per segment (behind d_wave_base in its range)
   uint32_t round_parity = 0;
   // host-side upper bounds that size the launches of a round (the exact counts live on the device): n_ub[i] >= vertex
   // count of problem i (exact after every sync, + the round's batch bound per enqueued round)
@@ -848,28 +849,50 @@ rkh_status upload_samples_all(rkh_planner* p, uint64_t ahead, int which) {
   return RKH_OK;
 }
 
-template <int DP>
-void launch_fixup(rkh_planner* p, uint32_t batch_ub) {
-  if (p->fixup_tiled)
-    hipLaunchKernelGGL((fixup_tiled_kernel<DP>), dim3((batch_ub + kFixCands - 1) / kFixCands, p->P), dim3(256), 0, p->stream,
-                       p->d_probs, p->D);
-  else
-    hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
+// fix-up of a round's candidates against the vertices the round itself would add
+rkh_status launch_fixup(rkh_planner* p, uint32_t batch_ub) {
+  const bool dims_ok = with_padded_dims(p->DP, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if (p->fixup_tiled)
+      hipLaunchKernelGGL((fixup_tiled_kernel<DP>), dim3((batch_ub + kFixCands - 1) / kFixCands, p->P), dim3(256), 0,
+                         p->stream, p->d_probs, p->D);
+    else
+      hipLaunchKernelGGL((fixup_kernel<DP>), dim3((batch_ub + 3) / 4, p->P), dim3(256), 0, p->stream, p->d_probs, p->D);
+  });
+  if (!dims_ok) {
+    set_error("planner: unsupported state dimension");
+    return RKH_ERR_UNSUPPORTED;
+  }
+  return RKH_OK;
 }
 
-// upper bound of the batch size round_begin_kernel will choose for a problem with at most n_ub vertices (same float
-// formula, monotone in n)
-uint32_t batch_upper_bound(const PlannerState& st, uint64_t n_ub, float batch_scale = 1.0f) {
-  const float want = batch_scale * st.batch_factor * sqrtf(float(n_ub));
-  uint32_t B = uint32_t(want);
-  if (B < st.b_min) B = st.b_min;
-  if (B > st.b_max) B = st.b_max;
-  return B;
+// upper bound of the batch round_begin_kernel will choose for a problem with at most n_ub vertices: the batch rule at the
+// host's bounds, whatever the problem has left of its sample stream
+uint32_t batch_upper_bound(const PlannerState& st, uint64_t n_ub, float batch_scale) {
+  return round_batch(BatchInputs{st.batch_factor, sqrtf(float(n_ub)), st.b_min, st.b_max}, batch_scale, 1u);
 }
 
-// steer / probe edges of all problems: RK4 propagation (dynamic space) or the min_interval walk (quasi-static space)
+// The steer plan of a launch of grid_a + grid_b edges per problem; compact: a regular round, over the (candidates, probes)
+// segments round_begin_kernel counted.
+SteerPlan auto_steer_plan(const rkh_planner* p, uint32_t grid_a, uint32_t grid_b, bool compact) {
+  SteerPlanInputs in;
+  in.lane_threshold = p->lane_threshold;
+  in.duo_threshold = p->duo_threshold;
+  in.split_min_edges = p->split_min_edges;
+  in.carry_min_edges = p->carry ? p->carry_min_edges : kCarryOff;
+  in.compact = compact && p->d_wave_base;
+  in.stepwise = p->d_step_cnt && p->dyn.n_steps > 1;
+  in.prismatic = p->scene->host.has_prismatic != 0;
+  // candidates + pending probes of all problems
+  in.edges_ub = std::min<uint64_t>(p->sum_batch_ub + p->prev_sum_batch_ub + uint64_t(p->P) * kProbeGranule,
+                                   uint64_t(grid_a + grid_b) * p->P);
+  return steer_plan(in);
+}
+
+// steer / probe edges of all problems: RK4 propagation (dynamic space) or the min_interval walk (quasi-static space).
+// plan: auto_steer_plan of the same grid (only Auto planners look at it).
 rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
-                        bool compact = false) {
+                        const SteerPlan& plan) {
   if (p->quasi_static)
     return launch_edge_check(p->stream, *p->scene, p->qs, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P);
   if (p->steer != SteerMapping::Auto) {
@@ -880,74 +903,46 @@ rkh_status launch_edges(rkh_planner* p, uint32_t grid_a, uint32_t grid_b, const 
     return launch_propagate(p->stream, *p->scene, p->steer, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
                             p->d_lane_ws, always);
   }
-  // Auto: every form of the sequence is launched; on the device each compares the round's edge count with its gate and
-  // the ones not chosen exit at once.  Small rounds -> Duo / Wave (latency), large -> Pair (32 edges per wave).
-  auto run = [&](SteerMapping m, double* ws, const KernelGate& gate) {
-    return launch_propagate(p->stream, *p->scene, m, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P, ws, gate);
-  };
-  KernelGate gate_wave{p->d_sel + p->round_parity, 0u, p->lane_threshold};
-  KernelGate gate_lane{p->d_sel + p->round_parity, p->lane_threshold, 0xFFFFFFFFu};
-  gate_wave.steps_exec = gate_lane.steps_exec = p->d_steps_exec;
-  gate_lane.clearance = p->steer_clearance;
-  gate_lane.clear_stats = p->scene->d_clear_stats.get();
-  if (compact && p->d_wave_base) {  // a regular round: (candidates, probes) segments as round_begin_kernel counted them
-    gate_lane.wave_base = p->d_wave_base;
-    gate_lane.n_segments = 2 * p->P;
-    gate_wave.wave_base = p->d_wave_base + (2 * p->P + 1);
-    gate_wave.n_segments = 2 * p->P;
-  }
-  rkh_status st = RKH_OK;
-  if (p->duo_threshold > 0 && compact && p->d_wave_base && !p->scene->host.has_prismatic) {
-    // the smallest rounds (at most half the chip's SIMDs at one wave per edge: a single problem, a few young trees):
-    // two waves per edge (state_derivative_duo), the f-eval's critical path instead of its instruction count
-    KernelGate gate_duo = gate_wave;
-    gate_duo.hi = std::min(p->duo_threshold, p->lane_threshold);
-    gate_wave.lo = gate_duo.hi;
-    st = run(SteerMapping::Duo, nullptr, gate_duo);
-    if (st != RKH_OK) return st;
-  }
-  // (chains with prismatic joints have no Duo form: their one-wave form covers [0, lane threshold))
-  if (gate_wave.lo < gate_wave.hi)
-    st = run(p->scene->host.has_prismatic ? SteerMapping::Prismatic : SteerMapping::Wave, nullptr, gate_wave);
-  if (st != RKH_OK) return st;
-  // The two-lanes mapping, step-wise when the round is a regular one: half of the edges of a round end within a few
-  // steps (tests/diag_edge_lifetimes.py) and leave their lanes idle for the rest of their wave, so one launch per step
-  // carries only the live edges -- in fewer waves.  Same arithmetic per edge, same results.
-  if (!(compact && p->d_step_cnt && p->dyn.n_steps > 1)) return run(SteerMapping::Pair, p->d_lane_ws, gate_lane);
-  // ... when the round is large enough; below that the extra launches and tails cost more than the idle lanes: such
-  // rounds take one whole-edge launch
-  const uint32_t split_edges = p->split_min_edges;
-  // host-side bound on the edges of this round (candidates + pending probes of all problems)
-  const uint64_t edges_ub = std::min<uint64_t>(p->sum_batch_ub + p->prev_sum_batch_ub + uint64_t(p->P) * kProbeGranule,
-                                               uint64_t(grid_a + grid_b) * p->P);
-  if (split_edges > gate_lane.lo) {
-    KernelGate whole = gate_lane;
-    whole.hi = split_edges;
-    if (edges_ub >= whole.lo) {  // (a round that cannot reach the gate needs no launch at all)
-      st = run(SteerMapping::Pair, p->d_lane_ws, whole);
-      if (st != RKH_OK) return st;
+  for (uint32_t k = 0; k < plan.n; ++k) {
+    const SteerLaunch& L = plan.launch[k];
+    const bool lanes = L.form == SteerForm::LanesWhole || L.form == SteerForm::LanesSteps;
+    KernelGate gate{p->d_sel + p->round_parity, L.lo, L.hi};
+    gate.steps_exec = p->d_steps_exec;
+    if (lanes) {
+      gate.clearance = p->steer_clearance;
+      gate.clear_stats = p->scene->d_clear_stats.get();
     }
-    gate_lane.lo = split_edges;
+    if (plan.in.compact) {  // the prefixes of round_begin_kernel: steer waves for the two-lanes forms, else single edges
+      gate.wave_base = lanes ? p->d_wave_base : p->d_edge_base;
+      gate.n_segments = 2 * p->P;
+    }
+    if (L.form != SteerForm::LanesSteps) {
+      SteerMapping m = SteerMapping::Pair;
+      if (L.form == SteerForm::TwoWaves) m = SteerMapping::Duo;
+      if (L.form == SteerForm::OneWave) m = plan.in.prismatic ? SteerMapping::Prismatic : SteerMapping::Wave;
+      RKH_TRY(launch_propagate(p->stream, *p->scene, m, p->dyn, EdgeIO(), grid_a, grid_b, tab_a, tab_b, p->P,
+                               lanes ? p->d_lane_ws : nullptr, gate));
+      continue;
+    }
+    const uint32_t epw = pair_kernel_edges_per_wave();
+    const uint32_t blocks = uint32_t(std::min<uint64_t>((plan.in.edges_ub + epw - 1) / epw, p->step_blocks_cap));
+    // a round that carries: the stashed results go to their slots and launch 0 gets the list of the edges left to steer
+    if (plan.restore) {
+      hipLaunchKernelGGL(carry_restore_kernel, dim3(p->P), dim3(256), 0, p->stream, p->d_probs, p->D, gate.count, gate.lo,
+                         gate.hi, plan.in.carry_min_edges, p->d_step_list[0], p->d_step_cnt, p->step_list_cap);
+    }
+    RKH_TRY(launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P, p->d_edge_base,
+                                        p->d_step_list[0], p->d_step_list[1], p->step_list_cap, p->d_step_cnt,
+                                        p->d_lane_ws, blocks, gate, p->d_steps_exec, plan.in.carry_min_edges));
   }
-  if (edges_ub < gate_lane.lo) return RKH_OK;
-  const uint32_t epw = pair_kernel_edges_per_wave();
-  const uint32_t blocks = uint32_t(std::min<uint64_t>((edges_ub + epw - 1) / epw, p->step_blocks_cap));
-  // a round that carries: the stashed results go to their slots and launch 0 gets the list of the edges left to steer
-  const uint32_t carry_min = p->carry ? p->carry_min_edges : kCarryOff;
-  if (p->carry && edges_ub >= carry_min) {
-    hipLaunchKernelGGL(carry_restore_kernel, dim3(p->P), dim3(256), 0, p->stream, p->d_probs, p->D, gate_lane.count,
-                       gate_lane.lo, gate_lane.hi, carry_min, p->d_step_list[0], p->d_step_cnt, p->step_list_cap);
-  }
-  return launch_propagate_pair_steps(p->stream, *p->scene, p->dyn, tab_a, tab_b, p->P,
-                                     p->d_wave_base + (2 * p->P + 1), p->d_step_list[0],
-                                     p->d_step_list[1], p->step_list_cap, p->d_step_cnt,
-                                     p->d_lane_ws, blocks, gate_lane, p->d_steps_exec, carry_min);
+  return RKH_OK;
 }
 
 // goal probes still pending after the last enqueued round
 rkh_status flush_probes(rkh_planner* p) {
   hipLaunchKernelGGL(probes_take_all_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
-  RKH_TRY(launch_edges(p, p->b_max + kProbeGranule, 0, p->d_io_probe, nullptr));
+  const uint32_t grid = p->b_max + kProbeGranule;
+  RKH_TRY(launch_edges(p, grid, 0, p->d_io_probe, nullptr, auto_steer_plan(p, grid, 0, false)));
   hipLaunchKernelGGL(probes_flushed_kernel, dim3(p->P), dim3(64), 0, p->stream, p->d_probs);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
@@ -963,6 +958,26 @@ rkh_status ensure_event_pair(std::vector<hipEvent_t>& ev, uint32_t slot) {
   return RKH_OK;
 }
 
+// round_begin_kernel's arguments for the round in profile slot `slot`; plan: the round's steer plan
+RoundBeginArgs round_begin_args(const rkh_planner* p, uint32_t slot, bool fit, const SteerPlan& plan) {
+  RoundBeginArgs a;
+  a.probs = p->d_probs;
+  a.P = p->P;
+  a.round_slot = slot;
+  a.sel = p->d_sel;
+  a.parity = p->round_parity;
+  a.fit_fill = fit ? float(p->wave_fill) : 0.0f;
+  a.slots = p->wave_slots;
+  a.wave_base = p->d_wave_base;
+  a.edge_base = p->d_edge_base;
+  a.nn_base = p->d_nn_base;
+  a.nn_queries = p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries();
+  a.epw = pair_kernel_edges_per_wave();
+  a.step_cnt = p->d_step_cnt;
+  a.carry_fit_lo = p->carry_fit ? plan.carry_lo : kCarryOff;
+  return a;
+}
+
 rkh_status enqueue_round(rkh_planner* p) {
   hipStream_t s = p->stream;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -976,7 +991,7 @@ rkh_status enqueue_round(rkh_planner* p) {
   }
   // the round's batch scale is chosen on the device (round_begin_kernel); the launches are sized for its upper end
   const bool fit = p->wave_fit && p->steer == SteerMapping::Auto;
-  const float scale = fit ? 1.4f : 1.0f;
+  const float scale = fit ? kFitScaleHi : 1.0f;
   // launch sizes of this round from the host-side bounds
   uint32_t batch_ub = 1;
   p->prev_sum_batch_ub = p->sum_batch_ub ? p->sum_batch_ub : uint64_t(p->b_max) * p->P;
@@ -993,13 +1008,8 @@ rkh_status enqueue_round(rkh_planner* p) {
   const uint32_t probe_ub = p->prev_batch_ub ? p->prev_batch_ub : p->b_max;
   p->prev_batch_ub = batch_ub + kProbeGranule;  // next round's probes: this round's vertices + what was left over
   p->round_parity ^= 1u;
-  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, p->d_probs, p->P, slot, p->d_sel, p->round_parity,
-                     fit ? float(p->wave_fill) : 0.0f, p->wave_slots, p->d_wave_base, p->d_nn_base,
-                     p->nn_mirror ? nn1_mirror_queries() : nn1_mfma_queries(),
-                     p->d_wave_base ? p->d_wave_base + (2 * p->P + 1) : nullptr, pair_kernel_edges_per_wave(),
-                     p->d_step_cnt,
-                     (p->carry && p->carry_fit) ? std::max(p->carry_min_edges, std::max(p->lane_threshold, p->split_min_edges))
-                                                : kCarryOff);
+  const SteerPlan plan = auto_steer_plan(p, batch_ub, probe_ub, true);
+  hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, round_begin_args(p, slot, fit, plan));
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
                       ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
@@ -1009,21 +1019,11 @@ rkh_status enqueue_round(rkh_planner* p) {
   if (st != RKH_OK) return st;
   // 2. speculative steer of all candidates + the goal probes of the vertices the previous round committed
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot], s);
-  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer, p->d_io_probe, true);
+  st = launch_edges(p, batch_ub, probe_ub, p->d_io_steer, p->d_io_probe, plan);
   if (st != RKH_OK) return st;
   if (ev0) (void)hipEventRecord(p->ev_steer[2 * slot + 1], s);
   // 3. fix-up against the vertices this round itself would add
-  switch (p->DP) {
-    case 2: launch_fixup<2>(p, batch_ub); break;
-    case 4: launch_fixup<4>(p, batch_ub); break;
-    case 6: launch_fixup<6>(p, batch_ub); break;
-    case 8: launch_fixup<8>(p, batch_ub); break;
-    case 12: launch_fixup<12>(p, batch_ub); break;
-    case 16: launch_fixup<16>(p, batch_ub); break;
-    case 24: launch_fixup<24>(p, batch_ub); break;
-    case 32: launch_fixup<32>(p, batch_ub); break;
-    default: set_error("planner: unsupported state dimension"); return RKH_ERR_UNSUPPORTED;
-  }
+  RKH_TRY(launch_fixup(p, batch_ub));
   // 4. commit the valid prefix
   hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u,
                      p->carry);
@@ -1353,6 +1353,7 @@ rkh_status alloc_planner_buffers(rkh_planner* p) {
   p->d_io_steer = A.at<EdgeIO>(L.shared[SR_IO_STEER]);
   p->d_io_probe = A.at<EdgeIO>(L.shared[SR_IO_PROBE]);
   p->d_wave_base = A.at<uint32_t>(L.shared[SR_WAVE_BASE]);
+  p->d_edge_base = p->d_wave_base ? p->d_wave_base + (2 * P + 1) : nullptr;
   p->d_step_cnt = A.at<uint32_t>(L.shared[SR_STEP_CNT]);
   p->d_nn_base = A.at<uint32_t>(L.shared[SR_NN_BASE]);
   p->d_sel = A.at<uint32_t>(L.shared[SR_SEL]);

@@ -320,8 +320,8 @@ inline void qs_set_speed(QsDev& qs, const double* speed_limits, int n) {
 // ---- steer mapping ---------------------------------------------------------------------------------------------------
 // The kernel form that steers the edges of a dynamic-space launch.
 enum class SteerMapping : uint8_t {
-  Auto,       // batch planner rounds: Duo, Wave or Pair by the round's edge count, read on the device (launch_edges);
-              // chains with prismatic joints: their one-wave form, then Pair (there is no Duo form for them)
+  Auto,       // batch planner rounds: the launches of steer_plan (round_plan.h), each gated on the device by the round's
+              // edge count
   Duo,        // two waves per edge (state_derivative_duo)
   Wave,       // one wave per edge (the form with the support-map query for scenes with vertex-set shapes)
   Wave16,     // four edges per wave, 16 lanes each (the form with the support-map query)
@@ -358,9 +358,7 @@ inline bool scene_fits_lane_kernel(const SceneDev& S) {
 //   Batch planner (rkh_planner_create*, dynamic space), at create: RKH_LANES_PER_EDGE 0 -> Auto, 2 -> Pair, 16 -> Wave16,
 //     any other value (128 included) -> Wave.  Unset: Auto if n_dof <= 6 and scene_fits_lane_kernel, else Wave16 if
 //     n_problems * 2 * b_max > 4096 (a round offers more waves than the chip has slots), else Wave.  Auto rounds run
-//     Duo below min(RKH_DUO_THRESHOLD, lane threshold) edges (compact rounds only; Auto never sees vertex-set shapes),
-//     Wave below the lane threshold and Pair from there on.  Chains with prismatic joints have no Duo form: their Auto
-//     rounds run the one-wave prismatic form below the lane threshold and Pair from there on.
+//     the forms steer_plan lists for their edge count (round_plan.h; Auto never sees vertex-set shapes).
 //   rkh_propagate, every call: unset -> Duo if edges <= 512, else Wave; 2 -> Pair, 16 -> Wave16, 128 -> Duo, any other
 //     value -> Wave.
 //   Graph planners (dynamic space), every launch: Duo if edges * n_problems <= RKH_DUO_THRESHOLD (read at create), else
