@@ -11,7 +11,7 @@
 //     quad_perm move (one VALU instruction per 32 bits, no LDS, no select);
 //   * the Jacobian columns of the current body live in REGISTERS: lane h computes the columns of the joints c = 2r + h
 //     (r unrolled: static register indices), from the end frames of those joints, which it also keeps in registers
-//     (a lane only ever needs the frames of its own columns);
+//     (a lane only ever needs the frames of its own columns): of a frame (p, q) it keeps q and (-p) * rotmat(q);
 //   * the mass matrix is accumulated in REGISTERS: lane h owns the rows i = 2r + h; Mcm * T of its own columns is formed
 //     once per body and handed to the neighbour by DPP, so each lane has all columns' products for its rows.  Every
 //     M(i, jx) receives its terms in the same ascending-body order (mat_alg_symmetric.hpp:551-566) -- no LDS
@@ -149,6 +149,37 @@ RKH_DI void ws_st(const PairWsRef& w, int slot, double d) {
   __builtin_amdgcn_raw_buffer_store_b64(v, w.rsrc, w.voff, slot * 512, 0);
 }
 
+// Jacobian column of the body at (pos, Q) w.r.t. the coordinate of a joint whose end frame is (p, cq): get_jac_relative_to
+// (motion_jacobians.hpp:238-251) with f2 = (~F_c) * F_b (frame_3D.hpp:184-189,222-238,368-382).  Rc = rotmat(cq) and
+// ipos = (-p) * Rc are the joint's own, fixed from the iteration that captured its frame.  MASK: the slot can hold a lane
+// whose column lies beyond the body (act false there); its column is an exact +0 vector.  (act is read only with MASK, pc
+// only in the prismatic forms.)
+template <bool MASK>
+RKH_DI void pair_jac_column(d3 ipos, d4 cq, const m33& Rc, d3 pos, d4 Q, d3 ax_c, bool pc, bool act, d3& Tv, d3& Tw) {
+  const d4 iq = qinv(cq);
+  // rotmat(conj(q)) is rotmat(q) transposed bit for bit (negating x, y, z flips the sign of the w-products and
+  // leaves the others unchanged), so Ri * pos is evaluated as pos * Rc: same products, same order
+  const d3 f2pos = ipos + mulT(pos, Rc);
+  const d4 f2q = qmul(iq, Q);
+  const m33 Rf = rotmat(f2q);
+  d3 wt = mulT(ax_c, Rf);
+  d3 vt = mulT(cross(ax_c, f2pos), Rf);
+  if (kPrismatic) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0.  The column differs between the edge's
+    // lanes: selects.  wt = +0 adds +-0 products to sums that are never -0, like a column beyond the body below.
+    vt = mk3(pc ? wt.x : vt.x, pc ? wt.y : vt.y, pc ? wt.z : vt.z);
+    wt = mk3(pc ? 0.0 : wt.x, pc ? 0.0 : wt.y, pc ? 0.0 : wt.z);
+  }
+  // A column beyond the body is an exact +0 vector: Mcm * 0 = +0 and s + (+-0) = s bit for bit (the sums start from +0
+  // or from a joint inertia, so they are never -0), hence the accumulation needs no masks.
+  if (MASK) {
+    Tw = mk3(act ? wt.x : 0.0, act ? wt.y : 0.0, act ? wt.z : 0.0);
+    Tv = mk3(act ? vt.x : 0.0, act ? vt.y : 0.0, act ? vt.z : 0.0);
+  } else {
+    Tw = wt;
+    Tv = vt;
+  }
+}
+
 // x' = f(x, u) of one edge.  In: the state in LD(XE..), the input in LD(U..).  Out: qdd[j] on both lanes (the q
 // components of x' are the qd components of x).  el = the edge's LDS column, h = which of the edge's two lanes this is.
 template <int N, bool DIAG = false>
@@ -184,14 +215,22 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
     const double ji1 = (2 * r + 1 < N) ? sc->joints[2 * r + 1 < N ? 2 * r + 1 : 0].joint_inertia : 0.0;
     Mo[r][r] = 0.0 + (h ? ji1 : ji0);
   }
-  // end frames of this lane's joints c = 2r + h (parents of its Jacobian columns)
-  d3 Ecp[R];
+  // end frames of this lane's joints c = 2r + h (parents of its Jacobian columns): the quaternion cq and, of the
+  // position p, the one thing a column needs, ipos = (-p) * rotmat(cq) -- formed once, where the frame is captured.  A
+  // slot whose joint has not been reached (or does not exist: an odd chain's last slot on lane 1) holds finite values
+  // and its column is masked.
+  d3 Eip[R];
   d4 Ecq[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    Ecp[r] = mk3(0.0, 0.0, 0.0);
+    Eip[r] = mk3(0.0, 0.0, 0.0);
     Ecq[r] = d4{1.0, 0.0, 0.0, 0.0};
   }
+  // rotmat(cq) of slot 0, the slot every body uses, kept where the registers are there for it (7 joints spill without
+  // it).  It costs 16 registers at N = 6 (240 of 256 in the step kernel) for 1.4 % of the f-eval: the first thing to give
+  // back if the register count tightens.
+  constexpr bool kRc0 = N >= 2 && N <= 6;
+  m33 Rc0 = m33{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
   // ---- base -> tip sweep (kte_map_chain::doMotion) with the Jacobian columns and M terms of each body
   d3 pos = ldg3(sc->base_pos);
@@ -235,20 +274,25 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
       Ew = wb + qa;
       Ealpha = mulT(alpha, R2) + cross(wb, qa);
     }
-    {  // the joint's end frame, kept by the lane that owns column j
+    const m33 Rm = rotmat(EQ);
+    {  // the joint's end frame, kept by the lane that owns column j, in slot j >> 1: a uniform branch, one select per value
       const bool mine = ((j & 1) == h);
       const int rj = j >> 1;
+      const d3 ip = mulT(-pos, Rm);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const bool take = (rj == r) && mine;  // selects, not branches
-        Ecp[r].x = take ? pos.x : Ecp[r].x; Ecp[r].y = take ? pos.y : Ecp[r].y; Ecp[r].z = take ? pos.z : Ecp[r].z;
-        Ecq[r].w = take ? EQ.w : Ecq[r].w; Ecq[r].x = take ? EQ.x : Ecq[r].x;
-        Ecq[r].y = take ? EQ.y : Ecq[r].y; Ecq[r].z = take ? EQ.z : Ecq[r].z;
+        if (rj == r) {
+          Eip[r] = mk3(mine ? ip.x : Eip[r].x, mine ? ip.y : Eip[r].y, mine ? ip.z : Eip[r].z);
+          Ecq[r] = d4{mine ? EQ.w : Ecq[r].w, mine ? EQ.x : Ecq[r].x, mine ? EQ.y : Ecq[r].y, mine ? EQ.z : Ecq[r].z};
+          if (kRc0 && r == 0)
+            Rc0 = m33{mine ? Rm.a11 : Rc0.a11, mine ? Rm.a12 : Rc0.a12, mine ? Rm.a13 : Rc0.a13,
+                      mine ? Rm.a21 : Rc0.a21, mine ? Rm.a22 : Rc0.a22, mine ? Rm.a23 : Rc0.a23,
+                      mine ? Rm.a31 : Rc0.a31, mine ? Rm.a32 : Rc0.a32, mine ? Rm.a33 : Rc0.a33};
+        }
       }
     }
     // rigid_link_3D::doMotion = frame * pose (frame_3D.hpp:240-255)
     const d3 op = ldg3(J.off_pos);
-    const m33 Rm = rotmat(EQ);
     pos = pos + mul(Rm, op);
     acc = acc + mul(Rm, cross(Ew, cross(Ew, op)) + cross(Ealpha, op));
     const m33 Ro = ldgm(J.off_R);
@@ -264,39 +308,24 @@ __device__ __forceinline__ void pair_state_derivative(ScenePtr sc_in, PairLds<N>
       RKH_LD(L_::FT + 6 * j + 3) = Ti.x; RKH_LD(L_::FT + 6 * j + 4) = Ti.y; RKH_LD(L_::FT + 6 * j + 5) = Ti.z;
     }
     RKH_STAMP(0)
-    // Jacobian columns of body j w.r.t. this lane's coords c = 2r + h <= j: get_jac_relative_to
-    // (motion_jacobians.hpp:238-251) with f2 = (~F_c) * F_b (frame_3D.hpp:184-189,222-238,368-382)
+    // Jacobian columns of body j w.r.t. this lane's coords c = 2r + h <= j.  The newest slot (2r == j) is the one slot
+    // that can hold a column beyond j (lane 1's), and its lane 0 column is joint j itself: rotmat(cq) is this
+    // iteration's Rm.  Lane 1 computes on Rm too, and on its (identity) frame; its column is masked.
     d3 Tv[R], Tw[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       Tv[r] = mk3(0.0, 0.0, 0.0);
       Tw[r] = mk3(0.0, 0.0, 0.0);
-      if (2 * r <= j) {  // uniform; a lane whose column 2r + 1 is beyond j computes on its (valid or identity) frame
-        const d3 cp = Ecp[r];
-        const d4 cq = Ecq[r];
-        const m33 Rc = rotmat(cq);
-        const d4 iq = qinv(cq);
-        const d3 ipos = mulT(-cp, Rc);
-        // rotmat(conj(q)) is rotmat(q) transposed bit for bit (negating x, y, z flips the sign of the w-products and
-        // leaves the others unchanged), so Ri * pos is evaluated as pos * Rc: same products, same order
-        const d3 f2pos = ipos + mulT(pos, Rc);
-        const d4 f2q = qmul(iq, Q);
-        const m33 Rf = rotmat(f2q);
-        const int c = 2 * r + h;  // <= N: the spare row of lds.axis covers an odd chain's last slot
+      const int c = 2 * r + h;  // <= N: the spare row of lds.axis covers an odd chain's last slot
+      const bool pc = kPrismatic && ((pmask >> c) & 1u) != 0u;
+      const bool act = (c <= j);
+      if (2 * r == j) {  // uniform
         const d3 ax_c = mk3(lds.axis[c][0], lds.axis[c][1], lds.axis[c][2]);
-        d3 wt = mulT(ax_c, Rf);
-        d3 vt = mulT(cross(ax_c, f2pos), Rf);
-        if (kPrismatic) {  // prismatic_joint_3D: qd_vel = mAxis, qd_avel = 0.  The column differs between the edge's
-          // lanes: selects.  wt = +0 adds +-0 products to sums that are never -0, like a column beyond j below.
-          const bool pc = ((pmask >> c) & 1u) != 0u;
-          vt = mk3(pc ? wt.x : vt.x, pc ? wt.y : vt.y, pc ? wt.z : vt.z);
-          wt = mk3(pc ? 0.0 : wt.x, pc ? 0.0 : wt.y, pc ? 0.0 : wt.z);
-        }
-        // A column beyond j is an exact +0 vector: Mcm * 0 = +0 and s + (+-0) = s bit for bit (the sums start from +0
-        // or from a joint inertia, so they are never -0), hence the accumulation below needs no masks.
-        const bool act = (c <= j);
-        Tw[r] = mk3(act ? wt.x : 0.0, act ? wt.y : 0.0, act ? wt.z : 0.0);
-        Tv[r] = mk3(act ? vt.x : 0.0, act ? vt.y : 0.0, act ? vt.z : 0.0);
+        pair_jac_column<true>(Eip[r], Ecq[r], Rm, pos, Q, ax_c, pc, act, Tv[r], Tw[r]);
+      } else if (2 * r < j) {  // uniform: both lanes' columns exist, nothing to mask
+        const d3 ax_c = mk3(lds.axis[c][0], lds.axis[c][1], lds.axis[c][2]);
+        const m33 Rc = (kRc0 && r == 0) ? Rc0 : rotmat(Ecq[r]);
+        pair_jac_column<false>(Eip[r], Ecq[r], Rc, pos, Q, ax_c, pc, act, Tv[r], Tw[r]);
       }
     }
     RKH_STAMP(1)
