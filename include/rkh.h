@@ -130,7 +130,16 @@ rkh_status rkh_nn_fill_uniform(rkh_nn* nn, uint64_t n, uint64_t seed);
  * RKH_ERR_UNSUPPORTED.  A prismatic_joint_3D may take the place of the revolute joint in any group of a
  * SERIAL chain (the CRS A465's track, :300-346), also after the optional mount link; such a scene runs on the
  * one-wave-per-edge and quasi-static kernels.  Refused with a prismatic joint: branching chains, a
- * flexible_beam_3D, mesh shapes, and a plane paired with a shape the joint carries (its travel is unbounded). */
+ * flexible_beam_3D, mesh shapes, and a plane paired with a shape the joint carries (its travel is unbounded).
+ * PLANAR chains (2D shapes only) are sequences of {revolute_joint_2D | prismatic_joint_2D, rigid_link_2D} groups, or with
+ * dynamics {driving_actuator_gen, inertia_gen, revolute_joint_2D | prismatic_joint_2D, rigid_link_2D, inertia_2D}, of 1,
+ * 2, 3, 4, 6 or 7 joints.  A prismatic_joint_2D (ctrl/mbd_kte/prismatic_joint.cpp:33-123: doMotion :33-80, doForce
+ * :82-102, applyReactionForce :120-123; the planar CRS A465 analog of examples/robot_airship/old/
+ * CRS_A465_2D_analog.cpp:139-360 rides one) may stand in any group, in any mix with revolute joints; its axis is used as
+ * given, and robot shapes anchor on any joint's end frame.  Such a scene runs on the rkh::planar_prismatic forms of the
+ * planar kernels behind every entry point that serves planar scenes.  Refused (RKH_ERR_UNSUPPORTED): a
+ * prismatic_joint_3D inside a planar chain, a prismatic_joint_2D inside a 3D chain, and the record queries on any
+ * planar scene. */
 rkh_status rkh_scene_create(rkh_ctx* ctx, const rkh_kte_op* prog, int n_ops, const rkh_chain_base* base,
                             const rkh_shape* shapes, int n_shapes, rkh_scene** out);
 /* The same with convex vertex sets among the shapes (RKH_SHAPE_MESH): mesh_vertices = the pool [n_mesh_vertices][3] the

@@ -38,13 +38,18 @@ enum rkh_kte_kind {
   RKH_KTE_FLEXIBLE_BEAM_3D = 6,
   /* Planar chains (position level: quasi-static free spaces).  Poses are pose_2D<double> carried in rkh_pose as
    * pos[0..1] = Position and quat[0..1] = rot_mat_2D::q = (cos, sin) (core/kinetostatics/rotations_2D.hpp:89);
-   * a chain is planar when its joints are REVOLUTE_JOINT_2D, and then all its links and shapes must be 2D. */
+   * a chain is planar when its joints are REVOLUTE_JOINT_2D or PRISMATIC_JOINT_2D, and then all its links and shapes
+   * must be 2D. */
   RKH_KTE_REVOLUTE_JOINT_2D = 7,    /* ctrl/mbd_kte/revolute_joint.cpp:30-97     : coord, base, end           */
   RKH_KTE_RIGID_LINK_2D = 8,        /* ctrl/mbd_kte/rigid_link.cpp:87-128        : base, end, pose offset     */
   RKH_KTE_INERTIA_2D = 9,           /* ctrl/mbd_kte/inertia.cpp:60-87            : frame(end), mass, inertia[0] = mMomentOfInertia */
   /* prismatic_joint_3D (ctrl/mbd_kte/prismatic_joint.cpp:116-222): a translation by q * mAxis along the base frame's axis.
    * axis = mAxis as given (the joint does not normalise it: tmp_pos = q * mAxis).  Serial 3D chains only (rkh.h). */
-  RKH_KTE_PRISMATIC_JOINT_3D = 10   /*                                          : coord, axis, base, end     */
+  RKH_KTE_PRISMATIC_JOINT_3D = 10,  /*                                          : coord, axis, base, end     */
+  /* prismatic_joint_2D (ctrl/mbd_kte/prismatic_joint.cpp:33-123): the planar twin, a translation by q * mAxis in the base
+   * frame.  axis[0..1] = mAxis as given (not normalised: tmp_pos = q * mAxis), axis[2] is ignored.  Planar chains only:
+   * it may stand wherever a REVOLUTE_JOINT_2D may (rkh.h). */
+  RKH_KTE_PRISMATIC_JOINT_2D = 11   /*                                          : coord, axis[0..1], base, end */
 };
 
 typedef struct rkh_kte_op {
@@ -54,7 +59,7 @@ typedef struct rkh_kte_op {
   int32_t end_frame;   /* frame index (frame_3D), or -1 */
   int32_t joint_op;    /* DRIVING_ACTUATOR_GEN: index of the joint op receiving applyReactionForce */
   uint32_t upstream;   /* INERTIA_*: bitmask of coords in mUpStreamJoints (jacobian_joint_map.hpp) */
-  double axis[3];      /* REVOLUTE_JOINT_3D / PRISMATIC_JOINT_3D: mAxis */
+  double axis[3];      /* REVOLUTE_JOINT_3D / PRISMATIC_JOINT_3D: mAxis; PRISMATIC_JOINT_2D: axis[0..1] */
   rkh_pose offset;     /* RIGID_LINK_3D: mPoseOffset */
   double mass;         /* INERTIA_GEN / INERTIA_3D: mMass */
   double inertia[6];   /* INERTIA_3D: mInertiaTensor, symmetric (a11,a12,a13,a22,a23,a33) */

@@ -754,11 +754,15 @@ __device__ double state_derivative_duo(const SceneDev* __restrict__ sc_beam, con
 // rigid_link.cpp:87-99), pose_2D::getGlobalPose of the robot shapes, then proxy_query_pair_2D::findMinimumDistance
 // (proxy_query_model.cpp:163-189) replayed in finder order: every lane computes one pair's cull value and distance,
 // and the sequence "skip if cull > running minimum, else take the minimum" is resolved lane by lane.
-template <int N, int GL, typename WS>
+// PRISM (the rkh::planar_prismatic kernels): joints whose bit is set in SceneDev::prismatic_mask are prismatic_joint_2D
+// (prismatic_joint.cpp:44-46,60): the end frame is the base moved by R (q a), no sincos.  The mask is uniform over the
+// launch, and the handovers through LDS keep the barriers of the revolute form.
+template <int N, int GL, bool PRISM = false, typename WS>
 __device__ double proximity_min_planar(const SceneDev* __restrict__ sc, const CPack<N>& cp, const double* __restrict__ base,
                                        const ShapeDev* __restrict__ env_lds, const PairDev* __restrict__ pairs, int n_pairs,
                                        WS& ws, int gl, int gb) {
   for (int jj = gl; jj < N; jj += GL) {
+    if (PRISM && ((sc->prismatic_mask >> jj) & 1u)) continue;
     double sn, cs;
     sincos(ws.x[2 * jj], &sn, &cs);
     ws.cs[jj][0] = cs;
@@ -771,7 +775,13 @@ __device__ double proximity_min_planar(const SceneDev* __restrict__ sc, const CP
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const int jb = j * 32;
-      const d2 ER = rmul(R, mk2(ws.cs[j][0], ws.cs[j][1]));
+      d2 ER;
+      if (PRISM && ((sc->prismatic_mask >> j) & 1u)) {
+        pos = pos + rrot(R, ws.x[2 * j] * mk2(cget(cp, jb + JC_AXIS), cget(cp, jb + JC_AXIS + 1)));
+        ER = R;
+      } else {
+        ER = rmul(R, mk2(ws.cs[j][0], ws.cs[j][1]));
+      }
       if (gl == 0) {
         ws.Epos[j][0] = pos.x;
         ws.Epos[j][1] = pos.y;
@@ -1225,8 +1235,9 @@ struct EdgeWalkArgs {
 };
 typedef const __attribute__((address_space(4))) EdgeWalkArgs* EdgeWalkArgP;
 
-// One edge walk of edge_check_kernel (the block's groups test G consecutive points per pass).
-template <int N, int W>
+// One edge walk of edge_check_kernel (the block's groups test G consecutive points per pass); PRISM: of
+// planar_prismatic::edge_check_kernel, for chains with prismatic_joint_2D groups.
+template <int N, int W, bool PRISM = false>
 __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs, int n_pairs,
                                           const QsDev& qs, const EdgeIO& io, BlockLdsQsW<N, W>& lds,
                                           const ShapeDev* __restrict__ env_lds, uint32_t e) {
@@ -1263,7 +1274,7 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
     const unsigned long long mo = __ballot(oob);
     const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
     __syncthreads();
-    const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
+    const double dmin = proximity_min_planar<N, GL, PRISM>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
     const bool is_free = !group_oob && !(dmin < 0.0);
     if (g == 0 && gl < N) io.x_out[uint64_t(e) * N + gl] = b_d;
     if (tid == 0) {
@@ -1305,7 +1316,7 @@ __device__ __forceinline__ void edge_walk(const SceneDev* __restrict__ sc, const
       const unsigned long long mo = __ballot(oob);
       const bool group_oob = ((mo >> gb) & ((1ull << GL) - 1ull)) != 0ull;
       __syncthreads();
-      const double dmin = proximity_min_planar<N, GL>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
+      const double dmin = proximity_min_planar<N, GL, PRISM>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, gl, gb);
       const bool is_free = valid && !group_oob && !(dmin < 0.0);
       {  // the wave's verdicts -> LDS, then every thread scans the block's groups in edge order
         const unsigned long long mv = __ballot(valid && gl == 0), mf = __ballot(is_free && gl == 0);
@@ -1389,6 +1400,34 @@ __global__ __launch_bounds__(64 * W) void edge_check_kernel(EdgeWalkArgs) {
   const PairDev* pairs = edge_check_stage<N, W>(sc, ka->pairs, n_pairs, ka->pairs_staged, lds, env_lds);
   edge_walk<N, W>(sc, pairs, n_pairs, *(const QsDev*)&ka->qs, io, lds, env_lds, e);
 }
+
+#ifdef RKH_PLANAR_PRISMATIC_QS
+// The position-level forms for planar chains with prismatic_joint_2D groups (SceneDev::planar && has_prismatic): the
+// edge walk here and the distance query below, over proximity_min_planar<.., PRISM = true>.  They are compiled in a
+// translation unit of their own (propagate_planar_qs_prismatic.hip defines RKH_PLANAR_PRISMATIC_QS and includes this
+// file), which instantiates these kernels and nothing else: a kernel added to this unit's module would shift the
+// code of the ones it holds.  (rkh::prismatic holds the forms of 3D chains.)
+namespace planar_prismatic {
+template <int N, int W>
+__global__ __launch_bounds__(64 * W) void edge_check_kernel(EdgeWalkArgs) {
+  EdgeWalkArgP ka = (EdgeWalkArgP)__builtin_amdgcn_kernarg_segment_ptr();
+  const SceneDev* __restrict__ sc = ka->sc;
+  const int n_pairs = ka->n_pairs;
+  const uint32_t grid_a = ka->grid_a;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  BlockLdsQsW<N, W>& lds = *reinterpret_cast<BlockLdsQsW<N, W>*>(smem_raw);
+  ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQsW<N, W>::block_bytes);
+  const bool group_b = blockIdx.x >= grid_a;
+  const EdgeIO* iok = (const EdgeIO*)(group_b ? &ka->io_b : &ka->io_a);
+  const EdgeIO io = ka->tab_a ? (group_b ? ka->tab_b[blockIdx.y] : ka->tab_a[blockIdx.y]) : *iok;
+  const uint32_t B = io.d_B ? *io.d_B : io.B;
+  const uint32_t e = group_b ? blockIdx.x - grid_a : blockIdx.x;
+  if (e >= B) return;
+  const PairDev* pairs = edge_check_stage<N, W>(sc, ka->pairs, n_pairs, ka->pairs_staged, lds, env_lds);
+  edge_walk<N, W, true>(sc, pairs, n_pairs, *(const QsDev*)&ka->qs, io, lds, env_lds, e);
+}
+}  // namespace planar_prismatic
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // The same edge walk for 3D scenes, with ONE LANE PER POINT in the chain kinematics (edge_points_kernel).  A 16-lane
@@ -1819,6 +1858,32 @@ __global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __rest
   if (lane == 0) dist[e] = dmin;
 }
 
+#ifdef RKH_PLANAR_PRISMATIC_QS
+namespace planar_prismatic {
+// min_distance_kernel for planar chains with prismatic_joint_2D groups
+template <int N>
+__global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                                           int n_pairs, const double* __restrict__ x, uint32_t B,
+                                                           double* __restrict__ dist) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  BlockLdsQs<N, 64>& lds = *reinterpret_cast<BlockLdsQs<N, 64>*>(smem_raw);
+  ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQs<N, 64>::block_bytes);
+  const uint32_t e = blockIdx.x;
+  if (e >= B) return;
+  const int lane = threadIdx.x;
+  constexpr int D = 2 * N;
+  stage_chain<N>(sc, lds.joints, lds.base, lane);
+  stage_env(sc, env_lds, lane);
+  GroupWsQs<N>& ws = lds.g[0];
+  if (lane < D) ws.x[lane] = x[uint64_t(e) * D + lane];
+  __syncthreads();
+  const CPack<N> cp = load_cpack<N>(lds.joints, lane);
+  const double dmin = proximity_min_planar<N, 64, true>(sc, cp, lds.base, env_lds, pairs, n_pairs, ws, lane, 0);
+  if (lane == 0) dist[e] = dmin;
+}
+}  // namespace planar_prismatic
+#endif
+
 #ifndef RKH_PRISMATIC_FORMS
 // ---- record queries (rkh_min_distance_records, rkh_collision_records) -----------------------------------------------
 // One form serves revolute and prismatic chains: proximity_frames with PRISM = true reads SceneDev::prismatic_mask at
@@ -2048,6 +2113,7 @@ static rkh_status launch_propagate_t(hipStream_t s, const rkh_scene& scene, cons
   });
 }
 
+#ifndef RKH_PLANAR_PRISMATIC_QS
 rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
                             uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
                             uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
@@ -2058,7 +2124,8 @@ rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping 
     st = launch_propagate_t<64, false>(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
   } else {
     // a scene with prismatic joints never reaches a revolute form: whatever one-wave mapping was asked for is theirs
-    if (scene.host.has_prismatic && m != SteerMapping::Pair) m = SteerMapping::Prismatic;
+    // (planar chains with prismatic joints have forms of their own behind launch_propagate_planar)
+    if (scene.host.has_prismatic && !scene.host.planar && m != SteerMapping::Pair) m = SteerMapping::Prismatic;
     switch (m) {
       case SteerMapping::Planar:
         return launch_propagate_planar(s, scene, dyn, io, grid_edges, eb, tab_a, tab_b, n_problems, gate);
@@ -2098,6 +2165,7 @@ rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const 
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
+#endif  // !RKH_PLANAR_PRISMATIC_QS
 
 // The number of waves W of a planar edge_check_kernel launch, by the number of edges (1 for launches of 4096 edges and
 // more, 4 below that, 8 below 512) and by what fits 64 KB of LDS (2 where 4 does not fit, 1 where neither does), and
@@ -2168,13 +2236,67 @@ static rkh_status launch_edge_walk(hipStream_t s, dim3 grid, const rkh_scene& sc
   return wide ? launch_edge_points_t<N, false, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, false, 32>(s, grid, n_env, ka);
 }
 
+#ifdef RKH_PLANAR_PRISMATIC_QS
+// The two launchers of the planar prismatic position-level forms (this translation unit holds nothing else).
+namespace planar_prismatic {
+template <int N, int W>
+static void launch_edge_check_w(hipStream_t s, dim3 grid, int n_env, const EdgeWalkArgs& ka) {
+  hipLaunchKernelGGL((edge_check_kernel<N, W>), grid, dim3(64 * W),
+                     (SmemLayoutQsW<N, W>::bytes(n_env, ka.pairs_staged ? ka.n_pairs : 0)), s, ka);
+}
+
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems) {
   const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
-  if constexpr (!kPrismatic)
+  EdgeWalkArgs ka;
+  ka.sc = scene.d_scene.get();
+  ka.pairs = scene.d_pairs.get();
+  ka.n_pairs = scene.n_pairs_verdict;
+  ka.qs = qs;
+  ka.io_a = io;
+  ka.io_b = EdgeIO();
+  ka.tab_a = tab_a;
+  ka.tab_b = tab_b;
+  ka.grid_a = grid_edges;
+  ka.pairs_staged = 0;
+  const dim3 grid(grid_edges + eb, n_problems);
+  const int n_env = scene.host.n_env;
+  RKH_TRY((with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    switch (edge_check_shape<N>(n_env, ka.n_pairs, uint64_t(grid.x) * grid.y, &ka.pairs_staged)) {  // the revolute rule
+      case 8: launch_edge_check_w<N, 8>(s, grid, n_env, ka); break;
+      case 4: launch_edge_check_w<N, 4>(s, grid, n_env, ka); break;
+      case 2: launch_edge_check_w<N, 2>(s, grid, n_env, ka); break;
+      default: launch_edge_check_w<N, 1>(s, grid, n_env, ka); break;
+    }
+  })));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
+  if (B == 0) return RKH_OK;
+  RKH_TRY((with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.n_pairs, d_x, B, d_dist);
+  })));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+}  // namespace planar_prismatic
+#else  // !RKH_PLANAR_PRISMATIC_QS
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+                             uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems) {
+  const uint32_t eb = tab_b ? grid_b : 0u;
+  if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
+  if constexpr (!kPrismatic) {
+    if (scene.host.has_prismatic && scene.host.planar)
+      return planar_prismatic::launch_edge_check(s, scene, qs, io, grid_edges, eb, tab_a, tab_b, n_problems);
     if (scene.host.has_prismatic)
       return prismatic::launch_edge_check(s, scene, qs, io, grid_edges, eb, tab_a, tab_b, n_problems);
+  }
   EdgeWalkArgs ka;
   ka.sc = scene.d_scene.get();
   ka.pairs = scene.d_pairs.get();
@@ -2233,8 +2355,10 @@ rkh_status launch_feval_cycles(hipStream_t s, const rkh_scene& scene, const doub
 
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist) {
   if (B == 0) return RKH_OK;
-  if constexpr (!kPrismatic)
+  if constexpr (!kPrismatic) {
+    if (scene.host.has_prismatic && scene.host.planar) return planar_prismatic::launch_min_distance(s, scene, d_x, B, d_dist);
     if (scene.host.has_prismatic) return prismatic::launch_min_distance(s, scene, d_x, B, d_dist);
+  }
   const rkh_status st = with_chain_n(scene.host.n_dof, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((min_distance_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
@@ -2276,6 +2400,8 @@ rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const
   });
 }
 #endif
+
+#endif  // RKH_PLANAR_PRISMATIC_QS
 
 #ifdef RKH_PRISMATIC_FORMS
 }  // namespace prismatic

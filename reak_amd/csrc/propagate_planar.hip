@@ -14,6 +14,17 @@
 // or cross-lane traffic; the proximity test walks the finder list serially per lane (the order matters:
 // proxy_query_model.cpp:176-180 culls against the running minimum).  Every product and sum is formed in the order of the
 // restated reference (-ffp-contract=off).
+//
+// Chains with prismatic_joint_2D groups (SceneDev::has_prismatic; prismatic_joint.cpp:33-123) run on forms compiled from
+// this same text in a translation unit of their own (propagate_planar_prismatic.hip defines RKH_PLANAR_PRISMATIC_FORMS
+// and includes this file): there everything below lives in rkh::planar_prismatic and kPlanarPrismatic is true, and
+// every joint loop asks the scene's prismatic_mask, which is uniform over the launch, so the branch is scalar.  Here
+// kPlanarPrismatic is false, the branches compile away and the revolute kernels keep their code.
+// That last point decides how the branches are written: each one is a whole `if constexpr (kPlanarPrismatic) { ... continue; }`
+// block in FRONT of the revolute statements, which stay the text they were -- folding the choice into them (a select, an
+// if / else around them) changed the register allocation of planar_state_derivative_kernel<3> -- and inside its block
+// the prismatic form handles both joint kinds and then runs the rest of the loop body once (two copies of the link
+// step behind a branch made planar_propagate_kernel<6> spill).  So the revolute joint and link steps stand twice.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -23,19 +34,32 @@
 #include "rkh_internal.h"
 
 namespace rkh {
+#ifdef RKH_PLANAR_PRISMATIC_FORMS
+namespace planar_prismatic {
+constexpr bool kPlanarPrismatic = true;
+#else
+constexpr bool kPlanarPrismatic = false;
+#endif
 
 RKH_DI d2 cross_sv(double S, d2 V) { return d2{-V.y * S, V.x * S}; }  // vect_alg.hpp:1171-1176
 RKH_DI double cross_vv(d2 a, d2 b) { return a.x * b.y - a.y * b.x; }  // vect_alg.hpp:1142-1144
+RKH_DI double dot_vv(d2 a, d2 b) { return (0.0 + a.x * b.x) + a.y * b.y; }  // vect_alg.hpp operator*(vect, vect)
+
+// joint j is a prismatic_joint_2D (uniform over the launch; always false in the revolute forms)
+RKH_DI bool planar_is_prismatic(const SceneDev* __restrict__ sc, int j) {
+  return kPlanarPrismatic && ((sc->prismatic_mask >> j) & 1u);
+}
 
 template <int N>
 struct PlanarFrames {
   d2 Epos[N], Erot[N], Eacc[N];  // revolute_joint_2D end frames
   d2 Lpos[N], Lrot[N], Lacc[N];  // rigid_link_2D end frames
   double w[N], alpha[N];         // angular velocity / acceleration of joint j's end frame (the link's is the same)
-  double cq[N], sq[N];           // cos / sin of the joint angles
+  double cq[N], sq[N];           // cos / sin of the joint angles (1, 0 for a prismatic joint)
 };
 
-// kte_map_chain::doMotion over {revolute_joint_2D, rigid_link_2D} (velocities only where a force term reads them)
+// kte_map_chain::doMotion over {revolute_joint_2D | prismatic_joint_2D, rigid_link_2D} (velocities only where a force
+// term reads them)
 template <int N>
 RKH_DI void planar_motion(const SceneDev* __restrict__ sc, const double* __restrict__ x, PlanarFrames<N>& F) {
   d2 pos = mk2(sc->base_pos[0], sc->base_pos[1]);
@@ -44,6 +68,41 @@ RKH_DI void planar_motion(const SceneDev* __restrict__ sc, const double* __restr
   double w = 0.0, alpha = 0.0;
 #pragma unroll
   for (int j = 0; j < N; ++j) {
+    if constexpr (kPlanarPrismatic) {  // either joint kind, then the link as below
+      d2 ERp;
+      if (planar_is_prismatic(sc, j)) {
+        // prismatic_joint_2D::doMotion (prismatic_joint.cpp:44-62): the base moved by R (q a); rotation and rates pass
+        const d2 a = mk2(sc->joints[j].axis[0], sc->joints[j].axis[1]);
+        const d2 tmp_pos = x[2 * j] * a, tmp_vel = x[2 * j + 1] * a;
+        F.cq[j] = 1.0;
+        F.sq[j] = 0.0;
+        pos = pos + rrot(R, tmp_pos);
+        acc = acc + rrot(R, (((-w * w) * tmp_pos + cross_sv(2.0 * w, tmp_vel)) + cross_sv(alpha, tmp_pos)) + 0.0 * a);
+        ERp = R;
+      } else {
+        double snp, csp;
+        sincos(x[2 * j], &snp, &csp);
+        F.cq[j] = csp;
+        F.sq[j] = snp;
+        ERp = rmul(R, mk2(csp, snp));
+        w = w + x[2 * j + 1];
+        alpha = alpha + 0.0;
+      }
+      F.Epos[j] = pos;
+      F.Erot[j] = ERp;
+      F.Eacc[j] = acc;
+      F.w[j] = w;
+      F.alpha[j] = alpha;
+      const d2 off = mk2(sc->joints[j].off_pos[0], sc->joints[j].off_pos[1]);
+      const d2 offR = mk2(sc->joints[j].off_quat[0], sc->joints[j].off_quat[1]);
+      pos = pos + rrot(ERp, off);
+      acc = acc + rrot(ERp, (-w * w) * off + cross_sv(alpha, off));
+      R = rmul(ERp, offR);
+      F.Lpos[j] = pos;
+      F.Lrot[j] = R;
+      F.Lacc[j] = acc;
+      continue;
+    }
     double sn, cs;
     sincos(x[2 * j], &sn, &cs);
     F.cq[j] = cs;
@@ -92,6 +151,28 @@ RKH_DI bool planar_state_derivative(const SceneDev* __restrict__ sc, const doubl
     const d2 tmp_force = rrot(offR, Lforce);
     const d2 Eforce = mk2(0.0, 0.0) + tmp_force;
     const double Etorque = 0.0 + (Ltorque + cross_vv(off, tmp_force));
+    if constexpr (kPlanarPrismatic) {
+      if (planar_is_prismatic(sc, j)) {
+        // prismatic_joint_2D::doForce (prismatic_joint.cpp:89-94): f += F . a; base.Force += F - (F . a) a;
+        // base.Torque += T + (q a) % F -- unlike the revolute joint, this one hands the torque on to its base
+        const d2 a = mk2(J.axis[0], J.axis[1]);
+        const double tmp_f = dot_vv(Eforce, a);
+        f[j] = 0.0 + tmp_f;
+        Lforce = mk2(0.0, 0.0) + (Eforce - tmp_f * a);
+        Ltorque = 0.0 + (Etorque + cross_vv(x[2 * j] * a, Eforce));
+        // inertia_gen::doForce; driving_actuator_gen::doForce: f += u, then applyReactionForce (:120-123): base.Force -= u a
+        f[j] = f[j] - J.joint_inertia * 0.0;
+        f[j] = f[j] + u[j];
+        Lforce = Lforce - u[j] * a;
+      } else {  // the revolute joint, as below
+        Lforce = mk2(0.0, 0.0) + rrot(mk2(F.cq[j], F.sq[j]), Eforce);
+        f[j] = 0.0 + Etorque;
+        f[j] = f[j] - J.joint_inertia * 0.0;
+        f[j] = f[j] + u[j];
+        Ltorque = 0.0 - u[j];
+      }
+      continue;
+    }
     // revolute_joint_2D::doForce: base.Force += R(q) * end.Force; f += end.Torque (nothing reaches the base's torque)
     Lforce = mk2(0.0, 0.0) + rrot(mk2(F.cq[j], F.sq[j]), Eforce);
     f[j] = 0.0 + Etorque;
@@ -102,6 +183,12 @@ RKH_DI bool planar_state_derivative(const SceneDev* __restrict__ sc, const doubl
   }
   // mass matrix: Tcm columns.  Rows: N generalized inertias, then (v_x, v_y, omega) of every inertia_2D
   double tv[N][N][2];  // tv[j][i] = qd_vel of joint i's jacobian relative to link j's end frame (i <= j)
+  // qd_avel of joint i's jacobian: 1 (revolute_joint.cpp:50-55), 0 for a prismatic joint (used by the prismatic forms only)
+  double wt[kPlanarPrismatic ? N : 1];
+  if constexpr (kPlanarPrismatic) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) wt[i] = planar_is_prismatic(sc, i) ? 0.0 : 1.0;
+  }
 #pragma unroll
   for (int j = 0; j < N; ++j) {
 #pragma unroll
@@ -111,6 +198,14 @@ RKH_DI bool planar_state_derivative(const SceneDev* __restrict__ sc, const doubl
       const d2 inv_rot = mk2(F.Erot[i].x, -F.Erot[i].y);
       const d2 f2_pos = inv_pos + rrot(inv_rot, F.Lpos[j]);
       const d2 f2_rot = rmul(inv_rot, F.Lrot[j]);
+      if constexpr (kPlanarPrismatic) {  // a prismatic joint's jacobian: qd_vel = a, qd_avel = 0 (prismatic_joint.cpp:53-54)
+        const d2 vp = planar_is_prismatic(sc, i)
+                          ? rrotT(cross_sv(0.0, f2_pos) + mk2(sc->joints[i].axis[0], sc->joints[i].axis[1]), f2_rot)
+                          : rrotT(cross_sv(1.0, f2_pos) + mk2(0.0, 0.0), f2_rot);
+        tv[j][i][0] = vp.x;
+        tv[j][i][1] = vp.y;
+        continue;
+      }
       const d2 v = rrotT(cross_sv(1.0, f2_pos) + mk2(0.0, 0.0), f2_rot);
       tv[j][i][0] = v.x;
       tv[j][i][1] = v.y;
@@ -132,7 +227,11 @@ RKH_DI bool planar_state_derivative(const SceneDev* __restrict__ sc, const doubl
         const JointDev& J = sc->joints[j];
         s = s + tv[j][i][0] * (J.mass * tv[j][jj][0]);
         s = s + tv[j][i][1] * (J.mass * tv[j][jj][1]);
-        s = s + 1.0 * (J.inertia[0] * 1.0);
+        if constexpr (kPlanarPrismatic) {  // the omega entry of a column: 1 for a revolute joint, 0 for a prismatic one
+          s = s + wt[i] * (J.inertia[0] * wt[jj]);
+        } else {
+          s = s + 1.0 * (J.inertia[0] * 1.0);
+        }
       }
       M[i][jj] = s;
     }
@@ -204,6 +303,16 @@ RKH_DI bool planar_is_free(const SceneDev* __restrict__ sc, const PairDev* __res
     d2 R = mk2(sc->base_quat[0], sc->base_quat[1]);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
+      if constexpr (kPlanarPrismatic) {
+        if (planar_is_prismatic(sc, j)) {  // the base moved by R (q a), same rotation; then the link as below
+          pos = pos + rrot(R, x[2 * j] * mk2(sc->joints[j].axis[0], sc->joints[j].axis[1]));
+          Epos[j] = pos;
+          Erot[j] = R;
+          pos = pos + rrot(R, mk2(sc->joints[j].off_pos[0], sc->joints[j].off_pos[1]));
+          R = rmul(R, mk2(sc->joints[j].off_quat[0], sc->joints[j].off_quat[1]));
+          continue;
+        }
+      }
       double sn, cs;
       sincos(x[2 * j], &sn, &cs);
       const d2 ER = rmul(R, mk2(cs, sn));
@@ -369,11 +478,15 @@ __global__ __launch_bounds__(64) void planar_state_derivative_kernel(const Scene
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// Written once for both joint kinds: the revolute launchers hand chains with prismatic joints on to rkh::planar_prismatic.
 rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
                                    uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
                                    uint32_t n_problems, KernelGate gate) {
   const uint32_t eb = tab_b ? grid_b : 0u;
   if (grid_edges + eb == 0 || n_problems == 0) return RKH_OK;
+  if constexpr (!kPlanarPrismatic)
+    if (scene.host.has_prismatic)
+      return planar_prismatic::launch_propagate_planar(s, scene, dyn, io, grid_edges, grid_b, tab_a, tab_b, n_problems, gate);
   const uint32_t blocks_a = (grid_edges + 63) / 64, blocks_b = (eb + 63) / 64;
   gate.wave_base = nullptr;  // the compact wave numbering of the 3D mappings does not apply: plain (block, problem) grid
   gate.n_segments = 0;
@@ -390,6 +503,9 @@ rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const 
 rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u,
                                           uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err) {
   if (B == 0) return RKH_OK;
+  if constexpr (!kPlanarPrismatic)
+    if (scene.host.has_prismatic)
+      return planar_prismatic::launch_state_derivative_planar(s, scene, d_x, d_u, B, d_pd, d_M, d_f, d_err);
   const rkh_status st = with_n<1, 2, 3, 4, 6, 7>(scene.host.n_dof, [&](auto c) {
     hipLaunchKernelGGL((planar_state_derivative_kernel<decltype(c)::value>), dim3((B + 63) / 64), dim3(64), 0, s,
                        scene.d_scene.get(), d_x, d_u, B, d_pd, d_M, d_f, d_err);
@@ -399,4 +515,7 @@ rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene,
   return RKH_OK;
 }
 
+#ifdef RKH_PLANAR_PRISMATIC_FORMS
+}  // namespace planar_prismatic
+#endif
 }  // namespace rkh

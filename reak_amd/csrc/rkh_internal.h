@@ -481,5 +481,18 @@ rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const 
                                    uint32_t n_problems, KernelGate gate);
 rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u,
                                           uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
+// the same two compiled for planar chains with prismatic_joint_2D groups (propagate_planar_prismatic.hip); the ones above
+// hand these scenes on
+namespace planar_prismatic {
+rkh_status launch_propagate_planar(hipStream_t s, const rkh_scene& scene, const DynDev& dyn, const EdgeIO& io,
+                                   uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
+                                   uint32_t n_problems, KernelGate gate);
+rkh_status launch_state_derivative_planar(hipStream_t s, const rkh_scene& scene, const double* d_x, const double* d_u,
+                                          uint32_t B, double* d_pd, double* d_M, double* d_f, int* d_err);
+// and the position-level forms (propagate_planar_qs_prismatic.hip); launch_edge_check / launch_min_distance hand on
+rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
+                             uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems);
+rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
+}  // namespace planar_prismatic
 rkh_status build_dyn_dev(const rkh_dyn_space& sp, double fraction, DynDev* out);
 }  // namespace rkh

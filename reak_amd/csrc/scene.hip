@@ -188,23 +188,29 @@ static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, cons
   return RKH_OK;
 }
 
-// Planar chain (manip_3R_arm.cpp:75-150 pattern): {revolute_joint_2D, rigid_link_2D} per joint, 2D shapes only.
-// Position level: the scene serves the quasi-static entry points; the dynamics entry points refuse it.
+// Planar chain (manip_3R_arm.cpp:75-150 pattern): {revolute_joint_2D | prismatic_joint_2D, rigid_link_2D} per joint, 2D
+// shapes only.  Given at the position level the scene serves the quasi-static entry points and the dynamics entry
+// points refuse it.  A prismatic_joint_2D (prismatic_joint.cpp:33-123) may stand in any group: its bit goes into
+// SceneDev::prismatic_mask and its axis into JointDev::axis[0..1], and the launchers pick the planar prismatic forms.
+static bool is_planar_joint(int kind) { return kind == RKH_KTE_REVOLUTE_JOINT_2D || kind == RKH_KTE_PRISMATIC_JOINT_2D; }
+
 static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int n_ops, const rkh_chain_base* base,
                                       const rkh_shape* shapes, int n_shapes, rkh_scene** out) {
-  // position level: {revolute_joint_2D, rigid_link_2D} per joint; with dynamics: {driving_actuator_gen, inertia_gen,
-  // revolute_joint_2D, rigid_link_2D, inertia_2D on the link's end frame} per joint
+  // position level: {joint, rigid_link_2D} per joint; with dynamics: {driving_actuator_gen, inertia_gen, joint,
+  // rigid_link_2D, inertia_2D on the link's end frame} per joint; joint = revolute_joint_2D or prismatic_joint_2D
   for (int k = 0; k < n_ops; ++k)
     if (prog[k].kind == RKH_KTE_PRISMATIC_JOINT_3D) {
-      set_error("rkh_scene_create: prismatic joints are not supported in planar chains");
+      set_error("rkh_scene_create: prismatic_joint_3D is not supported in planar chains (a planar chain takes "
+                "prismatic_joint_2D)");
       return RKH_ERR_UNSUPPORTED;
     }
   const bool dynamics = prog[0].kind == RKH_KTE_DRIVING_ACTUATOR_GEN;
   const int per = dynamics ? 5 : 2;
   const int n = n_ops / per;
   if (n_ops % per != 0 || n < 1 || n > kMaxDof) {
-    set_error("rkh_scene_create: a planar chain is a sequence of {revolute_joint_2D, rigid_link_2D} pairs, or of "
-              "{driving_actuator_gen, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D} groups");
+    set_error("rkh_scene_create: a planar chain is a sequence of {revolute_joint_2D or prismatic_joint_2D, rigid_link_2D} "
+              "pairs, or of {driving_actuator_gen, inertia_gen, revolute_joint_2D or prismatic_joint_2D, rigid_link_2D, "
+              "inertia_2D} groups");
     return RKH_ERR_UNSUPPORTED;
   }
   std::unique_ptr<rkh_scene> sc(new rkh_scene());
@@ -223,7 +229,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
   int prev_end = 0;
   for (int j = 0; j < n; ++j) {
     const rkh_kte_op& rev = prog[per * j + (dynamics ? 2 : 0)], &lnk = prog[per * j + (dynamics ? 3 : 1)];
-    if (rev.kind != RKH_KTE_REVOLUTE_JOINT_2D || lnk.kind != RKH_KTE_RIGID_LINK_2D || rev.coord != j ||
+    if (!is_planar_joint(rev.kind) || lnk.kind != RKH_KTE_RIGID_LINK_2D || rev.coord != j ||
         rev.base_frame != prev_end || lnk.base_frame != rev.end_frame) {
       set_error("rkh_scene_create: planar op group " + std::to_string(j) + " does not continue the serial chain");
       return RKH_ERR_UNSUPPORTED;
@@ -235,7 +241,8 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
           gen.kind != RKH_KTE_INERTIA_GEN || gen.coord != j || gen.upstream != (1u << j) ||
           in2.kind != RKH_KTE_INERTIA_2D || in2.end_frame != lnk.end_frame || in2.upstream != ((1u << (j + 1)) - 1u)) {
         set_error("rkh_scene_create: planar op group " + std::to_string(j) +
-                  " is not {actuator, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D} of one serial joint");
+                  " is not {actuator, inertia_gen, revolute_joint_2D or prismatic_joint_2D, rigid_link_2D, inertia_2D} of "
+                  "one serial joint");
         return RKH_ERR_UNSUPPORTED;
       }
       J.joint_inertia = gen.mass;
@@ -244,12 +251,18 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
     }
     prev_end = lnk.end_frame;
     joint_end_frame[j] = rev.end_frame;
+    if (rev.kind == RKH_KTE_PRISMATIC_JOINT_2D) {  // mAxis as given: the joint does not normalise it
+      S.prismatic_mask |= 1u << j;
+      J.axis[0] = rev.axis[0];
+      J.axis[1] = rev.axis[1];
+    }
     for (int i = 0; i < 2; ++i) {
       J.off_pos[i] = lnk.offset.pos[i];
       J.off_quat[i] = lnk.offset.quat[i];
     }
     S.mount_quat[j][0] = 1.0;
   }
+  S.has_prismatic = S.prismatic_mask != 0u ? 1 : 0;
   for (int i = 0; i < n_shapes; ++i) {
     const rkh_shape& s = shapes[i];
     if (s.kind < RKH_SHAPE_CIRCLE || s.kind > RKH_SHAPE_CRECT) {
@@ -271,7 +284,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       for (int j = 0; j < n; ++j)
         if (joint_end_frame[j] == s.anchor) link = j;
       if (link < 0 || S.n_robot >= 2 * kMaxDof) {
-        set_error("rkh_scene_create: robot shapes must be anchored on a revolute joint's end frame");
+        set_error("rkh_scene_create: robot shapes must be anchored on a joint's end frame");
         return RKH_ERR_UNSUPPORTED;
       }
       d.link = link;
@@ -328,9 +341,24 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
   if (n_mesh_vertices > 0 && !mesh_vertices) return RKH_ERR_BAD_ARG;
   g_mesh_vertices = mesh_vertices;  // for bounding_radius() / validation while the scene is built (one host thread per ctx)
   g_n_mesh_vertices = n_mesh_vertices;
-  if (prog[0].kind == RKH_KTE_REVOLUTE_JOINT_2D ||
-      (n_ops >= 3 && prog[0].kind == RKH_KTE_DRIVING_ACTUATOR_GEN && prog[2].kind == RKH_KTE_REVOLUTE_JOINT_2D))
+  // a planar chain: its first joint is a revolute_joint_2D, or it holds 2D elements and nothing three-dimensional (a
+  // chain whose first joint is a misplaced prismatic_joint_3D is answered by the planar builder, which names it; a
+  // prismatic_joint_2D among 3D elements is answered below)
+  bool any_2d = false, any_3d = false;
+  for (int k = 0; k < n_ops; ++k) {
+    const int kd = prog[k].kind;
+    any_2d = any_2d || kd == RKH_KTE_REVOLUTE_JOINT_2D || kd == RKH_KTE_RIGID_LINK_2D || kd == RKH_KTE_INERTIA_2D;
+    any_3d = any_3d || kd == RKH_KTE_REVOLUTE_JOINT_3D || kd == RKH_KTE_RIGID_LINK_3D || kd == RKH_KTE_INERTIA_3D ||
+             kd == RKH_KTE_FLEXIBLE_BEAM_3D;
+  }
+  const int first_joint = prog[0].kind == RKH_KTE_DRIVING_ACTUATOR_GEN && n_ops >= 3 ? prog[2].kind : prog[0].kind;
+  if (first_joint == RKH_KTE_REVOLUTE_JOINT_2D || (!any_3d && (any_2d || first_joint == RKH_KTE_PRISMATIC_JOINT_2D)))
     return create_planar_scene(ctx, prog, n_ops, base, shapes, n_shapes, out);
+  for (int k = 0; k < n_ops; ++k)
+    if (prog[k].kind == RKH_KTE_PRISMATIC_JOINT_2D) {
+      set_error("rkh_scene_create: prismatic_joint_2D is not supported in 3D chains (a 3D chain takes prismatic_joint_3D)");
+      return RKH_ERR_UNSUPPORTED;
+    }
   const bool has_beam = n_ops > 1 && prog[n_ops - 1].kind == RKH_KTE_FLEXIBLE_BEAM_3D;
   if (has_beam) --n_ops;  // the beam is validated below, after the chain
   // parse: [optional mount link from frame 0] {actuator, inertia_gen, revolute, link, inertia_3D} ...

@@ -272,18 +272,24 @@ def make_c1(world_seed=1, n_obstacles=10, min_interval=0.05):
     return scn
 
 
-def planar_chain_ops(lengths, dynamics=False, masses=None, moments=None, joint_inertias=None):
+def planar_chain_ops(lengths, dynamics=False, masses=None, moments=None, joint_inertias=None, kinds=None, axes=None):
     """kte_map_chain of a planar serial arm (manip_3R_arm.cpp:75-150): per joint {revolute_joint_2D, rigid_link_2D}, and
-    with dynamics {driving_actuator_gen, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D at the link's end}."""
+    with dynamics {driving_actuator_gen, inertia_gen, revolute_joint_2D, rigid_link_2D, inertia_2D at the link's end}.
+    kinds[j] = KTE_PRISMATIC_JOINT_2D puts a prismatic_joint_2D along axes[j] (given as is, not normalised) in group j;
+    lengths[j] may be a number (a link along x) or a pose_2D (T.make_pose_2d)."""
     ops = []
     for j, length in enumerate(lengths):
+        kind = T.KTE_REVOLUTE_JOINT_2D if kinds is None else kinds[j]
         if dynamics:
             ops.append(T.KteOp(kind=T.KTE_DRIVING_ACTUATOR_GEN, coord=j, base_frame=-1, end_frame=-1, joint_op=5 * j + 2))
             ops.append(T.KteOp(kind=T.KTE_INERTIA_GEN, coord=j, base_frame=-1, end_frame=-1, joint_op=-1, upstream=(1 << j),
                                mass=float(joint_inertias[j])))
-        ops.append(T.KteOp(kind=T.KTE_REVOLUTE_JOINT_2D, coord=j, base_frame=2 * j, end_frame=2 * j + 1, joint_op=-1))
+        jo = T.KteOp(kind=kind, coord=j, base_frame=2 * j, end_frame=2 * j + 1, joint_op=-1)
+        if kind == T.KTE_PRISMATIC_JOINT_2D:
+            jo.axis[:] = [float(axes[j][0]), float(axes[j][1]), 0.0]
+        ops.append(jo)
         l = T.KteOp(kind=T.KTE_RIGID_LINK_2D, coord=-1, base_frame=2 * j + 1, end_frame=2 * j + 2, joint_op=-1)
-        l.offset = T.make_pose_2d((length, 0.0))
+        l.offset = length if isinstance(length, T.Pose) else T.make_pose_2d((length, 0.0))
         ops.append(l)
         if dynamics:
             i2 = T.KteOp(kind=T.KTE_INERTIA_2D, coord=-1, base_frame=-1, end_frame=2 * j + 2, joint_op=-1,
@@ -382,6 +388,84 @@ def make_planar_mixed(seed=1, n=4, n_obstacles=24):
     return Scenario(name=f"planar{n}", ops=ops, base=base, shapes=shapes, dyn=dyn, n_dof=n, n_frames=2 * n + 1,
                     start=np.zeros(n), goal=goal,
                     meta={"lower": np.full(n, -np.pi), "upper": np.full(n, np.pi), "min_interval": 0.05})
+
+
+def make_crs_a465_2d(world_seed=1, n_obstacles=12, dynamics=False, min_interval=0.05, link_width=0.06):
+    """The planar analog of the CRS A465 on its track (examples/robot_airship/old/CRS_A465_2D_analog.cpp:139-360): a
+    prismatic_joint_2D along (1, 0) with 0 to 3 m of travel, link_0 with a zero offset, then three revolute_joint_2D with
+    links of 0.3048, 0.3302 and 0.0762 m; every rotor inertia, link mass and moment of inertia is 1.0 as in that file,
+    and so are the joint bounds, speed limits (0.8 m/s; 3.14, 3.14, 3.02 rad/s) and acceleration limits.  The file has no
+    geometry: links are capped_rectangle shapes on the revolute joints' end frames plus a circle on the carriage,
+    obstacles are rectangles and circles on both sides of the track (as in make_c1_planar), clear of the arm held along
+    +x at every track position.  Start and goal sit at opposite ends of the track.  meta carries the quasi-static box in
+    the RATE-LIMITED coordinates t_i = q_i / speed_i (lower, upper, min_interval, speed_limits, accel_limits) and
+    `qs`, the rkh_qs_space with speed_limits set; with dynamics the steerable space over (q, qd), velocities within the
+    speed limits (the reference model has no gravity: its base acceleration stays zero)."""
+    rng = np.random.Generator(np.random.PCG64(4650 + world_seed))
+    n = 4
+    lengths = [0.0, 0.3048, 0.3302, 0.0762]
+    kinds = [T.KTE_PRISMATIC_JOINT_2D] + [T.KTE_REVOLUTE_JOINT_2D] * 3
+    axes = [(1.0, 0.0)] + [None] * 3
+    ops = planar_chain_ops(lengths, dynamics=dynamics, masses=[1.0] * n, moments=[1.0] * n, joint_inertias=[1.0] * n,
+                           kinds=kinds, axes=axes)
+    q_lower = np.array([0.0, -3.05432619099, -1.91986217719, -1.83259571459])
+    q_upper = np.array([3.0, 3.05432619099, 1.91986217719, 1.83259571459])
+    speed = np.array([0.8, 3.14159265359, 3.14159265359, 3.01941960595])
+    accel = np.array([3.0, 12.5663706144, 12.5663706144, 24.9582083035])
+    shapes = []
+    s = T.Shape(kind=T.SHAPE_CIRCLE, anchor=1)  # the carriage
+    s.pose = T.make_pose_2d()
+    s.dims[:] = [0.08, 0.0, 0.0]
+    shapes.append(s)
+    for j in range(1, n):
+        s = T.Shape(kind=T.SHAPE_CRECT, anchor=2 * j + 1)
+        s.pose = T.make_pose_2d((0.5 * lengths[j], 0.0))
+        s.dims[:] = [lengths[j], link_width, 0.0]
+        shapes.append(s)
+    base = T.ChainBase()
+    base.pose = T.make_pose_2d()
+    reach = sum(lengths)
+    placed = 0
+    while placed < n_obstacles:
+        c = np.array([rng.uniform(-0.8, 3.8), rng.uniform(-1.0, 1.0), 0.0])
+        circle = placed % 3 == 2
+        if circle:
+            r = rng.uniform(0.05, 0.15)
+            dims, brad, yaw = [r, 0.0, 0.0], r, 0.0
+        else:
+            d = np.array([rng.uniform(0.1, 0.3), rng.uniform(0.1, 0.3)])
+            dims, brad, yaw = [float(d[0]), float(d[1]), 0.0], 0.5 * np.hypot(d[0], d[1]), rng.uniform(-np.pi, np.pi)
+        # keep-out: the strip the arm sweeps when it rides the track stretched along +x
+        if _dist_point_segment(c, np.zeros(3), np.array([3.0 + reach, 0.0, 0.0])) < brad + 0.5 * link_width + 0.12:
+            continue
+        s = T.Shape(kind=T.SHAPE_CIRCLE if circle else T.SHAPE_RECTANGLE, anchor=-1)
+        s.pose = T.make_pose_2d(c[:2], yaw)
+        s.dims[:] = dims
+        shapes.append(s)
+        placed += 1
+    q_start, q_goal = np.array([0.2, 0.0, 0.0, 0.0]), np.array([2.8, 0.0, 0.0, 0.0])
+    qs = T.QsSpace()
+    qs.n_dof = n
+    qs.min_interval = min_interval
+    for j in range(n):
+        qs.lower[j], qs.upper[j] = q_lower[j] / speed[j], q_upper[j] / speed[j]
+        qs.speed_limits[j] = speed[j]
+    dyn = T.DynSpace()
+    dyn.n_dof = n
+    start, goal = q_start / speed, q_goal / speed
+    if dynamics:
+        dyn.steps_per_edge, dyn.dt = 20, 1e-3
+        dyn.kp, dyn.kd, dyn.u_max, dyn.goal_tol = 50.0, 10.0, 50.0, 1e-3
+        for j in range(n):
+            dyn.lower[2 * j], dyn.upper[2 * j] = q_lower[j], q_upper[j]
+            dyn.lower[2 * j + 1], dyn.upper[2 * j + 1] = -speed[j], speed[j]
+        start, goal = np.zeros(2 * n), np.zeros(2 * n)
+        start[0::2], goal[0::2] = q_start, q_goal
+    return Scenario(name="crs_a465_2d", ops=ops, base=base, shapes=shapes, dyn=dyn, n_dof=n, n_frames=2 * n + 1,
+                    start=start, goal=goal,
+                    meta={"world_seed": world_seed, "lower": q_lower / speed, "upper": q_upper / speed,
+                          "min_interval": min_interval, "speed_limits": speed, "accel_limits": accel, "qs": qs,
+                          "q_start": q_start, "q_goal": q_goal})
 
 
 def make_c3(world_seed=1, min_interval=0.05):

@@ -18,6 +18,7 @@ KTE_REVOLUTE_JOINT_2D = 7
 KTE_RIGID_LINK_2D = 8
 KTE_INERTIA_2D = 9
 KTE_PRISMATIC_JOINT_3D = 10  # mAxis as given (prismatic_joint_3D does not normalise it)
+KTE_PRISMATIC_JOINT_2D = 11  # planar chains: axis[0..1] = mAxis as given, axis[2] ignored
 
 # rkh_shape_kind
 SHAPE_SPHERE = 1

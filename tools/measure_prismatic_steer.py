@@ -2,7 +2,9 @@
 
 Scenes: `track` = the CRS A465 on its linear track (scenarios.make_crs_a465_track, 7 joints), `chain6` = the random
 6-joint chain of scenarios.make_random_chain(6, seed=4, n_obstacles=16) with joints 0 and 3 turned prismatic (axis scaled
-by 0.7 / 1.1, position bounds +-0.5).  One warm-up solve at a tenth of the size, then --runs timed solves; the mapping
+by 0.7 / 1.1, position bounds +-0.5), `analog2d` = the planar CRS A465 analog of scenarios.make_crs_a465_2d(dynamics=True)
+(prismatic_joint_2D track + three revolute_joint_2D) and `analog2d_rev` = the same chain with joint 0 made revolute (the
+comparison within one build: the planar prismatic forms against the revolute ones).  One warm-up solve at a tenth of the size, then --runs timed solves; the mapping
 is whatever the environment asks for (RKH_LANES_PER_EDGE, see the steer plan in reak_amd/csrc/rkh_internal.h).  Prints
 one JSON line: valid node expansions/s of every run (vertices added / wall time of the solve), their min and max.
 --tree measures another checkout (its reak_amd package and built librkh.so) with the same scenes."""
@@ -13,7 +15,7 @@ import sys
 import time
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--scene", choices=["track", "chain6"], required=True)
+ap.add_argument("--scene", choices=["track", "chain6", "analog2d", "analog2d_rev"], required=True)
 ap.add_argument("--problems", type=int, default=256)
 ap.add_argument("--vertices", type=int, default=20000)
 ap.add_argument("--runs", type=int, default=3)
@@ -48,7 +50,15 @@ def solve(scene, scn, problems, vertices):
     return nodes / dt, dt, nodes, steps
 
 
-scn = scenarios.make_crs_a465_track() if args.scene == "track" else chain6()
+def analog2d(revolute_root):
+    scn = scenarios.make_crs_a465_2d(dynamics=True)
+    if revolute_root:
+        next(o for o in scn.ops if o.kind == T.KTE_PRISMATIC_JOINT_2D).kind = T.KTE_REVOLUTE_JOINT_2D
+    return scn
+
+
+scn = {"track": scenarios.make_crs_a465_track, "chain6": chain6, "analog2d": lambda: analog2d(False),
+       "analog2d_rev": lambda: analog2d(True)}[args.scene]()
 ctx = lib.Context(0)
 scene = lib.Scene(ctx, scn)
 solve(scene, scn, args.problems, max(200, args.vertices // 10))
