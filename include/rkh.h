@@ -179,7 +179,7 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
  * them are written to row b of the [B][cap] arrays; the slots behind them read dist +inf, shape ids 0xFFFFFFFF, points 0.
  * No pointer may be NULL (RKH_ERR_BAD_ARG); B == 0 is RKH_OK.  RKH_ERR_UNSUPPORTED, with an error text: scenes with
  * RKH_SHAPE_MESH shapes (the support-map query yields a distance and no points) and planar (2D) scenes
- * (proxy_query_pair_2D's records are not built). */
+ * (proxy_query_pair_2D's records come from the _2d entries below). */
 rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t B,
                                     double* dist,      /* [B]    */
                                     double* point1,    /* [B][3] */
@@ -190,6 +190,29 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
                                  uint32_t* n_found,                             /* [B] */
                                  double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
                                  uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
+/* The same for planar (2D) scenes: what proxy_query_pair_2D::findMinimumDistance()->getLastResult() and
+ * gatherCollisionPoints hold (proxy_query_model.cpp:163-187 and :189-208; proximity_record_2D.hpp:47-58: points are
+ * vect<double,2>).  x as for rkh_min_distance; shape1 / shape2 and the finder order as above, with createProxFinderList's
+ * 2D cascade (:75-161): the circle first, else the capped rectangle; rectangle / rectangle: the robot's shape.
+ * rkh_min_distance_records_2d: the record of mProxFinders[min_i] after the loop of :163-187.  Unlike in 3D, the cull
+ * against the running minimum can drop a finder that would win (capped_rectangle::getBoundingRadius is shorter than the
+ * caps reach), so the winner is NOT the lowest distance but what the sequence leaves: finder 0 is always computed,
+ * finder i >= 1 is skipped when |c2 - c1| - r1 - r2 > min_dist and otherwise takes over on a strictly smaller distance.
+ * dist[b] is bit-identical to rkh_min_distance's.  A scene without finders: dist = +inf, shape ids 0xFFFFFFFF, points 0.
+ * rkh_collision_records_2d: every finder whose bounding circles are not apart ("> 0.0" skips) and whose distance is
+ * < 0.0, in finder order; n_found, cap and the unused slots as for rkh_collision_records.
+ * No pointer may be NULL (RKH_ERR_BAD_ARG); B == 0 is RKH_OK.  RKH_ERR_UNSUPPORTED, with an error text: scenes that are
+ * not planar (their records come from rkh_min_distance_records / rkh_collision_records). */
+rkh_status rkh_min_distance_records_2d(rkh_scene* scene, const double* x, uint32_t B,
+                                       double* dist,      /* [B]    */
+                                       double* point1,    /* [B][2] */
+                                       double* point2,    /* [B][2] */
+                                       uint32_t* shape1,  /* [B]    */
+                                       uint32_t* shape2); /* [B]    */
+rkh_status rkh_collision_records_2d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap,
+                                    uint32_t* n_found,                             /* [B] */
+                                    double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][2], [B][cap][2] */
+                                    uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
 /* steer_position_toward of the steerable dynamic free space (rkh_dyn_space) for B (a,b) pairs:
  * x_out [B][2n] last collision-free state, steps_free[B] accepted RK4 steps, record (optional)
  * [B][steps_per_edge+1][2n] the steer record. RK4 = runge_kutta4_integrate_impl

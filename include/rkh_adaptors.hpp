@@ -426,7 +426,8 @@ struct is_steerable_space_tag<kte_dynamic_free_space<P> > {
 // (manip_direct_kin_map::apply_to_model), evaluates every finder of the pair list in one call and returns the winning
 // finder's whole record (rkh_min_distance_records), or the records of all colliding finders (rkh_collision_records).
 // Scenes whose records are not built (mesh shapes, planar chains: RKH_ERR_UNSUPPORTED from those entries) still answer
-// with the distance; their points are NaN and their shape indices no_shape.
+// with the distance; their points are NaN and their shape indices no_shape.  Planar callers who want the records use
+// hip_proxy_query_pair_2D below.
 struct proximity_record {  // proximity_record_3D (proximity_record_3D.hpp:47-56)
   double mPoint1[3] = {0.0, 0.0, 0.0};  // on the finder's shape1, world frame
   double mPoint2[3] = {0.0, 0.0, 0.0};  // on its shape2
@@ -490,6 +491,77 @@ class hip_proxy_query_pair {
       for (int k = 0; k < 3; ++k) {
         r.mPoint1[k] = p1[3 * std::size_t(i) + k];
         r.mPoint2[k] = p2[3 * std::size_t(i) + k];
+      }
+      r.mDistance = d[i];
+      aOutput.push_back(r);
+      if (shapes) shapes->push_back(std::make_pair(s1[i], s2[i]));
+    }
+    return n_found > 0;
+  }
+
+ private:
+  std::shared_ptr<rkh_scene> m_scene;
+  std::vector<double> m_state;
+};
+
+// The same socket for planar scenes: proxy_query_pair_2D::findMinimumDistance / gatherCollisionPoints
+// (proxy_query_model.cpp:163-187, :189-208; proximity_finder_2D.hpp:49-70) over rkh_min_distance_records_2d /
+// rkh_collision_records_2d.  The finder it returns is mProxFinders[min_i] of the reference's culled loop, which is not
+// always the finder at the lowest distance (rkh.h).  A scene that is not planar answers RKH_ERR_UNSUPPORTED (an exception).
+struct proximity_record_2D {  // proximity_record_2D (proximity_record_2D.hpp:47-58)
+  double mPoint1[2] = {0.0, 0.0};  // on the finder's shape1, world frame
+  double mPoint2[2] = {0.0, 0.0};  // on its shape2
+  double mDistance = std::numeric_limits<double>::infinity();
+};
+class hip_proximity_finder_2D {
+ public:
+  static const uint32_t no_shape = 0xFFFFFFFFu;
+  hip_proximity_finder_2D(const proximity_record_2D& r, uint32_t shape1, uint32_t shape2)
+      : m_last(r), m_shape1(shape1), m_shape2(shape2) {}
+  const proximity_record_2D& getLastResult() const { return m_last; }
+  // proximity_finder_2D::getShape1 / getShape2 as indices into the shapes array the scene was created from, in the
+  // finder's own order (the circle first, else the capped rectangle; rectangle / rectangle: the robot's shape)
+  uint32_t getShape1Index() const { return m_shape1; }
+  uint32_t getShape2Index() const { return m_shape2; }
+
+ private:
+  proximity_record_2D m_last;
+  uint32_t m_shape1 = no_shape, m_shape2 = no_shape;
+};
+class hip_proxy_query_pair_2D {
+ public:
+  explicit hip_proxy_query_pair_2D(const std::shared_ptr<rkh_scene>& scene) : m_scene(scene) {}
+  template <typename Point>
+  void apply_to_model(const Point& p) {
+    m_state.assign(&p[0], &p[0] + p.size());
+  }
+  std::shared_ptr<hip_proximity_finder_2D> findMinimumDistance() const {
+    if (rkh_scene_num_pairs(m_scene.get()) == 0) return std::shared_ptr<hip_proximity_finder_2D>();  // empty finder list
+    proximity_record_2D r;
+    uint32_t s1 = hip_proximity_finder_2D::no_shape, s2 = hip_proximity_finder_2D::no_shape;
+    check(rkh_min_distance_records_2d(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2));
+    return std::make_shared<hip_proximity_finder_2D>(r, s1, s2);
+  }
+  // appends the records of all colliding finders in finder order, returns whether there is one.  shapes (optional)
+  // receives their (shape1, shape2) indices.
+  bool gatherCollisionPoints(std::vector<proximity_record_2D>& aOutput,
+                             std::vector<std::pair<uint32_t, uint32_t> >* shapes = nullptr) const {
+    uint32_t cap = 8, n_found = 0;
+    std::vector<double> d, p1, p2;
+    std::vector<uint32_t> s1, s2;
+    for (;;) {  // grow until every colliding finder fits
+      d.resize(cap); p1.resize(2 * std::size_t(cap)); p2.resize(2 * std::size_t(cap));
+      s1.resize(cap); s2.resize(cap);
+      check(rkh_collision_records_2d(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
+                                     s1.data(), s2.data()));
+      if (n_found <= cap) break;
+      cap = n_found;
+    }
+    for (uint32_t i = 0; i < n_found; ++i) {
+      proximity_record_2D r;
+      for (int k = 0; k < 2; ++k) {
+        r.mPoint1[k] = p1[2 * std::size_t(i) + k];
+        r.mPoint2[k] = p2[2 * std::size_t(i) + k];
       }
       r.mDistance = d[i];
       aOutput.push_back(r);

@@ -85,8 +85,9 @@ rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2])
 rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]);
 
 /* Kernel time of the distance query on B states: `runs` launches of rkh_min_distance's kernel (records == 0) or of
- * rkh_min_distance_records' (records != 0) over the same device copy of x, each between two events on the context's
- * stream; ms[runs] = the elapsed times.  No copies are timed (tools/measure_record_query.py). */
+ * rkh_min_distance_records' (records != 0; on a planar scene rkh_min_distance_records_2d's) over the same device copy
+ * of x, each between two events on the context's stream; ms[runs] = the elapsed times.  No copies are timed
+ * (tools/measure_record_query.py). */
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms);
 
 #ifdef __cplusplus

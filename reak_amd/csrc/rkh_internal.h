@@ -290,7 +290,7 @@ struct rkh_scene {
   rkh::SceneDev host;
   rkh::DeviceBuffer<rkh::SceneDev> d_scene;
   rkh::DeviceBuffer<rkh::PairDev> d_pairs;   // [n_pairs], sorted by routine
-  rkh::DeviceBuffer<rkh::PairIdDev> d_pair_ids;  // [n_pairs] (3D scenes): finder rank and the caller's shape indices
+  rkh::DeviceBuffer<rkh::PairIdDev> d_pair_ids;  // [n_pairs]: finder rank and the caller's shape indices
   rkh::DeviceBuffer<double> d_mesh_verts;    // vertex pool of the mesh shapes
   rkh::DeviceBuffer<int> d_err;
   rkh::DeviceBuffer<unsigned long long> d_clear_stats;  // [2] KernelGate::clear_stats of every steer launch on this scene
@@ -430,6 +430,11 @@ struct RecordOut {
 rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
 rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
                                     RecordOut out);
+// Their planar twins (proximity_records_planar.hip; planar scenes, revolute and prismatic joints): points of two doubles
+// ([B][2], [B][cap][2]), finder rank = pair index.
+rkh_status launch_min_distance_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
+rkh_status launch_collision_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                       RecordOut out);
 // The same four compiled for chains with prismatic joints (propagate_prismatic.hip); the ones above hand these scenes on.
 namespace prismatic {
 rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,

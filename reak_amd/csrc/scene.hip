@@ -177,7 +177,7 @@ static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, cons
   RKH_HIP(hipMemcpy(sc->d_scene.get(), &S, sizeof(SceneDev), hipMemcpyHostToDevice));
   RKH_TRY(sc->d_pairs.alloc(std::max<size_t>(1, pairs.size())));
   if (!pairs.empty()) RKH_HIP(hipMemcpy(sc->d_pairs.get(), pairs.data(), pairs.size() * sizeof(PairDev), hipMemcpyHostToDevice));
-  if (pair_ids.size() == pairs.size() && !S.planar) {  // the record queries' table (3D scenes)
+  if (pair_ids.size() == pairs.size()) {  // the record queries' table
     RKH_TRY(sc->d_pair_ids.alloc(std::max<size_t>(1, pair_ids.size())));
     if (!pair_ids.empty())
       RKH_HIP(hipMemcpy(sc->d_pair_ids.get(), pair_ids.data(), pair_ids.size() * sizeof(PairIdDev), hipMemcpyHostToDevice));
@@ -226,6 +226,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
     S.base_acc[i] = base->acceleration[i];
   }
   std::vector<int> joint_end_frame(n);
+  std::vector<uint32_t> robot_src, env_src;  // the caller's shape index of every robot / environment slot
   int prev_end = 0;
   for (int j = 0; j < n; ++j) {
     const rkh_kte_op& rev = prog[per * j + (dynamics ? 2 : 0)], &lnk = prog[per * j + (dynamics ? 3 : 1)];
@@ -289,6 +290,7 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       }
       d.link = link;
       S.robot[S.n_robot++] = d;
+      robot_src.push_back(uint32_t(i));
     } else {
       if (S.n_env >= kMaxEnvShapes) {
         set_error("rkh_scene_create: too many environment shapes");
@@ -296,13 +298,17 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       }
       d.link = -1;
       S.env[S.n_env++] = d;
+      env_src.push_back(uint32_t(i));
     }
   }
   for (int r = 0; r < S.n_robot; ++r) S.robot_n_reach[r] = S.n_env;
   // proxy_query_pair_2D::createProxFinderList (proxy_query_model.cpp:75-161), kept in its i-major / j-minor order:
   // findMinimumDistance (:163-189) culls against the running minimum with a radius the capped rectangle's caps
   // reach beyond, so the result depends on the order and the device replays the sequence
+  // Every pair of kinds has a finder, so the pair index is the finder rank; the planar record queries
+  // (proximity_records_planar.hip) report the caller's indices of the finder's (shape1, shape2) from pair_ids.
   std::vector<PairDev> pairs;
+  std::vector<PairIdDev> pair_ids;
   for (int i = 0; i < S.n_robot; ++i)
     for (int j = 0; j < S.n_env; ++j) {
       const int ki = S.robot[i].kind, kj = S.env[j].kind;
@@ -322,9 +328,11 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
         p.s1_is_robot = 1;  // rectangle-rectangle: model1's shape is shape1
         p.routine = 16;
       }
+      pair_ids.push_back(PairIdDev{uint32_t(pairs.size()), p.s1_is_robot ? robot_src[i] : env_src[j],
+                                   p.s1_is_robot ? env_src[j] : robot_src[i]});
       pairs.push_back(p);
     }
-  return upload_scene(ctx, std::move(sc), pairs, out);
+  return upload_scene(ctx, std::move(sc), pairs, out, pair_ids);
 }
 
 extern "C" {
@@ -735,12 +743,20 @@ rkh_status check_err_flag(rkh_scene* scene) {
 }
 // the record queries serve 3D scenes whose pairs all have a closed form
 rkh_status records_supported(const rkh_scene* scene, const char* entry) {
-  const char* why = scene->host.planar      ? "planar (2D) scenes: the records of proxy_query_pair_2D are not built"
+  const char* why = scene->host.planar      ? "planar (2D) scenes: the records of proxy_query_pair_2D come from "
+                                              "rkh_min_distance_records_2d / rkh_collision_records_2d"
                     : scene->host.has_meshes ? "scenes with mesh shapes: the support-map (GJK) query yields a distance and no points"
                     : scene->n_pairs > kMaxRecordPairs ? "more proxy pairs than the record kernels keep track of"
                                                        : nullptr;
   if (!why) return RKH_OK;
   set_error(std::string(entry) + ": not supported for " + why);
+  return RKH_ERR_UNSUPPORTED;
+}
+// and their planar twins serve planar scenes
+rkh_status records_2d_supported(const rkh_scene* scene, const char* entry) {
+  if (scene->host.planar) return RKH_OK;
+  set_error(std::string(entry) + ": not supported for 3D scenes: their records come from rkh_min_distance_records / "
+            "rkh_collision_records");
   return RKH_ERR_UNSUPPORTED;
 }
 }  // namespace
@@ -819,7 +835,8 @@ rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t 
 
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms) {
   if (!scene || !x || !ms || B == 0) return RKH_ERR_BAD_ARG;
-  if (records) RKH_TRY(records_supported(scene, "rkh_diag_distance_query_ms"));
+  const bool planar = scene->host.planar != 0;  // planar scenes: the _2d record kernel (points of two doubles)
+  if (records && !planar) RKH_TRY(records_supported(scene, "rkh_diag_distance_query_ms"));
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
   DeviceBuffer<double> dx, dd, dp1, dp2;
@@ -843,7 +860,9 @@ rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_
   rkh_status st = RKH_OK;
   for (uint32_t r = 0; r < runs && st == RKH_OK; ++r) {
     hipError_t err = hipEventRecord(e0, s);
-    st = records ? launch_min_distance_records(s, *scene, dx.get(), B, out) : launch_min_distance(s, *scene, dx.get(), B, dd.get());
+    st = !records ? launch_min_distance(s, *scene, dx.get(), B, dd.get())
+         : planar ? launch_min_distance_records_2d(s, *scene, dx.get(), B, out)
+                  : launch_min_distance_records(s, *scene, dx.get(), B, out);
     if (err == hipSuccess) err = hipEventRecord(e1, s);
     if (err == hipSuccess) err = hipEventSynchronize(e1);
     if (err == hipSuccess) err = hipEventElapsedTime(&ms[r], e0, e1);
@@ -888,6 +907,76 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
     RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
+  }
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
+}
+
+rkh_status rkh_min_distance_records_2d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
+                                       double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_2d_supported(scene, "rkh_min_distance_records_2d"));
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dd.alloc(size_t(B)));
+  RKH_TRY(dp1.alloc(size_t(B) * 2));
+  RKH_TRY(dp2.alloc(size_t(B) * 2));
+  RKH_TRY(ds1.alloc(size_t(B)));
+  RKH_TRY(ds2.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch_min_distance_records_2d(s, *scene, dx.get(), B, out));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 2 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 2 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
+}
+
+rkh_status rkh_collision_records_2d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
+                                    double* dist, double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_2d_supported(scene, "rkh_collision_records_2d"));
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  const size_t slots = size_t(B) * cap;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> dn, ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dn.alloc(size_t(B)));
+  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 2)));
+  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 2)));
+  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.n_found = dn.get();
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch_collision_records_2d(s, *scene, dx.get(), B, cap, out));
+  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  if (slots) {
+    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 2 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 2 * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
   }

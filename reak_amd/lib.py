@@ -81,7 +81,7 @@ EXPORTS = [
     "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
     "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
-    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
+    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
     "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
@@ -147,6 +147,8 @@ def load():
     lib.rkh_min_distance.argtypes = [vp, dp, u32, dp]
     lib.rkh_min_distance_records.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
     lib.rkh_collision_records.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
+    lib.rkh_min_distance_records_2d.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
+    lib.rkh_collision_records_2d.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
     lib.rkh_diag_distance_query_ms.argtypes = [vp, dp, u32, C.c_int, u32, C.POINTER(C.c_float)]
     lib.rkh_propagate.argtypes = [vp, C.POINTER(T.DynSpace), dp, dp, u32, d, dp, u32p, dp]
     lib.rkh_diag_feval_cycles.argtypes = [vp, dp, dp, u32, C.c_int, C.POINTER(C.c_uint64)]
@@ -434,6 +436,30 @@ class Scene:
         s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
         _check(self.lib.rkh_collision_records(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1), T.dptr(p2),
                                               T.u32ptr(s1), T.u32ptr(s2)))
+        return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def min_distance_records_2d(self, x):
+        """proxy_query_pair_2D::findMinimumDistance()->getLastResult() per state of a planar scene
+        (rkh_min_distance_records_2d): the keys of min_distance_records with point1 / point2 [B][2].  The winner is what
+        the reference's culled loop leaves in min_i, which depends on the finder order."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B = x.shape[0]
+        d, p1, p2 = np.zeros(B), np.zeros((B, 2)), np.zeros((B, 2))
+        s1, s2 = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        _check(self.lib.rkh_min_distance_records_2d(self.h, T.dptr(x), B, T.dptr(d), T.dptr(p1), T.dptr(p2), T.u32ptr(s1),
+                                                    T.u32ptr(s2)))
+        return {"dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def collision_records_2d(self, x, cap):
+        """proxy_query_pair_2D::gatherCollisionPoints per state of a planar scene (rkh_collision_records_2d): the keys of
+        collision_records with point1 / point2 [B][cap][2]."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B, cap = x.shape[0], int(cap)
+        n = np.zeros(B, dtype=np.uint32)
+        d, p1, p2 = np.zeros((B, cap)), np.zeros((B, cap, 2)), np.zeros((B, cap, 2))
+        s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
+        _check(self.lib.rkh_collision_records_2d(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1), T.dptr(p2),
+                                                 T.u32ptr(s1), T.u32ptr(s2)))
         return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
 
     def move_position_toward(self, lower, upper, min_interval, a, b, fraction=1.0):
