@@ -231,17 +231,32 @@ __global__ __launch_bounds__(256) void round_begin_kernel(const RoundBeginArgs a
     uint32_t* wb = cached ? s_scan[0] : wave_base;
     uint32_t* eb = cached ? s_scan[1] : edge_base;
     uint32_t* nb = cached ? s_scan[2] : nn_base;
-    auto scan = [](uint32_t* a, uint32_t n) {
-      uint32_t acc = 0;
-      a[0] = 0;
-      for (uint32_t k = 1; k <= n; ++k) {
+    // by one whole wave: every lane sums a contiguous stretch of the counts a[1 .. n], the wave scans the 64 sums, and
+    // the lane writes its stretch's running totals (unsigned sums: the values do not depend on the grouping)
+    auto scan = [&](uint32_t* a, uint32_t n) {
+      const uint32_t lane = tid & 63u;
+      const uint32_t len = (n + 63u) / 64u;
+      const uint32_t k0 = 1u + lane * len;
+      const uint32_t k1 = k0 + len < n + 1u ? k0 + len : n + 1u;  // the stretch [k0, k1); empty beyond n
+      uint32_t s = 0;
+      for (uint32_t k = k0; k < k1; ++k) s += a[k];
+      uint32_t incl = s;
+#pragma unroll
+      for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+      }
+      uint32_t acc = incl - s;
+      for (uint32_t k = k0; k < k1; ++k) {
         acc += a[k];
         a[k] = acc;
       }
+      if (lane == 0) a[0] = 0;
     };
-    if (wave_base && tid == 0) scan(wb, 2 * P);
-    if (edge_base && tid == 128) scan(eb, 2 * P);
-    if (nn_base && tid == 64) scan(nb, P);
+    const uint32_t wave = tid >> 6;  // (uniform per wave: all of its lanes scan)
+    if (wave_base && wave == 0) scan(wb, 2 * P);
+    if (edge_base && wave == 2) scan(eb, 2 * P);
+    if (nn_base && wave == 1) scan(nb, P);
     if (cached) {
       __syncthreads();
       for (uint32_t k = tid; k <= 2 * P; k += blockDim.x) {

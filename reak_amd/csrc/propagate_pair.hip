@@ -149,6 +149,83 @@ RKH_DI void ws_st(const PairWsRef& w, int slot, double d) {
   __builtin_amdgcn_raw_buffer_store_b64(v, w.rsrc, w.voff, slot * 512, 0);
 }
 
+// The update after the f-eval of RK4 stage `stage` (runge_kutta4_integrator_sys.hpp:53-97).  Lane h advances the joints
+// 2 jr + h: components 2j (q: derivative = qd of the differentiated state) and 2j + 1 (qd: derivative = qdd), in its
+// private workspace slots sl = 2 jr + half (W_::W, KA, K3 + sl).  The slots are lane-private, so nothing aliases: a
+// stage issues every workspace load it needs before its first store -- one memory round trip per stage, not one per
+// slot (a load behind a buffer store is not moved over it).  Every slot's expression is the reference's.
+template <int N, class W_>
+RKH_DI void pair_rk4_stage_update(const PairWsRef& ws, PairLds<N>& lds, int el, int h, int stage, double h_dt,
+                                  const double (&qdd)[N]) {
+  typedef PairLayout<N> L_;
+  constexpr int R = L_::R;
+  double xv[2 * R], dp[2 * R], xn[2 * R];
+#pragma unroll
+  for (int jr = 0; jr < R; ++jr) {
+    const int j = 2 * jr + h;
+    const int jc = j < N ? j : 2 * jr;
+    // (the odd joint's value goes through an opaque copy: a plain `h ? qdd[2jr+1] : qdd[2jr]` is turned into a
+    // run-time-indexed read of the array, which puts the array into scratch)
+    double qdd_odd = qdd[2 * jr + 1 < N ? 2 * jr + 1 : 2 * jr];
+    asm volatile("" : "+v"(qdd_odd));
+    const double qdd_j = h ? qdd_odd : qdd[2 * jr];
+    const double xq = RKH_LD(L_::XE + 2 * jc), xqd = RKH_LD(L_::XE + 2 * jc + 1);
+    xv[2 * jr] = xq;
+    xv[2 * jr + 1] = xqd;
+    dp[2 * jr] = xqd;
+    dp[2 * jr + 1] = qdd_j;
+  }
+  if (stage == 0) {
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) {
+      const double k1 = h_dt * dp[sl];
+      ws_st(ws, W_::W + sl, xv[sl]);
+      ws_st(ws, W_::KA + sl, k1);
+      xn[sl] = xv[sl] + 0.5 * k1;
+    }
+  } else if (stage == 1) {
+    double k1[2 * R], w[2 * R];
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) {
+      k1[sl] = ws_ld(ws, W_::KA + sl);
+      w[sl] = ws_ld(ws, W_::W + sl);
+    }
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) {
+      const double k2 = h_dt * dp[sl];
+      ws_st(ws, W_::KA + sl, (1.0 / 6.0) * k1[sl] + (2.0 / 6.0) * k2);
+      xn[sl] = w[sl] + 0.5 * k2;
+    }
+  } else if (stage == 2) {
+    double w[2 * R];
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) w[sl] = ws_ld(ws, W_::W + sl);
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) {
+      const double k3v = h_dt * dp[sl];
+      ws_st(ws, W_::K3 + sl, k3v);
+      xn[sl] = w[sl] + k3v;
+    }
+  } else {
+    double ka[2 * R], k3[2 * R];
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) {
+      ka[sl] = ws_ld(ws, W_::KA + sl);
+      k3[sl] = ws_ld(ws, W_::K3 + sl);
+    }
+#pragma unroll
+    for (int sl = 0; sl < 2 * R; ++sl) xn[sl] = xv[sl] + ((ka[sl] + (h_dt / 6.0) * dp[sl]) - (2.0 / 3.0) * k3[sl]);
+  }
+#pragma unroll
+  for (int jr = 0; jr < R; ++jr) {
+    const int j = 2 * jr + h;
+    if (j < N) {
+      RKH_LD(L_::XE + 2 * j) = xn[2 * jr];
+      RKH_LD(L_::XE + 2 * j + 1) = xn[2 * jr + 1];
+    }
+  }
+}
+
 // Jacobian column of the body at (pos, Q) w.r.t. the coordinate of a joint whose end frame is (p, cq): get_jac_relative_to
 // (motion_jacobians.hpp:238-251) with f2 = (~F_c) * F_b (frame_3D.hpp:184-189,222-238,368-382).  Rc = rotmat(cq) and
 // ipos = (-p) * Rc are the joint's own, fixed from the iteration that captured its frame.  MASK: the slot can hold a lane
@@ -832,12 +909,53 @@ RKH_DI void pair_stage_axes(ScenePtr sc, PairLds<N>& lds) {
   __syncthreads();
 }
 
+// The rows of edge ec of an EdgeIO record, resolved in two levels of independent loads: every field at once, then the
+// words the fields point at (the source row's index, the target offset).  A word the record does not ask for is read
+// from the record itself, so that the second level has no branch to wait behind.  The values are meant to die before
+// the next f-eval: a kernel resolves again (from the edge's (record, ec)) where it needs rows after one.
+// Every caller gets every level, whatever it uses of it (a step launch at k > 0 reads neither si nor a): the record must
+// keep src_idx[ec] (or *d_src_first) and *d_tgt_off readable for every edge ec < B in every launch, and x_out allocated
+// for B rows before the first one; the step kernel's finishing edges also read best_case[ec] where best_case is set.
+struct PairEdgeRows {
+  uint32_t si;          // source row index
+  const double* a;      // source row
+  const double* b;      // target row
+  double* x;            // the edge's x_out row
+  double* record;       // the launch's record rows (null: none), record_stride states per edge
+  int record_stride;
+};
+template <int D>
+RKH_DI PairEdgeRows pair_edge_rows(const EdgeIO* io, uint32_t ec) {
+  const double* src = io->src;
+  const uint32_t* src_idx = io->src_idx;
+  const uint32_t* d_src_first = io->d_src_first;
+  const uint32_t src_stride = io->src_stride;
+  const double* tgt = io->tgt;
+  const uint32_t* d_tgt_off = io->d_tgt_off;
+  const uint32_t tgt_stride = io->tgt_stride;
+  PairEdgeRows r;
+  r.x = io->x_out + uint64_t(ec) * D;
+  r.record = io->record;
+  r.record_stride = io->record_stride;
+  const uint32_t w_src = *(src_idx ? src_idx + ec : (d_src_first ? d_src_first : &io->src_stride));
+  const uint32_t w_tgt = *(d_tgt_off ? d_tgt_off : &io->tgt_stride);
+  r.si = src_idx ? w_src : ((d_src_first ? w_src : 0u) + ec);
+  r.a = src + uint64_t(r.si) * src_stride;
+  r.b = tgt + ((d_tgt_off ? uint64_t(w_tgt) : 0ull) + ec) * tgt_stride;
+  return r;
+}
+// D values of a row as independent loads (8 bytes each: neither the bases nor the strides are 16-byte aligned by contract)
+template <int D>
+RKH_DI void pair_load_row(const double* p, double (&v)[D]) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) v[d] = p[d];
+}
+
 template <int N>
 __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
   __shared__ PairLds<N> lds;
   typedef PairLayout<N> L_;
   typedef PairWs<N> W_;
-  constexpr int R = L_::R;
   constexpr int D = 2 * N;
   const int lane = threadIdx.x;
   const int h = lane & 1;
@@ -896,23 +1014,17 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
       pair_args()->ws_all + (uint64_t(blockIdx.y) * gridDim.x + blockIdx.x) * uint64_t(W_::SLOTS * 64), 0,
       W_::SLOTS * 512, 0x00020000);
   ws.voff = lane * 8;
-  auto source_row = [&](const EdgeIO* io) -> uint32_t {
-    return io->src_idx ? io->src_idx[ec] : ((io->d_src_first ? *io->d_src_first : 0u) + ec);
-  };
-  {
-    const EdgeIO* io = edge_io();
-    const uint32_t si = source_row(io);
-    const uint64_t trow = (io->d_tgt_off ? uint64_t(*io->d_tgt_off) : 0ull) + ec;
-    const double* __restrict__ a_row = io->src + uint64_t(si) * io->src_stride;
-    const double* __restrict__ b_row = io->tgt + trow * io->tgt_stride;
-    double* __restrict__ record = writer ? io->record : nullptr;
-    const int record_stride = io->record_stride;
-#pragma unroll 1
+  {  // the edge's rows -> the workspace: both rows as one batch of loads
+    const PairEdgeRows rows = pair_edge_rows<D>(edge_io(), ec);
+    double av[D], bv[D];
+    pair_load_row<D>(rows.a, av);
+    pair_load_row<D>(rows.b, bv);
+    double* __restrict__ record = writer ? rows.record : nullptr;
+#pragma unroll
     for (int d = 0; d < D; ++d) {
-      const double av = a_row[d];
-      ws_st(ws, W_::X + d, av);
-      ws_st(ws, W_::B + d, b_row[d]);
-      if (record) record[(uint64_t(ec) * record_stride + 0) * D + d] = av;
+      ws_st(ws, W_::X + d, av[d]);
+      ws_st(ws, W_::B + d, bv[d]);
+      if (record) record[(uint64_t(ec) * rows.record_stride + 0) * D + d] = av[d];
     }
   }
 
@@ -927,13 +1039,19 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
 #pragma unroll 1
   for (int k = 0; k < n_steps; ++k) {
     // distance(x_current, x_goal) > goal_proximity_threshold (exact left-to-right sum, vect_distance_metrics.hpp:126-137)
+    // (the last free state and the target are read once per step, as one batch of workspace loads)
+    double xs[D], bv[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      xs[d] = ws_ld(ws, W_::X + d);
+      bv[d] = ws_ld(ws, W_::B + d);
+    }
     {
       double s = 0.0;
-#pragma unroll 1
+#pragma unroll
       for (int d = 0; d < D; ++d) {
-        const double xv = ws_ld(ws, W_::X + d);
-        RKH_LD(L_::XE + d) = xv;  // both lanes of the edge write the same value
-        const double df = xv - ws_ld(ws, W_::B + d);
+        RKH_LD(L_::XE + d) = xs[d];  // both lanes of the edge write the same value
+        const double df = xs[d] - bv[d];
         s = s + df * df;
       }
       if (!(sqrt(s) > pair_args()->dyn.goal_tol)) alive = false;
@@ -944,10 +1062,9 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     {
       PairArgP A = pair_args();
       const double kp = A->dyn.kp, kd = A->dyn.kd, u_max = A->dyn.u_max;
-#pragma unroll 1
+#pragma unroll
       for (int j = 0; j < N; ++j) {
-        double v = kp * (ws_ld(ws, W_::B + 2 * j) - ws_ld(ws, W_::X + 2 * j)) +
-                   kd * (ws_ld(ws, W_::B + 2 * j + 1) - ws_ld(ws, W_::X + 2 * j + 1));
+        double v = kp * (bv[2 * j] - xs[2 * j]) + kd * (bv[2 * j + 1] - xs[2 * j + 1]);
         if (v > u_max) v = u_max;
         else if (v < -u_max) v = -u_max;
         RKH_LD(L_::U + j) = v;
@@ -961,47 +1078,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     for (int ev = 0; ev < n_evals; ++ev) {
       double qdd[N];
       pair_state_derivative<N>(sc, lds, el, h, qdd, sing_now);
-      const int stage = ev & 3;
-      const double h_dt = pair_args()->dyn.dt;
-      // lane h advances the joints 2 jr + h: components 2j (q: derivative = qd of the differentiated state) and
-      // 2j + 1 (qd: derivative = qdd)
-#pragma unroll
-      for (int jr = 0; jr < R; ++jr) {
-        const int j = 2 * jr + h;
-        const bool jv = j < N;
-        const int jc = jv ? j : 2 * jr;
-        // (the odd joint's value goes through an opaque copy: a plain `h ? qdd[2jr+1] : qdd[2jr]` is turned into a
-        // run-time-indexed read of the array, which puts the array into scratch)
-        double qdd_odd = qdd[2 * jr + 1 < N ? 2 * jr + 1 : 2 * jr];
-        asm volatile("" : "+v"(qdd_odd));
-        const double qdd_j = h ? qdd_odd : qdd[2 * jr];
-        const double xq = RKH_LD(L_::XE + 2 * jc), xqd = RKH_LD(L_::XE + 2 * jc + 1);
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const int sl = 2 * jr + half;  // this lane's private slot
-          const double xv = half ? xqd : xq;
-          const double dp = half ? qdd_j : xqd;
-          double xn;
-          if (stage == 0) {
-            const double k1 = h_dt * dp;
-            ws_st(ws, W_::W + sl, xv);
-            ws_st(ws, W_::KA + sl, k1);
-            xn = xv + 0.5 * k1;
-          } else if (stage == 1) {
-            const double k2 = h_dt * dp;
-            const double k1 = ws_ld(ws, W_::KA + sl);
-            ws_st(ws, W_::KA + sl, (1.0 / 6.0) * k1 + (2.0 / 6.0) * k2);
-            xn = ws_ld(ws, W_::W + sl) + 0.5 * k2;
-          } else if (stage == 2) {
-            const double k3v = h_dt * dp;
-            ws_st(ws, W_::K3 + sl, k3v);
-            xn = ws_ld(ws, W_::W + sl) + k3v;
-          } else {
-            xn = xv + ((ws_ld(ws, W_::KA + sl) + (h_dt / 6.0) * dp) - (2.0 / 3.0) * ws_ld(ws, W_::K3 + sl));
-          }
-          if (jv) RKH_LD(L_::XE + 2 * jc + half) = xn;
-        }
-      }
+      pair_rk4_stage_update<N, W_>(ws, lds, el, h, ev & 3, pair_args()->dyn.dt, qdd);
     }
     pair_lds_handover();  // XE
     if (sing_now && alive) {
@@ -1025,9 +1102,12 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     if (!kPrismatic) {
       if (pair_args()->gate.clearance && sc->has_clearance) {
         // delta of this step, from its start (the last free state) to the state to be tested, rounded up
+        double q0[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) q0[j] = ws_ld(ws, W_::X + 2 * j);
         double dl = 0.0;
-#pragma unroll 1
-        for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - ws_ld(ws, W_::X + 2 * j));
+#pragma unroll
+        for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - q0[j]);
         budget -= float(dl) * 1.000001f + kClearStepPad;
         test = __any(alive && !(budget > 0.0f));
       }
@@ -1054,15 +1134,22 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_kernel(PairArgs) {
     }
   }
   const EdgeIO* io = edge_io();
-  if (singular && writer) atomicExch(io->err_flag, int(RKH_ERR_SINGULAR));
-  const uint32_t si = source_row(io);
-  const double* __restrict__ a_row = io->src + uint64_t(si) * io->src_stride;
-  double s_ar = 0.0, s_ab = 0.0, s_rb = 0.0;
-#pragma unroll 1
+  // the three rows of the accept test / goal probe as one batch of loads
+  const PairEdgeRows rows = pair_edge_rows<D>(io, ec);
+  const uint32_t si = rows.si;
+  double xs[D], av[D], bv[D];
+#pragma unroll
   for (int d = 0; d < D; ++d) {
-    const double xv = ws_ld(ws, W_::X + d), av = a_row[d], bv = ws_ld(ws, W_::B + d);
-    if (writer) io->x_out[uint64_t(ec) * D + d] = xv;
-    const double d_ar = av - xv, d_ab = av - bv, d_rb = xv - bv;
+    xs[d] = ws_ld(ws, W_::X + d);
+    bv[d] = ws_ld(ws, W_::B + d);
+  }
+  pair_load_row<D>(rows.a, av);
+  if (singular && writer) atomicExch(io->err_flag, int(RKH_ERR_SINGULAR));
+  double s_ar = 0.0, s_ab = 0.0, s_rb = 0.0;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    if (writer) rows.x[d] = xs[d];
+    const double d_ar = av[d] - xs[d], d_ab = av[d] - bv[d], d_rb = xs[d] - bv[d];
     s_ar = s_ar + d_ar * d_ar;
     s_ab = s_ab + d_ab * d_ab;
     s_rb = s_rb + d_rb * d_rb;
@@ -1201,57 +1288,53 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
       budget = __uint_as_float(ent.z);
     }
     const bool writer = edge_valid && h == 0;  // the lane that exports the edge's results
+    // the edge's EdgeIO record: both tables' addresses are scalar kernarg loads, selected per lane (left to itself the
+    // compiler selects the kernarg address and loads it per lane: a memory round trip)
     auto edge_io = [&]() -> const EdgeIO* {
       PairStepArgP A = pair_step_args();
-      return ((seg & 1u) ? A->tab_b : A->tab_a) + (seg >> 1);
-    };
-    auto source_row = [&](const EdgeIO* io) -> uint32_t {
-      return io->src_idx ? io->src_idx[ec] : ((io->d_src_first ? *io->d_src_first : 0u) + ec);
-    };
-    auto target_row = [&](const EdgeIO* io) -> const double* {
-      return io->tgt + ((io->d_tgt_off ? uint64_t(*io->d_tgt_off) : 0ull) + ec) * io->tgt_stride;
+      const EdgeIO* ta = A->tab_a;
+      const EdgeIO* tb = A->tab_b;
+      asm volatile("" : "+s"(ta), "+s"(tb));
+      return ((seg & 1u) ? tb : ta) + (seg >> 1);
     };
     // the state the edge has reached (its source row, or what the step before left in x_out), the steer target, and
-    // distance(x_current, x_goal) > goal_proximity_threshold (exact left-to-right sum, vect_distance_metrics.hpp:126-137)
+    // distance(x_current, x_goal) > goal_proximity_threshold (exact left-to-right sum, vect_distance_metrics.hpp:126-137).
+    // Both rows are one batch of loads; what the step needs of them goes to LDS (XE, U) before the first f-eval.
     bool alive = edge_valid;
+    bool singular = false;
+    float step_delta = 0.0f;  // this step's bound on the motion of the robot's points
     {
-      const EdgeIO* io = edge_io();
-      const double* __restrict__ a_row = k ? io->x_out + uint64_t(ec) * D : io->src + uint64_t(source_row(io)) * io->src_stride;
-      const double* __restrict__ b_row = target_row(io);
-      double* __restrict__ first = (k == 0 && writer) ? io->x_out + uint64_t(ec) * D : nullptr;
-      double* __restrict__ record = (k == 0 && writer) ? io->record : nullptr;
-      const int record_stride = io->record_stride;
+      const PairEdgeRows rows = pair_edge_rows<D>(edge_io(), ec);
+      double xs[D], bv[D];
+      pair_load_row<D>(k ? rows.x : rows.a, xs);
+      pair_load_row<D>(rows.b, bv);
+      double* __restrict__ first = (k == 0 && writer) ? rows.x : nullptr;
+      double* __restrict__ record = (k == 0 && writer) ? rows.record : nullptr;
       double s = 0.0;
-#pragma unroll 1
+#pragma unroll
       for (int d = 0; d < D; ++d) {
-        const double xv = a_row[d];
-        RKH_LD(L_::XE + d) = xv;  // both lanes of the edge write the same value
-        if (first) first[d] = xv;  // an edge that ends in its first step stays at its source
-        if (record) record[(uint64_t(ec) * record_stride + 0) * D + d] = xv;
-        const double df = xv - b_row[d];
+        RKH_LD(L_::XE + d) = xs[d];  // both lanes of the edge write the same value
+        if (first) first[d] = xs[d];  // an edge that ends in its first step stays at its source
+        if (record) record[(uint64_t(ec) * rows.record_stride + 0) * D + d] = xs[d];
+        const double df = xs[d] - bv[d];
         s = s + df * df;
       }
       if (!(sqrt(s) > pair_step_args()->dyn.goal_tol)) alive = false;
+      // PD law, zero-order hold over the step (read by the f-evals only: a wave without a live edge runs none)
+      PairStepArgP A = pair_step_args();
+      const double kp = A->dyn.kp, kd = A->dyn.kd, u_max = A->dyn.u_max;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        double v = kp * (bv[2 * j] - xs[2 * j]) + kd * (bv[2 * j + 1] - xs[2 * j + 1]);
+        if (v > u_max) v = u_max;
+        else if (v < -u_max) v = -u_max;
+        RKH_LD(L_::U + j) = v;
+      }
     }
-    bool singular = false;
-    float step_delta = 0.0f;  // this step's bound on the motion of the robot's points
     if (__any(alive)) {
       if (pair_step_args()->steps_exec) {
         const unsigned long long m = __ballot(alive && h == 0);
         if (lane == 0) atomicAdd(pair_step_args()->steps_exec, (unsigned long long)__popcll(m));
-      }
-      // PD law, zero-order hold over the step
-      {
-        PairStepArgP A = pair_step_args();
-        const double kp = A->dyn.kp, kd = A->dyn.kd, u_max = A->dyn.u_max;
-        const double* __restrict__ b_row = target_row(edge_io());
-#pragma unroll 1
-        for (int j = 0; j < N; ++j) {
-          double v = kp * (b_row[2 * j] - RKH_LD(L_::XE + 2 * j)) + kd * (b_row[2 * j + 1] - RKH_LD(L_::XE + 2 * j + 1));
-          if (v > u_max) v = u_max;
-          else if (v < -u_max) v = -u_max;
-          RKH_LD(L_::U + j) = v;
-        }
       }
       // runge_kutta4_integrate_impl (runge_kutta4_integrator_sys.hpp:53-97), see propagate_pair_kernel
       bool sing_now = false;
@@ -1260,43 +1343,7 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
       for (int ev = 0; ev < n_evals; ++ev) {
         double qdd[N];
         pair_state_derivative<N>(sc, lds, el, h, qdd, sing_now);
-        const int stage = ev & 3;
-        const double h_dt = pair_step_args()->dyn.dt;
-#pragma unroll
-        for (int jr = 0; jr < R; ++jr) {
-          const int j = 2 * jr + h;
-          const bool jv = j < N;
-          const int jc = jv ? j : 2 * jr;
-          double qdd_odd = qdd[2 * jr + 1 < N ? 2 * jr + 1 : 2 * jr];
-          asm volatile("" : "+v"(qdd_odd));
-          const double qdd_j = h ? qdd_odd : qdd[2 * jr];
-          const double xq = RKH_LD(L_::XE + 2 * jc), xqd = RKH_LD(L_::XE + 2 * jc + 1);
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int sl = 2 * jr + half;  // this lane's private slot
-            const double xv = half ? xqd : xq;
-            const double dp = half ? qdd_j : xqd;
-            double xn;
-            if (stage == 0) {
-              const double k1 = h_dt * dp;
-              ws_st(ws, W_::W + sl, xv);
-              ws_st(ws, W_::KA + sl, k1);
-              xn = xv + 0.5 * k1;
-            } else if (stage == 1) {
-              const double k2 = h_dt * dp;
-              const double k1 = ws_ld(ws, W_::KA + sl);
-              ws_st(ws, W_::KA + sl, (1.0 / 6.0) * k1 + (2.0 / 6.0) * k2);
-              xn = ws_ld(ws, W_::W + sl) + 0.5 * k2;
-            } else if (stage == 2) {
-              const double k3v = h_dt * dp;
-              ws_st(ws, W_::K3 + sl, k3v);
-              xn = ws_ld(ws, W_::W + sl) + k3v;
-            } else {
-              xn = xv + ((ws_ld(ws, W_::KA + sl) + (h_dt / 6.0) * dp) - (2.0 / 3.0) * ws_ld(ws, W_::K3 + sl));
-            }
-            if (jv) RKH_LD(L_::XE + 2 * jc + half) = xn;
-          }
-        }
+        pair_rk4_stage_update<N, W_>(ws, lds, el, h, ev & 3, pair_step_args()->dyn.dt, qdd);
       }
       pair_lds_handover();  // XE
       if (sing_now && alive) {
@@ -1319,13 +1366,29 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
         bool test = true;
         if (!kPrismatic) {
           if (pair_step_args()->gate.clearance && sc->has_clearance) {
-            // delta of this step: from the state the launch read (still in the edge's row; with inner sub-steps the
-            // workspace holds only the last one's start) to the state to be tested, rounded up
-            const EdgeIO* io = edge_io();
-            const double* __restrict__ a_row = k ? io->x_out + uint64_t(ec) * D : io->src + uint64_t(source_row(io)) * io->src_stride;
+            // delta of this step: from the state the launch read to the state to be tested, rounded up.  The start's
+            // angles are in the workspace's W slots (the lane's own joints; the neighbour's come by DPP) unless the
+            // step had inner sub-steps: then W holds only the last one's start, and the edge's row is read again.
+            double q0[N];
+            if (n_evals == 4) {  // (uniform) one RK4 iteration: dyn.inner[k] == 1
+              double own[R];
+#pragma unroll
+              for (int jr = 0; jr < R; ++jr) own[jr] = ws_ld(ws, W_::W + 2 * jr);
+#pragma unroll
+              for (int jr = 0; jr < R; ++jr) {
+                const double oth = xchg(own[jr]);
+                q0[2 * jr] = h ? oth : own[jr];
+                if (2 * jr + 1 < N) q0[2 * jr + 1] = h ? own[jr] : oth;
+              }
+            } else {
+              const PairEdgeRows rows = pair_edge_rows<D>(edge_io(), ec);
+              const double* __restrict__ a_row = k ? rows.x : rows.a;
+#pragma unroll
+              for (int j = 0; j < N; ++j) q0[j] = a_row[2 * j];
+            }
             double dl = 0.0;
-#pragma unroll 1
-            for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - a_row[2 * j]);
+#pragma unroll
+            for (int j = 0; j < N; ++j) dl = dl + sc->clear_arm[j] * fabs(RKH_LD(L_::XE + 2 * j) - q0[j]);
             step_delta = float(dl) * 1.000001f + kClearStepPad;
             budget -= step_delta;
             test = __any(alive && !(budget > 0.0f));
@@ -1349,11 +1412,13 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
     const uint32_t n_free = uint32_t(k) + (alive ? 1u : 0u);
     if (alive) {
       const EdgeIO* io = edge_io();
-      double* __restrict__ xo = writer ? io->x_out + uint64_t(ec) * D : nullptr;
-      double* __restrict__ record = writer ? io->record : nullptr;
+      double* const x_out = io->x_out;  // (the three fields as one batch of loads)
+      double* const rec = io->record;
       const int record_stride = io->record_stride;
+      double* __restrict__ xo = writer ? x_out + uint64_t(ec) * D : nullptr;
+      double* __restrict__ record = writer ? rec : nullptr;
       if (xo) {
-#pragma unroll 1
+#pragma unroll
         for (int d = 0; d < D; ++d) {
           const double xv = RKH_LD(L_::XE + d);
           xo[d] = xv;
@@ -1381,32 +1446,42 @@ __global__ __launch_bounds__(64, 2) void propagate_pair_step_kernel(PairStepArgs
       }
     }
     if (__any(finished)) {  // accept test / goal probe of the edges that end here
+      // Resolved again from (seg, ec): nothing of the prologue's batch lives through the f-evals.  Every field the
+      // verdict can need comes with the first level, the best-case distance with the second, the three rows in a third.
       const EdgeIO* io = edge_io();
-      if (singular && writer) atomicExch(io->err_flag, int(RKH_ERR_SINGULAR));
-      const uint32_t si = source_row(io);
-      const double* __restrict__ a_row = io->src + uint64_t(si) * io->src_stride;
-      const double* __restrict__ b_row = target_row(io);
-      const double* __restrict__ x_row = io->x_out + uint64_t(ec) * D;  // written above (alive) or by an earlier step
+      const int mode = io->mode;
+      uint32_t* const steps_free = io->steps_free;
+      uint8_t* const accept = io->accept;
+      double* const goal_dist = io->goal_dist;
+      const double* const best_case = io->best_case;
+      const double steer_tol = io->steer_tol;
+      int* const err_flag = io->err_flag;
+      const double bc = *(best_case ? best_case + ec : &io->steer_tol);
+      const PairEdgeRows rows = pair_edge_rows<D>(io, ec);
+      double av[D], bv[D], xr[D];
+      pair_load_row<D>(rows.a, av);
+      pair_load_row<D>(rows.b, bv);
+      pair_load_row<D>(rows.x, xr);  // written above (alive: not used) or by an earlier step (k > 0)
+      if (singular && writer) atomicExch(err_flag, int(RKH_ERR_SINGULAR));
       double s_ar = 0.0, s_ab = 0.0, s_rb = 0.0;
-#pragma unroll 1
+#pragma unroll
       for (int d = 0; d < D; ++d) {
-        const double av = a_row[d], bv = b_row[d];
-        const double xv = alive ? RKH_LD(L_::XE + d) : (k ? x_row[d] : av);
-        const double d_ar = av - xv, d_ab = av - bv, d_rb = xv - bv;
+        const double xv = alive ? RKH_LD(L_::XE + d) : (k ? xr[d] : av[d]);
+        const double d_ar = av[d] - xv, d_ab = av[d] - bv[d], d_rb = xv - bv[d];
         s_ar = s_ar + d_ar * d_ar;
         s_ab = s_ab + d_ab * d_ab;
         s_rb = s_rb + d_rb * d_rb;
       }
       if (finished && writer) {
-        io->steps_free[ec] = n_free;
-        if (io->mode != EDGE_PLAIN) {
+        steps_free[ec] = n_free;
+        if (mode != EDGE_PLAIN) {
           const double n_ar = sqrt(s_ar), n_ab = sqrt(s_ab), n_rb = sqrt(s_rb);
-          if (io->mode == EDGE_STEER_ACCEPT) {
+          if (mode == EDGE_STEER_ACCEPT) {
             // planning_visitor_base::steer_towards_position (planning_visitors.hpp:349-360)
-            io->accept[ec] = uint8_t(edge_accept(EDGE_STEER_ACCEPT, n_ar, n_ab, n_rb, io->best_case, ec, io->steer_tol, kNoWalk));
+            accept[ec] = uint8_t(edge_accept(EDGE_STEER_ACCEPT, n_ar, n_ab, n_rb, best_case ? &bc : nullptr, 0u, steer_tol, kNoWalk));
           } else {
             // C_free distance used by the goal probe (MEAQR_topology.hpp:995-1003)
-            io->goal_dist[si - 1] = goal_probe_steerable(n_ab, n_rb);
+            goal_dist[rows.si - 1] = goal_probe_steerable(n_ab, n_rb);
           }
         }
       }
