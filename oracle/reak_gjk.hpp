@@ -6,7 +6,8 @@
 // reak_amd/csrc/gjk_device.h for the definition) and this file is its CPU twin, written independently in the oracle's
 // own types.  What pins it: on sphere / capped-cylinder / box pairs it must reproduce the reference's closed forms
 // (restated in reak_proximity.hpp) while the cores are apart, and a box given as the mesh of its eight corners must
-// behave like the box (tests/test_oracle_kat.py); beyond that, "parity unpinned".
+// behave like the box (tests/test_oracle_kat.py); mesh pairs and mesh / primitive pairs must match the exact polytope
+// distance of tests/polytope_ref.py, which is no GJK (tests/test_gjk_polytope_cpu.py).
 //
 // Shape = convex core swept by a radius: sphere = point + r, capped cylinder = axis segment + r, box / mesh = themselves.
 // distance = |closest point of (coreA - coreB) to the origin| - rA - rB; intersecting cores: -(rA + rB) - 1e-9.
@@ -59,17 +60,29 @@ struct GjkShape {
 };
 
 namespace gjk_detail {
+constexpr double kGjkOverlap = 1e-9, kGjkRelTol = 1e-14, kGjkAbsTol = 1e-14, kGjkFlat = 1e-12;  // as in gjk_device.h
+constexpr int kGjkMaxIter = 64;
 inline V3 O() { return V3(0.0, 0.0, 0.0); }
-// closest point to the origin on a simplex of 1..3 points; reduces the simplex to the supporting face
+// foot of the origin on the line a + t * ab near the parameter t.  a + t * ab alone carries the rounding of |a| along ab,
+// which tilts a short v by |a| / |v| ulps; taking the component along ab out again leaves v perpendicular to the
+// edge to its own rounding, and that is what the exit test of gjk_distance relies on.
+inline V3 foot(const V3& a, const V3& ab, double t) {
+  const V3 p = a + t * ab;
+  return p - (dot(p, ab) / dot(ab, ab)) * ab;
+}
+// closest point to the origin on the segment a, b; the simplex W becomes the face that carries it
+inline V3 closest2(const V3& a, const V3& b, std::vector<V3>& W) {
+  const V3 ab = b - a;
+  const double t = dot(O() - a, ab), den = dot(ab, ab);
+  if (t <= 0.0 || den <= 0.0) { W = {a}; return a; }
+  if (t >= den) { W = {b}; return b; }
+  W = {a, b};
+  return foot(a, ab, t / den);
+}
+// the same on a simplex of 1..3 points
 inline V3 closest3(std::vector<V3>& W) {
   if (W.size() == 1) return W[0];
-  if (W.size() == 2) {
-    const V3 a = W[0], b = W[1], ab = b - a;
-    const double t = dot(O() - a, ab), den = dot(ab, ab);
-    if (t <= 0.0 || den <= 0.0) { W = {a}; return a; }
-    if (t >= den) { W = {b}; return b; }
-    return a + (t / den) * ab;
-  }
+  if (W.size() == 2) return closest2(V3(W[0]), V3(W[1]), W);
   const V3 a = W[0], b = W[1], c = W[2];
   const V3 ab = b - a, ac = c - a, ap = O() - a;
   const double d1 = dot(ab, ap), d2 = dot(ac, ap);
@@ -81,7 +94,7 @@ inline V3 closest3(std::vector<V3>& W) {
   if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
     const double t = d1 / (d1 - d3);
     W = {a, b};
-    return a + t * ab;
+    return foot(a, ab, t);
   }
   const V3 cp = O() - c;
   const double d5 = dot(ab, cp), d6 = dot(ac, cp);
@@ -90,17 +103,24 @@ inline V3 closest3(std::vector<V3>& W) {
   if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
     const double t = d2 / (d2 - d6);
     W = {a, c};
-    return a + t * ac;
+    return foot(a, ac, t);
   }
   const double va = d3 * d6 - d5 * d4;
   if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
     const double t = (d4 - d3) / ((d4 - d3) + (d5 - d6));
     W = {b, c};
-    return b + t * (c - b);
+    return foot(b, c - b, t);
   }
-  const double denom = 1.0 / (va + vb + vc);
-  const double vv = vb * denom, ww = vc * denom;
-  return a + vv * ab + ww * ac;
+  // inside the face: the foot of the origin on its plane, along the normal (the barycentric sum a + s ab + t ac would
+  // carry the rounding of |a| in every direction; the normal's direction is good to the rounding of the cross product)
+  const V3 nrm = cross(ab, ac);
+  const double nn = dot(nrm, nrm);
+  if (nn <= kGjkFlat * kGjkFlat * dot(ab, ab) * dot(ac, ac)) {  // collinear to rounding, no plane: the longest edge is the hull
+    const V3 bc = c - b;
+    const double lab = dot(ab, ab), lac = dot(ac, ac), lbc = dot(bc, bc);
+    return closest2((lbc > lab && lbc > lac) ? b : a, (lab >= lac && lab >= lbc) ? b : c, W);
+  }
+  return (dot(a, nrm) / nn) * nrm;
 }
 // the same for up to 4 points; false = the origin is inside the tetrahedron
 inline bool closest(std::vector<V3>& W, V3& v) {
@@ -118,7 +138,9 @@ inline bool closest(std::vector<V3>& W, V3& v) {
     const V3 a = P[F[f][0]], b = P[F[f][1]], c = P[F[f][2]], dd = P[F[f][3]];
     const V3 nrm = cross(b - a, c - a);
     const double so = dot(O() - a, nrm), sd = dot(dd - a, nrm);
-    if (so * sd < 0.0 || sd == 0.0) {
+    // flat: the opposite vertex lies in the face's plane to rounding, so the sign of sd is noise and so is the side test
+    const bool flat = sd * sd <= kGjkFlat * kGjkFlat * dot(nrm, nrm) * dot(dd - a, dd - a);
+    if (flat || so * sd < 0.0) {
       outside_any = true;
       std::vector<V3> T = {a, b, c};
       const V3 tv = closest3(T);
@@ -142,18 +164,19 @@ inline double gjk_distance(const GjkShape& A, const GjkShape& B) {
   V3 v = A.g.Position - B.g.Position;
   if (dot(v, v) == 0.0) v = V3(1.0, 0.0, 0.0);
   std::vector<V3> W;
-  for (int it = 0; it < 64; ++it) {
+  for (int it = 0;; ++it) {
     const V3 w = A.support(-v) - B.support(v);
     const double vv = dot(v, v), vw = dot(v, w);
-    if (!W.empty() && (vv - vw) <= 1e-14 * vv) break;
+    // certified: |v| - v.w / |v| <= kGjkRelTol |v| + kGjkAbsTol |w| (see gjk_device.h)
+    if (!W.empty() && (vv - vw) <= gjk_detail::kGjkRelTol * vv + gjk_detail::kGjkAbsTol * std::sqrt(vv * dot(w, w))) return std::sqrt(vv) - rsum;
     bool dup = false;
     for (const V3& p : W) dup = dup || (p[0] == w[0] && p[1] == w[1] && p[2] == w[2]);
-    if (dup) break;
+    // not certified and no way on (repeated vertex, iteration cap): the lower bound itself, never |v|
+    if (dup || it == gjk_detail::kGjkMaxIter) return (vw > 0.0 ? vw / std::sqrt(vv) : 0.0) - rsum;
     W.push_back(w);
-    if (!gjk_detail::closest(W, v)) return -rsum - 1e-9;
-    if (dot(v, v) <= 1e-30) return -rsum - 1e-9;
+    if (!gjk_detail::closest(W, v)) return -rsum - gjk_detail::kGjkOverlap;
+    if (dot(v, v) <= 1e-30) return -rsum - gjk_detail::kGjkOverlap;
   }
-  return norm_2(v) - rsum;
 }
 
 }  // namespace oracle

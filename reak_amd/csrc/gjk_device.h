@@ -10,6 +10,15 @@
 //     spheres / capped cylinders / boxes reproduce the reference's closed forms to rounding while the cores are apart;
 //   * core distance = Gilbert-Johnson-Keerthi on the Minkowski difference with polytope supports (finite termination),
 //     closest point of the simplex by Voronoi-region tests (Ericson, Real-Time Collision Detection 5.1);
+//   * termination: with v the closest point of the simplex and w the support point of A - B towards the origin,
+//     v.w / |v| <= distance <= |v|.  |v| is returned only when CERTIFIED by that bound:
+//         |v| - v.w / |v|  <=  kGjkRelTol |v| + kGjkAbsTol |w|
+//     (the second term is the rounding of v.(v - w) itself, a few ulps of |v| |w|; it needs a v perpendicular to its
+//     simplex to its OWN rounding, not to that of the far larger simplex points, hence gjk_foot and the normal form
+//     in gjk_closest3).  An uncertified v gains the support point and the loop goes on; a tetrahedron too flat for
+//     its side tests (kGjkFlat) takes the best of all four faces, so |v| never grows.  Where the loop cannot go on
+//     -- the support point is in the simplex already, or kGjkMaxIter (reached by curved cores only) -- the result is
+//     the lower bound max(v.w / |v|, 0) itself: below the distance by as much as the certificate missed, never above;
 //   * intersecting cores: the penetration depth is not computed; the result is -(rA + rB) - kGjkOverlap (negative =
 //     collision, which is all manip_dk_proxy_env_impl::is_free looks at, manip_free_workspace.hpp:85-95).
 // Closed forms stay the default for primitive pairs (they ARE the reference); GJK runs for mesh pairs, and for any
@@ -22,6 +31,9 @@ namespace rkh {
 
 constexpr double kGjkOverlap = 1e-9;
 constexpr int kGjkMaxIter = 64;
+constexpr double kGjkRelTol = 1e-14;  // certified exit: relative part
+constexpr double kGjkAbsTol = 1e-14;  // certified exit: rounding of v.(v - w), in units of |v| |w| (45 ulps)
+constexpr double kGjkFlat = 1e-12;    // height / edge below which a tetrahedron's (a triangle's) orientation is rounding noise
 
 struct GjkShape {
   int kind;
@@ -67,18 +79,31 @@ RKH_DI d3 gjk_support(const GjkShape& s, d3 dir) {
   return s.pos + mul(s.R, p);
 }
 
-// Closest point to the origin on the simplex W[0..n), n = 1..3; the simplex is reduced to the face that carries it.
+// Foot of the origin on the line a + t ab, near the parameter t.  a + t ab alone carries the rounding of |a| along ab,
+// which tilts a short v by |a| / |v| ulps; taking the component along ab out again leaves v perpendicular to the edge
+// to its own rounding, which is what the certified exit of gjk_distance relies on.
+RKH_DI d3 gjk_foot(d3 a, d3 ab, double t) {
+  const d3 p = a + t * ab;
+  return p - (dot(p, ab) / dot(ab, ab)) * ab;
+}
+
+// Closest point to the origin on the segment a, b; the simplex W[0..n) becomes the face that carries it.
+RKH_DI void gjk_closest2(d3 a, d3 b, d3* W, int& n, d3& v) {
+  const d3 ab = b - a;
+  const double t = dot(mk3(0, 0, 0) - a, ab), den = dot(ab, ab);
+  if (t <= 0.0 || den <= 0.0) { n = 1; W[0] = a; v = a; return; }
+  if (t >= den) { n = 1; W[0] = b; v = b; return; }
+  n = 2; W[0] = a; W[1] = b; v = gjk_foot(a, ab, t / den);
+}
+
+// The same on the simplex W[0..n), n = 1..3.
 RKH_DI void gjk_closest3(d3* W, int& n, d3& v) {
   if (n == 1) {
     v = W[0];
     return;
   }
   if (n == 2) {
-    const d3 a = W[0], b = W[1], ab = b - a;
-    const double t = dot(mk3(0, 0, 0) - a, ab), den = dot(ab, ab);
-    if (t <= 0.0 || den <= 0.0) { n = 1; W[0] = a; v = a; return; }
-    if (t >= den) { n = 1; W[0] = b; v = b; return; }
-    v = a + (t / den) * ab;
+    gjk_closest2(W[0], W[1], W, n, v);
     return;
   }
   if (n == 3) {  // Ericson 5.1.5, query point = origin
@@ -92,7 +117,7 @@ RKH_DI void gjk_closest3(d3* W, int& n, d3& v) {
     const double vc = d1 * d4 - d3_ * d2;
     if (vc <= 0.0 && d1 >= 0.0 && d3_ <= 0.0) {
       const double t = d1 / (d1 - d3_);
-      n = 2; W[0] = a; W[1] = b; v = a + t * ab;
+      n = 2; W[0] = a; W[1] = b; v = gjk_foot(a, ab, t);
       return;
     }
     const d3 cp = mk3(0, 0, 0) - c;
@@ -101,18 +126,26 @@ RKH_DI void gjk_closest3(d3* W, int& n, d3& v) {
     const double vb = d5 * d2 - d1 * d6;
     if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
       const double t = d2 / (d2 - d6);
-      n = 2; W[0] = a; W[1] = c; v = a + t * ac;
+      n = 2; W[0] = a; W[1] = c; v = gjk_foot(a, ac, t);
       return;
     }
     const double va = d3_ * d6 - d5 * d4;
     if (va <= 0.0 && (d4 - d3_) >= 0.0 && (d5 - d6) >= 0.0) {
       const double t = (d4 - d3_) / ((d4 - d3_) + (d5 - d6));
-      n = 2; W[0] = b; W[1] = c; v = b + t * (c - b);
+      n = 2; W[0] = b; W[1] = c; v = gjk_foot(b, c - b, t);
       return;
     }
-    const double denom = 1.0 / (va + vb + vc);
-    const double vv = vb * denom, ww = vc * denom;
-    v = a + vv * ab + ww * ac;
+    // inside the face: the foot of the origin on its plane, along the normal (the barycentric sum a + s ab + t ac would
+    // carry the rounding of |a| in every direction; the normal's direction is good to the rounding of the cross product)
+    const d3 nrm = cross(ab, ac);
+    const double nn = dot(nrm, nrm);
+    if (nn <= kGjkFlat * kGjkFlat * dot(ab, ab) * dot(ac, ac)) {  // collinear to rounding, no plane: the longest edge is the hull
+      const d3 bc = c - b;
+      const double lab = dot(ab, ab), lac = dot(ac, ac), lbc = dot(bc, bc);
+      gjk_closest2((lbc > lab && lbc > lac) ? b : a, (lab >= lac && lab >= lbc) ? b : c, W, n, v);
+      return;
+    }
+    v = (dot(a, nrm) / nn) * nrm;
     return;
   }
 }
@@ -136,8 +169,10 @@ RKH_DI bool gjk_closest(d3* W, int& n, d3& v) {
     const d3 a = P[F[f][0]], b = P[F[f][1]], c = P[F[f][2]], dd = P[F[f][3]];
     const d3 nrm = cross(b - a, c - a);
     const double so = dot(mk3(0, 0, 0) - a, nrm), sd = dot(dd - a, nrm);
-    // the origin is outside this face if it lies on the other side than the opposite vertex (degenerate: count as outside)
-    if (so * sd < 0.0 || sd == 0.0) {
+    // the origin is outside this face if it lies on the other side than the opposite vertex.  flat: that vertex lies in
+    // the face's plane to rounding, so the sign of sd is noise and so is the side test -- take the face in any case
+    const bool flat = sd * sd <= kGjkFlat * kGjkFlat * dot(nrm, nrm) * dot(dd - a, dd - a);
+    if (flat || so * sd < 0.0) {
       outside_any = true;
       d3 T[3] = {a, b, c};
       int tn = 3;
@@ -167,19 +202,19 @@ RKH_DI double gjk_distance(const GjkShape& A, const GjkShape& B) {
   d3 W[4];
   int n = 0;
 #pragma unroll 1
-  for (int it = 0; it < kGjkMaxIter; ++it) {
+  for (int it = 0;; ++it) {
     const d3 w = gjk_support(A, -v) - gjk_support(B, v);
     const double vv = dot(v, v), vw = dot(v, w);
-    // no support point closer to the origin than v along v: v is the closest point of A - B (first pass: n == 0)
-    if (n > 0 && (vv - vw) <= 1e-14 * vv) break;
+    // certified: no point of A - B is closer to the origin than v by more than the tolerance (first pass: n == 0)
+    if (n > 0 && (vv - vw) <= kGjkRelTol * vv + kGjkAbsTol * sqrt(vv * dot(w, w))) return sqrt(vv) - rsum;
     bool dup = false;
     for (int i = 0; i < n; ++i) dup = dup || (W[i].x == w.x && W[i].y == w.y && W[i].z == w.z);
-    if (dup) break;
+    // not certified and no way on (repeated vertex, iteration cap): the lower bound itself, never |v|
+    if (dup || it == kGjkMaxIter) return (vw > 0.0 ? vw / sqrt(vv) : 0.0) - rsum;
     W[n++] = w;
     if (!gjk_closest(W, n, v)) return -rsum - kGjkOverlap;
     if (dot(v, v) <= 1e-30) return -rsum - kGjkOverlap;  // the origin lies on the simplex
   }
-  return norm_2(v) - rsum;
 }
 
 }  // namespace rkh
