@@ -178,8 +178,8 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
  * whose distance is < 0.0 (:414), in finder order.  n_found[b] counts them all and may exceed cap; the first cap of
  * them are written to row b of the [B][cap] arrays; the slots behind them read dist +inf, shape ids 0xFFFFFFFF, points 0.
  * No pointer may be NULL (RKH_ERR_BAD_ARG); B == 0 is RKH_OK.  RKH_ERR_UNSUPPORTED, with an error text: scenes with
- * RKH_SHAPE_MESH shapes (the support-map query yields a distance and no points) and planar (2D) scenes
- * (proxy_query_pair_2D's records come from the _2d entries below). */
+ * RKH_SHAPE_MESH shapes (these two entries know the closed forms only; the _meshes entries below serve such scenes)
+ * and planar (2D) scenes (proxy_query_pair_2D's records come from the _2d entries below). */
 rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t B,
                                     double* dist,      /* [B]    */
                                     double* point1,    /* [B][3] */
@@ -190,6 +190,32 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
                                  uint32_t* n_found,                             /* [B] */
                                  double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
                                  uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
+/* The same two queries for EVERY non-planar scene, scenes with RKH_SHAPE_MESH shapes included: arguments, array shapes,
+ * finder order, tie rule, n_found / cap, unused slots, NULL and B == 0 rules as above; dist[b] of the first is
+ * bit-identical to rkh_min_distance's.  A scene without mesh shapes runs the kernels of the two entries above and the
+ * results are theirs bit for bit.  New names because the entries above are defined to refuse mesh scenes.
+ * A finder with a mesh in it is not the reference's (it has no mesh shape) but the build's support-map (GJK) query, which
+ * comes last in the cascade of kinds: mesh against sphere / capped cylinder / box / mesh, shape1 = model 1's (the
+ * robot's) shape, shape2 = the environment's.  Its record holds the witnesses of the search.  Each shape is a convex
+ * core swept by a radius r (sphere: centre; capped cylinder: axis segment; box and mesh: themselves, r = 0):
+ *   cores apart     point1 = pA + r1 n, point2 = pB - r2 n, where (pA, pB) is a closest pair of points of the two cores
+ *                   and n the unit vector from pA towards pB; dist = |pB - pA| - r1 - r2, which is negative when the
+ *                   swept shapes overlap while their cores do not.  Where the closest pair is not unique (parallel
+ *                   faces or edges) the points are one such pair, not a particular one.
+ *   cores crossing  dist = -(r1 + r2) - 1e-9, as rkh_min_distance reports it, and point1 = point2 (to rounding) = one
+ *                   point common to both cores.  The query computes NO penetration depth and the record invents none:
+ *                   neither dist nor the points measure how deep the cores cross.
+ * RKH_ERR_UNSUPPORTED, with an error text: planar (2D) scenes (the _2d entries below). */
+rkh_status rkh_min_distance_records_meshes(rkh_scene* scene, const double* x, uint32_t B,
+                                           double* dist,      /* [B]    */
+                                           double* point1,    /* [B][3] */
+                                           double* point2,    /* [B][3] */
+                                           uint32_t* shape1,  /* [B]    */
+                                           uint32_t* shape2); /* [B]    */
+rkh_status rkh_collision_records_meshes(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap,
+                                        uint32_t* n_found,                             /* [B] */
+                                        double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
+                                        uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
 /* The same for planar (2D) scenes: what proxy_query_pair_2D::findMinimumDistance()->getLastResult() and
  * gatherCollisionPoints hold (proxy_query_model.cpp:163-187 and :189-208; proximity_record_2D.hpp:47-58: points are
  * vect<double,2>).  x as for rkh_min_distance; shape1 / shape2 and the finder order as above, with createProxFinderList's

@@ -425,8 +425,11 @@ struct is_steerable_space_tag<kte_dynamic_free_space<P> > {
 // (manip_free_workspace.hpp:85-95; proximity_finder_3D.hpp:49-82).  The device applies the state to the chain
 // (manip_direct_kin_map::apply_to_model), evaluates every finder of the pair list in one call and returns the winning
 // finder's whole record (rkh_min_distance_records), or the records of all colliding finders (rkh_collision_records).
-// Scenes whose records are not built (mesh shapes, planar chains: RKH_ERR_UNSUPPORTED from those entries) still answer
-// with the distance; their points are NaN and their shape indices no_shape.  Planar callers who want the records use
+// Scenes with mesh shapes, which those two entries refuse (RKH_ERR_UNSUPPORTED), get their records from
+// rkh_min_distance_records_meshes / rkh_collision_records_meshes: a pair with a mesh in it reports the witnesses of the
+// support-map query -- a closest pair of points while the cores are apart, one common point and no penetration depth
+// when they cross (rkh.h).  Planar chains, which these refuse too, still answer findMinimumDistance with the distance;
+// their points are NaN and their shape indices no_shape.  Planar callers who want the records use
 // hip_proxy_query_pair_2D below.
 struct proximity_record {  // proximity_record_3D (proximity_record_3D.hpp:47-56)
   double mPoint1[3] = {0.0, 0.0, 0.0};  // on the finder's shape1, world frame
@@ -461,9 +464,11 @@ class hip_proxy_query_pair {
     if (rkh_scene_num_pairs(m_scene.get()) == 0) return std::shared_ptr<hip_proximity_finder>();  // empty finder list
     proximity_record r;
     uint32_t s1 = hip_proximity_finder::no_shape, s2 = hip_proximity_finder::no_shape;
-    const rkh_status st =
+    rkh_status st =
         rkh_min_distance_records(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
-    if (st == RKH_ERR_UNSUPPORTED) {  // no records for this kind of scene: the distance alone
+    if (st == RKH_ERR_UNSUPPORTED)  // mesh shapes
+      st = rkh_min_distance_records_meshes(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
+    if (st == RKH_ERR_UNSUPPORTED) {  // no records for this kind of scene (planar): the distance alone
       check(rkh_min_distance(m_scene.get(), m_state.data(), 1, &r.mDistance));
       for (int k = 0; k < 3; ++k) r.mPoint1[k] = r.mPoint2[k] = std::numeric_limits<double>::quiet_NaN();
     } else {
@@ -481,8 +486,12 @@ class hip_proxy_query_pair {
     for (;;) {  // grow until every colliding finder fits
       d.resize(cap); p1.resize(3 * std::size_t(cap)); p2.resize(3 * std::size_t(cap));
       s1.resize(cap); s2.resize(cap);
-      check(rkh_collision_records(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(), s1.data(),
-                                  s2.data()));
+      rkh_status st = rkh_collision_records(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
+                                            s1.data(), s2.data());
+      if (st == RKH_ERR_UNSUPPORTED)  // mesh shapes
+        st = rkh_collision_records_meshes(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
+                                          s1.data(), s2.data());
+      check(st);
       if (n_found <= cap) break;
       cap = n_found;
     }

@@ -217,4 +217,127 @@ RKH_DI double gjk_distance(const GjkShape& A, const GjkShape& B) {
   }
 }
 
+// ---- the record of a pair: gjk_distance's value with a closest pair of points ------------------------------------------
+// A search holds its witnesses: each simplex point is w_i = a_i - b_i with a_i, b_i support points of the two cores, and
+// the closest point v of the simplex is a convex combination of the w_i; the same combination of the a_i (the b_i) is a
+// point of core A (core B).  gjk_record runs gjk_distance's search -- the same support calls, the same exits in the same
+// order, so dist is that function's value -- and keeps the a_i beside the w_i.
+//   cores apart (every exit that returns ... - rsum): with lambda the barycentric coordinates of v in the final simplex,
+//     pA = sum lambda_i a_i, pB = pA - v (v is perpendicular to its simplex to its own rounding; sum lambda_i b_i would
+//     carry the rounding of |a| instead), n = -v / |v| (from A towards B; from the search's v, never from pB - pA, whose
+//     direction at a gap of 1e-8 is good to 1e-8 only), point1 = pA + rA n, point2 = pB - rB n.
+//   cores crossing (origin inside the tetrahedron, or on the simplex): lambda = the barycentric coordinates of the origin,
+//     point1 = sum lambda_i a_i, point2 = point1 - sum lambda_i w_i (the same combination of the b_i): one common point
+//     of the two cores, up to the conditioning of the simplex.  dist = -rsum - kGjkOverlap as in gjk_distance; there is no
+//     penetration depth and none is invented.
+// The combinations are taken about the first point, p_0 + sum_{i>0} lambda_i (p_i - p_0): the same point, and the
+// rounding of lambda then scales with the simplex's edges, not with the distance of the shapes from the world's origin.
+struct GjkRecord {
+  d3 p1, p2;  // on shape A, on shape B (world frame)
+  double dist;
+};
+
+// Barycentric coordinates of the closest point to the origin of the simplex W[0..n), n = 1..3, as gjk_closest leaves it:
+// that point lies in the simplex's relative interior (a vertex: 1; an edge: its parameter; a face: Ericson 5.1.5's
+// (va, vb, vc) / (va + vb + vc)).  Non-negative, sum 1.
+RKH_DI void gjk_barycentric(const d3* W, int n, double* lam) {
+  lam[0] = 1.0; lam[1] = 0.0; lam[2] = 0.0;
+  if (n == 2) {
+    const d3 ab = W[1] - W[0];
+    const double t = dot(mk3(0, 0, 0) - W[0], ab), den = dot(ab, ab);
+    const double s = (t <= 0.0 || den <= 0.0) ? 0.0 : (t >= den ? 1.0 : t / den);
+    lam[0] = 1.0 - s; lam[1] = s;
+  } else if (n == 3) {
+    const d3 a = W[0], b = W[1], c = W[2];
+    const d3 ab = b - a, ac = c - a, ap = mk3(0, 0, 0) - a, bp = mk3(0, 0, 0) - b, cp = mk3(0, 0, 0) - c;
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap), d3_ = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+    double va = d3_ * d6 - d5 * d4, vb = d5 * d2 - d1 * d6, vc = d1 * d4 - d3_ * d2;
+    va = va > 0.0 ? va : 0.0; vb = vb > 0.0 ? vb : 0.0; vc = vc > 0.0 ? vc : 0.0;
+    const double s = va + vb + vc;
+    if (s > 0.0) { lam[0] = va / s; lam[1] = vb / s; lam[2] = vc / s; }
+  }
+}
+
+// The same for the origin inside the tetrahedron W[0..4) (gjk_closest returned false, so no face of it is flat): ratios
+// of signed volumes, made non-negative and normalised.
+RKH_DI void gjk_barycentric4(const d3* W, double* lam) {
+  const double V0 = dot(W[1], cross(W[2], W[3])), V1 = -dot(W[0], cross(W[2], W[3]));
+  const double V2 = dot(W[0], cross(W[1], W[3])), V3 = -dot(W[0], cross(W[1], W[2]));
+  const double V = (V0 + V1) + (V2 + V3);  // the tetrahedron's own signed volume (x 6)
+  const double sg = V < 0.0 ? -1.0 : 1.0;
+  double l[4] = {sg * V0, sg * V1, sg * V2, sg * V3};
+  double s = 0.0;
+  for (int i = 0; i < 4; ++i) { l[i] = l[i] > 0.0 ? l[i] : 0.0; s += l[i]; }
+  for (int i = 0; i < 4; ++i) lam[i] = s > 0.0 ? l[i] / s : (i == 0 ? 1.0 : 0.0);
+}
+
+// sum lambda_i P_i, about P_0
+RKH_DI d3 gjk_combine(const d3* P, const double* lam, int n) {
+  d3 p = P[0];
+  for (int i = 1; i < n; ++i) p = p + lam[i] * (P[i] - P[0]);
+  return p;
+}
+
+RKH_DI GjkRecord gjk_record_apart(const d3* W, const d3* S, int n, d3 v, double dist, double rA, double rB) {
+  double lam[3];
+  gjk_barycentric(W, n, lam);
+  const d3 pA = gjk_combine(S, lam, n);
+  const d3 pB = pA - v;
+  const double len = sqrt(dot(v, v));
+  const d3 nrm = mk3(-v.x / len, -v.y / len, -v.z / len);
+  GjkRecord r;
+  r.p1 = pA + rA * nrm;
+  r.p2 = pB - rB * nrm;
+  r.dist = dist;
+  return r;
+}
+
+RKH_DI GjkRecord gjk_record_crossing(const d3* W, const d3* S, const double* lam, int n, double rsum) {
+  GjkRecord r;
+  r.p1 = gjk_combine(S, lam, n);
+  r.p2 = r.p1 - gjk_combine(W, lam, n);
+  r.dist = -rsum - kGjkOverlap;
+  return r;
+}
+
+RKH_DI GjkRecord gjk_record(const GjkShape& A, const GjkShape& B) {
+  const double rA = gjk_radius(A), rB = gjk_radius(B);
+  const double rsum = rA + rB;
+  d3 v = A.pos - B.pos;
+  if (dot(v, v) == 0.0) v = mk3(1.0, 0.0, 0.0);
+  d3 W[4], S[4];  // S[i]: A's support point of simplex point W[i]
+  int n = 0;
+#pragma unroll 1
+  for (int it = 0;; ++it) {
+    const d3 sa = gjk_support(A, -v);
+    const d3 w = sa - gjk_support(B, v);
+    const double vv = dot(v, v), vw = dot(v, w);
+    if (n > 0 && (vv - vw) <= kGjkRelTol * vv + kGjkAbsTol * sqrt(vv * dot(w, w))) return gjk_record_apart(W, S, n, v, sqrt(vv) - rsum, rA, rB);
+    bool dup = false;
+    for (int i = 0; i < n; ++i) dup = dup || (W[i].x == w.x && W[i].y == w.y && W[i].z == w.z);
+    if (dup || it == kGjkMaxIter) return gjk_record_apart(W, S, n, v, (vw > 0.0 ? vw / sqrt(vv) : 0.0) - rsum, rA, rB);
+    W[n] = w;
+    S[n] = sa;
+    ++n;
+    d3 W0[4], S0[4];
+    const int n0 = n;
+    for (int i = 0; i < n0; ++i) { W0[i] = W[i]; S0[i] = S[i]; }
+    if (!gjk_closest(W, n, v)) {  // W is untouched
+      double lam[4];
+      gjk_barycentric4(W, lam);
+      return gjk_record_crossing(W, S, lam, 4, rsum);
+    }
+    // gjk_closest moves and drops simplex points and computes none; no two are equal (dup above), so each survivor names
+    // the support point that came with it
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n0; ++j)
+        if (W[i].x == W0[j].x && W[i].y == W0[j].y && W[i].z == W0[j].z) S[i] = S0[j];
+    if (dot(v, v) <= 1e-30) {  // the origin lies on the simplex
+      double lam[3];
+      gjk_barycentric(W, n, lam);
+      return gjk_record_crossing(W, S, lam, n, rsum);
+    }
+  }
+}
+
 }  // namespace rkh

@@ -1888,7 +1888,8 @@ __global__ __launch_bounds__(64) void min_distance_kernel(const SceneDev* __rest
 // ---- record queries (rkh_min_distance_records, rkh_collision_records) -----------------------------------------------
 // One form serves revolute and prismatic chains: proximity_frames with PRISM = true reads SceneDev::prismatic_mask at
 // run time and does exactly the revolute arithmetic where the bit is clear, so these kernels exist once, here, and
-// rkh::prismatic gains none.  Scenes with vertex-set shapes and planar scenes never reach them.
+// rkh::prismatic gains none.  Planar scenes never reach them; scenes with vertex-set shapes reach the *_meshes_kernel forms
+// (rkh_min_distance_records_meshes, rkh_collision_records_meshes), whose records of such pairs are gjk_record's.
 
 // Pair pr at the frames proximity_frames left in ws: (shape1, shape2) in the finder's own order, and the gap of their
 // bounding spheres (transformToGlobal(0) of both shapes, then |c2 - c1| - r1 - r2: proxy_query_model.cpp:384-389,407-411)
@@ -1915,11 +1916,12 @@ RKH_DI double record_pair_shapes(const SceneDev* __restrict__ sc, const ShapeDev
   return norm_2(c2 - c1) - r1 - r2;
 }
 
-// slot `at` of the record arrays: the record of pair p (p < 0: no record)
-template <typename WS>
+// slot `at` of the record arrays: the record of pair p (p < 0: no record).  GJK: vertex-set pairs among them, answered
+// from mesh_pool (pair_record<true>)
+template <bool GJK = false, typename WS>
 RKH_DI void write_pair_record(const SceneDev* __restrict__ sc, const ShapeDev* __restrict__ env_lds, const WS& ws,
                               const PairDev* __restrict__ pairs, const PairIdDev* __restrict__ ids, int p, const RecordOut& out,
-                              uint64_t at, double dist) {
+                              uint64_t at, double dist, const double* __restrict__ mesh_pool = nullptr) {
   ProxRecordG r;
   r.p1 = r.p2 = mk3(0.0, 0.0, 0.0);
   uint32_t id1 = 0xFFFFFFFFu, id2 = 0xFFFFFFFFu;
@@ -1927,7 +1929,8 @@ RKH_DI void write_pair_record(const SceneDev* __restrict__ sc, const ShapeDev* _
     const PairDev pr = pairs[p];
     ShapeG s1, s2;
     record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-    r = pair_record(pr.routine, s1, s2);
+    if constexpr (GJK) r = pair_record<true>(pr.routine, s1, s2, mesh_pool);
+    else r = pair_record(pr.routine, s1, s2);
     id1 = ids[p].shape1;
     id2 = ids[p].shape2;
   }
@@ -1943,11 +1946,15 @@ RKH_DI void write_pair_record(const SceneDev* __restrict__ sc, const ShapeDev* _
 // comparison (so dist is its value bit for bit), and its best (distance, finder rank) in lexicographic order -- the
 // reference's loop takes a new minimum only on a strictly smaller distance, so among equal distances the earliest
 // finder stays.  A butterfly leaves the wave's winner in every lane; lane 0 evaluates that one pair's point form.
-template <int N>
-__global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
-                                                                   const PairIdDev* __restrict__ ids, int n_pairs,
-                                                                   const double* __restrict__ x, uint32_t B, RecordOut out) {
+// GJK = true is the form for scenes with vertex-set shapes: it searches with the support-map query as min_distance_kernel
+// does there, and lane 0 evaluates the winner's record with gjk_record where the winner is such a pair.  The two forms
+// are kernels of their own names (the closed-form one keeps the name and the code it had).
+template <int N, bool GJK>
+RKH_DI void min_distance_records_body(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                      const PairIdDev* __restrict__ ids, int n_pairs, const double* __restrict__ x, uint32_t B,
+                                      const RecordOut& out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const double* mesh_pool = GJK ? sc->mesh_verts : nullptr;
   BlockLdsQs<N, 64>& lds = *reinterpret_cast<BlockLdsQs<N, 64>*>(smem_raw);
   ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQs<N, 64>::block_bytes);
   const uint32_t e = blockIdx.x;
@@ -1969,7 +1976,7 @@ __global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev
     const PairDev pr = pairs[p];
     ShapeG s1, s2;
     record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-    const double d = pair_distance<false>(pr.routine, s1, s2);
+    const double d = pair_distance<GJK>(pr.routine, s1, s2, mesh_pool);
     if (d < dmin) dmin = d;
     const uint32_t rank = ids[p].rank;
     if (d < dbest || (d == dbest && rank < rbest)) {
@@ -1992,7 +1999,22 @@ __global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev
       pbest = op;
     }
   }
-  if (lane == 0) write_pair_record(sc, env_lds, ws, pairs, ids, pbest, out, e, dmin);
+  if (lane == 0) write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, pbest, out, e, dmin, mesh_pool);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                                                   const PairIdDev* __restrict__ ids, int n_pairs,
+                                                                   const double* __restrict__ x, uint32_t B, RecordOut out) {
+  min_distance_records_body<N, false>(sc, pairs, ids, n_pairs, x, B, out);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void min_distance_records_meshes_kernel(const SceneDev* __restrict__ sc,
+                                                                          const PairDev* __restrict__ pairs,
+                                                                          const PairIdDev* __restrict__ ids, int n_pairs,
+                                                                          const double* __restrict__ x, uint32_t B, RecordOut out) {
+  min_distance_records_body<N, true>(sc, pairs, ids, n_pairs, x, B, out);
 }
 
 // Kernel: proxy_query_pair_3D::gatherCollisionPoints for B states, one wave per state.  Every lane culls and measures
@@ -2000,12 +2022,14 @@ __global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev
 // p = 64 s + lane is bit s of (m0, m1), kMaxRecordPairs pairs at most.  The collisions leave in finder order: min(n_found,
 // cap) rounds, each a butterfly over every lane's lowest remaining rank; lane 0 evaluates the round's point form and
 // the owner drops its bit.  The round count is wave-uniform, so the butterflies run in uniform control flow.
-template <int N>
-__global__ __launch_bounds__(64) void collision_records_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
-                                                                const PairIdDev* __restrict__ ids, int n_pairs,
-                                                                const double* __restrict__ x, uint32_t B, uint32_t cap,
-                                                                RecordOut out) {
+// GJK = true: the form for scenes with vertex-set shapes, as for the minimum-distance records; only lane 0 runs
+// gjk_record, between the rounds' butterflies and never around them.
+template <int N, bool GJK>
+RKH_DI void collision_records_body(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                   const PairIdDev* __restrict__ ids, int n_pairs, const double* __restrict__ x, uint32_t B,
+                                   uint32_t cap, const RecordOut& out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const double* mesh_pool = GJK ? sc->mesh_verts : nullptr;
   BlockLdsQs<N, 64>& lds = *reinterpret_cast<BlockLdsQs<N, 64>*>(smem_raw);
   ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQs<N, 64>::block_bytes);
   const uint32_t e = blockIdx.x;
@@ -2025,7 +2049,7 @@ __global__ __launch_bounds__(64) void collision_records_kernel(const SceneDev* _
     ShapeG s1, s2;
     const double gap = record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
     if (gap > 0.0) continue;
-    if (pair_distance<false>(pr.routine, s1, s2) < 0.0) {
+    if (pair_distance<GJK>(pr.routine, s1, s2, mesh_pool) < 0.0) {
       const int s = p >> 6;
       if (s < 64) m0 |= 1ull << s;
       else m1 |= 1ull << (s - 64);
@@ -2066,10 +2090,29 @@ __global__ __launch_bounds__(64) void collision_records_kernel(const SceneDev* _
       const PairDev pr = pairs[pmin];
       ShapeG s1, s2;
       record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-      write_pair_record(sc, env_lds, ws, pairs, ids, pmin, out, row + k, pair_distance<false>(pr.routine, s1, s2));
+      write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, pmin, out, row + k, pair_distance<GJK>(pr.routine, s1, s2, mesh_pool),
+                             mesh_pool);
     }
   }
-  for (uint32_t k = n_out + lane; k < cap; k += 64) write_pair_record(sc, env_lds, ws, pairs, ids, -1, out, row + k, INFINITY);
+  for (uint32_t k = n_out + lane; k < cap; k += 64)
+    write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, -1, out, row + k, INFINITY, mesh_pool);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void collision_records_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                                                const PairIdDev* __restrict__ ids, int n_pairs,
+                                                                const double* __restrict__ x, uint32_t B, uint32_t cap,
+                                                                RecordOut out) {
+  collision_records_body<N, false>(sc, pairs, ids, n_pairs, x, B, cap, out);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void collision_records_meshes_kernel(const SceneDev* __restrict__ sc,
+                                                                       const PairDev* __restrict__ pairs,
+                                                                       const PairIdDev* __restrict__ ids, int n_pairs,
+                                                                       const double* __restrict__ x, uint32_t B, uint32_t cap,
+                                                                       RecordOut out) {
+  collision_records_body<N, true>(sc, pairs, ids, n_pairs, x, B, cap, out);
 }
 #endif  // !RKH_PRISMATIC_FORMS
 
@@ -2371,9 +2414,9 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
 
 #ifndef RKH_PRISMATIC_FORMS  // the record kernels exist once and serve both joint kinds (see above)
 template <class F>
-static rkh_status launch_records(const rkh_scene& scene, F&& f) {
-  if (scene.host.planar || scene.host.has_meshes || !scene.d_pair_ids.get() || scene.n_pairs > kMaxRecordPairs) {
-    set_error("record queries: 3D scenes without vertex-set shapes only");
+static rkh_status launch_records(const rkh_scene& scene, bool meshes, F&& f) {
+  if (scene.host.planar || (scene.host.has_meshes && !meshes) || !scene.d_pair_ids.get() || scene.n_pairs > kMaxRecordPairs) {
+    set_error(meshes ? "record queries: 3D scenes only" : "record queries: 3D scenes without vertex-set shapes only");
     return RKH_ERR_UNSUPPORTED;
   }
   RKH_TRY((with_n<1, 2, 3, 4, 6, 7, 12>(scene.host.n_dof, f)));
@@ -2383,7 +2426,7 @@ static rkh_status launch_records(const rkh_scene& scene, F&& f) {
 
 rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out) {
   if (B == 0) return RKH_OK;
-  return launch_records(scene, [&](auto c) {
+  return launch_records(scene, false, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((min_distance_records_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
                        scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, out);
@@ -2393,10 +2436,32 @@ rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, co
 rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
                                     RecordOut out) {
   if (B == 0) return RKH_OK;
-  return launch_records(scene, [&](auto c) {
+  return launch_records(scene, false, [&](auto c) {
     constexpr int N = decltype(c)::value;
     hipLaunchKernelGGL((collision_records_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
                        scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, cap, out);
+  });
+}
+
+// The same for every 3D scene: with vertex-set shapes the support-map forms, without them the kernels above
+rkh_status launch_min_distance_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out) {
+  if (!scene.host.has_meshes) return launch_min_distance_records(s, scene, d_x, B, out);
+  if (B == 0) return RKH_OK;
+  return launch_records(scene, true, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((min_distance_records_meshes_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)),
+                       s, scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, out);
+  });
+}
+
+rkh_status launch_collision_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                           RecordOut out) {
+  if (!scene.host.has_meshes) return launch_collision_records(s, scene, d_x, B, cap, out);
+  if (B == 0) return RKH_OK;
+  return launch_records(scene, true, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((collision_records_meshes_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)),
+                       s, scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, cap, out);
   });
 }
 #endif

@@ -344,8 +344,8 @@ RKH_DI ProxRecordG rec_sphere_cyl(const ShapeG& sp, const ShapeG& cy) {  // prox
   return r;
 }
 
-// (shape1, shape2) in the routine's own argument order, as for pair_distance.  Vertex-set pairs (PR_GJK) have no record:
-// the support-map query yields a distance only, and the record queries refuse scenes that hold such shapes.
+// (shape1, shape2) in the routine's own argument order, as for pair_distance.  This form knows the closed forms only:
+// vertex-set pairs (PR_GJK) get no record from it, and the plain record queries refuse scenes that hold such shapes.
 RKH_DI ProxRecordG pair_record(int routine, const ShapeG& s1, const ShapeG& s2) {
   switch (routine) {
     case PR_SPHERE_SPHERE: return rec_sphere_sphere(s1, s2);
@@ -364,6 +364,23 @@ RKH_DI ProxRecordG pair_record(int routine, const ShapeG& s1, const ShapeG& s2) 
   none.p1 = none.p2 = mk3(0.0, 0.0, 0.0);
   none.dist = INFINITY;
   return none;
+}
+
+// The same with the scene's vertex pool.  GJK = true answers vertex-set pairs too, with the witnesses of the support-map
+// search (gjk_record: shape1 = model 1's shape, as pair_routine orders a PR_GJK pair); GJK = false is the form above.
+template <bool GJK = false>
+RKH_DI ProxRecordG pair_record(int routine, const ShapeG& s1, const ShapeG& s2, const double* mesh_pool) {
+  if (GJK) {
+    if (routine == PR_GJK) {
+      const GjkRecord g = gjk_record(to_gjk(s1, mesh_pool), to_gjk(s2, mesh_pool));
+      ProxRecordG r;
+      r.p1 = g.p1;
+      r.p2 = g.p2;
+      r.dist = g.dist;
+      return r;
+    }
+  }
+  return pair_record(routine, s1, s2);
 }
 
 }  // namespace rkh

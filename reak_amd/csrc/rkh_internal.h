@@ -430,6 +430,11 @@ struct RecordOut {
 rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
 rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
                                     RecordOut out);
+// The same for every 3D scene: scenes with vertex-set shapes go to the support-map forms of the two kernels (records of
+// such pairs: gjk_record), all others to the launchers above.
+rkh_status launch_min_distance_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
+rkh_status launch_collision_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                           RecordOut out);
 // Their planar twins (proximity_records_planar.hip; planar scenes, revolute and prismatic joints): points of two doubles
 // ([B][2], [B][cap][2]), finder rank = pair index.
 rkh_status launch_min_distance_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);

@@ -156,6 +156,26 @@ __global__ void gjk_pairs_kernel(const rkh_shape* __restrict__ a, const rkh_shap
   out[i] = gjk_distance(to_gjk(conv(a[i]), pool), to_gjk(conv(b[i]), pool));
 }
 
+// its twin with the points: gjk_record on the same pairs (rkh_diag_gjk_records)
+__global__ void gjk_pair_records_kernel(const rkh_shape* __restrict__ a, const rkh_shape* __restrict__ b, uint32_t n,
+                                        const double* __restrict__ pool, double* __restrict__ dist, double* __restrict__ point1,
+                                        double* __restrict__ point2) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  auto conv = [](const rkh_shape& s) {
+    ShapeG g;
+    g.kind = s.kind;
+    g.pos = mk3(s.pose.pos[0], s.pose.pos[1], s.pose.pos[2]);
+    g.q = d4{s.pose.quat[0], s.pose.quat[1], s.pose.quat[2], s.pose.quat[3]};
+    g.d0 = s.dims[0]; g.d1 = s.dims[1]; g.d2 = s.dims[2];
+    return g;
+  };
+  const GjkRecord r = gjk_record(to_gjk(conv(a[i]), pool), to_gjk(conv(b[i]), pool));
+  dist[i] = r.dist;
+  point1[3 * size_t(i)] = r.p1.x; point1[3 * size_t(i) + 1] = r.p1.y; point1[3 * size_t(i) + 2] = r.p1.z;
+  point2[3 * size_t(i)] = r.p2.x; point2[3 * size_t(i) + 1] = r.p2.y; point2[3 * size_t(i) + 2] = r.p2.z;
+}
+
 
 static thread_local SteerMapping g_steer_mapping = SteerMapping::Wave;
 void note_steer_mapping(SteerMapping m) { g_steer_mapping = m; }
@@ -713,6 +733,32 @@ rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_sha
   return RKH_OK;
 }
 
+rkh_status rkh_diag_gjk_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n, const double* mesh_vertices,
+                                uint32_t n_mesh_vertices, double* dist, double* point1, double* point2) {
+  if (!ctx || !a || !b || !dist || !point1 || !point2) return RKH_ERR_BAD_ARG;
+  if (n == 0) return RKH_OK;
+  RKH_HIP(hipSetDevice(ctx->device));
+  DeviceBuffer<rkh_shape> da, db;
+  DeviceBuffer<double> dv, dd, dp1, dp2;
+  RKH_TRY(da.alloc(n));
+  RKH_TRY(db.alloc(n));
+  RKH_TRY(dd.alloc(n));
+  RKH_TRY(dp1.alloc(size_t(n) * 3));
+  RKH_TRY(dp2.alloc(size_t(n) * 3));
+  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
+  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(rkh::gjk_pair_records_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, da.get(), db.get(), n,
+                     dv.get(), dd.get(), dp1.get(), dp2.get());
+  RKH_HIP(hipGetLastError());
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipStreamSynchronize(ctx->stream));
+  return RKH_OK;
+}
+
 rkh_status rkh_scene_destroy(rkh_scene* scene) {
   delete scene;  // (its buffers free themselves; hipFree waits for the device)
   return RKH_OK;
@@ -752,12 +798,90 @@ rkh_status records_supported(const rkh_scene* scene, const char* entry) {
   set_error(std::string(entry) + ": not supported for " + why);
   return RKH_ERR_UNSUPPORTED;
 }
+// the _meshes entries serve every 3D scene
+rkh_status records_meshes_supported(const rkh_scene* scene, const char* entry) {
+  const char* why = scene->host.planar ? "planar (2D) scenes: the records of proxy_query_pair_2D come from "
+                                         "rkh_min_distance_records_2d / rkh_collision_records_2d"
+                    : scene->n_pairs > kMaxRecordPairs ? "more proxy pairs than the record kernels keep track of"
+                                                       : nullptr;
+  if (!why) return RKH_OK;
+  set_error(std::string(entry) + ": not supported for " + why);
+  return RKH_ERR_UNSUPPORTED;
+}
 // and their planar twins serve planar scenes
 rkh_status records_2d_supported(const rkh_scene* scene, const char* entry) {
   if (scene->host.planar) return RKH_OK;
   set_error(std::string(entry) + ": not supported for 3D scenes: their records come from rkh_min_distance_records / "
             "rkh_collision_records");
   return RKH_ERR_UNSUPPORTED;
+}
+// rkh_min_distance_records and rkh_min_distance_records_meshes after their checks: the same transfers around the launch
+using MinRecordsLaunch = rkh_status (*)(hipStream_t, const rkh_scene&, const double*, uint32_t, RecordOut);
+rkh_status min_distance_records_3d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1, double* point2,
+                                   uint32_t* shape1, uint32_t* shape2, MinRecordsLaunch launch) {
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dd.alloc(size_t(B)));
+  RKH_TRY(dp1.alloc(size_t(B) * 3));
+  RKH_TRY(dp2.alloc(size_t(B) * 3));
+  RKH_TRY(ds1.alloc(size_t(B)));
+  RKH_TRY(ds2.alloc(size_t(B)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch(s, *scene, dx.get(), B, out));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
+}
+// and the same for rkh_collision_records and rkh_collision_records_meshes
+using CollisionRecordsLaunch = rkh_status (*)(hipStream_t, const rkh_scene&, const double*, uint32_t, uint32_t, RecordOut);
+rkh_status collision_records_3d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found, double* dist,
+                                double* point1, double* point2, uint32_t* shape1, uint32_t* shape2, CollisionRecordsLaunch launch) {
+  if (B == 0) return RKH_OK;
+  const int n = scene->host.n_dof;
+  const size_t slots = size_t(B) * cap;
+  hipStream_t s = scene->ctx->stream;
+  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<uint32_t> dn, ds1, ds2;
+  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
+  RKH_TRY(dn.alloc(size_t(B)));
+  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 3)));
+  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 3)));
+  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
+  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
+  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  RecordOut out;
+  out.n_found = dn.get();
+  out.dist = dd.get();
+  out.point1 = dp1.get();
+  out.point2 = dp2.get();
+  out.shape1 = ds1.get();
+  out.shape2 = ds2.get();
+  RKH_TRY(launch(s, *scene, dx.get(), B, cap, out));
+  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
+  if (slots) {
+    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
+  }
+  RKH_HIP(hipStreamSynchronize(s));
+  return RKH_OK;
 }
 }  // namespace
 
@@ -805,38 +929,20 @@ rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t 
                                     double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_min_distance_records"));
-  if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
-  hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
-  DeviceBuffer<uint32_t> ds1, ds2;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dd.alloc(size_t(B)));
-  RKH_TRY(dp1.alloc(size_t(B) * 3));
-  RKH_TRY(dp2.alloc(size_t(B) * 3));
-  RKH_TRY(ds1.alloc(size_t(B)));
-  RKH_TRY(ds2.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RecordOut out;
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch_min_distance_records(s, *scene, dx.get(), B, out));
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return min_distance_records_3d(scene, x, B, dist, point1, point2, shape1, shape2, launch_min_distance_records);
+}
+
+rkh_status rkh_min_distance_records_meshes(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
+                                           double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_meshes_supported(scene, "rkh_min_distance_records_meshes"));
+  return min_distance_records_3d(scene, x, B, dist, point1, point2, shape1, shape2, launch_min_distance_records_meshes);
 }
 
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms) {
   if (!scene || !x || !ms || B == 0) return RKH_ERR_BAD_ARG;
   const bool planar = scene->host.planar != 0;  // planar scenes: the _2d record kernel (points of two doubles)
-  if (records && !planar) RKH_TRY(records_supported(scene, "rkh_diag_distance_query_ms"));
+  if (records && !planar) RKH_TRY(records_meshes_supported(scene, "rkh_diag_distance_query_ms"));
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
   DeviceBuffer<double> dx, dd, dp1, dp2;
@@ -862,7 +968,7 @@ rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_
     hipError_t err = hipEventRecord(e0, s);
     st = !records ? launch_min_distance(s, *scene, dx.get(), B, dd.get())
          : planar ? launch_min_distance_records_2d(s, *scene, dx.get(), B, out)
-                  : launch_min_distance_records(s, *scene, dx.get(), B, out);
+                  : launch_min_distance_records_meshes(s, *scene, dx.get(), B, out);  // (no meshes: the plain kernel)
     if (err == hipSuccess) err = hipEventRecord(e1, s);
     if (err == hipSuccess) err = hipEventSynchronize(e1);
     if (err == hipSuccess) err = hipEventElapsedTime(&ms[r], e0, e1);
@@ -880,38 +986,14 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
                                  double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_collision_records"));
-  if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
-  const size_t slots = size_t(B) * cap;
-  hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
-  DeviceBuffer<uint32_t> dn, ds1, ds2;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dn.alloc(size_t(B)));
-  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 3)));
-  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 3)));
-  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RecordOut out;
-  out.n_found = dn.get();
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch_collision_records(s, *scene, dx.get(), B, cap, out));
-  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  if (slots) {
-    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
-  }
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, shape1, shape2, launch_collision_records);
+}
+
+rkh_status rkh_collision_records_meshes(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
+                                        double* dist, double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_meshes_supported(scene, "rkh_collision_records_meshes"));
+  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, shape1, shape2, launch_collision_records_meshes);
 }
 
 rkh_status rkh_min_distance_records_2d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,

@@ -80,8 +80,8 @@ EXPORTS = [
     "rkh_nn_queryk", "rkh_nn_query1_async", "rkh_nn_queryk_async", "rkh_nn_fill_uniform", "rkh_nn_kernel_name",
     "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
-    "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
-    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
+    "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_diag_gjk_records", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
+    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_meshes", "rkh_collision_records_meshes", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
     "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
@@ -140,6 +140,7 @@ def load():
     lib.rkh_scene_create_with_meshes.argtypes = [vp, C.POINTER(T.KteOp), C.c_int, C.POINTER(T.ChainBase), C.POINTER(T.Shape),
                                                  C.c_int, dp, u32, C.POINTER(vp)]
     lib.rkh_diag_gjk_distance.argtypes = [vp, C.POINTER(T.Shape), C.POINTER(T.Shape), u32, dp, u32, dp]
+    lib.rkh_diag_gjk_records.argtypes = [vp, C.POINTER(T.Shape), C.POINTER(T.Shape), u32, dp, u32, dp, dp, dp]
     lib.rkh_scene_destroy.argtypes = [vp]
     lib.rkh_scene_num_dof.argtypes = [vp]
     lib.rkh_scene_num_pairs.argtypes = [vp]
@@ -147,6 +148,8 @@ def load():
     lib.rkh_min_distance.argtypes = [vp, dp, u32, dp]
     lib.rkh_min_distance_records.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
     lib.rkh_collision_records.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
+    lib.rkh_min_distance_records_meshes.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
+    lib.rkh_collision_records_meshes.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
     lib.rkh_min_distance_records_2d.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
     lib.rkh_collision_records_2d.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
     lib.rkh_diag_distance_query_ms.argtypes = [vp, dp, u32, C.c_int, u32, C.POINTER(C.c_float)]
@@ -325,6 +328,18 @@ def gjk_distance(ctx, a, b, mesh_vertices=None):
     return out
 
 
+def gjk_records(ctx, a, b, mesh_vertices=None):
+    """The records of the same searches (rkh_diag_gjk_records): dist [n] (gjk_distance's values), point1 [n][3] on a[i],
+    point2 [n][3] on b[i]."""
+    n = len(a)
+    aa, bb = T.as_array(list(a), T.Shape), T.as_array(list(b), T.Shape)
+    verts = np.zeros((0, 3)) if mesh_vertices is None else np.ascontiguousarray(mesh_vertices, dtype=np.float64).reshape(-1, 3)
+    d, p1, p2 = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
+    _check(ctx.lib.rkh_diag_gjk_records(ctx.h, aa, bb, n, T.dptr(verts) if len(verts) else None, len(verts), T.dptr(d),
+                                        T.dptr(p1), T.dptr(p2)))
+    return {"dist": d, "point1": p1, "point2": p2}
+
+
 def nn_mirror_query(ctx, pts, q, coord_bound):
     """1-NN of every query through the planner-regime sweep (half-precision mirror + exact resolution,
     rkh_diag_nn_mirror_query): (index, distance) arrays."""
@@ -436,6 +451,29 @@ class Scene:
         s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
         _check(self.lib.rkh_collision_records(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1), T.dptr(p2),
                                               T.u32ptr(s1), T.u32ptr(s2)))
+        return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def min_distance_records_meshes(self, x):
+        """min_distance_records for every non-planar scene, mesh shapes included (rkh_min_distance_records_meshes): the
+        same keys.  A pair with a mesh in it reports the witnesses of its support-map search: a closest pair of points
+        while the cores are apart, one common point of the cores (no penetration depth) when they cross."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B = x.shape[0]
+        d, p1, p2 = np.zeros(B), np.zeros((B, 3)), np.zeros((B, 3))
+        s1, s2 = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        _check(self.lib.rkh_min_distance_records_meshes(self.h, T.dptr(x), B, T.dptr(d), T.dptr(p1), T.dptr(p2),
+                                                        T.u32ptr(s1), T.u32ptr(s2)))
+        return {"dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def collision_records_meshes(self, x, cap):
+        """collision_records for every non-planar scene, mesh shapes included (rkh_collision_records_meshes)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B, cap = x.shape[0], int(cap)
+        n = np.zeros(B, dtype=np.uint32)
+        d, p1, p2 = np.zeros((B, cap)), np.zeros((B, cap, 3)), np.zeros((B, cap, 3))
+        s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
+        _check(self.lib.rkh_collision_records_meshes(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1),
+                                                     T.dptr(p2), T.u32ptr(s1), T.u32ptr(s2)))
         return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
 
     def min_distance_records_2d(self, x):

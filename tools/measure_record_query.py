@@ -5,6 +5,8 @@
     python tools/measure_record_query.py --out profiles/r07_record_query.json                       C2, rkh_min_distance_records
     python tools/measure_record_query.py --scene planar4 --out profiles/r14_planar_record_query.json   make_planar_mixed(n=4),
                                                                                                     rkh_min_distance_records_2d
+    python tools/measure_record_query.py --scene c4_meshes --out profiles/r16_mesh_record_query.json   make_c4(meshes=True),
+                                                                                                    rkh_min_distance_records_meshes
 """
 import argparse
 import json
@@ -20,13 +22,13 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--states", type=int, default=65536)
-    ap.add_argument("--scene", choices=("c2", "planar4"), default="c2")
+    ap.add_argument("--scene", choices=("c2", "planar4", "c4_meshes"), default="c2")
     a = ap.parse_args()
     from reak_amd import lib, scenarios
 
     rng = np.random.default_rng(5)
-    if a.scene == "c2":
-        scn, label = scenarios.make_c2(), "make_c2()"
+    if a.scene in ("c2", "c4_meshes"):  # (c4_meshes: 200 convex-mesh obstacles, 2400 support-map finders)
+        scn, label = (scenarios.make_c2(), "make_c2()") if a.scene == "c2" else (scenarios.make_c4(meshes=True), "make_c4(meshes=True)")
         lo = np.array([scn.dyn.lower[i] for i in range(scn.D)])
         hi = np.array([scn.dyn.upper[i] for i in range(scn.D)])
         x = rng.uniform(lo, hi, size=(a.states, scn.D))
