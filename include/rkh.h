@@ -216,6 +216,38 @@ rkh_status rkh_collision_records_meshes(rkh_scene* scene, const double* x, uint3
                                         uint32_t* n_found,                             /* [B] */
                                         double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
                                         uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
+/* The _meshes entries with a PENETRATION DEPTH and a CONTACT NORMAL (the _meshes entries themselves hold what they held).
+ * Finder order, caps, n_found, unused slots (normal: zeros), NULL and B == 0 rules, the refusal of planar scenes (the _2d
+ * entries below) and a scene without finders are those of the _meshes entries; normal is one more array of the points'
+ * shape.  What differs is the record of a support-map finder whose cores cross: the search goes on with the Expanding
+ * Polytope Algorithm on the Minkowski difference of the two cores (reak_amd/csrc/epa_device.h), and
+ *   cores crossing  depth = the least translation that brings the cores to touching, n = its unit direction, from shape1
+ *                   towards shape2 (moving shape2 by depth n separates the cores; ties between directions: one of them);
+ *                   dist = -(r1 + r2 + depth) - 1e-9 (the collision mark of rkh_min_distance is kept, so the verdict and
+ *                   the set of colliding finders are the _meshes entries'); point1 = a point of shape1's surface where
+ *                   that translation first makes contact, point2 = point1 - (depth + r1 + r2) n on shape2's.  Cores that
+ *                   touch exactly have depth 0; cores that lie in one plane or line have depth 0 and n = its normal.
+ *   cores apart     dist, point1, point2 as in the _meshes entries, bit for bit; normal = n.
+ *   closed forms    dist, point1, point2 as in the plain entries; normal = (point2 - point1) / dist componentwise, zeros
+ *                   where dist is 0 or not finite.  No more is claimed for it.
+ * rkh_min_distance_records_depth takes the minimum over THESE distances, with the same tie rule (first in finder order
+ * among equals): among crossing support-map finders the deepest wins, where the _meshes entry reports the first of those
+ * at -(r1 + r2) - 1e-9.  dist[b] is therefore bit-identical to rkh_min_distance's only when the winner's cores are apart
+ * or the winner is a closed form.  rkh_collision_records_depth lists exactly the finders rkh_collision_records_meshes
+ * lists, with the same n_found.  A scene without mesh shapes: dist, the points and the ids are the plain entries' byte
+ * for byte. */
+rkh_status rkh_min_distance_records_depth(rkh_scene* scene, const double* x, uint32_t B,
+                                          double* dist,      /* [B]    */
+                                          double* point1,    /* [B][3] */
+                                          double* point2,    /* [B][3] */
+                                          double* normal,    /* [B][3] */
+                                          uint32_t* shape1,  /* [B]    */
+                                          uint32_t* shape2); /* [B]    */
+rkh_status rkh_collision_records_depth(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap,
+                                       uint32_t* n_found,                             /* [B] */
+                                       double* dist, double* point1, double* point2,  /* [B][cap], [B][cap][3], [B][cap][3] */
+                                       double* normal,                                /* [B][cap][3] */
+                                       uint32_t* shape1, uint32_t* shape2);           /* [B][cap] */
 /* The same for planar (2D) scenes: what proxy_query_pair_2D::findMinimumDistance()->getLastResult() and
  * gatherCollisionPoints hold (proxy_query_model.cpp:163-187 and :189-208; proximity_record_2D.hpp:47-58: points are
  * vect<double,2>).  x as for rkh_min_distance; shape1 / shape2 and the finder order as above, with createProxFinderList's

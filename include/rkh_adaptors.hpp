@@ -431,10 +431,16 @@ struct is_steerable_space_tag<kte_dynamic_free_space<P> > {
 // when they cross (rkh.h).  Planar chains, which these refuse too, still answer findMinimumDistance with the distance;
 // their points are NaN and their shape indices no_shape.  Planar callers who want the records use
 // hip_proxy_query_pair_2D below.
+// Opt-in (the constructor's depth_records, or use_depth_records; default off): non-planar scenes answer from
+// rkh_min_distance_records_depth / rkh_collision_records_depth instead.  A mesh pair whose cores cross then reports a real
+// penetration depth (mDistance = -(r1 + r2 + depth) - 1e-9), the two contact points and the contact normal, and every
+// record carries a normal (rkh.h); the minimum is taken over those distances, so among crossing mesh pairs the deepest
+// one is the finder returned.
 struct proximity_record {  // proximity_record_3D (proximity_record_3D.hpp:47-56)
   double mPoint1[3] = {0.0, 0.0, 0.0};  // on the finder's shape1, world frame
   double mPoint2[3] = {0.0, 0.0, 0.0};  // on its shape2
   double mDistance = std::numeric_limits<double>::infinity();
+  double mNormal[3] = {0.0, 0.0, 0.0};  // not the reference's: unit, from shape1 towards shape2; zeros unless depth records are on
 };
 class hip_proximity_finder {
  public:
@@ -447,6 +453,8 @@ class hip_proximity_finder {
   // finder's own order (the plane first, else the sphere, else the capped cylinder)
   uint32_t getShape1Index() const { return m_shape1; }
   uint32_t getShape2Index() const { return m_shape2; }
+  // the contact normal of the record (three doubles; zeros unless the socket answers from the depth records)
+  const double* normal() const { return m_last.mNormal; }
 
  private:
   proximity_record m_last;
@@ -454,7 +462,10 @@ class hip_proximity_finder {
 };
 class hip_proxy_query_pair {
  public:
-  explicit hip_proxy_query_pair(const std::shared_ptr<rkh_scene>& scene) : m_scene(scene) {}
+  explicit hip_proxy_query_pair(const std::shared_ptr<rkh_scene>& scene, bool depth_records = false)
+      : m_scene(scene), m_depth(depth_records) {}
+  void use_depth_records(bool on) { m_depth = on; }
+  bool depth_records() const { return m_depth; }
   // the joint state the models are at (apply_to_model writes it into the KTE chain in ReaK)
   template <typename Point>
   void apply_to_model(const Point& p) {
@@ -465,8 +476,10 @@ class hip_proxy_query_pair {
     proximity_record r;
     uint32_t s1 = hip_proximity_finder::no_shape, s2 = hip_proximity_finder::no_shape;
     rkh_status st =
-        rkh_min_distance_records(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
-    if (st == RKH_ERR_UNSUPPORTED)  // mesh shapes
+        m_depth ? rkh_min_distance_records_depth(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2,
+                                                 r.mNormal, &s1, &s2)
+                : rkh_min_distance_records(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
+    if (st == RKH_ERR_UNSUPPORTED && !m_depth)  // mesh shapes
       st = rkh_min_distance_records_meshes(m_scene.get(), m_state.data(), 1, &r.mDistance, r.mPoint1, r.mPoint2, &s1, &s2);
     if (st == RKH_ERR_UNSUPPORTED) {  // no records for this kind of scene (planar): the distance alone
       check(rkh_min_distance(m_scene.get(), m_state.data(), 1, &r.mDistance));
@@ -481,14 +494,18 @@ class hip_proxy_query_pair {
   bool gatherCollisionPoints(std::vector<proximity_record>& aOutput,
                              std::vector<std::pair<uint32_t, uint32_t> >* shapes = nullptr) const {
     uint32_t cap = 8, n_found = 0;
-    std::vector<double> d, p1, p2;
+    std::vector<double> d, p1, p2, nr;
     std::vector<uint32_t> s1, s2;
     for (;;) {  // grow until every colliding finder fits
       d.resize(cap); p1.resize(3 * std::size_t(cap)); p2.resize(3 * std::size_t(cap));
+      nr.assign(3 * std::size_t(cap), 0.0);
       s1.resize(cap); s2.resize(cap);
-      rkh_status st = rkh_collision_records(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
-                                            s1.data(), s2.data());
-      if (st == RKH_ERR_UNSUPPORTED)  // mesh shapes
+      rkh_status st =
+          m_depth ? rkh_collision_records_depth(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
+                                                nr.data(), s1.data(), s2.data())
+                  : rkh_collision_records(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
+                                          s1.data(), s2.data());
+      if (st == RKH_ERR_UNSUPPORTED && !m_depth)  // mesh shapes
         st = rkh_collision_records_meshes(m_scene.get(), m_state.data(), 1, cap, &n_found, d.data(), p1.data(), p2.data(),
                                           s1.data(), s2.data());
       check(st);
@@ -500,6 +517,7 @@ class hip_proxy_query_pair {
       for (int k = 0; k < 3; ++k) {
         r.mPoint1[k] = p1[3 * std::size_t(i) + k];
         r.mPoint2[k] = p2[3 * std::size_t(i) + k];
+        r.mNormal[k] = nr[3 * std::size_t(i) + k];
       }
       r.mDistance = d[i];
       aOutput.push_back(r);
@@ -511,6 +529,7 @@ class hip_proxy_query_pair {
  private:
   std::shared_ptr<rkh_scene> m_scene;
   std::vector<double> m_state;
+  bool m_depth = false;
 };
 
 // The same socket for planar scenes: proxy_query_pair_2D::findMinimumDistance / gatherCollisionPoints

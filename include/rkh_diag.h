@@ -39,6 +39,11 @@ rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_sha
 rkh_status rkh_diag_gjk_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n,
                                 const double* mesh_vertices, uint32_t n_mesh_vertices, double* dist, double* point1,
                                 double* point2);
+/* And with the penetration depth and the contact normal: gjk_depth_record (reak_amd/csrc/epa_device.h; the definition is
+ * at rkh_min_distance_records_depth in rkh.h) for each pair.  normal[n][3]: unit, from a[i] towards b[i]. */
+rkh_status rkh_diag_gjk_depth_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n,
+                                      const double* mesh_vertices, uint32_t n_mesh_vertices, double* dist, double* point1,
+                                      double* point2, double* normal);
 
 /* The planner-regime 1-NN sweep (half-precision mirror of the vertex rows + exact resolution of the one or two rows the
  * estimate leaves, reak_amd/csrc/nn_mirror.hip) on a caller's point cloud: n points [n][D], B queries [B][D], every
@@ -92,7 +97,7 @@ rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]);
 
 /* Kernel time of the distance query on B states: `runs` launches of rkh_min_distance's kernel (records == 0) or of
  * rkh_min_distance_records' (records != 0; on a planar scene rkh_min_distance_records_2d's, on a scene with mesh shapes
- * rkh_min_distance_records_meshes') over the same device copy of x, each between two events on the context's stream; ms[runs] = the elapsed times.  No copies are timed
+ * rkh_min_distance_records_meshes'; records == 2 on a 3D scene: rkh_min_distance_records_depth's) over the same device copy of x, each between two events on the context's stream; ms[runs] = the elapsed times.  No copies are timed
  * (tools/measure_record_query.py). */
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms);
 

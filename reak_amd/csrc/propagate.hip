@@ -42,6 +42,12 @@
 #include "proximity_record_device.h"
 #include "rkh_internal.h"
 
+// Two more translation units take single forms out of this text and none of its other kernels or launchers:
+// propagate_planar_qs_prismatic.hip (RKH_PLANAR_PRISMATIC_QS) and propagate_depth.hip (RKH_DEPTH_RECORDS).
+#if defined(RKH_PLANAR_PRISMATIC_QS) || defined(RKH_DEPTH_RECORDS)
+#define RKH_FORMS_ONLY 1
+#endif
+
 namespace rkh {
 #ifdef RKH_PRISMATIC_FORMS
 namespace prismatic {
@@ -1916,20 +1922,48 @@ RKH_DI double record_pair_shapes(const SceneDev* __restrict__ sc, const ShapeDev
   return norm_2(c2 - c1) - r1 - r2;
 }
 
-// slot `at` of the record arrays: the record of pair p (p < 0: no record).  GJK: vertex-set pairs among them, answered
-// from mesh_pool (pair_record<true>)
-template <bool GJK = false, typename WS>
+// The three modes of the record kernels: closed forms only; vertex-set pairs through gjk_distance / gjk_record; the same
+// pairs through gjk_depth_distance / gjk_depth_record (a penetration depth where the cores cross, and a normal with
+// every record: pair_distance_depth / pair_record_depth).
+constexpr int kRecClosed = 0, kRecGjk = 1, kRecDepth = 2;
+
+template <int MODE>
+RKH_DI double record_pair_distance(int routine, const ShapeG& s1, const ShapeG& s2, const double* __restrict__ mesh_pool) {
+  if constexpr (MODE == kRecDepth) return pair_distance_depth(routine, s1, s2, mesh_pool);
+  else return pair_distance<MODE == kRecGjk>(routine, s1, s2, mesh_pool);
+}
+
+// slot `at` of the record arrays: the record of pair p (p < 0: no record).  kRecGjk, kRecDepth: vertex-set pairs among
+// them, answered from mesh_pool; kRecDepth: three doubles of normal as well (zeros without a record), and the dist of a
+// vertex-set pair is its record's own -- gjk_depth_distance's value bit for bit, so a caller need not search twice
+template <int MODE = kRecClosed, typename WS>
 RKH_DI void write_pair_record(const SceneDev* __restrict__ sc, const ShapeDev* __restrict__ env_lds, const WS& ws,
                               const PairDev* __restrict__ pairs, const PairIdDev* __restrict__ ids, int p, const RecordOut& out,
-                              uint64_t at, double dist, const double* __restrict__ mesh_pool = nullptr) {
+                              uint64_t at, double dist, const double* __restrict__ mesh_pool = nullptr,
+                              double* __restrict__ normal = nullptr) {
   ProxRecordG r;
   r.p1 = r.p2 = mk3(0.0, 0.0, 0.0);
   uint32_t id1 = 0xFFFFFFFFu, id2 = 0xFFFFFFFFu;
-  if (p >= 0) {
+  if constexpr (MODE == kRecDepth) {
+    d3 nrm = mk3(0.0, 0.0, 0.0);
+    if (p >= 0) {
+      const PairDev pr = pairs[p];
+      ShapeG s1, s2;
+      record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
+      const ProxRecordN rn = pair_record_depth(pr.routine, s1, s2, mesh_pool);
+      r.p1 = rn.p1;
+      r.p2 = rn.p2;
+      nrm = rn.nrm;
+      if (pr.routine == PR_GJK) dist = rn.dist;
+      id1 = ids[p].shape1;
+      id2 = ids[p].shape2;
+    }
+    st3(normal + 3 * at, nrm);
+  } else if (p >= 0) {
     const PairDev pr = pairs[p];
     ShapeG s1, s2;
     record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-    if constexpr (GJK) r = pair_record<true>(pr.routine, s1, s2, mesh_pool);
+    if constexpr (MODE == kRecGjk) r = pair_record<true>(pr.routine, s1, s2, mesh_pool);
     else r = pair_record(pr.routine, s1, s2);
     id1 = ids[p].shape1;
     id2 = ids[p].shape2;
@@ -1948,13 +1982,15 @@ RKH_DI void write_pair_record(const SceneDev* __restrict__ sc, const ShapeDev* _
 // finder stays.  A butterfly leaves the wave's winner in every lane; lane 0 evaluates that one pair's point form.
 // GJK = true is the form for scenes with vertex-set shapes: it searches with the support-map query as min_distance_kernel
 // does there, and lane 0 evaluates the winner's record with gjk_record where the winner is such a pair.  The two forms
-// are kernels of their own names (the closed-form one keeps the name and the code it had).
-template <int N, bool GJK>
+// are kernels of their own names (the closed-form one keeps the name and the code it had).  MODE = kRecDepth is the
+// third form (min_distance_depth_kernel, in propagate_depth.hip's module): the same search over pair_distance_depth, so
+// among crossing vertex-set pairs the deepest wins, and lane 0 writes the winner's normal too.
+template <int N, int MODE>
 RKH_DI void min_distance_records_body(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
                                       const PairIdDev* __restrict__ ids, int n_pairs, const double* __restrict__ x, uint32_t B,
-                                      const RecordOut& out) {
+                                      const RecordOut& out, double* __restrict__ normal = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const double* mesh_pool = GJK ? sc->mesh_verts : nullptr;
+  const double* mesh_pool = MODE != kRecClosed ? sc->mesh_verts : nullptr;
   BlockLdsQs<N, 64>& lds = *reinterpret_cast<BlockLdsQs<N, 64>*>(smem_raw);
   ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQs<N, 64>::block_bytes);
   const uint32_t e = blockIdx.x;
@@ -1976,7 +2012,7 @@ RKH_DI void min_distance_records_body(const SceneDev* __restrict__ sc, const Pai
     const PairDev pr = pairs[p];
     ShapeG s1, s2;
     record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-    const double d = pair_distance<GJK>(pr.routine, s1, s2, mesh_pool);
+    const double d = record_pair_distance<MODE>(pr.routine, s1, s2, mesh_pool);
     if (d < dmin) dmin = d;
     const uint32_t rank = ids[p].rank;
     if (d < dbest || (d == dbest && rank < rbest)) {
@@ -1999,14 +2035,14 @@ RKH_DI void min_distance_records_body(const SceneDev* __restrict__ sc, const Pai
       pbest = op;
     }
   }
-  if (lane == 0) write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, pbest, out, e, dmin, mesh_pool);
+  if (lane == 0) write_pair_record<MODE>(sc, env_lds, ws, pairs, ids, pbest, out, e, dmin, mesh_pool, normal);
 }
 
 template <int N>
 __global__ __launch_bounds__(64) void min_distance_records_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
                                                                    const PairIdDev* __restrict__ ids, int n_pairs,
                                                                    const double* __restrict__ x, uint32_t B, RecordOut out) {
-  min_distance_records_body<N, false>(sc, pairs, ids, n_pairs, x, B, out);
+  min_distance_records_body<N, kRecClosed>(sc, pairs, ids, n_pairs, x, B, out);
 }
 
 template <int N>
@@ -2014,7 +2050,7 @@ __global__ __launch_bounds__(64) void min_distance_records_meshes_kernel(const S
                                                                           const PairDev* __restrict__ pairs,
                                                                           const PairIdDev* __restrict__ ids, int n_pairs,
                                                                           const double* __restrict__ x, uint32_t B, RecordOut out) {
-  min_distance_records_body<N, true>(sc, pairs, ids, n_pairs, x, B, out);
+  min_distance_records_body<N, kRecGjk>(sc, pairs, ids, n_pairs, x, B, out);
 }
 
 // Kernel: proxy_query_pair_3D::gatherCollisionPoints for B states, one wave per state.  Every lane culls and measures
@@ -2023,13 +2059,14 @@ __global__ __launch_bounds__(64) void min_distance_records_meshes_kernel(const S
 // cap) rounds, each a butterfly over every lane's lowest remaining rank; lane 0 evaluates the round's point form and
 // the owner drops its bit.  The round count is wave-uniform, so the butterflies run in uniform control flow.
 // GJK = true: the form for scenes with vertex-set shapes, as for the minimum-distance records; only lane 0 runs
-// gjk_record, between the rounds' butterflies and never around them.
-template <int N, bool GJK>
+// gjk_record, between the rounds' butterflies and never around them.  MODE = kRecDepth (collision_depth_kernel): the
+// same pairs in the same order (the depth mode keeps the collision mark), their records with depth and normal.
+template <int N, int MODE>
 RKH_DI void collision_records_body(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
                                    const PairIdDev* __restrict__ ids, int n_pairs, const double* __restrict__ x, uint32_t B,
-                                   uint32_t cap, const RecordOut& out) {
+                                   uint32_t cap, const RecordOut& out, double* __restrict__ normal = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const double* mesh_pool = GJK ? sc->mesh_verts : nullptr;
+  const double* mesh_pool = MODE != kRecClosed ? sc->mesh_verts : nullptr;
   BlockLdsQs<N, 64>& lds = *reinterpret_cast<BlockLdsQs<N, 64>*>(smem_raw);
   ShapeDev* env_lds = reinterpret_cast<ShapeDev*>(smem_raw + SmemLayoutQs<N, 64>::block_bytes);
   const uint32_t e = blockIdx.x;
@@ -2049,7 +2086,9 @@ RKH_DI void collision_records_body(const SceneDev* __restrict__ sc, const PairDe
     ShapeG s1, s2;
     const double gap = record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
     if (gap > 0.0) continue;
-    if (pair_distance<GJK>(pr.routine, s1, s2, mesh_pool) < 0.0) {
+    // (kRecDepth: the depth mode keeps the collision mark, so gjk_distance gives its verdict without the expansion)
+    constexpr int VMODE = MODE == kRecDepth ? kRecGjk : MODE;
+    if (record_pair_distance<VMODE>(pr.routine, s1, s2, mesh_pool) < 0.0) {
       const int s = p >> 6;
       if (s < 64) m0 |= 1ull << s;
       else m1 |= 1ull << (s - 64);
@@ -2090,12 +2129,14 @@ RKH_DI void collision_records_body(const SceneDev* __restrict__ sc, const PairDe
       const PairDev pr = pairs[pmin];
       ShapeG s1, s2;
       record_pair_shapes(sc, env_lds, ws, pr, &s1, &s2);
-      write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, pmin, out, row + k, pair_distance<GJK>(pr.routine, s1, s2, mesh_pool),
-                             mesh_pool);
+      // (kRecDepth: a vertex-set pair's dist comes with its record, see write_pair_record)
+      constexpr int DMODE = MODE == kRecDepth ? kRecClosed : MODE;
+      write_pair_record<MODE>(sc, env_lds, ws, pairs, ids, pmin, out, row + k,
+                              record_pair_distance<DMODE>(pr.routine, s1, s2, mesh_pool), mesh_pool, normal);
     }
   }
   for (uint32_t k = n_out + lane; k < cap; k += 64)
-    write_pair_record<GJK>(sc, env_lds, ws, pairs, ids, -1, out, row + k, INFINITY, mesh_pool);
+    write_pair_record<MODE>(sc, env_lds, ws, pairs, ids, -1, out, row + k, INFINITY, mesh_pool, normal);
 }
 
 template <int N>
@@ -2103,7 +2144,7 @@ __global__ __launch_bounds__(64) void collision_records_kernel(const SceneDev* _
                                                                 const PairIdDev* __restrict__ ids, int n_pairs,
                                                                 const double* __restrict__ x, uint32_t B, uint32_t cap,
                                                                 RecordOut out) {
-  collision_records_body<N, false>(sc, pairs, ids, n_pairs, x, B, cap, out);
+  collision_records_body<N, kRecClosed>(sc, pairs, ids, n_pairs, x, B, cap, out);
 }
 
 template <int N>
@@ -2112,8 +2153,49 @@ __global__ __launch_bounds__(64) void collision_records_meshes_kernel(const Scen
                                                                        const PairIdDev* __restrict__ ids, int n_pairs,
                                                                        const double* __restrict__ x, uint32_t B, uint32_t cap,
                                                                        RecordOut out) {
-  collision_records_body<N, true>(sc, pairs, ids, n_pairs, x, B, cap, out);
+  collision_records_body<N, kRecGjk>(sc, pairs, ids, n_pairs, x, B, cap, out);
 }
+
+#ifdef RKH_DEPTH_RECORDS
+// The depth forms of the two record kernels, and the pair-by-pair form of the diagnostic entry (rkh_diag_gjk_depth_records).
+// propagate_depth.hip instantiates these three and nothing else of this text.
+template <int N>
+__global__ __launch_bounds__(64) void min_distance_depth_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                                                 const PairIdDev* __restrict__ ids, int n_pairs,
+                                                                 const double* __restrict__ x, uint32_t B, RecordOut out,
+                                                                 double* __restrict__ normal) {
+  min_distance_records_body<N, kRecDepth>(sc, pairs, ids, n_pairs, x, B, out, normal);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void collision_depth_kernel(const SceneDev* __restrict__ sc, const PairDev* __restrict__ pairs,
+                                                              const PairIdDev* __restrict__ ids, int n_pairs,
+                                                              const double* __restrict__ x, uint32_t B, uint32_t cap, RecordOut out,
+                                                              double* __restrict__ normal) {
+  collision_records_body<N, kRecDepth>(sc, pairs, ids, n_pairs, x, B, cap, out, normal);
+}
+
+__global__ __launch_bounds__(64) void gjk_pair_depth_kernel(const rkh_shape* __restrict__ a, const rkh_shape* __restrict__ b,
+                                                             uint32_t n, const double* __restrict__ pool, double* __restrict__ dist,
+                                                             double* __restrict__ point1, double* __restrict__ point2,
+                                                             double* __restrict__ normal) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  auto conv = [](const rkh_shape& s) {
+    ShapeG g;
+    g.kind = s.kind;
+    g.pos = mk3(s.pose.pos[0], s.pose.pos[1], s.pose.pos[2]);
+    g.q = d4{s.pose.quat[0], s.pose.quat[1], s.pose.quat[2], s.pose.quat[3]};
+    g.d0 = s.dims[0]; g.d1 = s.dims[1]; g.d2 = s.dims[2];
+    return g;
+  };
+  const ProxRecordN r = pair_record_depth(PR_GJK, conv(a[i]), conv(b[i]), pool);
+  dist[i] = r.dist;
+  st3(point1 + 3 * size_t(i), r.p1);
+  st3(point2 + 3 * size_t(i), r.p2);
+  st3(normal + 3 * size_t(i), r.nrm);
+}
+#endif  // RKH_DEPTH_RECORDS
 #endif  // !RKH_PRISMATIC_FORMS
 
 // ---- host launchers ------------------------------------------------------------------------
@@ -2156,7 +2238,7 @@ static rkh_status launch_propagate_t(hipStream_t s, const rkh_scene& scene, cons
   });
 }
 
-#ifndef RKH_PLANAR_PRISMATIC_QS
+#ifndef RKH_FORMS_ONLY
 rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
                             uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,
                             uint32_t n_problems, double* d_lane_ws, KernelGate gate) {
@@ -2208,7 +2290,7 @@ rkh_status launch_state_derivative(hipStream_t s, const rkh_scene& scene, const 
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
-#endif  // !RKH_PLANAR_PRISMATIC_QS
+#endif  // !RKH_FORMS_ONLY
 
 // The number of waves W of a planar edge_check_kernel launch, by the number of edges (1 for launches of 4096 edges and
 // more, 4 below that, 8 below 512) and by what fits 64 KB of LDS (2 where 4 does not fit, 1 where neither does), and
@@ -2279,7 +2361,52 @@ static rkh_status launch_edge_walk(hipStream_t s, dim3 grid, const rkh_scene& sc
   return wide ? launch_edge_points_t<N, false, GW>(s, grid, n_env, ka) : launch_edge_points_t<N, false, 32>(s, grid, n_env, ka);
 }
 
-#ifdef RKH_PLANAR_PRISMATIC_QS
+#ifndef RKH_PRISMATIC_FORMS
+// the checks and the chain-size dispatch of every record launch (the depth forms' too)
+template <class F>
+static rkh_status launch_records(const rkh_scene& scene, bool meshes, F&& f) {
+  if (scene.host.planar || (scene.host.has_meshes && !meshes) || !scene.d_pair_ids.get() || scene.n_pairs > kMaxRecordPairs) {
+    set_error(meshes ? "record queries: 3D scenes only" : "record queries: 3D scenes without vertex-set shapes only");
+    return RKH_ERR_UNSUPPORTED;
+  }
+  RKH_TRY((with_n<1, 2, 3, 4, 6, 7, 12>(scene.host.n_dof, f)));
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+#endif
+
+#ifdef RKH_DEPTH_RECORDS
+// The launchers of the depth forms (this translation unit holds nothing else).  A scene without vertex-set shapes has
+// no pair for them to answer differently, but its records still gain their normals: the same kernels serve it.
+rkh_status launch_min_distance_records_depth(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out,
+                                             double* d_normal) {
+  if (B == 0) return RKH_OK;
+  return launch_records(scene, true, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((min_distance_depth_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, out, d_normal);
+  });
+}
+
+rkh_status launch_collision_records_depth(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                          RecordOut out, double* d_normal) {
+  if (B == 0) return RKH_OK;
+  return launch_records(scene, true, [&](auto c) {
+    constexpr int N = decltype(c)::value;
+    hipLaunchKernelGGL((collision_depth_kernel<N>), dim3(B), dim3(64), (SmemLayoutQs<N, 64>::bytes(scene.host.n_env)), s,
+                       scene.d_scene.get(), scene.d_pairs.get(), scene.d_pair_ids.get(), scene.n_pairs, d_x, B, cap, out, d_normal);
+  });
+}
+
+rkh_status launch_gjk_pair_depth(hipStream_t s, const rkh_shape* d_a, const rkh_shape* d_b, uint32_t n, const double* d_pool,
+                                 double* d_dist, double* d_point1, double* d_point2, double* d_normal) {
+  if (n == 0) return RKH_OK;
+  hipLaunchKernelGGL(gjk_pair_depth_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_a, d_b, n, d_pool, d_dist, d_point1, d_point2,
+                     d_normal);
+  RKH_HIP(hipGetLastError());
+  return RKH_OK;
+}
+#elif defined(RKH_PLANAR_PRISMATIC_QS)
 // The two launchers of the planar prismatic position-level forms (this translation unit holds nothing else).
 namespace planar_prismatic {
 template <int N, int W>
@@ -2329,7 +2456,7 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
   return RKH_OK;
 }
 }  // namespace planar_prismatic
-#else  // !RKH_PLANAR_PRISMATIC_QS
+#else  // the unit's own launchers
 rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev& qs, const EdgeIO& io, uint32_t grid_edges,
                              uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b, uint32_t n_problems) {
   const uint32_t eb = tab_b ? grid_b : 0u;
@@ -2413,17 +2540,6 @@ rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const doub
 }
 
 #ifndef RKH_PRISMATIC_FORMS  // the record kernels exist once and serve both joint kinds (see above)
-template <class F>
-static rkh_status launch_records(const rkh_scene& scene, bool meshes, F&& f) {
-  if (scene.host.planar || (scene.host.has_meshes && !meshes) || !scene.d_pair_ids.get() || scene.n_pairs > kMaxRecordPairs) {
-    set_error(meshes ? "record queries: 3D scenes only" : "record queries: 3D scenes without vertex-set shapes only");
-    return RKH_ERR_UNSUPPORTED;
-  }
-  RKH_TRY((with_n<1, 2, 3, 4, 6, 7, 12>(scene.host.n_dof, f)));
-  RKH_HIP(hipGetLastError());
-  return RKH_OK;
-}
-
 rkh_status launch_min_distance_records(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out) {
   if (B == 0) return RKH_OK;
   return launch_records(scene, false, [&](auto c) {
@@ -2466,7 +2582,7 @@ rkh_status launch_collision_records_meshes(hipStream_t s, const rkh_scene& scene
 }
 #endif
 
-#endif  // RKH_PLANAR_PRISMATIC_QS
+#endif  // RKH_DEPTH_RECORDS / RKH_PLANAR_PRISMATIC_QS / the unit's own launchers
 
 #ifdef RKH_PRISMATIC_FORMS
 }  // namespace prismatic

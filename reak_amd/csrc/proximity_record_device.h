@@ -16,6 +16,7 @@
 // (tests/cpp/prox_record_host.cpp).
 #pragma once
 #include "proximity_device.h"
+#include "epa_device.h"
 
 namespace rkh {
 
@@ -381,6 +382,41 @@ RKH_DI ProxRecordG pair_record(int routine, const ShapeG& s1, const ShapeG& s2, 
     }
   }
   return pair_record(routine, s1, s2);
+}
+
+// ---- the third mode: records with a penetration depth and a normal (the *_depth entries) -------------------------------
+// Vertex-set pairs (PR_GJK) go through gjk_depth_distance / gjk_depth_record of epa_device.h: where the cores cross, dist
+// is -(r1 + r2 + depth) - kGjkOverlap and nrm the contact normal; where they are apart, gjk_distance's / gjk_record's
+// values.  Every other pair is the closed form above, unchanged, with nrm = (point2 - point1) / dist componentwise
+// (zeros where dist is 0 or not finite); no more is claimed for those.
+struct ProxRecordN {
+  d3 p1, p2, nrm;
+  double dist;
+};
+
+RKH_DI double pair_distance_depth(int routine, const ShapeG& s1, const ShapeG& s2, const double* mesh_pool) {
+  if (routine == PR_GJK) return gjk_depth_distance(to_gjk(s1, mesh_pool), to_gjk(s2, mesh_pool));
+  return pair_distance<false>(routine, s1, s2);
+}
+
+RKH_DI ProxRecordN pair_record_depth(int routine, const ShapeG& s1, const ShapeG& s2, const double* mesh_pool) {
+  ProxRecordN r;
+  if (routine == PR_GJK) {
+    const GjkDepthRecord g = gjk_depth_record(to_gjk(s1, mesh_pool), to_gjk(s2, mesh_pool));
+    r.p1 = g.p1;
+    r.p2 = g.p2;
+    r.nrm = g.nrm;
+    r.dist = g.dist;
+    return r;
+  }
+  const ProxRecordG c = pair_record(routine, s1, s2);
+  r.p1 = c.p1;
+  r.p2 = c.p2;
+  r.dist = c.dist;
+  const bool usable = c.dist != 0.0 && fabs(c.dist) < INFINITY;  // (a NaN fails both)
+  const d3 diff = c.p2 - c.p1;
+  r.nrm = usable ? mk3(diff.x / c.dist, diff.y / c.dist, diff.z / c.dist) : mk3(0.0, 0.0, 0.0);
+  return r;
 }
 
 }  // namespace rkh

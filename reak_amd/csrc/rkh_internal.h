@@ -435,6 +435,14 @@ rkh_status launch_collision_records(hipStream_t s, const rkh_scene& scene, const
 rkh_status launch_min_distance_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
 rkh_status launch_collision_records_meshes(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
                                            RecordOut out);
+// Their depth forms (propagate_depth.hip): vertex-set pairs with crossing cores carry a penetration depth, and every record
+// a normal (d_normal: three doubles per slot of out); and the pair-by-pair form of rkh_diag_gjk_depth_records
+rkh_status launch_min_distance_records_depth(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out,
+                                             double* d_normal);
+rkh_status launch_collision_records_depth(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
+                                          RecordOut out, double* d_normal);
+rkh_status launch_gjk_pair_depth(hipStream_t s, const rkh_shape* d_a, const rkh_shape* d_b, uint32_t n, const double* d_pool,
+                                 double* d_dist, double* d_point1, double* d_point2, double* d_normal);
 // Their planar twins (proximity_records_planar.hip; planar scenes, revolute and prismatic joints): points of two doubles
 // ([B][2], [B][cap][2]), finder rank = pair index.
 rkh_status launch_min_distance_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);

@@ -759,6 +759,32 @@ rkh_status rkh_diag_gjk_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shap
   return RKH_OK;
 }
 
+rkh_status rkh_diag_gjk_depth_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n, const double* mesh_vertices,
+                                      uint32_t n_mesh_vertices, double* dist, double* point1, double* point2, double* normal) {
+  if (!ctx || !a || !b || !dist || !point1 || !point2 || !normal) return RKH_ERR_BAD_ARG;
+  if (n == 0) return RKH_OK;
+  RKH_HIP(hipSetDevice(ctx->device));
+  DeviceBuffer<rkh_shape> da, db;
+  DeviceBuffer<double> dv, dd, dp1, dp2, dn3;
+  RKH_TRY(da.alloc(n));
+  RKH_TRY(db.alloc(n));
+  RKH_TRY(dd.alloc(n));
+  RKH_TRY(dp1.alloc(size_t(n) * 3));
+  RKH_TRY(dp2.alloc(size_t(n) * 3));
+  RKH_TRY(dn3.alloc(size_t(n) * 3));
+  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
+  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
+  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
+  RKH_TRY(launch_gjk_pair_depth(ctx->stream, da.get(), db.get(), n, dv.get(), dd.get(), dp1.get(), dp2.get(), dn3.get()));
+  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipMemcpyAsync(normal, dn3.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RKH_HIP(hipStreamSynchronize(ctx->stream));
+  return RKH_OK;
+}
+
 rkh_status rkh_scene_destroy(rkh_scene* scene) {
   delete scene;  // (its buffers free themselves; hipFree waits for the device)
   return RKH_OK;
@@ -815,15 +841,17 @@ rkh_status records_2d_supported(const rkh_scene* scene, const char* entry) {
             "rkh_collision_records");
   return RKH_ERR_UNSUPPORTED;
 }
-// rkh_min_distance_records and rkh_min_distance_records_meshes after their checks: the same transfers around the launch
-using MinRecordsLaunch = rkh_status (*)(hipStream_t, const rkh_scene&, const double*, uint32_t, RecordOut);
+// rkh_min_distance_records, rkh_min_distance_records_meshes and rkh_min_distance_records_depth after their checks: the
+// same transfers around the launch(stream, scene, d_x, B, out, d_normal); normal: the depth entry's, else nullptr
+template <class Launch>
 rkh_status min_distance_records_3d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1, double* point2,
-                                   uint32_t* shape1, uint32_t* shape2, MinRecordsLaunch launch) {
+                                   double* normal, uint32_t* shape1, uint32_t* shape2, Launch launch) {
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
   DeviceBuffer<uint32_t> ds1, ds2;
+  if (normal) RKH_TRY(dn3.alloc(size_t(B) * 3));
   RKH_TRY(dx.alloc(size_t(B) * 2 * n));
   RKH_TRY(dd.alloc(size_t(B)));
   RKH_TRY(dp1.alloc(size_t(B) * 3));
@@ -837,7 +865,8 @@ rkh_status min_distance_records_3d(rkh_scene* scene, const double* x, uint32_t B
   out.point2 = dp2.get();
   out.shape1 = ds1.get();
   out.shape2 = ds2.get();
-  RKH_TRY(launch(s, *scene, dx.get(), B, out));
+  RKH_TRY(launch(s, *scene, dx.get(), B, out, dn3.get()));
+  if (normal) RKH_HIP(hipMemcpyAsync(normal, dn3.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
   RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
@@ -846,16 +875,18 @@ rkh_status min_distance_records_3d(rkh_scene* scene, const double* x, uint32_t B
   RKH_HIP(hipStreamSynchronize(s));
   return RKH_OK;
 }
-// and the same for rkh_collision_records and rkh_collision_records_meshes
-using CollisionRecordsLaunch = rkh_status (*)(hipStream_t, const rkh_scene&, const double*, uint32_t, uint32_t, RecordOut);
+// and the same for rkh_collision_records, rkh_collision_records_meshes and rkh_collision_records_depth:
+// launch(stream, scene, d_x, B, cap, out, d_normal)
+template <class Launch>
 rkh_status collision_records_3d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found, double* dist,
-                                double* point1, double* point2, uint32_t* shape1, uint32_t* shape2, CollisionRecordsLaunch launch) {
+                                double* point1, double* point2, double* normal, uint32_t* shape1, uint32_t* shape2, Launch launch) {
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   const size_t slots = size_t(B) * cap;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
+  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
   DeviceBuffer<uint32_t> dn, ds1, ds2;
+  if (normal) RKH_TRY(dn3.alloc(std::max<size_t>(1, slots * 3)));
   RKH_TRY(dx.alloc(size_t(B) * 2 * n));
   RKH_TRY(dn.alloc(size_t(B)));
   RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
@@ -871,9 +902,10 @@ rkh_status collision_records_3d(rkh_scene* scene, const double* x, uint32_t B, u
   out.point2 = dp2.get();
   out.shape1 = ds1.get();
   out.shape2 = ds2.get();
-  RKH_TRY(launch(s, *scene, dx.get(), B, cap, out));
+  RKH_TRY(launch(s, *scene, dx.get(), B, cap, out, dn3.get()));
   RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
   if (slots) {
+    if (normal) RKH_HIP(hipMemcpyAsync(normal, dn3.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
     RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
@@ -929,14 +961,27 @@ rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t 
                                     double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_min_distance_records"));
-  return min_distance_records_3d(scene, x, B, dist, point1, point2, shape1, shape2, launch_min_distance_records);
+  return min_distance_records_3d(scene, x, B, dist, point1, point2, nullptr, shape1, shape2,
+                                 [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, RecordOut out, double*) {
+                                   return launch_min_distance_records(s, sc, dx, b, out);
+                                 });
 }
 
 rkh_status rkh_min_distance_records_meshes(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
                                            double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_min_distance_records_meshes"));
-  return min_distance_records_3d(scene, x, B, dist, point1, point2, shape1, shape2, launch_min_distance_records_meshes);
+  return min_distance_records_3d(scene, x, B, dist, point1, point2, nullptr, shape1, shape2,
+                                 [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, RecordOut out, double*) {
+                                   return launch_min_distance_records_meshes(s, sc, dx, b, out);
+                                 });
+}
+
+rkh_status rkh_min_distance_records_depth(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
+                                          double* point2, double* normal, uint32_t* shape1, uint32_t* shape2) {
+  if (!scene || !x || !dist || !point1 || !point2 || !normal || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_meshes_supported(scene, "rkh_min_distance_records_depth"));
+  return min_distance_records_3d(scene, x, B, dist, point1, point2, normal, shape1, shape2, launch_min_distance_records_depth);
 }
 
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms) {
@@ -945,12 +990,14 @@ rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_
   if (records && !planar) RKH_TRY(records_meshes_supported(scene, "rkh_diag_distance_query_ms"));
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
+  const bool depth = records == 2 && !planar;  // the depth form of the 3D record kernel
+  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
   DeviceBuffer<uint32_t> ds1, ds2;
   RKH_TRY(dx.alloc(size_t(B) * 2 * n));
   RKH_TRY(dd.alloc(size_t(B)));
   RKH_TRY(dp1.alloc(size_t(B) * 3));
   RKH_TRY(dp2.alloc(size_t(B) * 3));
+  if (depth) RKH_TRY(dn3.alloc(size_t(B) * 3));
   RKH_TRY(ds1.alloc(size_t(B)));
   RKH_TRY(ds2.alloc(size_t(B)));
   RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
@@ -968,6 +1015,7 @@ rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_
     hipError_t err = hipEventRecord(e0, s);
     st = !records ? launch_min_distance(s, *scene, dx.get(), B, dd.get())
          : planar ? launch_min_distance_records_2d(s, *scene, dx.get(), B, out)
+         : depth  ? launch_min_distance_records_depth(s, *scene, dx.get(), B, out, dn3.get())
                   : launch_min_distance_records_meshes(s, *scene, dx.get(), B, out);  // (no meshes: the plain kernel)
     if (err == hipSuccess) err = hipEventRecord(e1, s);
     if (err == hipSuccess) err = hipEventSynchronize(e1);
@@ -986,14 +1034,31 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
                                  double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_collision_records"));
-  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, shape1, shape2, launch_collision_records);
+  return collision_records_3d(
+      scene, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
+      [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, uint32_t c, RecordOut out, double*) {
+        return launch_collision_records(s, sc, dx, b, c, out);
+      });
 }
 
 rkh_status rkh_collision_records_meshes(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
                                         double* dist, double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_collision_records_meshes"));
-  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, shape1, shape2, launch_collision_records_meshes);
+  return collision_records_3d(
+      scene, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
+      [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, uint32_t c, RecordOut out, double*) {
+        return launch_collision_records_meshes(s, sc, dx, b, c, out);
+      });
+}
+
+rkh_status rkh_collision_records_depth(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
+                                       double* dist, double* point1, double* point2, double* normal, uint32_t* shape1,
+                                       uint32_t* shape2) {
+  if (!scene || !x || !n_found || !dist || !point1 || !point2 || !normal || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
+  RKH_TRY(records_meshes_supported(scene, "rkh_collision_records_depth"));
+  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, normal, shape1, shape2,
+                              launch_collision_records_depth);
 }
 
 rkh_status rkh_min_distance_records_2d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,

@@ -80,8 +80,8 @@ EXPORTS = [
     "rkh_nn_queryk", "rkh_nn_query1_async", "rkh_nn_queryk_async", "rkh_nn_fill_uniform", "rkh_nn_kernel_name",
     "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
-    "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_diag_gjk_records", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
-    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_meshes", "rkh_collision_records_meshes", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
+    "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_diag_gjk_records", "rkh_diag_gjk_depth_records", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
+    "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_meshes", "rkh_collision_records_meshes", "rkh_min_distance_records_depth", "rkh_collision_records_depth", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
     "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
@@ -141,6 +141,7 @@ def load():
                                                  C.c_int, dp, u32, C.POINTER(vp)]
     lib.rkh_diag_gjk_distance.argtypes = [vp, C.POINTER(T.Shape), C.POINTER(T.Shape), u32, dp, u32, dp]
     lib.rkh_diag_gjk_records.argtypes = [vp, C.POINTER(T.Shape), C.POINTER(T.Shape), u32, dp, u32, dp, dp, dp]
+    lib.rkh_diag_gjk_depth_records.argtypes = [vp, C.POINTER(T.Shape), C.POINTER(T.Shape), u32, dp, u32, dp, dp, dp, dp]
     lib.rkh_scene_destroy.argtypes = [vp]
     lib.rkh_scene_num_dof.argtypes = [vp]
     lib.rkh_scene_num_pairs.argtypes = [vp]
@@ -150,6 +151,8 @@ def load():
     lib.rkh_collision_records.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
     lib.rkh_min_distance_records_meshes.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
     lib.rkh_collision_records_meshes.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
+    lib.rkh_min_distance_records_depth.argtypes = [vp, dp, u32, dp, dp, dp, dp, u32p, u32p]
+    lib.rkh_collision_records_depth.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, dp, u32p, u32p]
     lib.rkh_min_distance_records_2d.argtypes = [vp, dp, u32, dp, dp, dp, u32p, u32p]
     lib.rkh_collision_records_2d.argtypes = [vp, dp, u32, u32, u32p, dp, dp, dp, u32p, u32p]
     lib.rkh_diag_distance_query_ms.argtypes = [vp, dp, u32, C.c_int, u32, C.POINTER(C.c_float)]
@@ -340,6 +343,20 @@ def gjk_records(ctx, a, b, mesh_vertices=None):
     return {"dist": d, "point1": p1, "point2": p2}
 
 
+def gjk_depth_records(ctx, a, b, mesh_vertices=None):
+    """The same pairs with a penetration depth and a contact normal (rkh_diag_gjk_depth_records): where the cores are
+    apart, gjk_records' values and normal [n][3] = the unit vector from a[i]'s closest point towards b[i]'s; where they
+    cross, dist = -(r1 + r2 + depth) - 1e-9, the normal of the least separating translation (from a[i] towards b[i]),
+    point1 on a[i] and point2 = point1 - (depth + r1 + r2) normal on b[i]."""
+    n = len(a)
+    aa, bb = T.as_array(list(a), T.Shape), T.as_array(list(b), T.Shape)
+    verts = np.zeros((0, 3)) if mesh_vertices is None else np.ascontiguousarray(mesh_vertices, dtype=np.float64).reshape(-1, 3)
+    d, p1, p2, nr = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    _check(ctx.lib.rkh_diag_gjk_depth_records(ctx.h, aa, bb, n, T.dptr(verts) if len(verts) else None, len(verts), T.dptr(d),
+                                              T.dptr(p1), T.dptr(p2), T.dptr(nr)))
+    return {"dist": d, "point1": p1, "point2": p2, "normal": nr}
+
+
 def nn_mirror_query(ctx, pts, q, coord_bound):
     """1-NN of every query through the planner-regime sweep (half-precision mirror + exact resolution,
     rkh_diag_nn_mirror_query): (index, distance) arrays."""
@@ -432,11 +449,11 @@ class Scene:
         return {"dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
 
     def distance_query_ms(self, x, records, runs):
-        """Kernel times [runs] in ms of the distance query (records=False) or the record query (True) on the states x,
-        events around each launch (rkh_diag_distance_query_ms)."""
+        """Kernel times [runs] in ms of the distance query (records=False), the record query (True) or the depth record
+        query (records="depth"; 3D scenes) on the states x, events around each launch (rkh_diag_distance_query_ms)."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
         ms = np.zeros(int(runs), dtype=np.float32)
-        _check(self.lib.rkh_diag_distance_query_ms(self.h, T.dptr(x), x.shape[0], 1 if records else 0, int(runs),
+        _check(self.lib.rkh_diag_distance_query_ms(self.h, T.dptr(x), x.shape[0], 2 if records == "depth" else (1 if records else 0), int(runs),
                                                    ms.ctypes.data_as(C.POINTER(C.c_float))))
         return ms
 
@@ -475,6 +492,32 @@ class Scene:
         _check(self.lib.rkh_collision_records_meshes(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1),
                                                      T.dptr(p2), T.u32ptr(s1), T.u32ptr(s2)))
         return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "shape1": s1, "shape2": s2}
+
+    def min_distance_records_depth(self, x):
+        """min_distance_records_meshes with a penetration depth and a contact normal (rkh_min_distance_records_depth): the
+        same keys and "normal" [B][3].  A pair with a mesh in it whose cores cross reports dist = -(r1 + r2 + depth) - 1e-9,
+        the unit normal of the least separating translation (from shape1 towards shape2) and the two contact points; the
+        minimum is taken over these distances, so among crossing mesh pairs the deepest wins.  Every other record is the
+        _meshes entry's, with normal = the unit vector of the closest pair (closed forms: (point2 - point1) / dist)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B = x.shape[0]
+        d, p1, p2, nr = np.zeros(B), np.zeros((B, 3)), np.zeros((B, 3)), np.zeros((B, 3))
+        s1, s2 = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        _check(self.lib.rkh_min_distance_records_depth(self.h, T.dptr(x), B, T.dptr(d), T.dptr(p1), T.dptr(p2), T.dptr(nr),
+                                                       T.u32ptr(s1), T.u32ptr(s2)))
+        return {"dist": d, "point1": p1, "point2": p2, "normal": nr, "shape1": s1, "shape2": s2}
+
+    def collision_records_depth(self, x, cap):
+        """collision_records_meshes with depths and normals (rkh_collision_records_depth): the same finders in the same
+        order with the same n_found, and "normal" [B][cap][3] (zeros in unused slots)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.D)
+        B, cap = x.shape[0], int(cap)
+        n = np.zeros(B, dtype=np.uint32)
+        d, p1, p2, nr = np.zeros((B, cap)), np.zeros((B, cap, 3)), np.zeros((B, cap, 3)), np.zeros((B, cap, 3))
+        s1, s2 = np.zeros((B, cap), dtype=np.uint32), np.zeros((B, cap), dtype=np.uint32)
+        _check(self.lib.rkh_collision_records_depth(self.h, T.dptr(x), B, cap, T.u32ptr(n), T.dptr(d), T.dptr(p1),
+                                                    T.dptr(p2), T.dptr(nr), T.u32ptr(s1), T.u32ptr(s2)))
+        return {"n_found": n, "dist": d, "point1": p1, "point2": p2, "normal": nr, "shape1": s1, "shape2": s2}
 
     def min_distance_records_2d(self, x):
         """proxy_query_pair_2D::findMinimumDistance()->getLastResult() per state of a planar scene
