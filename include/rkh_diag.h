@@ -95,6 +95,17 @@ rkh_status rkh_diag_steer_clearance_counts(rkh_scene* scene, uint64_t counts[2])
  * the environment at rkh_planner_create* switches the reuse off. */
 rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]);
 
+/* Goal probes of one problem of a batch RRT planner (waits for the planner's stream).  A vertex whose joint angles are
+ * farther from the goal's than a steered edge can travel, plus 5 % of its distance to the goal, gets its goal-probe
+ * result (+inf) when it is committed; only the other vertices' probes are steered (reak_amd/csrc/probe_reach.h).
+ * counts[0] = probes settled at commit, counts[1] = probes a steer launch ran, counts[2] = probed_n (vertices
+ * [1, probed_n) have their result), counts[3] = open probes waiting for a launch, counts[4] = the first vertex whose
+ * probe is open (the vertex count if none is).  reach_q (may be null) = the travel bound in joint-angle norm, +inf where
+ * the scene or the space gives no certificate or RKH_PROBE_REACH=0 was set at rkh_planner_create*.  Only rounds of at least
+ * RKH_PROBE_REACH_MIN_EDGES edges (default: half the resident steer waves x 32 edges, the round carry's threshold)
+ * settle probes. */
+rkh_status rkh_diag_planner_probe_counts(rkh_planner* p, uint32_t problem, uint64_t counts[5], double* reach_q);
+
 /* Kernel time of the distance query on B states: `runs` launches of rkh_min_distance's kernel (records == 0) or of
  * rkh_min_distance_records' (records != 0; on a planar scene rkh_min_distance_records_2d's, on a scene with mesh shapes
  * rkh_min_distance_records_meshes'; records == 2 on a 3D scene: rkh_min_distance_records_depth's) over the same device copy of x, each between two events on the context's stream; ms[runs] = the elapsed times.  No copies are timed

@@ -32,11 +32,13 @@ enum SharedRange : int {
   SR_SAMPLE_TAB0 = SR_UPLOAD_END, SR_SAMPLE_TAB1, SR_GOAL_TAB, SR_LANE_WS, SR_STEP_LIST0, SR_STEP_LIST1,
   SR_COUNT
 };
-// The 25 buffers of one problem.  PR_STASH_*: what a round's discarded candidates leave for the next one (round_carry.h).
+// The 26 buffers of one problem.  PR_STASH_*: what a round's discarded candidates leave for the next one (round_carry.h).
+// PR_PROBE_LIST: the vertices whose goal probe is open (round_plan.h, the granule rule: fewer than the granule wait, a
+// round appends at most b_max).
 enum ProblemRange : int {
   PR_MT, PR_TREE, PR_PARENT, PR_NODE_SAMPLE, PR_GOAL_DIST, PR_SAMPLES, PR_NN_SEQ, PR_ACCEPT_LOG, PR_NN_IDX, PR_NN_DIST,
-  PR_X_OUT, PR_STEPS, PR_ACCEPT, PR_PROBE_X, PR_PROBE_STEPS, PR_GOAL, PR_PART_DIST, PR_PART_IDX, PR_ROUND_N, PR_MIRROR,
-  PR_CAND, PR_STASH_X, PR_STASH_NN, PR_STASH_STEPS, PR_STASH_ACCEPT,
+  PR_X_OUT, PR_STEPS, PR_ACCEPT, PR_PROBE_X, PR_PROBE_STEPS, PR_PROBE_LIST, PR_GOAL, PR_PART_DIST, PR_PART_IDX, PR_ROUND_N,
+  PR_MIRROR, PR_CAND, PR_STASH_X, PR_STASH_NN, PR_STASH_STEPS, PR_STASH_ACCEPT,
   PR_COUNT
 };
 
@@ -123,6 +125,7 @@ inline ArenaLayout planner_arena_layout(const ArenaShape& s) {
     r[PR_ACCEPT] = take(b);
     r[PR_PROBE_X] = take((b + s.probe_granule) * D * sizeof(double));
     r[PR_PROBE_STEPS] = take((b + s.probe_granule) * sizeof(uint32_t));
+    r[PR_PROBE_LIST] = take((b + s.probe_granule) * sizeof(uint32_t));
     r[PR_GOAL] = take(D * sizeof(double));
     r[PR_PART_DIST] = take(size_t(s.part_blocks) * b * sizeof(double));
     // one more row than the partials need: NnArgs::seed (sampled minima of the matrix-core sweep, "none" = all ones)

@@ -9,8 +9,9 @@
 // snapshot:
 //   1. nn1 sweep            (nn_sweep.hip)    nearest snapshot vertex of every sample
 //   2. propagate            (propagate.hip)   steer + collision-check all B candidate edges, accept test;
-//                                             the same launch runs the goal probes (edge_added's
-//                                             query.get_distance_to_goal) of the previous round's new vertices
+//                                             the same launch runs the open goal probes (edge_added's
+//                                             query.get_distance_to_goal) of the previous round's new vertices: those
+//                                             the commit could not settle from a travel bound (probe_reach.h)
 //   3. fixup  (this file)   candidate b is INVALID iff a vertex that an earlier accepted candidate of the
 //                           same round would add is strictly closer to sample b than its snapshot NN
 //                           (strict '<' = first-minimum-wins, new vertices have higher indices)
@@ -32,6 +33,7 @@
 #include "arena_layout.h"
 #include "nn_device.h"
 #include "nn_mirror.h"
+#include "probe_reach.h"
 #include "rkh_internal.h"
 #include "round_carry.h"
 #include "round_plan.h"
@@ -43,8 +45,8 @@ struct PlannerState {  // device-resident, one per problem
   uint32_t s0;           // next sample (== generate_rrt iterations so far)
   uint32_t B;            // candidates of the current round
   uint32_t F;            // first invalid candidate of the current round
-  uint32_t n_before;     // first vertex whose goal probe is still pending
-  uint32_t n_new;        // number of vertices whose goal probe is pending (they ride in the next propagate launch)
+  uint32_t list_n;       // open goal probes: entries of ProblemDev::probe_list (vertices probe_certified did not settle)
+  uint32_t n_new;        // the first n_new entries of the list ride in the next propagate launch (probe_ride_count)
   uint32_t probed_n;     // vertices [1, probed_n) have their goal probe result in goal_dist
   uint32_t done;         // 1: keep_going() == false (vertex budget reached); 2: sample stream exhausted
   uint32_t max_total;    // max_vertices + 1 (root is not counted by m_iteration_count)
@@ -55,6 +57,7 @@ struct PlannerState {  // device-resident, one per problem
   uint32_t carried;      // candidates the last commit left in the stash (round_carry.h); 0 wherever the stash is not valid
   unsigned long long rounds, edges_speculated, fixup_cut;
   unsigned long long cand_discarded, cand_reused;  // candidates [cut, B) of all rounds; those a later round did not steer again
+  unsigned long long probes_certified, probes_run;  // goal probes settled at commit (probe_reach.h); those a steer launch ran
 };
 
 struct ProblemDev {  // device pointers of one problem
@@ -78,6 +81,23 @@ struct ProblemDev {  // device pointers of one problem
   uint32_t* round_n;  // profiling: vertex count at the start of each round (may be null)
   uint4* mirror;      // half-precision mirror of the tree rows (nn_mirror.h), or null
   uint32_t* dx_max_bits;  // its running maximum of |x - x_h|
+  // the goal probes: the query's goal state, the results (indexed by vertex - 1), and the list of the open ones in vertex
+  // order -- the probe EdgeIO's src_idx ([b_max + kProbeGranule], round_plan.h: the granule rule)
+  const double* goal;
+  double* goal_dist;
+  uint32_t* probe_list;
+};
+
+// what commit_kernel settles goal probes by (probe_reach.h); reach_q = +inf: no certificate, every vertex goes to the list
+// Only rounds of at least min_edges edges (*round_edges, the count round_begin_kernel summed) settle probes: a smaller
+// round runs under one steer wave per SIMD, where its length is that of its longest edge and the probes ride in slots
+// that are idle anyway -- the scope of the round carry (round_carry.h), and for its reason: below it every mapping still
+// steers the same edges in the same segments, so executed steps and tested wave-steps compare across the mappings.
+struct ProbeReachDev {
+  double reach_q;
+  const uint32_t* round_edges;
+  uint32_t min_edges;
+  double v_lower[kReachMaxDof], v_upper[kReachMaxDof];  // the velocity bounds of the state box, per joint
 };
 
 // round_begin_kernel's arguments (round_begin_args builds them from the planner)
@@ -379,15 +399,17 @@ __global__ __launch_bounds__(256) void fixup_tiled_kernel(const ProblemDev* __re
 
 // One 256-thread block per problem: commit candidates [0, F) in order (prefix scan of the accept flags),
 // honouring the vertex budget of keep_going() (motion_planner_base.hpp:355-374).
-// probe_granule: goal probes ride in the next steer launch in whole groups of this many (32 = one steer wave of the
-// two-lanes mapping: a (problem, probes) segment of the grid then has no half-empty last wave; what is left over waits
-// for the vertices of the next round, the last ones for flush_probes; 1 = every pending probe rides along).
+// The goal probe of every vertex it commits is settled here where probe_certified (probe_reach.h) holds for the row being
+// written -- goal_dist = +inf at once -- and the vertex otherwise joins the problem's list of open probes, in vertex order
+// (round_plan.h, the granule rule: the entries the round's launch ran leave the list, what it left behind moves to the
+// front).  probe_granule: 32 = one steer wave of the two-lanes mapping when the wave fit is on, else 1.
 // stash: the candidates this round throws away, [cut, B), leave their results for the next round (round_carry.h).
 __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restrict__ probs, int D, int DP,
-                                                      uint32_t probe_granule, bool stash) {
+                                                      uint32_t probe_granule, bool stash, const ProbeReachDev reach) {
   __shared__ uint32_t scan[256];
-  __shared__ uint32_t carry;
+  __shared__ uint32_t carry, open_carry;
   __shared__ uint32_t cut;  // number of candidates actually consumed
+  __shared__ uint32_t opened;  // committed vertices appended to the list
   const ProblemDev pr = probs[blockIdx.x];
   PlannerState* st = pr.st;
   const uint32_t F = st->F;
@@ -396,15 +418,29 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
   const uint32_t budget = st->max_total - n0;  // vertices that may still be added
   const uint32_t B = st->B;
   const bool was_done = st->done != 0u;  // (read by every thread before thread 0 may change it below)
+  // the round's launch ran the first n_new entries of the list; the `waited` ones behind them move to the front
+  const uint32_t ran = st->n_new;
+  const uint32_t waited = st->list_n - ran;
+  const double reach_q = *reach.round_edges >= reach.min_edges ? reach.reach_q : INFINITY;
   if (threadIdx.x == 0) {
-    carry = 0;
+    carry = open_carry = 0;
     cut = F;
+    opened = 0;
+  }
+  for (uint32_t base = 0; base < waited; base += 256) {  // (uniform; dest < src: read, barrier, write)
+    const uint32_t k = base + threadIdx.x;
+    const uint32_t v = k < waited ? pr.probe_list[ran + k] : 0u;
+    __syncthreads();
+    if (k < waited) pr.probe_list[k] = v;
   }
   __syncthreads();
   for (uint32_t base = 0; base < F; base += 256) {
     const uint32_t b = base + threadIdx.x;
     const uint32_t a = (b < F && pr.accept[b]) ? 1u : 0u;
-    scan[threadIdx.x] = a;
+    // an accepted candidate whose goal probe stays open; both counts are scanned in one word (at most 256 each per pass)
+    const uint32_t o =
+        (a && !probe_certified(pr.x_out + uint64_t(b) * D, pr.goal, D, reach_q, reach.v_lower, reach.v_upper)) ? 1u : 0u;
+    scan[threadIdx.x] = a | (o << 16);
     __syncthreads();
     for (uint32_t off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan
       uint32_t v = 0;
@@ -413,7 +449,8 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
       scan[threadIdx.x] += v;
       __syncthreads();
     }
-    const uint32_t incl = carry + scan[threadIdx.x];  // accepted among [0, b]
+    const uint32_t incl = carry + (scan[threadIdx.x] & 0xFFFFu);       // accepted among [0, b]
+    const uint32_t open_incl = open_carry + (scan[threadIdx.x] >> 16);  // ... of them, with an open probe
     if (b < F) {
       // the candidate whose vertex exhausts the budget is the last one the sequential loop runs
       if (a && incl == budget) atomicMin(&cut, b + 1);
@@ -427,23 +464,32 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
           if (pr.mirror) mirror_store_row(pr.mirror, row, pr.x_out + uint64_t(b) * D, D, pr.dx_max_bits);
           pr.parent[row] = pr.nn_idx[b];
           pr.node_sample[row] = s0 + b;
+          if (o) {
+            pr.probe_list[waited + open_incl - 1] = row;
+            atomicMax(&opened, open_incl);
+          } else {
+            pr.goal_dist[row - 1] = INFINITY;  // what goal_probe_steerable would leave
+          }
         }
       }
     }
     __syncthreads();
-    if (threadIdx.x == 255) carry = incl;
+    if (threadIdx.x == 255) {
+      carry = incl;
+      open_carry = open_incl;
+    }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
     const uint32_t added = carry < budget ? carry : budget;
-    st->n = n0 + added;
-    // the propagate launch of this round also ran the first n_new of the pending goal probes: [n_before, n_before+n_new)
-    const uint32_t first_pending = st->n_before + st->n_new;
-    st->probed_n = first_pending;
-    st->n_before = first_pending;
-    // the next launch takes the pending ones (this round's vertices included) in whole granules
-    const uint32_t pending = n0 + added - first_pending;
-    st->n_new = pending - pending % probe_granule;
+    const uint32_t n = n0 + added;
+    st->n = n;
+    const uint32_t list_n = waited + opened;
+    st->list_n = list_n;
+    st->n_new = probe_ride_count(list_n, waited, probe_granule);
+    st->probed_n = probe_probed_n(pr.probe_list, list_n, n);
+    st->probes_run += ran;
+    st->probes_certified += added - opened;
     st->s0 = s0 + cut;
     st->fixup_cut += (B - F);
     st->cand_discarded += (B - cut);
@@ -504,7 +550,6 @@ __global__ __launch_bounds__(256) void carry_restore_kernel(const ProblemDev* __
   if (lane == 0 && n_reused) atomicAdd(&st->cand_reused, (unsigned long long)n_reused);
 }
 
-// after a probe-only flush launch: nothing is pending any more
 // The sample stream is generated ON THE DEVICE: hyperbox_topology::random_point (hyperbox_topology.hpp:97-103) draws D
 // times uniform_01<mt19937&, double> = eng() * 2^-32 per sample (Boost.Random on a 32-bit engine: one draw per
 // coordinate), so draw number k * D + d is coordinate d of sample k whatever happens in the planner.  One block per
@@ -592,14 +637,16 @@ __global__ __launch_bounds__(256) void gather_goal_dist_kernel(const GoalSeg* __
 __global__ void probes_take_all_kernel(const ProblemDev* __restrict__ probs) {
   if (threadIdx.x != 0) return;
   PlannerState* st = probs[blockIdx.x].st;
-  st->n_new = st->n - st->n_before;
+  st->n_new = st->list_n;
 }
 
+// after a probe-only flush launch: the list is empty, every vertex has its result
 __global__ void probes_flushed_kernel(const ProblemDev* __restrict__ probs) {
   if (threadIdx.x != 0) return;
   PlannerState* st = probs[blockIdx.x].st;
-  st->probed_n = st->n_before + st->n_new;
-  st->n_before = st->n;
+  st->probes_run += st->n_new;
+  st->probed_n = st->n;
+  st->list_n = 0;
   st->n_new = 0;
 }
 
@@ -669,6 +716,7 @@ struct Problem {  // host view of one planning problem
   uint32_t *d_nn_idx = nullptr, *d_steps = nullptr, *d_probe_steps = nullptr;  // [b_max (+ kProbeGranule)] a round's candidates and probes
   double *d_nn_dist = nullptr, *d_x_out = nullptr, *d_probe_x = nullptr;
   uint8_t* d_accept = nullptr;
+  uint32_t* d_probe_list = nullptr;  // [b_max + kProbeGranule] vertices whose goal probe is open, in vertex order
   double* d_stash_x = nullptr;  // [b_max] the last round's discarded candidates (round_carry.h); null: no carry
   uint32_t *d_stash_nn = nullptr, *d_stash_steps = nullptr;
   uint8_t* d_stash_accept = nullptr;
@@ -772,6 +820,10 @@ struct rkh_planner {
   // the wave fit takes the expected reuse off a carrying round's work: measured 0.5 % slower than counting the candidates
   // (DESIGN 5), so off unless RKH_STEER_CARRY_FIT=1 asks for it
   bool carry_fit = false;
+  // Goal probes that cannot reach the goal are settled at commit (probe_reach.h): the travel bound of this scene and
+  // space, computed once at create.  reach_q = +inf -- the quasi-static space, every scene outside probe_travel's
+  // conditions, RKH_PROBE_REACH=0 -- certifies nothing: every vertex's probe is steered.
+  ProbeReachDev reach;
   uint64_t max_n_ub = 1;  // largest vertex-count bound over the problems (sizes the mirror sweep's row slices)
   uint64_t sum_batch_ub = 0, prev_sum_batch_ub = 0;  // host-side bounds on the candidates of this / the previous round, all problems
   // segment tables of the sample generator: [0] what the enqueued rounds need, [1] the next call's share, generated
@@ -1040,8 +1092,10 @@ rkh_status enqueue_round(rkh_planner* p) {
   // 3. fix-up against the vertices this round itself would add
   RKH_TRY(launch_fixup(p, batch_ub));
   // 4. commit the valid prefix
+  ProbeReachDev reach = p->reach;
+  reach.round_edges = p->d_sel + p->round_parity;  // this round's edges; the next round's begin clears the other word
   hipLaunchKernelGGL(commit_kernel, dim3(p->P), dim3(256), 0, s, p->d_probs, p->D, p->DP, fit ? kProbeGranule : 1u,
-                     p->carry);
+                     p->carry, reach);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
@@ -1069,6 +1123,9 @@ ProblemDev problem_dev(const rkh_planner* p, uint32_t i) {
   pd.round_n = q.d_round_n;
   pd.mirror = static_cast<uint4*>(q.d_mirror);
   pd.dx_max_bits = q.dx_max_bits;
+  pd.goal = q.d_goal;
+  pd.goal_dist = q.d_goal_dist;
+  pd.probe_list = q.d_probe_list;
   return pd;
 }
 
@@ -1122,7 +1179,7 @@ EdgeIO probe_io(const rkh_planner* p, uint32_t i) {
   PlannerState* st = p->d_states + i;
   EdgeIO gp;
   gp.src = q.d_tree;
-  gp.d_src_first = &st->n_before;
+  gp.src_idx = q.d_probe_list;  // edge e = the e-th open probe; edge_source_row / pair_edge_rows of every steer form
   gp.src_stride = p->DP;
   gp.tgt = q.d_goal;
   gp.tgt_stride = 0;
@@ -1309,6 +1366,54 @@ void tune_planner(rkh_planner* p, const rkh_rrt_params* prms) {
   if (const char* e = getenv("RKH_ARENA_POISON")) p->arena_poison = atoi(e) != 0;
 }
 
+// 3b. The travel bound of a steered edge of this scene and space (probe_reach.h), from the scene's host chain and the
+// space's device form; +inf wherever probe_travel gives no certificate.
+static_assert(kMaxDof <= kReachMaxDof, "probe_reach.h holds a chain of kMaxDof joints");
+void setup_probe_reach(rkh_planner* p) {
+  ProbeReachDev& r = p->reach;
+  r.reach_q = INFINITY;
+  r.round_edges = nullptr;  // (set per round, enqueue_round)
+  // rounds that fill the chip: the default of carry_min_edges (RKH_PROBE_REACH_MIN_EDGES overrides it)
+  r.min_edges = p->wave_slots / 2 * pair_kernel_edges_per_wave();
+  if (const char* e = getenv("RKH_PROBE_REACH_MIN_EDGES")) r.min_edges = uint32_t(std::max(0, atoi(e)));
+  for (int j = 0; j < kReachMaxDof; ++j) r.v_lower[j] = r.v_upper[j] = 0.0;
+  if (p->quasi_static) return;
+  if (const char* e = getenv("RKH_PROBE_REACH"))
+    if (atoi(e) == 0) return;
+  const SceneDev& S = p->scene->host;
+  ReachChain c;
+  c.n_dof = S.n_dof;
+  c.serial = S.n_branches == 0 && S.planar == 0;
+  c.all_revolute = S.prismatic_mask == 0u;
+  c.beam = S.beam_on != 0;
+  for (int k = 0; k < 3; ++k) c.base_acc[k] = S.base_acc[k];
+  for (int j = 0; j < S.n_dof && j < kReachMaxDof; ++j) {
+    const JointDev& J = S.joints[j];
+    ReachJoint& o = c.joints[j];
+    for (int k = 0; k < 3; ++k) {
+      o.axis[k] = J.axis[k];
+      o.off_pos[k] = J.off_pos[k];
+    }
+    o.joint_inertia = J.joint_inertia;
+    o.mass = J.mass;
+    for (int k = 0; k < 6; ++k) o.inertia[k] = J.inertia[k];
+  }
+  ReachDyn d;
+  d.n_dof = p->n_dof;
+  d.n_steps = p->dyn.n_steps;
+  d.dt = p->dyn.dt;
+  d.u_max = p->dyn.u_max;
+  d.single_inner = true;
+  for (int k = 0; k < p->dyn.n_steps; ++k) d.single_inner = d.single_inner && p->dyn.inner[k] == 1;
+  for (int j = 0; j < p->n_dof; ++j) {  // state layout (q0, qd0, q1, qd1, ...)
+    d.v_lower[j] = r.v_lower[j] = p->dyn.lower[2 * j + 1];
+    d.v_upper[j] = r.v_upper[j] = p->dyn.upper[2 * j + 1];
+  }
+  double T[kReachMaxDof];
+  if (probe_travel(c, d, T)) r.reach_q = probe_reach_norm(T, c.n_dof);
+  if (getenv("RKH_VERBOSE")) fprintf(stderr, "rkh planner: goal-probe reach %g rad\n", r.reach_q);
+}
+
 // 4. The streams, then the memory: the arena's layout from the shape of the batch, the slab itself -- one the context
 // kept from an earlier planner, or a new one -- and every device pointer of the planner set to its range; the pinned
 // block beside it.
@@ -1396,6 +1501,7 @@ rkh_status alloc_planner_buffers(rkh_planner* p) {
     q.d_accept = A.at<uint8_t>(L.of(i, PR_ACCEPT));
     q.d_probe_x = A.at<double>(L.of(i, PR_PROBE_X));
     q.d_probe_steps = A.at<uint32_t>(L.of(i, PR_PROBE_STEPS));
+    q.d_probe_list = A.at<uint32_t>(L.of(i, PR_PROBE_LIST));
     q.d_goal = A.at<double>(L.of(i, PR_GOAL));
     q.d_part_dist = A.at<double>(L.of(i, PR_PART_DIST));
     q.d_part_idx = A.at<uint32_t>(L.of(i, PR_PART_IDX));
@@ -1442,8 +1548,7 @@ void fill_upload_image(rkh_planner* p) {
     PlannerState& s0 = q.h_state;
     std::memset(&s0, 0, sizeof(s0));
     s0.n = 1;  // root vertex = query start (create_root, rrt_path_planner.tpp:131-133)
-    s0.n_before = 1;
-    s0.probed_n = 1;
+    s0.probed_n = 1;  // (the list of open probes is empty: list_n = n_new = 0)
     s0.max_total = uint32_t(q.prm.max_vertices) + 1;
     s0.b_max = p->b_max;
     s0.b_min = p->b_min;
@@ -1500,6 +1605,7 @@ rkh_status planner_create_common(rkh_scene* scene, const rkh_dyn_space* space, c
   RKH_TRY(setup_space(p.get(), space, qspace, prms));
   RKH_HIP(hipSetDevice(scene->ctx->device));  // (before the tuning: its occupancy query acts on the current device)
   tune_planner(p.get(), prms);
+  setup_probe_reach(p.get());
   p->prob.resize(n_problems);
   for (uint32_t i = 0; i < n_problems; ++i) {
     Problem& q = p->prob[i];
@@ -1548,7 +1654,9 @@ uint64_t new_goal_probes(const Problem& q) {
 }
 
 // 2. The new goal-probe results of all problems: gathered on the device, one copy into the pinned buffer, one wait.
-// Problem i's gd_cnt[i] results start at h_gd[gd_off[i]].
+// Problem i's gd_cnt[i] results start at h_gd[gd_off[i]].  probed_n jumps to n wherever commit_kernel settled every new
+// vertex, so one sync may take all of a problem's vertices since the last one: both buffers are sized here, from the
+// exact total of this call, before anything is copied -- no gather can outgrow them.
 rkh_status gather_goal_probes(rkh_planner* p, std::vector<uint64_t>& gd_off, std::vector<uint64_t>& gd_cnt) {
   gd_off.assign(p->P, 0);
   gd_cnt.assign(p->P, 0);
@@ -1733,6 +1841,22 @@ rkh_status rkh_diag_planner_carry_counts(rkh_planner* p, uint64_t counts[2]) {
     counts[0] += q.h_state.cand_discarded;
     counts[1] += q.h_state.cand_reused;
   }
+  return RKH_OK;
+}
+
+rkh_status rkh_diag_planner_probe_counts(rkh_planner* p, uint32_t problem, uint64_t counts[5], double* reach_q) {
+  if (!p || problem >= p->P || !counts) return RKH_ERR_BAD_ARG;
+  RKH_TRY(read_states(p));
+  const Problem& q = p->prob[problem];
+  const PlannerState& hs = q.h_state;
+  counts[0] = hs.probes_certified;
+  counts[1] = hs.probes_run;
+  counts[2] = hs.probed_n;
+  counts[3] = hs.list_n;
+  uint32_t first = hs.n;  // the first vertex whose probe is open
+  if (hs.list_n) RKH_HIP(hipMemcpy(&first, q.d_probe_list, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  counts[4] = first;
+  if (reach_q) *reach_q = p->reach.reach_q;
   return RKH_OK;
 }
 

@@ -34,6 +34,20 @@ RKH_HD uint32_t round_batch(const BatchInputs& in, float scale, uint32_t epw) {
   return B;
 }
 
+// ---- the probe list's granule rule ------------------------------------------------------------------------------------
+// A problem's open goal probes (the vertices probe_certified, probe_reach.h, did not settle at commit) wait in a list, in
+// vertex order.  A commit first drops the entries the round's launch ran from the front, keeps what that launch left
+// behind -- `waited` entries, fewer than the granule -- and appends the round's open vertices behind them: list_n in all.
+// The next launch takes the list's whole granules (a (problem, probes) segment of the steer grid then has no half-empty
+// last wave), but at least the entries that have waited one round already: open probes are rare, and a waiting one holds
+// back probed_n and with it the sync's gather.  What stays behind is again fewer than the granule; granule 1: all ride.
+RKH_HD uint32_t probe_ride_count(uint32_t list_n, uint32_t waited, uint32_t granule) {
+  const uint32_t whole = granule > 1u ? list_n - list_n % granule : list_n;
+  return whole > waited ? whole : waited;
+}
+// vertices [1, probed_n) have their goal-probe result: up to the first vertex still in the list, else all n
+RKH_HD uint32_t probe_probed_n(const uint32_t* list, uint32_t list_n, uint32_t n) { return list_n ? list[0] : n; }
+
 // steer waves (or query blocks) that `count` edges (queries) of one segment take
 RKH_HD uint32_t round_waves(uint32_t count, uint32_t epw) { return (count + epw - 1u) / epw; }
 

@@ -83,7 +83,7 @@ EXPORTS = [
     "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_diag_gjk_records", "rkh_diag_gjk_depth_records", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
     "rkh_min_distance", "rkh_min_distance_records", "rkh_collision_records", "rkh_min_distance_records_meshes", "rkh_collision_records_meshes", "rkh_min_distance_records_depth", "rkh_collision_records_depth", "rkh_min_distance_records_2d", "rkh_collision_records_2d", "rkh_propagate", "rkh_edge_check", "rkh_planner_create", "rkh_planner_destroy",
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
-    "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
+    "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_diag_planner_probe_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
     "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
 ]
@@ -199,6 +199,7 @@ def load():
     lib.rkh_planner_steer_steps.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.rkh_diag_planner_sample_cap.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
     lib.rkh_diag_planner_carry_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.rkh_diag_planner_probe_counts.argtypes = [vp, u32, C.POINTER(C.c_uint64), dp]
     lib.rkh_diag_nn_mirror_query.argtypes = [vp, dp, C.c_uint64, C.c_int, dp, C.c_uint32, C.c_double, C.POINTER(C.c_uint32), dp]
     lib.rkh_abi_version.restype = C.c_uint32
     lib.rkh_abi_check.argtypes = [C.c_uint32] + [C.c_size_t] * 10
@@ -669,6 +670,15 @@ class RrtPlanner:
         _check(self.lib.rkh_diag_planner_carry_counts(self.h, c))
         return int(c[0]), int(c[1])
 
+    def probe_counts(self, problem=0):
+        """Goal probes of one problem (rkh_diag_planner_probe_counts): a dict with the probes settled at commit
+        (certified), the probes a steer launch ran (run), probed_n, the open probes (open), the first vertex whose probe
+        is open (first_open) and the travel bound reach_q (inf: no certificate)."""
+        c, r = (C.c_uint64 * 5)(), C.c_double()
+        _check(self.lib.rkh_diag_planner_probe_counts(self.h, problem, c, C.byref(r)))
+        return {"certified": int(c[0]), "run": int(c[1]), "probed_n": int(c[2]), "open": int(c[3]),
+                "first_open": int(c[4]), "reach_q": r.value}
+
     def sample_cap(self, problem=0):
         """Samples the problem's stream buffers hold at present (they grow at a sync)."""
         n = C.c_uint64()
@@ -774,6 +784,11 @@ class RrtPlannerPool:
     def carry_counts(self):
         counts = [pl.carry_counts() for pl in self.planners]
         return sum(c[0] for c in counts), sum(c[1] for c in counts)
+
+    def probe_counts(self):
+        """(goal probes settled at commit, goal probes a steer launch ran), summed over all problems."""
+        counts = [pl.probe_counts(i) for pl in self.planners for i in range(pl.P)]
+        return sum(c["certified"] for c in counts), sum(c["run"] for c in counts)
 
     def close(self):
         for pl in self.planners:
