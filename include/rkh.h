@@ -419,6 +419,46 @@ rkh_status rkh_prm_solve(rkh_prm* p, int64_t max_loop_iterations, rkh_prm_stats*
  * expansion iterations, else 0xFFFFFFFF).  Any pointer may be NULL. */
 rkh_status rkh_prm_get_graph(rkh_prm* p, uint32_t problem, double* pos, uint32_t* edge_u, uint32_t* edge_v,
                              double* edge_w, double* density, uint32_t* cc_root, uint8_t* kind, uint32_t* expanded);
+/* ---- Roadmap queries: what prm_planner_visitor::publish_path (ctrl/path_planning/prm_path_planner.tpp:97-122) does and
+ * the solve above never reaches -- a shortest-path search over the motion graph with EdgeProp::weight that writes
+ * predecessor / distance_accum, and the predecessor walk from the goal (solution_path_factories.hpp).  They are queries
+ * on the roadmap as it stands (finished, or stopped by max_loop_iterations and resumed later); the solve, its stats and
+ * the roadmap are untouched and still no solution is registered during the solve.  The graph and its weights are what
+ * rkh_prm_get_graph returns, over quasi-static and dynamic roadmaps alike.
+ * Searches run on the device, one workgroup per (roadmap, source) pair (reak_amd/csrc/roadmap_paths.hip).  dist is the
+ * minimum over paths of the left-to-right fp64 sum of the weights from the source: bit for bit what a sequential
+ * Dijkstra computes.  The reference's search (BGL's astar_search, not in its tree; never run) yields these distances
+ * too, but its choice among equal-cost predecessors follows its queue's history.  Defined here instead: pred[v] is the
+ * LOWEST vertex id u among v's edges with dist[u] + w == dist[v]; a query point that is not a roadmap vertex counts as
+ * lower than every id (RKH_PRM_QUERY_POINT).  The source itself: dist 0, pred 0xFFFFFFFF; an unreached vertex: dist +inf,
+ * pred 0xFFFFFFFF. */
+#define RKH_PRM_QUERY_POINT 0xFFFFFFFEu
+/* distance_accum / predecessor of every vertex of problem's roadmap from each of S source vertices, the S searches in one
+ * launch.  dist, pred [S][num_vertices]; either may be NULL, not both.  RKH_ERR_BAD_ARG: a source >= num_vertices, S > 0
+ * without sources, problem out of range, both outputs NULL.  S == 0 is RKH_OK. */
+rkh_status rkh_prm_shortest_paths(rkh_prm* p, uint32_t problem, const uint32_t* sources, uint32_t S,
+                                  double* dist /* [S][num_vertices] */, uint32_t* pred /* [S][num_vertices] */);
+/* start (vertex 0) -> goal (vertex 1) through the roadmap as it stands: cost = distance_accum of the goal, path = the
+ * predecessor walk from the goal, start first.  Capacity, NULL path and n_path = 0 (goal not reached: cost +inf) as for
+ * rkh_rrtstar_get_solution below.  The first call after a solve searches from vertex 0 in all problems of the batch in
+ * one launch; the handle keeps a problem's tree until rkh_prm_solve adds a vertex or an edge to it. */
+rkh_status rkh_prm_get_solution(rkh_prm* p, uint32_t problem, uint32_t* path, uint32_t capacity,
+                                uint32_t* n_path, double* cost);
+/* Multi-query: B (start, goal) pairs of points [B][n_dof] that need not be roadmap vertices (quasi-static roadmaps;
+ * a dynamic roadmap: RKH_ERR_UNSUPPORTED, its connections are directional propagations between states).  Each point
+ * is connected to its k nearest roadmap vertices strictly inside radius (the rule of rkh_nn_queryk: ascending
+ * (distance, index)) by the quasi-static walk in the direction of travel, start -> u and u -> goal, judged by
+ * can_be_connected (planning_visitors.hpp:385-395) with the problem's conn_tol and weighted like a roadmap edge
+ * (|first point of the walk - its end point|).  A point that coincides with a roadmap vertex connects to it with weight 0.
+ * cost[b] = min over the accepted goal connections v of dist[v] + w(v, goal), the lowest v winning ties, dist from the
+ * accepted start connections; path[b] = the roadmap vertices between the two points in travel order, n_path[b] their
+ * count (the first min(n_path[b], capacity) are written); no path: n_path[b] = 0, cost[b] = +inf.  path may be NULL.
+ * One k-NN launch, one edge-walk launch and one search launch serve all B pairs.  A direct start -> goal walk is not
+ * tried: rkh_edge_check answers that.  RKH_ERR_BAD_ARG: NULL starts / goals / cost / n_path with B > 0, k == 0,
+ * problem out of range.  B == 0 is RKH_OK. */
+rkh_status rkh_prm_query_paths(rkh_prm* p, uint32_t problem, const double* starts, const double* goals, uint32_t B,
+                               uint32_t k, double radius, uint32_t capacity,
+                               double* cost /* [B] */, uint32_t* path /* [B][capacity] */, uint32_t* n_path /* [B] */);
 /* ---- Bidirectional RRT: rrt_planner with BIDIRECTIONAL_PLANNING (the reference's default flag,
  * ctrl/path_planning/rrt_path_planner.hpp:114) -> generate_bidirectional_rrt (ctrl/graph_alg/rr_tree.hpp:256-317),
  * joining_vertex_found (planning_visitors.hpp:223-231), two-graph solution registration

@@ -863,6 +863,8 @@ class hip_rrtstar_planner : public hip_planner_base<FreeSpace> {
 
 // ---- prm_planner (prm_path_planner.tpp:131-365).  As in the reference (density_plan_visitor; rkh.h), the roadmap grows to
 // max_vertex_count and no solution is registered: the query's records stay as they were; the roadmap is motion_graph().
+// What prm_planner_visitor::publish_path (prm_path_planner.tpp:97-122) would have found is a query on the finished
+// roadmap: roadmap_solution() (rkh_prm_get_solution).
 template <typename FreeSpace>
 class hip_prm_planner : public hip_planner_base<FreeSpace> {
   typedef hip_planner_base<FreeSpace> base;
@@ -886,6 +888,7 @@ class hip_prm_planner : public hip_planner_base<FreeSpace> {
     prm.sampling_radius = this->m_sampling_radius;
     prm.expand_probability = 0.2;  // fixed by the reference's generate_prm call (prm_path_planner.tpp:250-253)
     std::shared_ptr<rkh_prm> pl = create(prm, static_cast<const FreeSpace*>(nullptr));
+    m_roadmap = pl;  // kept for roadmap_solution()
     rkh_prm_stats st = rkh_prm_stats();
     check(rkh_prm_solve(pl.get(), -1, &st));
     const std::size_t nv = std::size_t(st.num_vertices), ne = std::size_t(st.num_edges);
@@ -914,7 +917,21 @@ class hip_prm_planner : public hip_planner_base<FreeSpace> {
     detail::consume_global_draws(uint64_t(st.samples));
   }
 
+  // The shortest start -> goal path through the roadmap of the last solve_planning_query, as vertices of motion_graph()
+  // (start first), and its cost = the goal's distance_accum; no path: empty and +inf.  Ties between equal-cost
+  // predecessors go to the lowest vertex (rkh.h).  Nothing is registered with the query and motion_graph() is not touched.
+  std::pair<std::vector<std::size_t>, double> roadmap_solution() {
+    if (!m_roadmap) throw std::runtime_error("hip_prm_planner::roadmap_solution: no roadmap (call solve_planning_query first)");
+    uint32_t n = 0;
+    double cost = std::numeric_limits<double>::infinity();
+    check(rkh_prm_get_solution(m_roadmap.get(), 0, nullptr, 0, &n, &cost));
+    std::vector<uint32_t> path(n ? n : 1);
+    check(rkh_prm_get_solution(m_roadmap.get(), 0, path.data(), uint32_t(path.size()), &n, &cost));
+    return std::make_pair(std::vector<std::size_t>(path.begin(), path.begin() + n), cost);
+  }
+
  private:
+  std::shared_ptr<rkh_prm> m_roadmap;
   std::shared_ptr<rkh_prm> create(const rkh_prm_params& prm, const kte_dynamic_free_space<point_type>*) {
     rkh_prm* raw = nullptr;
     check(rkh_prm_create_batch(this->m_space->scene().get(), &this->m_space->dyn_space(), &prm, 1, &raw));

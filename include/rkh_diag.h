@@ -112,6 +112,26 @@ rkh_status rkh_diag_planner_probe_counts(rkh_planner* p, uint32_t problem, uint6
  * (tools/measure_record_query.py). */
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms);
 
+/* The roadmap search kernel (reak_amd/csrc/roadmap_paths.hip; the definition is at rkh_prm_shortest_paths in rkh.h) on a
+ * caller's graph, so that graphs a planner never builds can be tested.  The graph is a CSR adjacency of n >= 1 vertices
+ * (row_ptr[n + 1] ascending from 0, col / w [row_ptr[n]], col < n, w >= 0; an undirected edge is listed under both ends).
+ * S searches run in one launch; search s starts from the seed list (seed_v[i], seed_d[i]), i in
+ * [seed_ptr[s], seed_ptr[s + 1]): vertex seed_v[i] at distance seed_d[i] >= 0 (a roadmap vertex v as the source is the list
+ * {(v, 0.0)}).  seed_mark[s] is the predecessor written where a seed is the vertex's distance: 0xFFFFFFFF for a vertex
+ * source, RKH_PRM_QUERY_POINT for a query point's connections.  dist / pred [S][n] (either may be NULL), rounds [S] or
+ * NULL: relaxation rounds each search ran.  Malformed input: RKH_ERR_BAD_ARG. */
+rkh_status rkh_diag_sssp(rkh_ctx* ctx, uint32_t n, const uint32_t* row_ptr, const uint32_t* col, const double* w, uint32_t S,
+                         const uint32_t* seed_ptr, const uint32_t* seed_v, const double* seed_d, const uint32_t* seed_mark,
+                         double* dist, uint32_t* pred, uint32_t* rounds);
+/* Time of the search launch alone on the roadmaps of a PRM handle (tools/measure_prm_queries.py).  problem == 0xFFFFFFFF:
+ * one search from vertex 0 in every problem of the batch (the launch of rkh_prm_get_solution; sources / S unused);
+ * else the S searches of rkh_prm_shortest_paths on that problem.  After one warm-up launch, `runs` launches, each between
+ * two events on the handle's stream: ms[runs].  max_rounds: the most relaxation rounds any search took.  host_ms (may be
+ * NULL): the time a single-thread std::priority_queue Dijkstra takes for the same searches over the same CSRs, once
+ * (reference code for the comparison, not the code under test). */
+rkh_status rkh_diag_prm_search_ms(rkh_prm* p, uint32_t problem, const uint32_t* sources, uint32_t S, uint32_t runs, float* ms,
+                                  uint32_t* max_rounds, double* host_ms);
+
 #ifdef __cplusplus
 }
 #endif

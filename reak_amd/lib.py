@@ -85,7 +85,7 @@ EXPORTS = [
     "rkh_planner_enqueue", "rkh_planner_sync", "rkh_planner_solve", "rkh_planner_get_tree", "rkh_planner_stream",
     "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_diag_planner_probe_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
-    "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
+    "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_prm_shortest_paths", "rkh_prm_get_solution", "rkh_prm_query_paths", "rkh_diag_sssp", "rkh_diag_prm_search_ms", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
 ]
 
 
@@ -184,6 +184,11 @@ def load():
     lib.rkh_birrt_solve.argtypes = [vp, C.c_int64, C.POINTER(BiRrtStats)]
     lib.rkh_birrt_get_trees.argtypes = [vp, u32, dp, u32p, dp, u32p, u32p, C.POINTER(C.c_uint8)]
     lib.rkh_prm_get_graph.argtypes = [vp, u32, dp, u32p, u32p, dp, dp, u32p, C.POINTER(C.c_uint8), u32p]
+    lib.rkh_prm_shortest_paths.argtypes = [vp, u32, u32p, u32, dp, u32p]
+    lib.rkh_prm_get_solution.argtypes = [vp, u32, u32p, u32, u32p, dp]
+    lib.rkh_prm_query_paths.argtypes = [vp, u32, dp, dp, u32, u32, d, u32, dp, u32p, u32p]
+    lib.rkh_diag_sssp.argtypes = [vp, u32, u32p, u32p, dp, u32, u32p, u32p, dp, u32p, dp, u32p, u32p]
+    lib.rkh_diag_prm_search_ms.argtypes = [vp, u32, u32p, u32, u32, C.POINTER(C.c_float), u32p, dp]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -217,6 +222,28 @@ def _check(status):
         if status == -3:
             raise SingularityError(status, msg)
         raise RkhError(status, msg)
+
+
+def diag_sssp(ctx, row_ptr, col, w, seed_lists, seed_marks):
+    """rkh_diag_sssp: the roadmap search kernel on a caller's CSR graph.  seed_lists: one list of (vertex, distance) per
+    search; seed_marks: the predecessor written where a seed is the distance.  Returns (dist [S][n], pred [S][n], rounds [S])."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint32)
+    col = np.ascontiguousarray(col, dtype=np.uint32)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    n, S = len(row_ptr) - 1, len(seed_lists)
+    seed_ptr = np.zeros(S + 1, dtype=np.uint32)
+    seed_ptr[1:] = np.cumsum([len(sl) for sl in seed_lists])
+    seed_v = np.array([v for sl in seed_lists for v, _ in sl] + [0], dtype=np.uint32)
+    seed_d = np.array([x for sl in seed_lists for _, x in sl] + [0.0], dtype=np.float64)
+    marks = np.ascontiguousarray(seed_marks, dtype=np.uint32)
+    dist = np.zeros((S, n))
+    pred = np.zeros((S, n), dtype=np.uint32)
+    rounds = np.zeros(max(S, 1), dtype=np.uint32)
+    colp = np.concatenate([col, np.zeros(1, np.uint32)])  # (never an empty buffer)
+    wp = np.concatenate([w, np.zeros(1)])
+    _check(ctx.lib.rkh_diag_sssp(ctx.h, n, T.u32ptr(row_ptr), T.u32ptr(colp), T.dptr(wp), S, T.u32ptr(seed_ptr), T.u32ptr(seed_v),
+                                 T.dptr(seed_d), T.u32ptr(marks), T.dptr(dist), T.u32ptr(pred), T.u32ptr(rounds)))
+    return dist, pred, rounds[:S]
 
 
 class Context:
@@ -945,6 +972,53 @@ class PrmPlanner:
                                           T.u32ptr(cc), kind.ctypes.data_as(C.POINTER(C.c_uint8)), T.u32ptr(exp)))
         return {"pos": pos, "edge_u": eu[:ne], "edge_v": ev[:ne], "edge_w": ew[:ne], "density": dens, "cc_root": cc,
                 "kind": kind[:it], "expanded": exp[:it]}
+
+    # ---- roadmap queries (prm_planner_visitor::publish_path's search, on the roadmap as it stands)
+    def shortest_paths(self, sources, problem=0):
+        """(dist [S][num_vertices], pred [S][num_vertices]) from each source vertex; pred: 0xFFFFFFFF = none."""
+        src = np.ascontiguousarray(sources, dtype=np.uint32).reshape(-1)
+        nv = int(self.all_stats[problem].num_vertices)
+        dist = np.zeros((len(src), nv))
+        pred = np.zeros((len(src), nv), dtype=np.uint32)
+        _check(self.lib.rkh_prm_shortest_paths(self.h, problem, T.u32ptr(src), len(src), T.dptr(dist), T.u32ptr(pred)))
+        return dist, pred
+
+    def solution(self, problem=0):
+        """(path, cost): start (vertex 0) -> goal (vertex 1) through the roadmap; path is empty and cost +inf if they are
+        not connected."""
+        n, cost = C.c_uint32(0), C.c_double(0.0)
+        _check(self.lib.rkh_prm_get_solution(self.h, problem, None, 0, C.byref(n), C.byref(cost)))
+        path = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(self.lib.rkh_prm_get_solution(self.h, problem, T.u32ptr(path), len(path), C.byref(n), C.byref(cost)))
+        return path[:n.value], cost.value
+
+    def query_paths(self, starts, goals, k, radius, problem=0, capacity=None):
+        """Multi-query over a quasi-static roadmap: (cost [B], paths: list of B arrays of roadmap vertex ids in travel
+        order; empty and +inf where no path exists).  capacity: path slots per query (default: the vertex count)."""
+        a = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, self.D)
+        b = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, self.D)
+        assert len(a) == len(b)
+        B = len(a)
+        cap = int(self.all_stats[problem].num_vertices) if capacity is None else int(capacity)
+        cost = np.zeros(max(B, 1))
+        path = np.zeros((max(B, 1), max(cap, 1)), dtype=np.uint32)
+        n_path = np.zeros(max(B, 1), dtype=np.uint32)
+        _check(self.lib.rkh_prm_query_paths(self.h, problem, T.dptr(a), T.dptr(b), B, int(k), float(radius), cap,
+                                            T.dptr(cost), T.u32ptr(path), T.u32ptr(n_path)))
+        return cost[:B], [path[i, :min(int(n_path[i]), cap)].copy() for i in range(B)]
+
+    def search_ms(self, sources=None, problem=0, runs=5):
+        """rkh_diag_prm_search_ms: (ms [runs], max_rounds, host_dijkstra_ms); sources None: vertex 0 of every problem."""
+        ms = np.zeros(runs, dtype=np.float32)
+        rounds, host = C.c_uint32(0), C.c_double(0.0)
+        if sources is None:
+            _check(self.lib.rkh_diag_prm_search_ms(self.h, 0xFFFFFFFF, None, 0, runs, ms.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   C.byref(rounds), C.byref(host)))
+        else:
+            src = np.ascontiguousarray(sources, dtype=np.uint32).reshape(-1)
+            _check(self.lib.rkh_diag_prm_search_ms(self.h, problem, T.u32ptr(src), len(src), runs,
+                                                   ms.ctypes.data_as(C.POINTER(C.c_float)), C.byref(rounds), C.byref(host)))
+        return ms, rounds.value, host.value
 
     def close(self):
         if self.h:
