@@ -454,7 +454,8 @@ rkh_status rkh_prm_get_solution(rkh_prm* p, uint32_t problem, uint32_t* path, ui
  * accepted start connections; path[b] = the roadmap vertices between the two points in travel order, n_path[b] their
  * count (the first min(n_path[b], capacity) are written); no path: n_path[b] = 0, cost[b] = +inf.  path may be NULL.
  * One k-NN launch, one edge-walk launch and one search launch serve all B pairs.  A direct start -> goal walk is not
- * tried: rkh_edge_check answers that.  RKH_ERR_BAD_ARG: NULL starts / goals / cost / n_path with B > 0, k == 0,
+ * tried here: rkh_shortcut_paths on the answer (start, path vertices, goal) tries it as its pair (0, L - 1).
+ * RKH_ERR_BAD_ARG: NULL starts / goals / cost / n_path with B > 0, k == 0,
  * problem out of range.  B == 0 is RKH_OK. */
 rkh_status rkh_prm_query_paths(rkh_prm* p, uint32_t problem, const double* starts, const double* goals, uint32_t B,
                                uint32_t k, double radius, uint32_t capacity,
@@ -488,6 +489,41 @@ rkh_status rkh_rrtstar_get_solution(rkh_rrtstar* p, uint32_t problem, uint32_t* 
                                     double* cost);
 rkh_status rkh_birrt_get_solution(rkh_birrt* p, uint32_t problem, uint32_t* path1, uint32_t* n_path1, uint32_t* path2,
                                   uint32_t* n_path2, uint32_t capacity, double* cost);
+/* ---- Shortcutting: the paths above come straight off a random tree or roadmap and zig-zag.  This entry removes the
+ * vertices a straight collision-free hop makes unnecessary, for B paths at once, exactly.  The reference has no
+ * shortcutter; the walk it rests on is the one of rkh_edge_check.
+ * Input: B paths over a quasi-static space (rate-limited spaces included; metric and interpolation in space coordinates).
+ * Path b is the L_b >= 1 points points[path_ptr[b] .. path_ptr[b + 1]), each [n_dof], start first (the rows of
+ * rkh_*_get_graph / get_tree picked by a solution's indices, with any off-roadmap start and goal point added).
+ * Weight: w(i, j) = the left-to-right fp64 euclidean norm of p_i - p_j (s = s + d * d in coordinate order, a correctly
+ * rounded sqrt, no contraction): what the walk computes as the length of the hop.
+ * Strict verdict: ok(i, j) is the verdict of the full-fraction walk p_i -> p_j in the direction of travel: true if
+ * w(i, j) < min_interval (move_position_toward makes no predicate call there), else iff the predicate loop ran to its end
+ * without a failing point, i.e. the walk returns p_j bit for bit.  This is stricter than can_be_connected
+ * (planning_visitors.hpp:385-395), which accepts a walk that stopped within conn_tol of its target; a shortcut must not.
+ * Candidates: with span = max_span ? max_span : L - 1, all pairs (i, j) with 1 <= j - i <= span, in the order i ascending,
+ * then j ascending; every one of them is walked, all paths' pairs in ONE walk launch.
+ * Search: dist[0] = 0, dist[j] = min over the allowed i < j of dist[i] + w(i, j), that one fp64 addition; allowed means
+ * j == i + 1 (the caller's own hops, whatever their verdict: roadmap edges were accepted under a tolerance) or ok(i, j) with
+ * j - i <= span; the LOWEST i wins ties.  Bit for bit the sequential double loop (i ascending, update under strict <).  All
+ * pairs are tried, so the result is the optimum over all subsequences of the path: a second pass cannot improve it.
+ * Outputs per path: keep = the predecessor walk from L - 1, start first, as path-local indices, written at
+ * keep[path_ptr[b] ..], n_keep[b] <= L_b of them (the path's slots behind them hold 0xFFFFFFFF); cost_in = the left-to-right sum of the consecutive hops; cost_out =
+ * dist[L - 1] <= cost_in (the input is a candidate and fp addition is monotone); n_blocked = the hops of the RETURNED path
+ * whose strict verdict is false (they can only be input hops; 0: the returned path passed the strict walk hop by hop).
+ * The direct start -> goal connection is the pair (0, L - 1): n_keep == 2.
+ * B == 0 is RKH_OK.  RKH_ERR_BAD_ARG: a NULL scene, space, points, path_ptr, keep, n_keep or cost_out; path_ptr not
+ * ascending from 0; an empty path; space->n_dof != rkh_scene_num_dof; min_interval <= 0; a coordinate that is not finite.
+ * RKH_ERR_CAPACITY: a path of more than 1024 points, or more than 2147483647 candidate pairs in the call (a path of L
+ * points has L (L - 1) / 2 of them; max_span is the caller's way under it: about L * max_span).  Every pair takes
+ * 8 n_dof + 25 bytes of device memory for the duration of the call (the walk's scratch included), so memory ends a call
+ * (RKH_ERR_OOM) long before that count: 100 million pairs of a 3-joint chain take 4.9 GB.
+ * Paths of dynamic states (rkh_dyn_space) are not served: their hops are propagations, not straight walks. */
+rkh_status rkh_shortcut_paths(rkh_scene* scene, const rkh_qs_space* space, const double* points,
+                              const uint32_t* path_ptr /* [B+1] */, uint32_t B, uint32_t max_span,
+                              uint32_t* keep /* [path_ptr[B]] */, uint32_t* n_keep /* [B] */,
+                              double* cost_in /* [B], may be NULL */, double* cost_out /* [B] */,
+                              uint32_t* n_blocked /* [B], may be NULL */);
 
 #ifdef __cplusplus
 }

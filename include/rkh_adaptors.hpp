@@ -385,6 +385,29 @@ class manip_quasi_static_free_space {
                          &n_checked));
     return out;
   }
+  // rkh_shortcut_paths on one path of points of this space, start first (a solution path's vertex positions): the indices
+  // of the points to keep, the path's length before and after, and the kept hops that fail the strict walk (input hops
+  // accepted under a tolerance; 0 = every kept hop walks through).  max_span: the longest hop tried, in points (0: all).
+  struct shortcut_result {
+    std::vector<std::size_t> keep;
+    double cost_in, cost_out;
+    std::size_t n_blocked;
+  };
+  shortcut_result shortcut_path(const std::vector<Point>& path, uint32_t max_span = 0) const {
+    const std::size_t n = dimensions();
+    std::vector<double> pts(path.size() * n);
+    for (std::size_t v = 0; v < path.size(); ++v)
+      for (std::size_t d = 0; d < n; ++d) pts[v * n + d] = path[v][d];
+    const uint32_t path_ptr[2] = {0u, uint32_t(path.size())};
+    std::vector<uint32_t> keep(path.size() + 1);
+    uint32_t n_keep = 0, n_blocked = 0;
+    shortcut_result r;
+    check(rkh_shortcut_paths(m_scene.get(), &m_sp, pts.data(), path_ptr, 1, max_span, keep.data(), &n_keep, &r.cost_in,
+                             &r.cost_out, &n_blocked));
+    r.keep.assign(keep.begin(), keep.begin() + n_keep);
+    r.n_blocked = n_blocked;
+    return r;
+  }
   double distance(const Point& a, const Point& b) const {  // interp_topo_get_distance_pred
     const Point r = move_position_toward(a, 1.0, b);
     return (m_super.distance(r, b) < std::numeric_limits<double>::epsilon()) ? m_super.distance(a, b)

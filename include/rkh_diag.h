@@ -132,6 +132,20 @@ rkh_status rkh_diag_sssp(rkh_ctx* ctx, uint32_t n, const uint32_t* row_ptr, cons
 rkh_status rkh_diag_prm_search_ms(rkh_prm* p, uint32_t problem, const uint32_t* sources, uint32_t S, uint32_t runs, float* ms,
                                   uint32_t* max_rounds, double* host_ms);
 
+/* The search kernel of rkh_shortcut_paths (reak_amd/csrc/path_shortcut.hip; the definitions are at that entry in rkh.h) on
+ * a caller's verdicts and weights, so that matrices no scene produces can be tested.  path_ptr [B + 1] as there (only the
+ * lengths matter); ok / w hold one entry per candidate pair, path after path, each path's pairs in pair order (i ascending,
+ * then j ascending, 1 <= j - i <= span): ok != 0 is a true strict verdict, w finite and >= 0.  Outputs as there.
+ * RKH_ERR_BAD_ARG / RKH_ERR_CAPACITY as there, and BAD_ARG for a weight that is negative or not finite. */
+rkh_status rkh_diag_shortcut_dp(rkh_ctx* ctx, const uint32_t* path_ptr, uint32_t B, uint32_t max_span,
+                                const uint8_t* ok, const double* w, /* per candidate pair, in pair order */
+                                uint32_t* keep, uint32_t* n_keep, double* cost_out, uint32_t* n_blocked);
+/* Time of the three launches of rkh_shortcut_paths on the same arguments (tools/measure_shortcut.py): after one warm-up,
+ * `runs` times the pair kernel, the walk launch and the search, each between two events on the context's stream:
+ * ms[runs][3] = pairs, walks, search.  No copies are timed.  B > 0. */
+rkh_status rkh_diag_shortcut_ms(rkh_scene* scene, const rkh_qs_space* space, const double* points, const uint32_t* path_ptr,
+                                uint32_t B, uint32_t max_span, uint32_t runs, float* ms /* [runs][3] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,7 @@ EXPORTS = [
     "rkh_planner_nn_profile", "rkh_planner_nn_pairs", "rkh_planner_steer_profile", "rkh_planner_steer_steps", "rkh_diag_nn_mirror_query", "rkh_diag_feval_cycles", "rkh_diag_proximity_counts", "rkh_diag_distance_query_ms", "rkh_diag_proximity_clearance", "rkh_diag_steer_clearance_counts", "rkh_diag_planner_carry_counts", "rkh_diag_planner_probe_counts", "rkh_planner_create_batch", "rkh_planner_num_problems", "rkh_nn_set_events", "rkh_planner_create_qs_batch", "rkh_rrtstar_create_qs_batch", "rkh_rrtstar_create_batch", "rkh_birrtstar_create_qs_batch", "rkh_birrtstar_solve",
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
     "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_prm_shortest_paths", "rkh_prm_get_solution", "rkh_prm_query_paths", "rkh_diag_sssp", "rkh_diag_prm_search_ms", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
+    "rkh_shortcut_paths", "rkh_diag_shortcut_dp", "rkh_diag_shortcut_ms",
 ]
 
 
@@ -189,6 +190,10 @@ def load():
     lib.rkh_prm_query_paths.argtypes = [vp, u32, dp, dp, u32, u32, d, u32, dp, u32p, u32p]
     lib.rkh_diag_sssp.argtypes = [vp, u32, u32p, u32p, dp, u32, u32p, u32p, dp, u32p, dp, u32p, u32p]
     lib.rkh_diag_prm_search_ms.argtypes = [vp, u32, u32p, u32, u32, C.POINTER(C.c_float), u32p, dp]
+    u8p = C.POINTER(C.c_uint8)
+    lib.rkh_shortcut_paths.argtypes = [vp, C.POINTER(T.QsSpace), dp, u32p, u32, u32, u32p, u32p, dp, dp, u32p]
+    lib.rkh_diag_shortcut_dp.argtypes = [vp, u32p, u32, u32, u8p, dp, u32p, u32p, dp, u32p]
+    lib.rkh_diag_shortcut_ms.argtypes = [vp, C.POINTER(T.QsSpace), dp, u32p, u32, u32, u32, C.POINTER(C.c_float)]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -244,6 +249,49 @@ def diag_sssp(ctx, row_ptr, col, w, seed_lists, seed_marks):
     _check(ctx.lib.rkh_diag_sssp(ctx.h, n, T.u32ptr(row_ptr), T.u32ptr(colp), T.dptr(wp), S, T.u32ptr(seed_ptr), T.u32ptr(seed_v),
                                  T.dptr(seed_d), T.u32ptr(marks), T.dptr(dist), T.u32ptr(pred), T.u32ptr(rounds)))
     return dist, pred, rounds[:S]
+
+
+def _path_table(paths, n):
+    """(points [sum L][n], path_ptr [B + 1]) of a list of [L][n] arrays"""
+    paths = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, n) for p in paths]
+    path_ptr = np.zeros(len(paths) + 1, dtype=np.uint32)
+    path_ptr[1:] = np.cumsum([len(p) for p in paths])
+    pts = np.concatenate(paths + [np.zeros((1, n))])  # (never an empty buffer)
+    return np.ascontiguousarray(pts), path_ptr
+
+
+def _keep_lists(keep, n_keep, path_ptr):
+    return [keep[path_ptr[b]:path_ptr[b] + n_keep[b]].copy() for b in range(len(n_keep))]
+
+
+def diag_shortcut_dp(ctx, lengths, ok, w, max_span=0):
+    """rkh_diag_shortcut_dp: the search kernel of rkh_shortcut_paths on a caller's verdicts and weights.  lengths: the
+    point count of each path; ok / w: one entry per candidate pair, path after path, in pair order.  Returns
+    (keep lists, cost_out [B], n_blocked [B])."""
+    B = len(lengths)
+    path_ptr = np.zeros(B + 1, dtype=np.uint32)
+    path_ptr[1:] = np.cumsum(lengths)
+    ok = np.concatenate([np.ascontiguousarray(ok, dtype=np.uint8).reshape(-1), np.zeros(1, np.uint8)])
+    w = np.concatenate([np.ascontiguousarray(w, dtype=np.float64).reshape(-1), np.zeros(1)])
+    keep = np.zeros(max(int(path_ptr[B]), 1), dtype=np.uint32)
+    n_keep, n_blocked = np.zeros(max(B, 1), dtype=np.uint32), np.zeros(max(B, 1), dtype=np.uint32)
+    cost_out = np.zeros(max(B, 1))
+    _check(ctx.lib.rkh_diag_shortcut_dp(ctx.h, T.u32ptr(path_ptr), B, int(max_span), ok.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        T.dptr(w), T.u32ptr(keep), T.u32ptr(n_keep), T.dptr(cost_out), T.u32ptr(n_blocked)))
+    return _keep_lists(keep, n_keep[:B], path_ptr), cost_out[:B], n_blocked[:B]
+
+
+def path_points(pos, indices, start=None, goal=None):
+    """The points of a planner's solution as rkh_shortcut_paths takes them: the rows of `pos` (a planner's vertex
+    positions) picked by the solution's vertex indices, with an off-roadmap start point in front and goal point behind
+    (the query points of PrmPlanner.query_paths)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    rows = [pos[np.asarray(indices, dtype=np.int64)].reshape(-1, pos.shape[1])]
+    if start is not None:
+        rows.insert(0, np.asarray(start, dtype=np.float64).reshape(1, -1))
+    if goal is not None:
+        rows.append(np.asarray(goal, dtype=np.float64).reshape(1, -1))
+    return np.ascontiguousarray(np.concatenate(rows))
 
 
 class Context:
@@ -582,6 +630,28 @@ class Scene:
         _check(self.lib.rkh_edge_check(self.h, T.dptr(lower), T.dptr(upper), float(min_interval), T.dptr(a), T.dptr(b),
                                        a.shape[0], float(fraction), T.dptr(out), T.u32ptr(nchk)))
         return out, nchk
+
+    def shortcut_paths(self, space, paths, max_span=0):
+        """rkh_shortcut_paths over the quasi-static space `space` (make_qs_space): `paths` is a list of [L][n] arrays of
+        points, start first.  Returns (keep: one array of path-local indices per path, cost_in [B], cost_out [B],
+        n_blocked [B]); the shortcut path b is paths[b][keep[b]].  max_span: the longest hop tried, in vertices (0: all)."""
+        pts, path_ptr = _path_table(paths, self.n)
+        B = len(path_ptr) - 1
+        keep = np.zeros(max(int(path_ptr[B]), 1), dtype=np.uint32)
+        n_keep, n_blocked = np.zeros(max(B, 1), dtype=np.uint32), np.zeros(max(B, 1), dtype=np.uint32)
+        cost_in, cost_out = np.zeros(max(B, 1)), np.zeros(max(B, 1))
+        _check(self.lib.rkh_shortcut_paths(self.h, C.byref(space), T.dptr(pts), T.u32ptr(path_ptr), B, int(max_span),
+                                           T.u32ptr(keep), T.u32ptr(n_keep), T.dptr(cost_in), T.dptr(cost_out),
+                                           T.u32ptr(n_blocked)))
+        return _keep_lists(keep, n_keep[:B], path_ptr), cost_in[:B], cost_out[:B], n_blocked[:B]
+
+    def shortcut_ms(self, space, paths, max_span=0, runs=5):
+        """rkh_diag_shortcut_ms: ms [runs][3] of the pair kernel, the walk launch and the search, events around each."""
+        pts, path_ptr = _path_table(paths, self.n)
+        ms = np.zeros((int(runs), 3), dtype=np.float32)
+        _check(self.lib.rkh_diag_shortcut_ms(self.h, C.byref(space), T.dptr(pts), T.u32ptr(path_ptr), len(path_ptr) - 1,
+                                             int(max_span), int(runs), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
 
     def steer_position_toward(self, a, b, fraction=1.0, record=False, dyn=None):
         a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, self.D)
