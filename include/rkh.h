@@ -112,7 +112,10 @@ rkh_status rkh_nn_queryk_async(rkh_nn* nn, const double* d_q, uint32_t B, uint32
  * the largest |corner coordinate|, ctrl/topologies/hyperbox_topology.hpp:97-103).  Sweeps of 5 or more queries then run a
  * single-precision pre-filter (the fp32 matrix instructions for 5..32 queries over at least 8192 vertices and for more
  * than 32 queries, as a split-bf16 estimate from 7 dimensions on) in front of the exact fp64 test; results stay
- * bit-identical.  bound = 0 (default) switches the pre-filters off, and so does a bound outside [1e-6, 1e6].
+ * bit-identical for every bound in [1e-6, 1e6], whether the vertices fill it or lie far inside it.  bound = 0 (default)
+ * switches the pre-filters off, and so does a bound outside [1e-6, 1e6].  (A planner derives its bound from its
+ * hyperbox; with 1e-3 <= bound <= 32 and at most 12 dimensions its rounds search over a half-precision mirror of the
+ * tree instead, kept in units of the power of two that brings the bound into [16, 32): reak_amd/csrc/nn_mirror.h.)
  * The promise is checked where the library holds the data on the host: rkh_nn_append and rkh_nn_query1 return
  * RKH_ERR_BAD_ARG for a coordinate beyond the bound, and so does this call if rows already stored exceed it.  Queries
  * handed over in HBM (rkh_nn_query1_async) are the caller's responsibility: a query outside the bound may return a

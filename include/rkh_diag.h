@@ -47,8 +47,10 @@ rkh_status rkh_diag_gjk_depth_records(rkh_ctx* ctx, const rkh_shape* a, const rk
 
 /* The planner-regime 1-NN sweep (half-precision mirror of the vertex rows + exact resolution of the one or two rows the
  * estimate leaves, reak_amd/csrc/nn_mirror.hip) on a caller's point cloud: n points [n][D], B queries [B][D], every
- * |coordinate| <= coord_bound (1e-3 .. 32), D <= 12.  idx / dist: the nearest point of each query, first minimum wins
- * (min_dist_linear_search, topological_search.hpp:95-118), bit-identical to the fp64 sweeps. */
+ * |coordinate| <= coord_bound, 1e-3 <= coord_bound <= 32 (else RKH_ERR_UNSUPPORTED), D <= 12.  The mirror is kept in
+ * units of the power of two that brings coord_bound into [16, 32), so the cloud may fill the bound or be far smaller.
+ * idx / dist: the nearest point of each query, first minimum wins (min_dist_linear_search,
+ * topological_search.hpp:95-118), bit-identical to the fp64 sweeps (tests/test_nn_mirror_bounds_gpu.py). */
 rkh_status rkh_diag_nn_mirror_query(rkh_ctx* ctx, const double* pts, uint64_t n, int D, const double* q, uint32_t B,
                                     double coord_bound, uint32_t* idx, double* dist);
 

@@ -38,20 +38,29 @@
 //     prefix over its four waves, plain stores), so the lengths need no zeroing between rounds and the lists come out
 //     in query order.
 //
-// Error bound.  x_h, q_h = half(float(x)), half(float(q)) per coordinate.  The rounding errors are MEASURED, not bounded:
+// Error bound.  Everything below is in the mirror's PRESCALED units (nn_mirror.h): x, q stand for p x, p q with the tree's
+// power of two p, which brings the coordinate bound into [16, 32) -- exact, so the nearest row and every comparison are
+// those of the unscaled problem, and the bound holds alike for a box of side 0.002 and one of side 64.  x_h, q_h =
+// half(float(x)), half(float(q)) per coordinate, 0 where that half is below the normal range.  The rounding errors are
+// MEASURED, not bounded:
 //   dx = max over the rows of a tree of |x - x_h| (kept per tree: mirror_store_row's callers raise it, ordered-integer
 //        atomicMax on the float's bits), dq = |q - q_h| of the query, delta = dx + dq >= | |x_h - q_h| - |x - q| |;
 //   c_real = |x_h|^2 - 2 x_h.q_h = |x_h - q_h|^2 - |q_h|^2  =>  | c_real + |q_h|^2 - s | <= 2 d delta + delta^2
 // with s = |x - q|^2, d = sqrt(s).  The instruction sums <= 16 exact products in float (order and intermediate roundings
-// unspecified: 15 roundings of 2^-24 on partial sums below S = X^2 + 2 X |q|, X >= |x_h| for every row) and the float
-// |x_h|^2 of the mirror carries 12 more: together below eps = 2^-19 S.  So s_r = c_r + |q_h|^2 + e_r with
+// unspecified: 15 roundings of 2^-24 on partial sums below S = X^2 + 2 X |q|, X >= |x_h| for every row; no operand is
+// subnormal, and the accumulator never flushes) and the float |x_h|^2 of the mirror carries 12 more: together below
+// 2^-19 S.  The three stored pieces of |x_h|^2 add up to it exactly while they are normal halves and leave out less
+// than 2^-14 otherwise (kMirrorSplitLoss: every row within 0.35 of the origin has such a piece; S >= 16^2, so the term
+// widens eps by an eighth at most and by 0.2 % at the planner's scale): eps = 2^-19 S + 2^-14.  So s_r = c_r + |q_h|^2 + e_r with
 // |e_r| <= E(d_r) := 2 d_r delta + delta^2 + eps.  Let m be the row of the smallest estimate and r* the true nearest row
 // (any row tying with it included): d_r* <= d_m, hence
 //   c_r* = s_r* - |q_h|^2 - e_r* <= s_m - |q_h|^2 + E(d_m) = c_m + e_m + E(d_m) <= c_m + 2 E(d_m),
 // and d_m <= delta + sqrt(c_m + |q_h|^2 + 2 delta^2 + eps).  Rows with c <= c_min + band(c_min), band = 2 E(that bound)
-// (evaluated in double, rounded up) are a superset of the candidates; distances that differ in the last bits of their
-// sqrt lie far inside the band, so "first minimum wins" is decided by the exact pass among them.  At the planner's
-// scale (12-D, |x| ~ 9, nearest neighbours at d ~ 2) delta ~ 3e-3 and the band ~ 0.03 in squared-distance units.
+// (mirror_threshold, nn_mirror.h: evaluated in double, rounded up) are a superset of the candidates; distances that
+// differ in the last bits of their sqrt lie far inside the band, so "first minimum wins" is decided by the exact pass
+// among them.  At the planner's scale (12-D, |x| ~ 9, nearest neighbours at d ~ 2, p = 8) delta ~ 3e-3 and the band
+// ~ 0.03 in squared-distance units of the unscaled problem.  tests/test_nn_mirror_band_cpu.py checks the superset claim
+// on a model of the operands.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -82,8 +91,8 @@ constexpr uint32_t kMirMaxSlices = 32;     // row slices per tree (rows of NnArg
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
 
 // ---- once per round and query: the B operand and the query's share of the error bound
-// qinfo[q] = {|q_h|^2 (rounded up), dq = |q - q_h| (rounded up), |q| (rounded up)}
-__global__ __launch_bounds__(256) void nn1_mirror_prep_kernel(const NnArgs* __restrict__ table, int D) {
+// qinfo[q] = {|q_h|^2 (rounded up), dq = |q - q_h| (rounded up), |q| (rounded up)} of the query times `scale`
+__global__ __launch_bounds__(256) void nn1_mirror_prep_kernel(const NnArgs* __restrict__ table, int D, double scale) {
   const NnArgs a = table[blockIdx.y];
   const uint32_t B = a.d_B ? *a.d_B : a.B;
   const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
@@ -93,8 +102,8 @@ __global__ __launch_bounds__(256) void nn1_mirror_prep_kernel(const NnArgs* __re
   double qn2 = 0.0, qh2 = 0.0, dq2 = 0.0;
 #pragma unroll
   for (int d = 0; d < kMirrorMaxDims; ++d) {
-    const double qv = d < D ? qq[d < D ? d : 0] : 0.0;
-    const uint32_t hb = mirror_half_bits(float(qv));
+    const double qv = (d < D ? qq[d < D ? d : 0] : 0.0) * scale;  // (scaled after the select: the loads stay independent)
+    const uint32_t hb = mirror_operand_bits(float(qv));
     const double qh = double(mirror_half_value(hb));
     qn2 += qv * qv;
     qh2 += qh * qh;
@@ -113,7 +122,7 @@ __global__ __launch_bounds__(256) void nn1_mirror_prep_kernel(const NnArgs* __re
 }
 
 // ---- between the passes: threshold of a query = (minimum over the row slices) + band; with open_lists, the list of the
-// open queries of every slice (NnArgs::open_list, open_cnt).  Lists: grid (1, trees), the block walks its tree's queries
+// open queries of every slice (NnArgs::open_list, open_cnt).  x_norm_bound is in the mirror's prescaled units.  Lists: grid (1, trees), the block walks its tree's queries
 // 256 at a time and appends each slice's open ones in query order -- ballot per wave, prefix over the four waves in
 // LDS, plain stores, so nothing needs to be zero when the kernel starts.  Without: grid (ceil(B / 256), trees).
 __global__ __launch_bounds__(256) void nn1_mirror_thr_kernel(const NnArgs* __restrict__ table, uint32_t gx,
@@ -139,16 +148,9 @@ __global__ __launch_bounds__(256) void nn1_mirror_thr_kernel(const NnArgs* __res
       for (uint32_t sl = 0; sl < kMirMaxSlices; ++sl) cmin = __builtin_fminf(cmin, est[sl]);
       const double* __restrict__ qi3 = a.qinfo + uint64_t(qi) * 3;
       const double qh2 = qi3[0], dq = qi3[1], qn = qi3[2];
-      const double dx = double(__uint_as_float(*a.dx_max_bits)) * (1.0 + 1e-6);
-      const double delta = dx + dq;
-      const double X = x_norm_bound * (1.0 + 1e-3);  // |x_h| <= |x| (1 + 2^-11)
-      const double eps = 1.9073486328125e-06 * (X * X + 2.0 * X * qn) + 1e-9;
-      const double base = fmax(0.0, double(cmin) + qh2) + 2.0 * delta * delta + eps;
-      const double d_up = delta + sqrt(base) * (1.0 + 1e-12);
-      const double E = 2.0 * d_up * delta + delta * delta + eps;
-      const double band = 2.0 * E * (1.0 + 1e-9);
+      const double dx = double(__uint_as_float(*a.dx_max_bits));
       // (+inf, an empty tree, stays +inf: every row is a candidate and the resolve kernel sorts it out)
-      thr = cmin < INFINITY ? __double2float_ru(double(cmin) + band) : INFINITY;
+      thr = cmin < INFINITY ? __double2float_ru(mirror_threshold(double(cmin), qh2, dq, qn, dx, x_norm_bound)) : INFINITY;
       a.thr[qi] = thr;
     }
     if (!open_lists) continue;
@@ -397,10 +399,11 @@ __global__ __launch_bounds__(256) void mirror_fill_kernel(uint4* __restrict__ mi
 }
 
 __global__ __launch_bounds__(256) void mirror_build_kernel(uint4* __restrict__ mirror, const double* __restrict__ pos,
-                                                           uint64_t n, int D, int DP, uint32_t* __restrict__ dx_max_bits) {
+                                                           uint64_t n, int D, int DP, double scale,
+                                                           uint32_t* __restrict__ dx_max_bits) {
   const uint64_t row = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;
   if (row >= n) return;
-  mirror_store_row(mirror, row, pos + row * DP, D, dx_max_bits);
+  mirror_store_row(mirror, row, pos + row * DP, D, scale, dx_max_bits);
 }
 
 }  // namespace
@@ -449,7 +452,7 @@ bool nn1_mirror_open_lists() {
 
 // does the mirror sweep take this problem shape?
 bool nn1_mirror_applies(int D, double coord_bound) {
-  return D >= 1 && D <= kMirrorMaxDims && coord_bound >= 1e-3 && coord_bound <= kMirrorMaxBound;
+  return D >= 1 && D <= kMirrorMaxDims && coord_bound >= kMirrorMinBound && coord_bound <= kMirrorMaxBound;
 }
 
 rkh_status launch_mirror_fill(hipStream_t s, void* d_mirror, uint64_t capacity_rows) {
@@ -460,21 +463,22 @@ rkh_status launch_mirror_fill(hipStream_t s, void* d_mirror, uint64_t capacity_r
   return RKH_OK;
 }
 
-rkh_status launch_mirror_build(hipStream_t s, void* d_mirror, const double* d_pos, uint64_t n, int D, int DP,
+rkh_status launch_mirror_build(hipStream_t s, void* d_mirror, const double* d_pos, uint64_t n, int D, int DP, double scale,
                                uint32_t* d_dx_max_bits) {
   if (n == 0) return RKH_OK;
   hipLaunchKernelGGL(mirror_build_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, static_cast<uint4*>(d_mirror),
-                     d_pos, n, D, DP, d_dx_max_bits);
+                     d_pos, n, D, DP, scale, d_dx_max_bits);
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
 
 // The launches of a round's NN search over the mirrors: B operands, pass 1, thresholds, pass 2, exact resolution.
 // d_yblock_base: [n_problems + 1] exclusive prefix of ceil(B_p / nn1_mirror_queries()); n_upper / B_upper (host bounds)
-// only size the grids; x_norm_bound >= |x| for every vertex.  ev0 / ev1 bracket all five launches.
+// only size the grids; x_norm_bound >= |x| for every vertex; scale = the mirrors' prescale (mirror_prescale of the
+// coordinate bound they were written with).  ev0 / ev1 bracket all five launches.
 rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32_t n_problems, uint64_t n_upper,
-                             uint32_t B_upper, double x_norm_bound, const uint32_t* d_yblock_base, bool open_lists,
-                             hipEvent_t ev0, hipEvent_t ev1) {
+                             uint32_t B_upper, double x_norm_bound, double scale, const uint32_t* d_yblock_base,
+                             bool open_lists, hipEvent_t ev0, hipEvent_t ev1) {
   if (B_upper == 0 || n_problems == 0) return RKH_OK;
   if (B_upper > 0xFFFFu) open_lists = false;  // (list entries are 16-bit query numbers; a planner's batch is <= 4096)
   const uint32_t gy = (B_upper + kMirQueries - 1) / kMirQueries;
@@ -488,11 +492,11 @@ rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32
   const dim3 qgrid((B_upper + 255) / 256, n_problems);
   nn_set_last_kernel_name("nn1_mirror_kernel");
   if (ev0) (void)hipEventRecord(ev0, s);
-  hipLaunchKernelGGL(nn1_mirror_prep_kernel, qgrid, dim3(256), 0, s, d_table, D);
+  hipLaunchKernelGGL(nn1_mirror_prep_kernel, qgrid, dim3(256), 0, s, d_table, D, scale);
   hipLaunchKernelGGL((nn1_mirror_kernel<1>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx),
                      0u);
   hipLaunchKernelGGL(nn1_mirror_thr_kernel, open_lists ? dim3(1, n_problems) : qgrid, dim3(256), 0, s, d_table, uint32_t(gx),
-                     x_norm_bound, open_lists ? 1u : 0u);
+                     x_norm_bound * scale, open_lists ? 1u : 0u);
   hipLaunchKernelGGL((nn1_mirror_kernel<2>), grid, dim3(kMirThreads), 0, s, d_table, d_yblock_base, n_problems, uint32_t(gx),
                      open_lists ? 1u : 0u);
   const dim3 rgrid((B_upper + 15) / 16, n_problems);
@@ -562,8 +566,9 @@ extern "C" rkh_status rkh_diag_nn_mirror_query(rkh_ctx* ctx, const double* pts, 
   nn1_mirror_carve(d_scratch.get(), Bp, &a);
   RKH_HIP(hipMemcpy(d_tab.get(), &a, sizeof(a), hipMemcpyHostToDevice));
   RKH_TRY(launch_mirror_fill(s, d_mirror.get(), n));
-  RKH_TRY(launch_mirror_build(s, d_mirror.get(), d_pos.get(), n, D, DP, d_dx.get()));
-  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, d_yb.get(),
+  const double scale = mirror_prescale(coord_bound);
+  RKH_TRY(launch_mirror_build(s, d_mirror.get(), d_pos.get(), n, D, DP, scale, d_dx.get()));
+  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, scale, d_yb.get(),
                             nn1_mirror_open_lists(), nullptr, nullptr));
   RKH_HIP(hipStreamSynchronize(s));
   RKH_HIP(hipMemcpy(idx, d_idx.get(), size_t(B) * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -81,6 +81,7 @@ struct ProblemDev {  // device pointers of one problem
   uint32_t* round_n;  // profiling: vertex count at the start of each round (may be null)
   uint4* mirror;      // half-precision mirror of the tree rows (nn_mirror.h), or null
   uint32_t* dx_max_bits;  // its running maximum of |x - x_h|
+  double mirror_scale;    // its prescale (mirror_prescale of the planner's coordinate bound)
   // the goal probes: the query's goal state, the results (indexed by vertex - 1), and the list of the open ones in vertex
   // order -- the probe EdgeIO's src_idx ([b_max + kProbeGranule], round_plan.h: the granule rule)
   const double* goal;
@@ -461,7 +462,7 @@ __global__ __launch_bounds__(256) void commit_kernel(const ProblemDev* __restric
         if (a) {
           const uint32_t row = n0 + incl - 1;
           for (int d = 0; d < DP; ++d) pr.tree[uint64_t(row) * DP + d] = d < D ? pr.x_out[uint64_t(b) * D + d] : 0.0;
-          if (pr.mirror) mirror_store_row(pr.mirror, row, pr.x_out + uint64_t(b) * D, D, pr.dx_max_bits);
+          if (pr.mirror) mirror_store_row(pr.mirror, row, pr.x_out + uint64_t(b) * D, D, pr.mirror_scale, pr.dx_max_bits);
           pr.parent[row] = pr.nn_idx[b];
           pr.node_sample[row] = s0 + b;
           if (o) {
@@ -664,6 +665,7 @@ struct ProblemInit {  // one problem's row of the init table
   uint4* mirror;          // pad rows everywhere, then the root's row
   uint32_t* dx_max_bits;
   uint64_t mirror_frags;  // 16-byte fragments of the mirror
+  double mirror_scale;    // the prescale its rows are written with
   uint32_t seed, pad;
   double start[RKH_MAX_STATE], goal_x[RKH_MAX_STATE];
 };
@@ -696,7 +698,7 @@ __global__ __launch_bounds__(256) void planner_init_kernel(const ProblemInit* __
     pi.mt[kMtN] = uint32_t(kMtN);
   }
   __syncthreads();  // the error word is zero before the root's row raises it
-  if (tid == 0 && pi.mirror) mirror_store_row(pi.mirror, 0, pi.start, D, pi.dx_max_bits);
+  if (tid == 0 && pi.mirror) mirror_store_row(pi.mirror, 0, pi.start, D, pi.mirror_scale, pi.dx_max_bits);
 }
 
 }  // namespace rkh
@@ -797,6 +799,7 @@ struct rkh_planner {
   EdgeIO* d_io_steer = nullptr;
   EdgeIO* d_io_probe = nullptr;
   bool nn_mirror = false;  // the NN search of a round runs over the trees' half-precision mirrors (nn_mirror.hip)
+  double mirror_scale = 1.0;  // ... written in units of this power of two (mirror_prescale(coord_bound))
   bool nn_open = true;     // ... its second pass only where a query is open (RKH_NN_MIRROR_OPEN)
   bool fixup_tiled = true; // the fix-up stages accepted end states in LDS (RKH_FIXUP_TILED; 0: one wave per candidate)
   double x_norm_bound = 0.0;  // >= |x| of every vertex (hyperbox corners, start states)
@@ -1079,8 +1082,8 @@ rkh_status enqueue_round(rkh_planner* p) {
   hipLaunchKernelGGL(round_begin_kernel, dim3(1), dim3(256), 0, s, round_begin_args(p, slot, fit, plan));
   // 1. NN sweep of every problem's samples over its snapshot
   rkh_status st = p->nn_mirror
-                      ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->d_nn_base,
-                                          p->nn_open, ev0, ev1)
+                      ? launch_nn1_mirror(s, p->D, p->d_nn_args, p->P, p->max_n_ub, batch_ub, p->x_norm_bound, p->mirror_scale,
+                                          p->d_nn_base, p->nn_open, ev0, ev1)
                       : launch_nn1(s, p->D, NnArgs(), p->d_nn_args, p->P, p->max_capacity, batch_ub, p->part_blocks, ev0,
                                    ev1, p->coord_bound, p->d_nn_base, true);
   if (st != RKH_OK) return st;
@@ -1123,6 +1126,7 @@ ProblemDev problem_dev(const rkh_planner* p, uint32_t i) {
   pd.round_n = q.d_round_n;
   pd.mirror = static_cast<uint4*>(q.d_mirror);
   pd.dx_max_bits = q.dx_max_bits;
+  pd.mirror_scale = p->mirror_scale;
   pd.goal = q.d_goal;
   pd.goal_dist = q.d_goal_dist;
   pd.probe_list = q.d_probe_list;
@@ -1302,6 +1306,7 @@ rkh_status setup_space(rkh_planner* p, const rkh_dyn_space* space, const rkh_qs_
   }
   p->x_norm_bound = std::sqrt(p->x_norm_bound) * (1.0 + 1e-9);
   p->nn_mirror = nn1_mirror_applies(p->D, p->coord_bound);
+  if (p->nn_mirror) p->mirror_scale = mirror_prescale(p->coord_bound);
   return RKH_OK;
 }
 
@@ -1568,6 +1573,7 @@ void fill_upload_image(rkh_planner* p) {
     pi.mirror = static_cast<uint4*>(q.d_mirror);
     pi.dx_max_bits = q.dx_max_bits;
     pi.mirror_frags = q.d_mirror ? nn1_mirror_bytes(q.capacity) / sizeof(uint4) : 0;
+    pi.mirror_scale = p->mirror_scale;
     pi.seed = uint32_t(q.prm.seed);
     for (int d = 0; d < p->D; ++d) {
       pi.start[d] = q.prm.start[d];

@@ -94,11 +94,11 @@ void nn1_mirror_carve(void* base, uint32_t b_max, NnArgs* a);
 bool nn1_mirror_applies(int D, double coord_bound);
 bool nn1_mirror_open_lists();  // RKH_NN_MIRROR_OPEN (default on)
 rkh_status launch_mirror_fill(hipStream_t s, void* d_mirror, uint64_t capacity_rows);
-rkh_status launch_mirror_build(hipStream_t s, void* d_mirror, const double* d_pos, uint64_t n, int D, int DP,
+rkh_status launch_mirror_build(hipStream_t s, void* d_mirror, const double* d_pos, uint64_t n, int D, int DP, double scale,
                                uint32_t* d_dx_max_bits);
 rkh_status launch_nn1_mirror(hipStream_t s, int D, const NnArgs* d_table, uint32_t n_problems, uint64_t n_upper,
-                             uint32_t B_upper, double x_norm_bound, const uint32_t* d_yblock_base, bool open_lists,
-                             hipEvent_t ev0, hipEvent_t ev1);
+                             uint32_t B_upper, double x_norm_bound, double scale, const uint32_t* d_yblock_base,
+                             bool open_lists, hipEvent_t ev0, hipEvent_t ev1);
 int nn_padded_dims(int D);
 rkh_status launch_nn1(hipStream_t s, int D, const NnArgs& single, const NnArgs* d_table, uint32_t n_problems,
                       uint64_t n_upper, uint32_t B, uint32_t part_capacity_blocks, hipEvent_t ev0 = nullptr,

@@ -87,6 +87,40 @@ def test_nn1_single_precision_prefilters_are_bit_exact(L, ctx, oracle, D, n, B, 
     assert np.array_equal(dist, rdist)
 
 
+@pytest.mark.parametrize("bound,spread", [(2e-3, 2e-3), (1e3, 1e3), (1e-6, 1e-6), (1e6, 1e6), (1.0, 0.002), (1e3, np.pi)])
+@pytest.mark.parametrize("D,n,B,expect", [(12, 30000, 300, "nn1_sweep_bf16_kernel"), (3, 5000, 1000, "nn1_sweep_mfma_kernel"),
+                                           (24, 4000, 48, "nn1_sweep_f32_kernel"), (12, 70001, 8, "nn1_few_mfma_kernel")])
+def test_nn1_single_precision_prefilters_at_other_bounds(L, ctx, oracle, D, n, B, expect, bound, spread):
+    """The pre-filters of nn_sweep.hip take every problem the mirror sweep's gate turns away.  One shape per kernel, the
+    adversarial cloud of the test above scaled to `spread`, under promised bounds far from pi: small and large ones the
+    cloud fills, the two ends of the pre-filters' own gate [1e-6, 1e6], and LOOSE promises -- a cloud 500 and 300 times
+    smaller than its bound, where the band is wide against the cloud and candidate lists overflow.  The kernel name is
+    asserted: no case passes by falling back to the fp64 sweep."""
+    rng = np.random.default_rng(7 * D + n + B)
+    pts = rng.uniform(-spread, spread, size=(n, D))
+    dup = rng.integers(0, n // 2, size=n // 50)
+    pts[n // 2 + np.arange(len(dup))] = pts[dup]                       # exact duplicates at higher indices
+    near = rng.integers(0, n // 2, size=n // 50)
+    pts[n - 1 - np.arange(len(near))] = np.clip(np.nextafter(pts[near], np.inf), -bound, bound)  # one ulp away
+    q = rng.uniform(-spread, spread, size=(B, D))
+    q[::7] = pts[rng.integers(0, n, size=len(q[::7]))]                 # queries on vertices
+    q[1::7] = np.clip(pts[dup[rng.integers(0, len(dup), size=len(q[1::7]))]] + rng.normal(0, 1e-9 * spread, size=(len(q[1::7]), D)),
+                      -bound, bound)
+    pts[100:124] = pts[100]  # more coincident vertices than a lane's candidate list holds
+    pts[300:400:7] = pts[100]
+    q[2 % B] = np.clip(pts[100] + 1e-9 * spread, -bound, bound)
+    q[3 % B] = pts[100]
+    assert np.all(np.abs(pts) <= bound) and np.all(np.abs(q) <= bound)
+    nn = L.HipNeighborSearch(ctx, D, n + 10)
+    nn.added_vertices(pts)
+    nn.set_coord_bound(bound)
+    idx, dist = nn.nearest(q)
+    assert nn.kernel_name() == expect
+    ridx, rdist = oracle.nn1(q, pts)
+    assert np.array_equal(idx, ridx)
+    assert np.array_equal(dist, rdist)
+
+
 @pytest.mark.parametrize("D,n,B,bound", [(12, 30000, 300, np.pi), (12, 777, 129, np.pi), (12, 1, 5, np.pi), (12, 33, 1, 3.0),
                                          (6, 100000, 500, np.pi), (3, 5000, 1000, 1.0), (2, 300, 37, 0.5), (7, 5000, 64, 2.0),
                                          (12, 65536, 385, 30.0), (12, 200000, 777, np.pi), (8, 40000, 32, 0.01)])
@@ -96,7 +130,9 @@ def test_nn1_mirror_sweep_is_bit_exact(L, ctx, oracle, D, n, B, bound):
     those of the linear search.  The cloud contains exact duplicates (ties resolve to the lower index), near-duplicates
     one ulp apart, queries sitting on vertices, queries 1e-9 away from duplicated vertices, and more coincident vertices
     than a query's candidate list holds (the resolve kernel's exact scan); sizes cover one row, partial slabs, several
-    query blocks (B > 384) and coordinate bounds from 0.01 to 30."""
+    query blocks (B > 384) and coordinate bounds from 0.5 to 30.  The one cloud at bound 0.01 is too sparse (40000 rows
+    in 8-D) to say anything about small bounds: dense clouds at the small end of the admitted range, clouds far smaller
+    than their bound and the ends of the gate are in tests/test_nn_mirror_bounds_gpu.py."""
     rng = np.random.default_rng(11 * D + n + B)
     pts = rng.uniform(-bound, bound, size=(n, D))
     q = rng.uniform(-bound, bound, size=(B, D))
@@ -1575,6 +1611,32 @@ def test_reference_hidim_scenario_without_obstacles(L, ctx, oracle, D):
     for k in ("pos", "edge_u", "edge_v", "edge_w", "density"):
         assert np.array_equal(g[k], rg[k]), k
     pr.close()
+
+
+def test_rrt_over_a_small_box_grows_the_oracles_tree(L, ctx, oracle):
+    """The planner switches the mirror sweep on from the hyperbox alone (|coordinate| bound in [1e-3, 32]).  A 2-D box of
+    side 0.004 with 3000 vertices has nearest neighbours at d^2 ~ 1e-9 and squared norms ~ 1e-5: both far below what a
+    half holds unless the mirror is prescaled, and a sweep that loses the nearest vertex grows another tree without any
+    error.  Same assertions as the unit hypercube above, and the rounds must have run the mirror sweep: the test does
+    not pass by the planner taking another one."""
+    side = 0.004
+    hd = scenarios.make_hidim(2, side=side)
+    sc, osc = L.Scene(ctx, hd), oracle.OracleScene(hd)
+    lo, hi, mi = hd.meta["lower"], hd.meta["upper"], hd.meta["min_interval"]
+    assert np.array_equal(hi, [side, side]) and mi == 0.05 * side and np.array_equal(hd.start, [0.05 * side] * 2)
+    qs = L.make_qs_space(2, lo, hi, mi)
+    prm = hd.rrt_params(seed=2, max_vertices=3000, steer_tol=hd.meta["steer_tol"], conn_tol=hd.meta["conn_tol"])
+    rc, ro, rt = osc.rrt_qs(lo, hi, mi, prm)
+    assert ro.num_vertices >= 3000 and ro.num_solutions > 0
+    pl = L.RrtPlanner(sc, prm, qs=qs)
+    st, tree = pl.solve_planning_query(), pl.tree()
+    assert L.load().rkh_nn_kernel_name().decode() == "nn1_mirror_kernel"
+    assert (st.num_vertices, st.iterations, st.edges_checked, st.num_solutions) == (ro.num_vertices, ro.iterations,
+                                                                                  ro.edges_checked, ro.num_solutions)
+    for k in ("nn_seq", "accept", "parent", "pos", "goal_dist"):
+        assert np.array_equal(tree[k], rt[k]), k
+    assert st.best_cost == ro.best_cost
+    pl.close()
 
 
 def test_planning_in_an_obstacle_course_read_from_an_rkx_archive(L, ctx, oracle, tmp_path):
