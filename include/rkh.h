@@ -98,7 +98,8 @@ rkh_status rkh_nn_append(rkh_nn* nn, const double* pts, uint64_t n);
 rkh_status rkh_nn_query1(rkh_nn* nn, const double* q, uint32_t B, uint32_t* idx, double* dist);
 /* k-NN with radius: idx/dist are [B][k], nearest first, padded with 0xFFFFFFFF / +inf; count[B].
  * Among exactly equal distances the reference's order is std::heap-defined; this returns
- * ascending (distance, index). */
+ * ascending (distance, index).  k in [1, 1024] (else RKH_ERR_BAD_ARG).  RKH_ERR_CAPACITY only for coincident
+ * vertices: more than 1024 vertices, besides the k nearest, at exactly the k-th nearest distance. */
 rkh_status rkh_nn_queryk(rkh_nn* nn, const double* q, uint32_t B, uint32_t k, double radius, uint32_t* idx,
                          double* dist, uint32_t* count);
 /* Device-pointer variants for callers that keep queries / results in HBM (bench, planner).

@@ -17,6 +17,12 @@ extern "C" {
 rkh_status rkh_nn_set_events(rkh_nn* nn, void* ev_start, void* ev_stop);
 /* Name of the sweep kernel the last query launched (for profile bookkeeping). */
 const char* rkh_nn_kernel_name(void);
+/* Exact retries of the k-NN search launched in this process so far: rkh_nn_queryk / rkh_prm_query_paths calls and
+ * graph-planner steps whose first pass overflowed a candidate list (reak_amd/csrc/knn_plan.h).  RKH_KNN_LIST_CAP=N in the
+ * environment -- read by every rkh_nn_queryk* and rkh_prm_query_paths call, and by a graph planner at create --
+ * shortens the candidate lists to max(N, 2 k) slots, rounded up to a power of two: first passes then overflow on
+ * ordinary data, which is how the tests make the planners take the retry.  Results do not depend on it. */
+uint64_t rkh_diag_knn_retries(void);
 /* The mapping the steer plan chose at this thread's last rkh_propagate or rkh_planner_create* over a dynamic space:
  * "auto", "duo", "wave", "wave16", "pair", "planar" or "prismatic" (one wave per edge, prismatic form). */
 const char* rkh_steer_mapping_name(void);

@@ -174,7 +174,7 @@ struct GraphBatch {
   int D = 0, DP = 0;
   uint32_t P = 0, kmax = 0, emax = 0;
   std::vector<GbProblem> prob;
-  static constexpr size_t kKnnWsBytes = 128 * 1024;
+  static constexpr size_t kKnnWsBytes = kKnnBatchWsBytes;  // knn_plan.h: holds every plan of one query
   // command block: [KnnArgs x P][EdgeIO x P][EdgeIO (stage A) x P][GbAux x P], pinned host copy + device copy
   PinnedBuffer<unsigned char> h_cmd;
   DeviceBuffer<unsigned char> d_cmd;
@@ -196,6 +196,7 @@ struct GraphBatch {
          off_aaccept = 0, off_axout = 0;
   bool any_knn = false, any_edges = false, any_append = false, any_stage_a = false;
   uint64_t steps = 0;
+  uint32_t knn_list_cap = 0;  // RKH_KNN_LIST_CAP at init (rkh_diag.h): shorter candidate lists, same results
   std::vector<uint32_t> knn_k;       // per problem: k, n and radius of the last cmd_knn
   std::vector<uint64_t> knn_n;
   std::vector<double> knn_radius;
@@ -274,6 +275,10 @@ struct GraphBatch {
 
   // one device step: command upload, the launches the commands ask for, result download
   rkh_status run();
+  // run()'s part behind the k-NN search (it runs a second time after an exact k-NN retry), and whether a search of the
+  // results just downloaded overflowed its candidate list
+  rkh_status run_after_knn();
+  bool knn_overflowed() const;
 };
 
 }  // namespace rkh

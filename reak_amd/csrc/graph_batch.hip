@@ -116,6 +116,7 @@ rkh_status GraphBatch::init_common(rkh_scene* sc, int D_, uint32_t n_problems, c
   D = D_;
   DP = nn_padded_dims(D);
   P = n_problems;
+  knn_list_cap = knn_list_cap_from_env();
   kmax = kmax_ + 1;  // one neighbour more than asked for: a tie across the k-th place must be visible (neighbours())
   emax = 2 * kmax;
   knn_k.assign(P, 0);
@@ -357,7 +358,7 @@ rkh_status GraphBatch::cmd_knn(uint32_t i, const double* query, uint64_t n, uint
   for (int d = 0; d < RKH_MAX_DOF; ++d) h_aux[i].query[d] = d < D ? query[d] : 0.0;
   KnnArgs& a = h_knn[i];
   size_t bytes = 0;
-  rkh_status st = knn_plan(n, 1, k, &a.ws, &bytes);
+  rkh_status st = knn_plan_or_error(n, 1, k, &a.ws, &bytes, knn_list_cap);
   if (st != RKH_OK) return st;
   if (bytes > kKnnWsBytes) {
     set_error("graph batch: k-NN workspace too small");
@@ -426,6 +427,31 @@ rkh_status GraphBatch::run() {
     rkh_status st = launch_nnk_table(s, D, d_knn, h_knn, P);
     if (st != RKH_OK) return st;
   }
+  RKH_TRY(run_after_knn());
+  ++steps;
+  if (!knn_overflowed()) return RKH_OK;
+  // A problem's first k-NN pass named more vertices than its list holds: the exact retry (knn_plan.h) redoes those
+  // problems' searches -- every other problem's neighbourhood is written again as it was -- and what follows the search
+  // in a step, a function of the neighbourhoods and of this step's commands alone, runs again on the results.  Rare: a
+  // step without an overflow launches nothing of this.
+  RKH_TRY(launch_nnk_table_retry(stream, D, d_knn, h_knn, P));
+  RKH_TRY(run_after_knn());
+  if (knn_overflowed()) {
+    set_error(std::string("graph batch: ") + knn_capacity_text());
+    return RKH_ERR_CAPACITY;
+  }
+  return RKH_OK;
+}
+
+bool GraphBatch::knn_overflowed() const {
+  for (uint32_t i = 0; i < P; ++i)
+    if (h_knn[i].B && overflow(i)) return true;
+  return false;
+}
+
+// the part of a step behind the k-NN search: edge lists, edge walks, and the results' way to the host
+rkh_status GraphBatch::run_after_knn() {
+  hipStream_t s = stream;
   hipLaunchKernelGGL(gb_list_kernel, dim3(P), dim3(64), 0, s, d_aux);
   if (any_edges) {
     // one wave per edge: a step holds at most 2 k candidates per problem, far from filling the two-lanes mappings
@@ -449,12 +475,6 @@ rkh_status GraphBatch::run() {
       }
     }
   }
-  ++steps;
-  for (uint32_t i = 0; i < P; ++i)
-    if (h_knn[i].B && overflow(i)) {
-      set_error("graph batch: k-NN candidate capacity exceeded");
-      return RKH_ERR_CAPACITY;
-    }
   return RKH_OK;
 }
 

@@ -12,12 +12,16 @@
 //   B. collect sweep : every vertex with d <= tau and d < radius is appended to the query's candidate list
 //                      (about 1.2 k entries when M >= 4k); exact: the true k nearest are all in the list
 //   C. select        : one block per query sorts its candidates by (distance, index) and writes the first k.
+// tau is a bound, not a promise (fewer than k finite subset minima: tau = +inf): a query whose list of cmax slots
+// overflowed is answered by the EXACT RETRY (knn_exact_tau_kernel below, then B and C again for that query alone),
+// which the callers launch only after they have seen the overflow word set (knn_plan.h: the guarantee).
 // Distances are the reference's left-to-right fp64 sums with a correctly rounded sqrt, so the returned set and
 // its order equal the CPU search's (among exactly equal distances the reference order is std::heap-defined; here
 // it is ascending index).  Same tile / broadcast structure as nn_sweep.hip; traffic is two passes over the rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 
@@ -28,11 +32,9 @@ namespace rkh {
 
 int nn_padded_dims(int D);
 
-static constexpr int kTileRows = 256;
-static constexpr int kThreads = 256;
-static constexpr int kSelMax = 8;  // a block contributes the ksel <= 8 smallest of its row-subset minima per query
-
-static inline int knn_query_block(uint32_t B) { return B <= 8 ? 8 : 32; }  // queries per block
+// the launch shape (gx, ksel, m_sub, cmax), the workspace and what the plan guarantees: knn_plan.h
+static constexpr int kTileRows = kKnnTileRows;
+static constexpr int kThreads = kKnnThreads;
 
 // MODE 0: bound sweep (per query, the kSel smallest of the block's R = 256/QB row-subset minima).
 // MODE 1: collect sweep (appends candidates).
@@ -226,71 +228,99 @@ __global__ __launch_bounds__(256) void knn_select_kernel(KnnArgs single, const K
   if (threadIdx.x == 0) out_cnt[qi] = found;
 }
 
-uint32_t next_pow2(uint32_t v) {
-  uint32_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-rkh_status knn_plan(uint64_t n, uint32_t B, uint32_t k, KnnWorkspace* ws, size_t* bytes) {
-  if (k == 0 || k > 1024) {
-    set_error("k-NN: k must be in [1, 1024]");
-    return RKH_ERR_BAD_ARG;
+// THE EXACT RETRY (knn_plan.h, the guarantee).  One block per query, after a first pass: a query whose list overflowed
+// (cnt > cmax) gets tau = the k-th smallest distance among the vertices with d < radius, found by bisection over the bit
+// patterns of the non-negative doubles -- 63 counting passes over the rows, no list, the same nn_exact_sq and sqrt as
+// the sweeps, so the bound is the very number the collect sweep compares with -- and an empty list; every other query
+// gets tau = -1, which no distance is below: the collect sweep that follows appends nothing to its list and the select
+// kernel writes its result again as it was.  Fewer than k vertices inside the radius: tau = +inf (they all fit).
+template <int DP>
+__global__ __launch_bounds__(kThreads) void knn_exact_tau_kernel(KnnArgs single, const KnnArgs* __restrict__ tab) {
+  const KnnArgs a = tab ? tab[blockIdx.z] : single;
+  const uint32_t qi = blockIdx.x;
+  if (qi >= a.B) return;
+  const int tid = threadIdx.x;
+  const bool redo = a.ws.cnt[qi] > a.ws.cmax;  // the same for the whole block
+  if (tid == 0 && qi == 0) *a.ws.overflow = 0;  // nobody sets it before the collect sweep
+  if (!redo) {
+    if (tid == 0) a.ws.tau[qi] = -1.0;
+    return;
   }
-  const uint32_t qb = knn_query_block(B);
-  const uint32_t gy = (B + qb - 1) / qb;
-  uint64_t tiles = (n + kTileRows - 1) / kTileRows;
-  if (tiles < 1) tiles = 1;
-  // enough subsets for a tight bound (M >= 4k) and enough blocks to fill the chip, but M <= 4096 (LDS sort)
-  uint64_t gx = std::max<uint64_t>((4ull * k + kSelMax - 1) / kSelMax, 2048 / gy);
-  if (gx > tiles) gx = tiles;
-  if (gx > 4096 / kSelMax) gx = 4096 / kSelMax;
-  ws->gx = uint32_t(gx);
-  // about 4k subset minima in total are plenty for a tight bound (the k-th smallest of M minima leaves ~ -M ln(1 - k/M)
-  // candidates); fewer minima = a shorter sort in knn_tau_kernel
-  uint32_t ksel = uint32_t((4ull * k + gx - 1) / gx);
-  if (ksel < 1) ksel = 1;
-  if (ksel > uint32_t(kSelMax)) ksel = kSelMax;
-  ws->ksel = ksel;
-  ws->m_sub = uint32_t(gx) * ksel;
-  ws->cmax = std::max<uint32_t>(2048, next_pow2(8 * k));
-  if (ws->cmax > 4096) ws->cmax = 4096;
-  *bytes = 256 + size_t(ws->m_sub) * B * 8 + size_t(B) * 8 + size_t(B) * 4 + size_t(B) * ws->cmax * 12 + 64;
-  return RKH_OK;
+  const double* __restrict__ pos = a.pos;
+  const uint64_t n = a.n;
+  const double radius = a.radius;
+  __shared__ uint32_t red[kThreads];
+  double qv[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) qv[d] = d < a.D ? a.q[uint64_t(qi) * a.D + d] : 0.0;
+  // vertices with d <= t and d < radius (the same value in every thread)
+  auto count_le = [&](double t) -> uint32_t {
+    uint32_t c = 0;
+    for (uint64_t row = tid; row < n; row += kThreads) {
+      const double* p = pos + row * DP;
+      const double dd = sqrt(nn_exact_sq<DP>([&](int d) { return qv[d] - p[d]; }));
+      c += (dd <= t && dd < radius) ? 1u : 0u;
+    }
+    red[tid] = c;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+      if (tid < h) red[tid] += red[tid + h];
+      __syncthreads();
+    }
+    const uint32_t total = red[0];
+    __syncthreads();
+    return total;
+  };
+  double t = INFINITY;
+  if (count_le(INFINITY) >= a.k) {
+    // every counted distance is finite (d < radius <= +inf): the answer is the smallest bit pattern with count >= k
+    unsigned long long lo = 0ull, hi = 0x7FEFFFFFFFFFFFFFull;  // +0 .. DBL_MAX
+    while (lo < hi) {
+      const unsigned long long mid = lo + (hi - lo) / 2;
+      if (count_le(__longlong_as_double((long long)mid)) >= a.k) hi = mid;
+      else lo = mid + 1;
+    }
+    t = __longlong_as_double((long long)lo);
+  }
+  if (tid == 0) {
+    a.ws.tau[qi] = t;
+    a.ws.cnt[qi] = 0;
+  }
 }
 
-void knn_carve(void* base, uint32_t B, KnnWorkspace* ws) {
-  unsigned char* p = static_cast<unsigned char*>(base);
-  ws->overflow = reinterpret_cast<uint32_t*>(p);
-  p += 256;
-  ws->sub = reinterpret_cast<double*>(p);
-  p += size_t(ws->m_sub) * B * 8;
-  ws->tau = reinterpret_cast<double*>(p);
-  p += size_t(B) * 8;
-  ws->cand_d = reinterpret_cast<double*>(p);
-  p += size_t(B) * ws->cmax * 8;
-  ws->cand_i = reinterpret_cast<uint32_t*>(p);
-  p += size_t(B) * ws->cmax * 4;
-  ws->cnt = reinterpret_cast<uint32_t*>(p);
-}
+struct KnnGrid {  // the grid of one job, or the largest of a table's jobs
+  uint32_t gx = 0, gy = 0, b_max = 0, m_pow2 = 0, cmax = 0, n_jobs = 0;
+};
 
 template <int DP>
-static void launch_nnk_dp(hipStream_t s, const KnnArgs& single, const KnnArgs* d_tab, uint32_t gx, uint32_t gy,
-                          uint32_t b_max, uint32_t m_pow2, uint32_t cmax, uint32_t n_jobs) {
-  dim3 grid(gx, gy, n_jobs), block(kThreads);
-  const bool few = knn_query_block(b_max) == 8;
-  if (few) hipLaunchKernelGGL((knn_sweep_kernel<DP, 8, 0>), grid, block, 0, s, single, d_tab);
-  else hipLaunchKernelGGL((knn_sweep_kernel<DP, 32, 0>), grid, block, 0, s, single, d_tab);
-  hipLaunchKernelGGL(knn_tau_kernel, dim3(b_max, 1, n_jobs), dim3(256), size_t(m_pow2) * 12, s, single, d_tab);
+static void launch_nnk_dp(hipStream_t s, const KnnArgs& single, const KnnArgs* d_tab, const KnnGrid& g, bool retry) {
+  dim3 grid(g.gx, g.gy, g.n_jobs), block(kThreads), per_query(g.b_max, 1, g.n_jobs);
+  const bool few = knn_query_block(g.b_max) == 8;
+  if (!retry) {
+    if (few) hipLaunchKernelGGL((knn_sweep_kernel<DP, 8, 0>), grid, block, 0, s, single, d_tab);
+    else hipLaunchKernelGGL((knn_sweep_kernel<DP, 32, 0>), grid, block, 0, s, single, d_tab);
+    hipLaunchKernelGGL(knn_tau_kernel, per_query, dim3(256), size_t(g.m_pow2) * 12, s, single, d_tab);
+  } else {
+    hipLaunchKernelGGL(knn_exact_tau_kernel<DP>, per_query, block, 0, s, single, d_tab);
+  }
   if (few) hipLaunchKernelGGL((knn_sweep_kernel<DP, 8, 1>), grid, block, 0, s, single, d_tab);
   else hipLaunchKernelGGL((knn_sweep_kernel<DP, 32, 1>), grid, block, 0, s, single, d_tab);
-  hipLaunchKernelGGL(knn_select_kernel, dim3(b_max, 1, n_jobs), dim3(256), size_t(cmax) * 12, s, single, d_tab);
+  hipLaunchKernelGGL(knn_select_kernel, per_query, dim3(256), size_t(g.cmax) * 12, s, single, d_tab);
 }
 
-static rkh_status launch_nnk_any(hipStream_t s, int D, const KnnArgs& single, const KnnArgs* d_tab, uint32_t gx,
-                                 uint32_t gy, uint32_t b_max, uint32_t m_pow2, uint32_t cmax, uint32_t n_jobs) {
+static std::atomic<uint64_t> g_knn_retries{0};
+uint64_t knn_retry_count() { return g_knn_retries.load(std::memory_order_relaxed); }
+
+uint32_t knn_list_cap_from_env() {
+  const char* e = getenv("RKH_KNN_LIST_CAP");
+  return e ? uint32_t(std::max(0, atoi(e))) : 0u;
+}
+
+static rkh_status launch_nnk_any(hipStream_t s, int D, const KnnArgs& single, const KnnArgs* d_tab, const KnnGrid& g,
+                                 bool retry) {
+  if (retry) g_knn_retries.fetch_add(1, std::memory_order_relaxed);
   const bool dims_ok = with_padded_dims(D, [&](auto dp) {
-    launch_nnk_dp<decltype(dp)::value>(s, single, d_tab, gx, gy, b_max, m_pow2, cmax, n_jobs);
+    launch_nnk_dp<decltype(dp)::value>(s, single, d_tab, g, retry);
   });
   if (!dims_ok) {
     set_error("k-NN: unsupported dimension");
@@ -300,8 +330,9 @@ static rkh_status launch_nnk_any(hipStream_t s, int D, const KnnArgs& single, co
   return RKH_OK;
 }
 
-rkh_status launch_nnk(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
-                      double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws) {
+static rkh_status launch_nnk_one(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
+                                 double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws,
+                                 bool retry) {
   if (B == 0) return RKH_OK;
   KnnArgs a;
   a.pos = st.d_pos;
@@ -316,21 +347,49 @@ rkh_status launch_nnk(hipStream_t s, const NnStore& st, uint64_t n, const double
   a.out_idx = d_idx;
   a.out_dist = d_dist;
   a.out_cnt = d_count;
-  return launch_nnk_any(s, st.D, a, nullptr, ws.gx, (B + knn_query_block(B) - 1) / knn_query_block(B), B, a.m_pow2, ws.cmax, 1);
+  KnnGrid g;
+  g.gx = ws.gx;
+  g.gy = (B + knn_query_block(B) - 1) / knn_query_block(B);
+  g.b_max = B;
+  g.m_pow2 = a.m_pow2;
+  g.cmax = ws.cmax;
+  g.n_jobs = 1;
+  return launch_nnk_any(s, st.D, a, nullptr, g, retry);
 }
 
-rkh_status launch_nnk_table(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs) {
-  uint32_t gx = 0, b_max = 0, m_pow2 = 0, cmax = 0;
+rkh_status launch_nnk(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
+                      double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws) {
+  return launch_nnk_one(s, st, n, d_q, B, k, radius, d_idx, d_dist, d_count, ws, false);
+}
+
+rkh_status launch_nnk_retry(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
+                            double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws) {
+  return launch_nnk_one(s, st, n, d_q, B, k, radius, d_idx, d_dist, d_count, ws, true);
+}
+
+static rkh_status launch_nnk_jobs(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs,
+                                  bool retry) {
+  KnnGrid g;
   for (uint32_t i = 0; i < n_jobs; ++i) {
     const KnnArgs& a = h_table[i];
     if (a.B == 0) continue;
-    gx = std::max(gx, a.ws.gx);
-    b_max = std::max(b_max, a.B);
-    m_pow2 = std::max(m_pow2, a.m_pow2);
-    cmax = std::max(cmax, a.ws.cmax);
+    g.gx = std::max(g.gx, a.ws.gx);
+    g.b_max = std::max(g.b_max, a.B);
+    g.m_pow2 = std::max(g.m_pow2, a.m_pow2);
+    g.cmax = std::max(g.cmax, a.ws.cmax);
   }
-  if (b_max == 0) return RKH_OK;
-  return launch_nnk_any(s, D, KnnArgs(), d_table, gx, (b_max + knn_query_block(b_max) - 1) / knn_query_block(b_max), b_max, m_pow2, cmax, n_jobs);
+  if (g.b_max == 0) return RKH_OK;
+  g.gy = (g.b_max + knn_query_block(g.b_max) - 1) / knn_query_block(g.b_max);
+  g.n_jobs = n_jobs;
+  return launch_nnk_any(s, D, KnnArgs(), d_table, g, retry);
+}
+
+rkh_status launch_nnk_table(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs) {
+  return launch_nnk_jobs(s, D, d_table, h_table, n_jobs, false);
+}
+
+rkh_status launch_nnk_table_retry(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs) {
+  return launch_nnk_jobs(s, D, d_table, h_table, n_jobs, true);
 }
 
 }  // namespace rkh

@@ -612,7 +612,7 @@ rkh_status rkh_prm_query_paths(rkh_prm* p, uint32_t problem, const double* start
   // 1. neighbourhoods: one k-NN launch for the 2B points (starts, then goals) over the problem's device rows
   KnnWorkspace ws;
   size_t ws_bytes = 0;
-  RKH_TRY(knn_plan(n, Q, k, &ws, &ws_bytes));
+  RKH_TRY(knn_plan_or_error(n, Q, k, &ws, &ws_bytes, knn_list_cap_from_env()));
   RKH_TRY(grow(p->d_knn_ws, ws_bytes));
   knn_carve(p->d_knn_ws.get(), Q, &ws);
   RKH_TRY(grow(p->d_qpts, size_t(Q) * D));
@@ -625,15 +625,21 @@ rkh_status rkh_prm_query_paths(rkh_prm* p, uint32_t problem, const double* start
                      p->d_kcnt.get(), ws));
   std::vector<uint32_t> kidx(size_t(Q) * k), kcnt(Q);
   std::vector<double> kdist(size_t(Q) * k);
-  uint32_t overflow = 0;  // first word of the k-NN workspace
-  RKH_HIP(hipMemcpyAsync(kidx.data(), p->d_kidx.get(), kidx.size() * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(kdist.data(), p->d_kdist.get(), kdist.size() * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(kcnt.data(), p->d_kcnt.get(), size_t(Q) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(&overflow, p->d_knn_ws.get(), 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  if (overflow) {
-    set_error("rkh_prm_query_paths: k-NN candidate capacity exceeded (too many vertices within the bound; shrink the radius)");
-    return RKH_ERR_CAPACITY;
+  // a first pass whose bound named more vertices than a list holds is followed by the exact retry (knn_plan.h)
+  for (int pass = 0;; ++pass) {
+    uint32_t overflow = 0;  // first word of the k-NN workspace
+    RKH_HIP(hipMemcpyAsync(kidx.data(), p->d_kidx.get(), kidx.size() * 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(kdist.data(), p->d_kdist.get(), kdist.size() * 8, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(kcnt.data(), p->d_kcnt.get(), size_t(Q) * 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(&overflow, p->d_knn_ws.get(), 4, hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipStreamSynchronize(s));
+    if (!overflow) break;
+    if (pass == 1) {
+      set_error(std::string("rkh_prm_query_paths: ") + knn_capacity_text());
+      return RKH_ERR_CAPACITY;
+    }
+    RKH_TRY(launch_nnk_retry(s, gb.prob[problem].tree, n, p->d_qpts.get(), Q, k, radius, p->d_kidx.get(),
+                             p->d_kdist.get(), p->d_kcnt.get(), ws));
   }
   // 2. connections: every candidate edge in the direction of travel (start -> u, u -> goal), one edge-walk launch.  A point
   //    that coincides with a roadmap vertex is connected to it with weight 0 (a walk of no length is never accepted).

@@ -323,7 +323,7 @@ rkh_status rkh_nn_queryk_async(rkh_nn* nn, const double* d_q, uint32_t B, uint32
   if (B == 0) return RKH_OK;
   KnnWorkspace ws;
   size_t bytes = 0;
-  RKH_TRY(knn_plan(nn->n, B, k, &ws, &bytes));
+  RKH_TRY(knn_plan_or_error(nn->n, B, k, &ws, &bytes, knn_list_cap_from_env()));
   if (bytes > nn->d_knn_ws.size()) RKH_TRY(nn->d_knn_ws.alloc(bytes));
   knn_carve(nn->d_knn_ws.get(), B, &ws);
   RKH_TRY(launch_nnk(nn->ctx->stream, nn->st, nn->n, d_q, B, k, radius, d_idx, d_dist, d_count, ws));
@@ -338,17 +338,25 @@ rkh_status rkh_nn_queryk(rkh_nn* nn, const double* q, uint32_t B, uint32_t k, do
   hipStream_t s = nn->ctx->stream;
   RKH_HIP(hipMemcpyAsync(nn->d_q.get(), q, uint64_t(B) * nn->st.D * sizeof(double), hipMemcpyHostToDevice, s));
   RKH_TRY(rkh_nn_queryk_async(nn, nn->d_q.get(), B, k, radius, nn->d_idx.get(), nn->d_dist.get(), nn->d_count.get()));
-  RKH_HIP(hipMemcpyAsync(idx, nn->d_idx.get(), uint64_t(B) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(dist, nn->d_dist.get(), uint64_t(B) * k * sizeof(double), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(count, nn->d_count.get(), B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  uint32_t overflow = 0;  // first word of the k-NN workspace
-  RKH_HIP(hipMemcpyAsync(&overflow, nn->d_knn_ws.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  if (overflow) {
-    set_error("rkh_nn_queryk: candidate capacity exceeded (too many vertices within the bound; shrink the radius)");
-    return RKH_ERR_CAPACITY;
+  // a first pass whose bound named more vertices than a list holds is followed by the exact retry (knn_plan.h)
+  for (int pass = 0;; ++pass) {
+    RKH_HIP(hipMemcpyAsync(idx, nn->d_idx.get(), uint64_t(B) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(dist, nn->d_dist.get(), uint64_t(B) * k * sizeof(double), hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipMemcpyAsync(count, nn->d_count.get(), B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    uint32_t overflow = 0;  // first word of the k-NN workspace
+    RKH_HIP(hipMemcpyAsync(&overflow, nn->d_knn_ws.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipStreamSynchronize(s));
+    if (!overflow) return RKH_OK;
+    if (pass == 1) break;
+    KnnWorkspace ws;
+    size_t bytes = 0;
+    RKH_TRY(knn_plan_or_error(nn->n, B, k, &ws, &bytes, knn_list_cap_from_env()));
+    knn_carve(nn->d_knn_ws.get(), B, &ws);
+    RKH_TRY(launch_nnk_retry(s, nn->st, nn->n, nn->d_q.get(), B, k, radius, nn->d_idx.get(), nn->d_dist.get(),
+                             nn->d_count.get(), ws));
   }
-  return RKH_OK;
+  set_error(std::string("rkh_nn_queryk: ") + knn_capacity_text());
+  return RKH_ERR_CAPACITY;
 }
 
 rkh_status rkh_nn_fill_uniform(rkh_nn* nn, uint64_t n, uint64_t seed) {
@@ -377,5 +385,6 @@ rkh_status rkh_nn_set_events(rkh_nn* nn, void* ev_start, void* ev_stop) {
 }
 
 const char* rkh_nn_kernel_name(void) { return nn_last_kernel_name(); }
+uint64_t rkh_diag_knn_retries(void) { return knn_retry_count(); }
 
 }  // extern "C"

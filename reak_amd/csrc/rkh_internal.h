@@ -13,6 +13,7 @@
 #include "../../include/rkh.h"
 #include "../../include/rkh_diag.h"
 #include "device_buffer.h"
+#include "knn_plan.h"    // KnnWorkspace, knn_plan, knn_carve
 #include "steer_edge.h"  // EdgeMode, EdgeIO, KernelGate, kMaxSteps
 
 namespace rkh {
@@ -111,22 +112,35 @@ uint32_t nn1_mfma_queries();
 // then run the single-precision pre-filter variant (identical results).
 // Partial minima per query (row slices) that launch_nn1 may write for at most B_max queries per problem.
 uint32_t nn1_partial_blocks(int D, uint64_t n_upper, uint32_t B_max, uint32_t n_problems, double coord_bound);
-// k-NN with radius (knn_sweep.hip).  ws: device workspace from knn_workspace_bytes(); *d_overflow is set (non-zero)
-// if a query met more than the candidate capacity (pathological ties).
-struct KnnWorkspace {
-  double* sub = nullptr;       // [M][Bpad] per-subrange minima (phase A)
-  double* tau = nullptr;       // [B] inclusive bound on the k-th smallest distance
-  uint32_t* cnt = nullptr;     // [B] candidates collected
-  double* cand_d = nullptr;    // [B][cmax]
-  uint32_t* cand_i = nullptr;  // [B][cmax]
-  uint32_t* overflow = nullptr;
-  uint32_t cmax = 0, m_sub = 0, gx = 0;
-  uint32_t ksel = 8;           // subset minima a block contributes per query (1..8)
-};
-rkh_status knn_plan(uint64_t n, uint32_t B, uint32_t k, KnnWorkspace* ws, size_t* bytes);
-void knn_carve(void* base, uint32_t B, KnnWorkspace* ws);
+// k-NN with radius (knn_sweep.hip).  ws: device workspace planned and carved by knn_plan.h (KnnWorkspace, knn_plan,
+// knn_carve); *ws.overflow is set (non-zero) if a query met more than the candidate capacity.  After a first pass
+// (launch_nnk / launch_nnk_table) that left the word set, the caller runs the exact retry of the same job(s) once
+// (launch_nnk_retry / launch_nnk_table_retry: three launches that redo only the queries whose list overflowed and
+// leave every other query's result as it is); the word is then set only for coincident vertices (knn_plan.h).
+// list_cap > 0 (knn_list_cap_from_env(): RKH_KNN_LIST_CAP, rkh_diag.h) shortens the candidate lists to
+// next_pow2(max(list_cap, 2 k)) slots inside the workspace planned for the full ones: first passes then overflow on
+// ordinary data and the exact retry answers, with the same results.
+uint32_t knn_list_cap_from_env();  // 0: not set
+uint64_t knn_retry_count();        // exact retries launched in this process
+inline rkh_status knn_plan_or_error(uint64_t n, uint32_t B, uint32_t k, KnnWorkspace* ws, size_t* bytes,
+                                    uint32_t list_cap = 0) {
+  const rkh_status st = knn_plan(n, B, k, ws, bytes);
+  if (st != RKH_OK) {
+    set_error("k-NN: k must be in [1, 1024]");
+    return st;
+  }
+  if (list_cap) ws->cmax = std::min(ws->cmax, next_pow2(std::max(list_cap, 2 * k)));
+  return st;
+}
+// what a caller reports when the word is still set after the retry
+inline const char* knn_capacity_text() {
+  return "k-NN candidate capacity exceeded: too many vertices at exactly the k-th nearest distance (coincident "
+         "vertices; a smaller k or radius that ends before them avoids it)";
+}
 rkh_status launch_nnk(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
                       double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws);
+rkh_status launch_nnk_retry(hipStream_t s, const NnStore& st, uint64_t n, const double* d_q, uint32_t B, uint32_t k,
+                            double radius, uint32_t* d_idx, double* d_dist, uint32_t* d_count, const KnnWorkspace& ws);
 // One k-NN job (one tree, B queries).  A launch serves either one job (by value) or a device table of jobs
 // (blockIdx.z = job; RRT* / PRM batches: one query per problem, all problems in the same four launches).
 struct KnnArgs {
@@ -142,9 +156,9 @@ struct KnnArgs {
   double* out_dist = nullptr;
   uint32_t* out_cnt = nullptr;  // [B]
 };
-uint32_t next_pow2(uint32_t v);
 // Launch a table of jobs (d_table on the device, h_table its host copy for grid sizing).  All jobs share D.
 rkh_status launch_nnk_table(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs);
+rkh_status launch_nnk_table_retry(hipStream_t s, int D, const KnnArgs* d_table, const KnnArgs* h_table, uint32_t n_jobs);
 rkh_status launch_fill_uniform(hipStream_t s, const NnStore& st, uint64_t n, uint64_t seed);
 
 // ---- scene (propagate.hip) ---------------------------------------------------------------------

@@ -78,6 +78,7 @@ EXPORTS = [
     "rkh_ctx_release_cached_memory", "rkh_diag_planner_sample_cap",
     "rkh_nn_create", "rkh_nn_destroy", "rkh_nn_clear", "rkh_nn_size", "rkh_nn_remove", "rkh_nn_live_size", "rkh_nn_append", "rkh_nn_query1",
     "rkh_nn_queryk", "rkh_nn_query1_async", "rkh_nn_queryk_async", "rkh_nn_fill_uniform", "rkh_nn_kernel_name",
+    "rkh_diag_knn_retries",
     "rkh_steer_mapping_name",
     "rkh_nn_set_coord_bound",
     "rkh_scene_create", "rkh_scene_create_with_meshes", "rkh_diag_gjk_distance", "rkh_diag_gjk_records", "rkh_diag_gjk_depth_records", "rkh_scene_destroy", "rkh_scene_num_dof", "rkh_scene_num_pairs", "rkh_state_derivative",
@@ -135,6 +136,8 @@ def load():
     lib.rkh_nn_set_coord_bound.argtypes = [vp, C.c_double]
     lib.rkh_nn_set_events.argtypes = [vp, vp, vp]
     lib.rkh_nn_kernel_name.restype = C.c_char_p
+    lib.rkh_diag_knn_retries.restype = u64
+    lib.rkh_diag_knn_retries.argtypes = []
     lib.rkh_steer_mapping_name.restype = C.c_char_p
     lib.rkh_scene_create.argtypes = [vp, C.POINTER(T.KteOp), C.c_int, C.POINTER(T.ChainBase), C.POINTER(T.Shape), C.c_int,
                                      C.POINTER(vp)]

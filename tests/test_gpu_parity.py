@@ -293,6 +293,11 @@ def test_knn_ties_and_star_neighborhood(L, ctx, oracle):
     ridx, rdist, rcnt = oracle.knn(q, pts, 10)
     assert np.array_equal(cnt, rcnt) and np.array_equal(dist, rdist)  # same distance multiset
     assert np.array_equal(np.sort(idx % 400, axis=1), np.sort(ridx % 400, axis=1))  # same vertices up to the duplicate
+    # ... and exactly the documented order, ascending (distance, index): the lower copy of a pair comes first
+    import knn_ref
+
+    pidx, pdist, pcnt = knn_ref.knn(q, pts, 10)
+    assert np.array_equal(cnt, pcnt) and np.array_equal(dist, pdist) and np.array_equal(idx, pidx)
 
 
 def test_sqrt_and_divide_are_correctly_rounded(L, ctx, oracle):
