@@ -529,6 +529,81 @@ rkh_status rkh_shortcut_paths(rkh_scene* scene, const rkh_qs_space* space, const
                               double* cost_in /* [B], may be NULL */, double* cost_out /* [B] */,
                               uint32_t* n_blocked /* [B], may be NULL */);
 
+/* ---- Direct kinematics, Jacobians and pose IK -------------------------------------------------------------------------
+ * Where a frame of the chain is, how it moves with the joints, and joint configurations that put it at a pose.  The
+ * planners above work in joint space; these entries are the way between joint space and workspace.
+ * Frames are named by the caller's own indices: the numbering of rkh_kte_op::base_frame / end_frame and rkh_shape::anchor
+ * (frame 0 = the chain base, plus every joint end frame, link end frame and mount link end frame of the program).
+ * q [B][n_dof] joint positions, qd [B][n_dof] joint rates or NULL for zero rates; frames [F].
+ *
+ * rkh_direct_kinematics answers manip_direct_kin_map::map_to_space (ctrl/topologies/direct_kinematics_topomap.hpp:57-103):
+ * per (state, frame) what kte_map_chain::doMotion leaves in the frame with q'' = 0, in the conventions of a parentless
+ * frame_3D: pos [B][F][3] and vel [B][F][3] in world coordinates, quat [B][F][4] (w, x, y, z), ang_vel [B][F][3] in the
+ * frame's OWN coordinates.  The pose is computed in the operation order of the distance query, so it is bit for bit the
+ * pose rkh_min_distance gives the shapes anchored on the frame.  Any output may be NULL, not all of them.
+ * rkh_direct_kinematics_2d: the same for planar scenes (frame_2D): pos [B][F][2], rot [B][F][2] = (cos, sin),
+ * vel [B][F][2], ang_vel [B][F].
+ *
+ * rkh_jacobians answers manipulator_kinematics_model::getJacobianMatrix / getJacobianMatrixAndDerivative
+ * (ctrl/kte_models/manip_kinematics_model.cpp:70-77, manip_kinematics_helper.cpp:249-318) for one dependent frame per
+ * asked frame: jac [B][F][6][n_dof], jac_dot the same shape (either may be NULL, not both; jac_dot with NULL qd is zeros).
+ * Column i of frame f is all zeros unless joint i is upstream of f (mUpStreamJoints: a joint gives up[end] = up[base] |
+ * bit(coord), a link up[end] = up[base], the base has none); otherwise it is jacobian_gen_3D::get_jac_relative_to
+ * (core/kinetostatics/motion_jacobians.hpp:238-251) of the joint's generator -- revolute qd_avel = mAxis, prismatic
+ * qd_vel = mAxis as given (revolute_joint.cpp:145-148, prismatic_joint.cpp:150-153), the rest 0 -- relative to f, written
+ * in write_to_matrices' row order: velocity (3), angular velocity (3), both in f's own coordinates.  So
+ * jac qd = (R(quat)^T vel, ang_vel) of rkh_direct_kinematics.
+ * rkh_jacobians_2d: jacobian_gen_2D (:138-146), jac [B][F][3][n_dof], rows (vx, vy, omega) in f's coordinates.
+ *
+ * B == 0 or F == 0 is RKH_OK.  RKH_ERR_BAD_ARG: a frame index that is not a frame of the chain, NULL q or frames, every
+ * output NULL.  RKH_ERR_UNSUPPORTED, with an error text: the 3D entries on a planar scene, the _2d entries on a 3D scene.
+ * Every chain rkh_scene_create[_with_meshes] accepts is served. */
+rkh_status rkh_direct_kinematics(rkh_scene* scene, const double* q, const double* qd, uint32_t B, const int32_t* frames,
+                                 uint32_t F, double* pos /* [B][F][3] */, double* quat /* [B][F][4] */,
+                                 double* vel /* [B][F][3] */, double* ang_vel /* [B][F][3] */);
+rkh_status rkh_direct_kinematics_2d(rkh_scene* scene, const double* q, const double* qd, uint32_t B, const int32_t* frames,
+                                    uint32_t F, double* pos /* [B][F][2] */, double* rot /* [B][F][2] */,
+                                    double* vel /* [B][F][2] */, double* ang_vel /* [B][F] */);
+rkh_status rkh_jacobians(rkh_scene* scene, const double* q, const double* qd, uint32_t B, const int32_t* frames, uint32_t F,
+                         double* jac /* [B][F][6][n_dof] */, double* jac_dot /* [B][F][6][n_dof] */);
+rkh_status rkh_jacobians_2d(rkh_scene* scene, const double* q, const double* qd, uint32_t B, const int32_t* frames, uint32_t F,
+                            double* jac /* [B][F][3][n_dof] */, double* jac_dot /* [B][F][3][n_dof] */);
+/* Pose IK for 3D chains: T targets x S seeds, all T S solves in one launch.  It stands where the reference's manipulator
+ * applications run an inverse-kinematics step in front of the planner (chaser_kin_model->doInverseMotion(),
+ * examples/robot_airship/CRS_planner_exec.cpp:309: closed forms per arm, else ctrl/kte_models/manip_clik_calculator.cpp over
+ * an NLP solver); neither is restated.  Defined here instead, a damped
+ * least-squares iteration per solve, q = clamp(seed, lower, upper), then for k = 0, 1, ...:
+ *   1. (p, Q) = pose of `frame` at q, J = its Jacobian [6][n_dof] as rkh_jacobians defines it
+ *   2. e_v = (p* - p) R(Q): the position error in the frame's coordinates
+ *   3. dQ = Q^-1 Q*, negated if its w < 0; e_w = 2 (dQ.x, dQ.y, dQ.z)
+ *   4. |e_v| <= tol_pos and |e_w| <= tol_rot: converged, stop, iters = k
+ *   5. k == max_iters: stop, not converged, iters = k
+ *   6. A = J J^T + damping^2 I (6 x 6); A y = e, e = (e_v, e_w), by decompose_Cholesky / backsub_Cholesky
+ *      (lin_alg/mat_cholesky.hpp), the sequence of the f-eval; a pivot that is not positive: stop, not converged
+ *   7. dq = J^T y; if max |dq_i| > max_step: dq = dq * (max_step / max |dq_i|)
+ *   8. q = clamp(q + dq, lower, upper)
+ * in fp64, every sum left to right (over the joints, then + damping^2; over the six rows), no contraction.
+ * Then ONE launch of the distance query of rkh_min_distance over all T S results: free = (minimum distance > 0); a scene
+ * without proxy pairs is free.
+ * seeds [T][S][n_dof]; lower / upper [n_dof] (lower <= upper); q_out [T][S][n_dof]; res_pos / res_rot [T][S] the last |e_v| /
+ * |e_w|; iters [T][S]; flags [T][S]: bit 0 converged, bit 1 free; best [T]: the lowest seed index that is converged and
+ * free, else 0xFFFFFFFF.  Every output but q_out may be NULL.  T == 0 or S == 0 is RKH_OK.
+ * RKH_ERR_BAD_ARG: params->struct_size != sizeof(rkh_ik_params) (the entry checks it itself), damping or max_step not
+ * positive, a negative tolerance, lower > upper, a target that is not finite or whose quaternion is not unit to 1e-9, a
+ * seed that is not finite, a frame that is not a frame of the chain, NULL targets / seeds / bounds / q_out.
+ * RKH_ERR_UNSUPPORTED: planar scenes.  Not built: planar IK, position-only or partial-pose targets, null-space objectives
+ * for redundant chains, the reference's closed-form arm solutions. */
+typedef struct rkh_ik_params {
+  uint32_t struct_size; /* sizeof(rkh_ik_params) */
+  uint32_t max_iters;
+  double damping, max_step, tol_pos, tol_rot;
+} rkh_ik_params;
+rkh_status rkh_inverse_kinematics(rkh_scene* scene, int32_t frame, const rkh_pose* targets /* [T] */, uint32_t T,
+                                  const double* seeds /* [T][S][n_dof] */, uint32_t S, const double* lower, const double* upper,
+                                  const rkh_ik_params* params, double* q_out /* [T][S][n_dof] */, double* res_pos /* [T][S] */,
+                                  double* res_rot /* [T][S] */, uint32_t* iters /* [T][S] */, uint32_t* flags /* [T][S] */,
+                                  uint32_t* best /* [T] */);
+
 #ifdef __cplusplus
 }
 #endif

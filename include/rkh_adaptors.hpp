@@ -626,6 +626,162 @@ class hip_proxy_query_pair_2D {
   std::vector<double> m_state;
 };
 
+// ---- direct kinematics, Jacobians and pose IK (rkh_direct_kinematics, rkh_jacobians, rkh_inverse_kinematics) --------------
+// frame_3D as the reference hands a dependent frame out (parentless: Position and Velocity in world coordinates, Quat
+// (w, x, y, z), AngVelocity in the frame's own coordinates).
+struct frame_pose_twist {
+  double Position[3] = {0.0, 0.0, 0.0};
+  double Quat[4] = {1.0, 0.0, 0.0, 0.0};
+  double Velocity[3] = {0.0, 0.0, 0.0};
+  double AngVelocity[3] = {0.0, 0.0, 0.0};
+};
+// manip_direct_kin_map (R/ctrl/topologies/direct_kinematics_topomap.hpp:57-103) for one dependent frame of a 3D scene: the
+// call shape of map_to_space -- a joint-space point in, the frame's pose and twist out.  The input point is the
+// joint-space point of the topology the caller maps from: positions alone (size n_dof: zero rates) or kte_nl_system's
+// interleaved state (q0, qd0, q1, qd1, ...: size 2 n_dof), which is what the dynamic free space's points are.  The two
+// space arguments of the reference only pick the reader / writer of the point types; here they are accepted and unused.
+// map_batch is the same for many points in one launch (a returned solution path).
+class hip_direct_kin_map {
+ public:
+  hip_direct_kin_map(const std::shared_ptr<rkh_scene>& scene, int32_t frame) : m_scene(scene), m_frame(frame) {}
+  int32_t frame() const { return m_frame; }
+  template <typename PointType>
+  frame_pose_twist map_to_space(const PointType& pt) const {
+    return map_batch(std::vector<PointType>(1, pt))[0];
+  }
+  template <typename PointType, typename InSpace, typename OutSpace>
+  frame_pose_twist map_to_space(const PointType& pt, const InSpace&, const OutSpace&) const {
+    return map_to_space(pt);
+  }
+  template <typename PointType>
+  std::vector<frame_pose_twist> map_batch(const std::vector<PointType>& pts) const {
+    std::vector<double> q, qd;
+    const bool rates = split(pts, q, qd);
+    const std::size_t B = pts.size();
+    std::vector<double> pos(3 * B), quat(4 * B), vel(3 * B), w(3 * B);
+    check(rkh_direct_kinematics(m_scene.get(), q.data(), rates ? qd.data() : nullptr, uint32_t(B), &m_frame, 1, pos.data(),
+                                quat.data(), vel.data(), w.data()));
+    std::vector<frame_pose_twist> out(B);
+    for (std::size_t b = 0; b < B; ++b) {
+      for (int k = 0; k < 3; ++k) {
+        out[b].Position[k] = pos[3 * b + k];
+        out[b].Velocity[k] = vel[3 * b + k];
+        out[b].AngVelocity[k] = w[3 * b + k];
+      }
+      for (int k = 0; k < 4; ++k) out[b].Quat[k] = quat[4 * b + k];
+    }
+    return out;
+  }
+  // points of size n_dof (positions) or 2 n_dof (interleaved q, qd) -> q [B][n], qd [B][n]; returns whether rates came
+  template <typename PointType>
+  bool split(const std::vector<PointType>& pts, std::vector<double>& q, std::vector<double>& qd) const {
+    const std::size_t n = std::size_t(rkh_scene_num_dof(m_scene.get()));
+    if (pts.empty()) return false;
+    const std::size_t sz = pts[0].size();
+    if (sz != n && sz != 2 * n) throw std::range_error("hip_direct_kin_map: a point holds n_dof positions or 2 n_dof (q, qd) pairs");
+    const bool rates = sz == 2 * n;
+    q.resize(pts.size() * n);
+    qd.resize(rates ? pts.size() * n : 0);
+    for (std::size_t b = 0; b < pts.size(); ++b) {
+      if (pts[b].size() != sz) throw std::range_error("hip_direct_kin_map: points of different sizes");
+      for (std::size_t j = 0; j < n; ++j) {
+        q[b * n + j] = rates ? pts[b][2 * j] : pts[b][j];
+        if (rates) qd[b * n + j] = pts[b][2 * j + 1];
+      }
+    }
+    return rates;
+  }
+
+ protected:
+  std::shared_ptr<rkh_scene> m_scene;
+  int32_t m_frame;
+};
+
+// manipulator_kinematics_model::getJacobianMatrix / getJacobianMatrixAndDerivative (R/ctrl/kte_models/
+// manip_kinematics_model.cpp:70-77, manip_kinematics_helper.cpp:249-318) of a model whose dependent frames are `frames` (in
+// that order: six rows each) and whose joints are the scene's coordinates: Jac is (6 F) x n_dof, row-major, the rows of
+// frame f at [6 f, 6 f + 6).  The model is "at" the point last given to apply_to_model, as in the reference (doMotion
+// first, then the getters).  Matrix: anything with operator()(row, col) sized (6 F) x n_dof, or use the flat getters.
+class hip_manip_kinematics_model {
+ public:
+  hip_manip_kinematics_model(const std::shared_ptr<rkh_scene>& scene, const std::vector<int32_t>& frames)
+      : m_map(scene, frames.empty() ? 0 : frames[0]), m_scene(scene), m_frames(frames) {}
+  std::size_t getJointPositionsCount() const { return std::size_t(rkh_scene_num_dof(m_scene.get())); }
+  std::size_t getDependentVelocitiesCount() const { return 6 * m_frames.size(); }
+  template <typename PointType>
+  void apply_to_model(const PointType& pt) {
+    m_rates = m_map.split(std::vector<PointType>(1, pt), m_q, m_qd);
+  }
+  void getJacobianMatrix(std::vector<double>& Jac) const { run(&Jac, nullptr); }
+  void getJacobianMatrixAndDerivative(std::vector<double>& Jac, std::vector<double>& JacDot) const { run(&Jac, &JacDot); }
+  template <typename Matrix>
+  void getJacobianMatrix(Matrix& Jac) const {
+    std::vector<double> J;
+    run(&J, nullptr);
+    fill(Jac, J);
+  }
+  template <typename Matrix1, typename Matrix2>
+  void getJacobianMatrixAndDerivative(Matrix1& Jac, Matrix2& JacDot) const {
+    std::vector<double> J, Jd;
+    run(&J, &Jd);
+    fill(Jac, J);
+    fill(JacDot, Jd);
+  }
+
+ private:
+  void run(std::vector<double>* J, std::vector<double>* Jd) const {
+    if (m_q.empty()) throw std::range_error("hip_manip_kinematics_model: apply_to_model first");
+    const std::size_t sz = getDependentVelocitiesCount() * getJointPositionsCount();
+    J->assign(sz, 0.0);
+    if (Jd) Jd->assign(sz, 0.0);
+    if (m_frames.empty()) return;
+    check(rkh_jacobians(m_scene.get(), m_q.data(), m_rates ? m_qd.data() : nullptr, 1, m_frames.data(),
+                        uint32_t(m_frames.size()), J->data(), Jd ? Jd->data() : nullptr));
+  }
+  template <typename Matrix>
+  void fill(Matrix& M, const std::vector<double>& flat) const {
+    const std::size_t rows = getDependentVelocitiesCount(), cols = getJointPositionsCount();
+    for (std::size_t r = 0; r < rows; ++r)
+      for (std::size_t c = 0; c < cols; ++c) M(r, c) = flat[r * cols + c];
+  }
+  hip_direct_kin_map m_map;
+  std::shared_ptr<rkh_scene> m_scene;
+  std::vector<int32_t> m_frames;
+  std::vector<double> m_q, m_qd;
+  bool m_rates = false;
+};
+
+// Goal configurations for a tool pose: rkh_inverse_kinematics for one target from S seeds (the step the reference's
+// manipulator applications run in front of the planner).  Returns the converged, collision-free results, best first in
+// seed order; empty if none.
+inline std::vector<std::vector<double> > hip_pose_ik(const std::shared_ptr<rkh_scene>& scene, int32_t frame, const rkh_pose& target,
+                                                     const std::vector<std::vector<double> >& seeds, const std::vector<double>& lower,
+                                                     const std::vector<double>& upper, double damping = 0.02, double max_step = 0.5,
+                                                     uint32_t max_iters = 100, double tol_pos = 1e-6, double tol_rot = 1e-6) {
+  const std::size_t n = std::size_t(rkh_scene_num_dof(scene.get())), S = seeds.size();
+  if (lower.size() < n || upper.size() < n) throw std::range_error("hip_pose_ik: bounds shorter than n_dof");
+  std::vector<double> flat(S * n), q(S * n);
+  for (std::size_t s = 0; s < S; ++s) {
+    if (seeds[s].size() != n) throw std::range_error("hip_pose_ik: a seed must hold n_dof positions");
+    for (std::size_t j = 0; j < n; ++j) flat[s * n + j] = seeds[s][j];
+  }
+  rkh_ik_params prm;
+  prm.struct_size = uint32_t(sizeof(rkh_ik_params));
+  prm.max_iters = max_iters;
+  prm.damping = damping;
+  prm.max_step = max_step;
+  prm.tol_pos = tol_pos;
+  prm.tol_rot = tol_rot;
+  std::vector<uint32_t> flags(S);
+  std::vector<std::vector<double> > out;
+  if (S == 0) return out;
+  check(rkh_inverse_kinematics(scene.get(), frame, &target, 1, flat.data(), uint32_t(S), lower.data(), upper.data(), &prm, q.data(),
+                               nullptr, nullptr, nullptr, flags.data(), nullptr));
+  for (std::size_t s = 0; s < S; ++s)
+    if (flags[s] == 3u) out.push_back(std::vector<double>(q.begin() + s * n, q.begin() + (s + 1) * n));
+  return out;
+}
+
 // ---- planner entry: sample_based_planner<FreeSpace>::solve_planning_query(planning_query<FreeSpace>&) ---------------
 // (motion_planner_base.hpp:102, options :400-422, report_progress / report_solution :343-351).  The batched device
 // drivers build exactly the graphs of the sequential algorithms on the seed of the global generator; an adaptor hands

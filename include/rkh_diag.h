@@ -153,6 +153,16 @@ rkh_status rkh_diag_shortcut_dp(rkh_ctx* ctx, const uint32_t* path_ptr, uint32_t
  * ms[runs][3] = pairs, walks, search.  No copies are timed.  B > 0. */
 rkh_status rkh_diag_shortcut_ms(rkh_scene* scene, const rkh_qs_space* space, const double* points, const uint32_t* path_ptr,
                                 uint32_t B, uint32_t max_span, uint32_t runs, float* ms /* [runs][3] */);
+/* Times of the kinematics launches on the same arguments (tools/measure_kinematics.py), events on the context's stream,
+ * after one warm-up; no copies are timed.  rkh_diag_kinematics_ms: the one launch that answers rkh_direct_kinematics AND
+ * rkh_jacobians (all six outputs, JacDot included; planar scenes: the _2d forms) with the clear of the two Jacobian arrays
+ * in front of it, ms[runs].  rkh_diag_ik_ms: rkh_inverse_kinematics' solve launch and its distance launch,
+ * ms[runs][2] = solves, distance query (0 for a scene without proxy pairs).  B, F, T, S, runs > 0. */
+rkh_status rkh_diag_kinematics_ms(rkh_scene* scene, const double* q, const double* qd, uint32_t B, const int32_t* frames,
+                                  uint32_t F, uint32_t runs, float* ms /* [runs] */);
+rkh_status rkh_diag_ik_ms(rkh_scene* scene, int32_t frame, const rkh_pose* targets, uint32_t T, const double* seeds, uint32_t S,
+                          const double* lower, const double* upper, const rkh_ik_params* params, uint32_t runs,
+                          float* ms /* [runs][2] */);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 #include "../../include/rkh.h"
 #include "../../include/rkh_diag.h"
 #include "device_buffer.h"
+#include "kinematics_device.h"  // KinChain, KinFrameRef
 #include "knn_plan.h"    // KnnWorkspace, knn_plan, knn_carve
 #include "steer_edge.h"  // EdgeMode, EdgeIO, KernelGate, kMaxSteps
 
@@ -310,6 +311,12 @@ struct rkh_scene {
   rkh::DeviceBuffer<unsigned long long> d_clear_stats;  // [2] KernelGate::clear_stats of every steer launch on this scene
   int n_pairs = 0;
   int n_pairs_verdict = -1;  // the first entries of d_pairs: pairs whose shapes can touch at all (verdict kernels scan these)
+  // the kinematics entries (kinematics_frames.hip): the chain as their kernels walk it, and where every frame of the
+  // caller's numbering (rkh_kte_op::base_frame / end_frame, rkh_shape::anchor) sits in it -- a host table, indexed by
+  // frame id; the refs of the frames a call asks for are uploaded with the call
+  rkh::KinChain kin;
+  rkh::DeviceBuffer<rkh::KinChain> d_kin;
+  std::vector<rkh::KinFrameRef> frame_table;
 };
 
 namespace rkh {

@@ -181,6 +181,39 @@ static thread_local SteerMapping g_steer_mapping = SteerMapping::Wave;
 void note_steer_mapping(SteerMapping m) { g_steer_mapping = m; }
 }  // namespace rkh
 
+// The chain as the kinematics kernels walk it (kinematics_device.h): a copy of the joint groups of SceneDev.
+static void fill_kin_chain(rkh_scene* sc) {
+  const SceneDev& S = sc->host;
+  KinChain& K = sc->kin;
+  std::memset(&K, 0, sizeof(K));
+  K.n_dof = S.n_dof;
+  K.planar = S.planar;
+  std::memcpy(K.base_pos, S.base_pos, sizeof(K.base_pos));
+  std::memcpy(K.base_quat, S.base_quat, sizeof(K.base_quat));
+  for (int j = 0; j < S.n_dof; ++j) {
+    KinJoint& J = K.joints[j];
+    std::memcpy(J.axis, S.joints[j].axis, sizeof(J.axis));
+    std::memcpy(J.axis_n, S.joints[j].axis_n, sizeof(J.axis_n));
+    std::memcpy(J.off_pos, S.joints[j].off_pos, sizeof(J.off_pos));
+    std::memcpy(J.off_quat, S.joints[j].off_quat, sizeof(J.off_quat));
+    std::memcpy(J.mount_pos, S.mount_pos[j], sizeof(J.mount_pos));
+    std::memcpy(J.mount_quat, S.mount_quat[j], sizeof(J.mount_quat));
+    J.prismatic = int32_t((S.prismatic_mask >> j) & 1u);
+    J.branch_start = S.branch_start[j];
+  }
+}
+
+// One entry of rkh_scene::frame_table.  Frame ids are the caller's; an id the table cannot hold stays unknown to the
+// kinematics entries (they answer RKH_ERR_BAD_ARG for it).
+static void note_frame(rkh_scene* sc, int frame, KinFrameKind kind, int first, int last, uint32_t up) {
+  if (frame < 0 || frame >= 65536) return;
+  if (size_t(frame) >= sc->frame_table.size()) sc->frame_table.resize(size_t(frame) + 1, KinFrameRef{KIN_INVALID, 0, 0, 0u});
+  sc->frame_table[frame] = KinFrameRef{kind, first, last, up};
+}
+static uint32_t frame_up(const rkh_scene* sc, int frame) {
+  return (frame >= 0 && size_t(frame) < sc->frame_table.size()) ? sc->frame_table[frame].up : 0u;
+}
+
 // the last step of both scene builders: the handle is the caller's only once everything is on the device
 static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, const std::vector<PairDev>& pairs,
                                rkh_scene** out, const std::vector<PairIdDev>& pair_ids = std::vector<PairIdDev>()) {
@@ -204,6 +237,9 @@ static rkh_status upload_scene(rkh_ctx* ctx, std::unique_ptr<rkh_scene> sc, cons
   }
   RKH_TRY(sc->d_err.alloc_zeroed(1));
   RKH_TRY(sc->d_clear_stats.alloc_zeroed(2));
+  fill_kin_chain(sc.get());
+  RKH_TRY(sc->d_kin.alloc(1));
+  RKH_HIP(hipMemcpy(sc->d_kin.get(), &sc->kin, sizeof(KinChain), hipMemcpyHostToDevice));
   *out = sc.release();
   return RKH_OK;
 }
@@ -270,6 +306,9 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
       J.mass = in2.mass;
       J.inertia[0] = in2.inertia[0];
     }
+    if (j == 0) note_frame(sc.get(), 0, KIN_BASE, 0, 0, 0u);
+    note_frame(sc.get(), rev.end_frame, KIN_JOINT_END, 0, j, frame_up(sc.get(), rev.base_frame) | (1u << j));
+    note_frame(sc.get(), lnk.end_frame, KIN_LINK_END, 0, j, frame_up(sc.get(), lnk.base_frame));
     prev_end = lnk.end_frame;
     joint_end_frame[j] = rev.end_frame;
     if (rev.kind == RKH_KTE_PRISMATIC_JOINT_2D) {  // mAxis as given: the joint does not normalise it
@@ -465,6 +504,10 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
       set_error("rkh_scene_create: op group " + std::to_string(j) + " does not match the chain pattern");
       return RKH_ERR_UNSUPPORTED;
     }
+    if (j == 0) note_frame(sc.get(), 0, KIN_BASE, 0, 0, 0u);
+    if (groups[j].mount_op >= 0) note_frame(sc.get(), prog[groups[j].mount_op].end_frame, KIN_MOUNT, j, j, frame_up(sc.get(), 0));
+    note_frame(sc.get(), rev.end_frame, KIN_JOINT_END, branch_first, j, frame_up(sc.get(), rev.base_frame) | (1u << j));
+    note_frame(sc.get(), lnk.end_frame, KIN_LINK_END, branch_first, j, frame_up(sc.get(), lnk.base_frame));
     first = false;
     prev_end = lnk.end_frame;
     joint_end_frame[j] = rev.end_frame;

@@ -88,6 +88,8 @@ EXPORTS = [
     "rkh_birrtstar_get_graph", "rkh_rrtstar_set_branch_and_bound", "rkh_rrtstar_get_removed", "rkh_rrtstar_destroy", "rkh_rrtstar_solve",
     "rkh_rrtstar_get_graph", "rkh_prm_create_qs_batch", "rkh_prm_create_batch", "rkh_prm_destroy", "rkh_prm_solve", "rkh_prm_get_graph", "rkh_prm_shortest_paths", "rkh_prm_get_solution", "rkh_prm_query_paths", "rkh_diag_sssp", "rkh_diag_prm_search_ms", "rkh_birrt_create_qs_batch", "rkh_birrt_destroy", "rkh_birrt_solve", "rkh_birrt_get_trees", "rkh_planner_get_solution", "rkh_rrtstar_get_solution", "rkh_birrt_get_solution",
     "rkh_shortcut_paths", "rkh_diag_shortcut_dp", "rkh_diag_shortcut_ms",
+    "rkh_direct_kinematics", "rkh_direct_kinematics_2d", "rkh_jacobians", "rkh_jacobians_2d", "rkh_inverse_kinematics",
+    "rkh_diag_kinematics_ms", "rkh_diag_ik_ms",
 ]
 
 
@@ -197,6 +199,16 @@ def load():
     lib.rkh_shortcut_paths.argtypes = [vp, C.POINTER(T.QsSpace), dp, u32p, u32, u32, u32p, u32p, dp, dp, u32p]
     lib.rkh_diag_shortcut_dp.argtypes = [vp, u32p, u32, u32, u8p, dp, u32p, u32p, dp, u32p]
     lib.rkh_diag_shortcut_ms.argtypes = [vp, C.POINTER(T.QsSpace), dp, u32p, u32, u32, u32, C.POINTER(C.c_float)]
+    i32p = C.POINTER(C.c_int32)
+    lib.rkh_direct_kinematics.argtypes = [vp, dp, dp, u32, i32p, u32, dp, dp, dp, dp]
+    lib.rkh_direct_kinematics_2d.argtypes = [vp, dp, dp, u32, i32p, u32, dp, dp, dp, dp]
+    lib.rkh_jacobians.argtypes = [vp, dp, dp, u32, i32p, u32, dp, dp]
+    lib.rkh_jacobians_2d.argtypes = [vp, dp, dp, u32, i32p, u32, dp, dp]
+    lib.rkh_inverse_kinematics.argtypes = [vp, C.c_int32, C.POINTER(T.Pose), u32, dp, u32, dp, dp, C.POINTER(T.IkParams), dp, dp,
+                                           dp, u32p, u32p, u32p]
+    lib.rkh_diag_kinematics_ms.argtypes = [vp, dp, dp, u32, i32p, u32, u32, C.POINTER(C.c_float)]
+    lib.rkh_diag_ik_ms.argtypes = [vp, C.c_int32, C.POINTER(T.Pose), u32, dp, u32, dp, dp, C.POINTER(T.IkParams), u32,
+                                   C.POINTER(C.c_float)]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -654,6 +666,88 @@ class Scene:
         ms = np.zeros((int(runs), 3), dtype=np.float32)
         _check(self.lib.rkh_diag_shortcut_ms(self.h, C.byref(space), T.dptr(pts), T.u32ptr(path_ptr), len(path_ptr) - 1,
                                              int(max_span), int(runs), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
+
+    # ---- direct kinematics, Jacobians, pose IK (rkh_direct_kinematics[_2d], rkh_jacobians[_2d], rkh_inverse_kinematics) ----
+    @property
+    def planar(self):
+        return any(o.kind in (T.KTE_REVOLUTE_JOINT_2D, T.KTE_PRISMATIC_JOINT_2D) for o in self.scn.ops)
+
+    def _kin_args(self, q, qd, frames):
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, self.n)
+        qd = None if qd is None else np.ascontiguousarray(qd, dtype=np.float64).reshape(-1, self.n)
+        frames = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        return q, qd, frames, frames.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def direct_kinematics(self, q, frames, qd=None, want=("pos", "rot", "vel", "ang_vel"), planar=None):
+        """Frames of the chain for B joint points q [B][n] (rates qd or None): a dict of the arrays named in `want`.
+        3D scenes (rkh_direct_kinematics): pos [B][F][3], rot = quat [B][F][4] (w, x, y, z), vel [B][F][3] (world),
+        ang_vel [B][F][3] (the frame's own coordinates).  Planar scenes (rkh_direct_kinematics_2d): pos [B][F][2], rot
+        [B][F][2] = (cos, sin), vel [B][F][2], ang_vel [B][F].  `planar` forces the entry (to see it refuse)."""
+        planar = self.planar if planar is None else planar
+        q, qd, frames, fp = self._kin_args(q, qd, frames)
+        B, F = q.shape[0], len(frames)
+        shapes = {"pos": (B, F, 2), "rot": (B, F, 2), "vel": (B, F, 2), "ang_vel": (B, F)} if planar else \
+            {"pos": (B, F, 3), "rot": (B, F, 4), "vel": (B, F, 3), "ang_vel": (B, F, 3)}
+        out = {k: np.zeros(shapes[k]) for k in want}
+        ptr = [T.dptr(out[k]) if k in out else None for k in ("pos", "rot", "vel", "ang_vel")]
+        fn = self.lib.rkh_direct_kinematics_2d if planar else self.lib.rkh_direct_kinematics
+        _check(fn(self.h, T.dptr(q), None if qd is None else T.dptr(qd), B, fp, F, *ptr))
+        return out
+
+    def jacobians(self, q, frames, qd=None, want=("jac", "jac_dot"), planar=None):
+        """getJacobianMatrix[AndDerivative] per (point, frame): jac / jac_dot [B][F][6][n] (planar: [B][F][3][n]), rows
+        (velocity, angular velocity) in the frame's own coordinates (rkh_jacobians / rkh_jacobians_2d)."""
+        planar = self.planar if planar is None else planar
+        q, qd, frames, fp = self._kin_args(q, qd, frames)
+        B, F = q.shape[0], len(frames)
+        out = {k: np.zeros((B, F, 3 if planar else 6, self.n)) for k in want}
+        ptr = [T.dptr(out[k]) if k in out else None for k in ("jac", "jac_dot")]
+        fn = self.lib.rkh_jacobians_2d if planar else self.lib.rkh_jacobians
+        _check(fn(self.h, T.dptr(q), None if qd is None else T.dptr(qd), B, fp, F, *ptr))
+        return out
+
+    def _ik_args(self, targets, seeds, lower, upper):
+        tg = T.as_array(list(targets), T.Pose) if len(targets) else (T.Pose * 1)()
+        seeds = np.ascontiguousarray(seeds, dtype=np.float64)
+        seeds = seeds.reshape(len(targets), -1, self.n) if len(targets) else seeds.reshape(0, 0, self.n)
+        lower = np.ascontiguousarray(lower, dtype=np.float64).reshape(-1)
+        upper = np.ascontiguousarray(upper, dtype=np.float64).reshape(-1)
+        assert len(lower) >= self.n and len(upper) >= self.n
+        return tg, seeds, lower, upper
+
+    def inverse_kinematics(self, frame, targets, seeds, lower, upper, params=None):
+        """rkh_inverse_kinematics: `targets` a list of T.Pose, seeds [T][S][n], joint box lower / upper [n], params =
+        T.make_ik_params(...).  Returns a dict: q [T][S][n], res_pos, res_rot, iters [T][S], converged, free [T][S]
+        (bool), best [T] (seed index, or -1 if no seed is converged and free)."""
+        params = params if params is not None else T.make_ik_params()
+        tg, seeds, lower, upper = self._ik_args(targets, seeds, lower, upper)
+        Tn, S = seeds.shape[0], seeds.shape[1]
+        q = np.zeros((Tn, S, self.n))
+        rp, rr = np.zeros((Tn, S)), np.zeros((Tn, S))
+        it, fl = np.zeros((Tn, S), dtype=np.uint32), np.zeros((Tn, S), dtype=np.uint32)
+        best = np.zeros(max(Tn, 1), dtype=np.uint32)
+        _check(self.lib.rkh_inverse_kinematics(self.h, int(frame), tg, Tn, T.dptr(seeds), S, T.dptr(lower), T.dptr(upper),
+                                               C.byref(params), T.dptr(q), T.dptr(rp), T.dptr(rr), T.u32ptr(it), T.u32ptr(fl),
+                                               T.u32ptr(best)))
+        return {"q": q, "res_pos": rp, "res_rot": rr, "iters": it, "converged": (fl & 1) != 0, "free": (fl & 2) != 0,
+                "best": np.where(best[:Tn] == 0xFFFFFFFF, -1, best[:Tn].astype(np.int64))}
+
+    def kinematics_ms(self, q, frames, qd=None, runs=5):
+        """rkh_diag_kinematics_ms: ms [runs] of the launch that answers direct_kinematics and jacobians together."""
+        q, qd, frames, fp = self._kin_args(q, qd, frames)
+        ms = np.zeros(int(runs), dtype=np.float32)
+        _check(self.lib.rkh_diag_kinematics_ms(self.h, T.dptr(q), None if qd is None else T.dptr(qd), q.shape[0], fp, len(frames),
+                                               int(runs), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
+
+    def ik_ms(self, frame, targets, seeds, lower, upper, params=None, runs=5):
+        """rkh_diag_ik_ms: ms [runs][2] of the solve launch and the distance launch of inverse_kinematics."""
+        params = params if params is not None else T.make_ik_params()
+        tg, seeds, lower, upper = self._ik_args(targets, seeds, lower, upper)
+        ms = np.zeros((int(runs), 2), dtype=np.float32)
+        _check(self.lib.rkh_diag_ik_ms(self.h, int(frame), tg, seeds.shape[0], T.dptr(seeds), seeds.shape[1], T.dptr(lower),
+                                       T.dptr(upper), C.byref(params), int(runs), ms.ctypes.data_as(C.POINTER(C.c_float))))
         return ms
 
     def steer_position_toward(self, a, b, fraction=1.0, record=False, dyn=None):

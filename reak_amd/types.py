@@ -95,6 +95,17 @@ class PrmParams(C.Structure):
     _fields_ = [("base", RrtParams), ("sampling_radius", C.c_double), ("expand_probability", C.c_double)]
 
 
+class IkParams(C.Structure):
+    """rkh_ik_params (include/rkh.h): the damped least-squares pose iteration of rkh_inverse_kinematics."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_uint32), ("damping", C.c_double), ("max_step", C.c_double),
+                ("tol_pos", C.c_double), ("tol_rot", C.c_double)]
+
+
+def make_ik_params(max_iters=100, damping=0.02, max_step=0.5, tol_pos=1e-6, tol_rot=1e-6):
+    return IkParams(struct_size=C.sizeof(IkParams), max_iters=int(max_iters), damping=float(damping),
+                    max_step=float(max_step), tol_pos=float(tol_pos), tol_rot=float(tol_rot))
+
+
 def make_pose(pos=(0.0, 0.0, 0.0), quat=(1.0, 0.0, 0.0, 0.0)):
     p = Pose()
     p.pos[:] = [float(v) for v in pos]
