@@ -604,6 +604,56 @@ rkh_status rkh_inverse_kinematics(rkh_scene* scene, int32_t frame, const rkh_pos
                                   double* res_rot /* [T][S] */, uint32_t* iters /* [T][S] */, uint32_t* flags /* [T][S] */,
                                   uint32_t* best /* [T] */);
 
+/* ---- the order-1 rate-limited joint space with SVP profiles (rkh_svp_space, rkh_types.h) ----------------------------------
+ * These entries stand in for svp_Ndof_reach_time_metric, svp_Ndof_interpolator and the move_pt_toward of
+ * svp_Ndof_reach_topologies.hpp over manip_quasi_static_env::is_free.  Points are [2 n_dof] doubles (p0, v0, p1, v1, ...).
+ *
+ * Reach time d(a -> b): per joint the minimum time of a ramp / cruise / ramp velocity profile
+ * (svp_Ndof_compute_min_delta_time), T = their maximum, then per joint the peak velocity that takes exactly T
+ * (svp_Ndof_compute_peak_velocity).  A joint without a solution in either pass (a velocity beyond vm, or the known gap of a
+ * velocity-bounded double integrator that cannot stretch its time), or coordinates that are not finite, make d = +inf.
+ * d is not symmetric.
+ *
+ * rkh_svp_in_bounds: svp_Ndof_is_in_bounds, on the host (no device needed): the point, the point where each joint could
+ * stop (p + v |v| / (2 vm)) and the point it could have started from (p - v |v| / (2 vm)) inside [lower, upper], v inside
+ * +-vm.  ok [B]: 1 or 0.
+ * rkh_svp_reach_time: time [B] and, if not NULL, peak [B][n_dof] (zeros for an infinite pair).
+ * rkh_svp_nearest: the k nearest of `points` per query.  direction 0: by d(point -> query), the predecessors an RRT extends
+ * from; direction 1: by d(query -> point), the successors.  idx / dist [B][k] ascend by (distance, index); infinite
+ * distances are never returned: a query with fewer than k finite neighbours is padded with 0xFFFFFFFF and +inf.  k in [1, 64];
+ * at most 16 777 216 points and 65 535 queries per call (RKH_ERR_CAPACITY).
+ * rkh_svp_nearest_async: the same with device pointers, enqueued on the context's stream: no host copy, no synchronisation.
+ * The context keeps the scratch of launches that slice the points; it grows with the largest request.
+ * rkh_svp_edge_check: the collision-tested walk.  T = d(a -> b); T = +inf: out = a, nothing tested.  Else dt = T fraction
+ * (fraction NULL: 1.0), and the points at travel times d = min_interval, + min_interval, ... (repeated addition) below dt are
+ * tested in order with "in bounds (above), and no proxy pair closer than 0" at q_i = p_i speed_limits[i],
+ * qd_i = v_i accel_limits[i]; the first failure ends the walk at the last point that passed (a if none).  Without a failure:
+ * fraction == 1.0 returns b, fraction == 0.0 returns a, any other the (untested) point at dt.  out [B][2 n_dof];
+ * reach_time [B]; n_checked [B]: points tested, the failing one included; reached [B]: 1 where the loop ran to dt without a
+ * failure.  Every output but out may be NULL.  An edge with more than 1 048 576 points to test: RKH_ERR_CAPACITY.
+ * rkh_svp_interpolate: the profile of each pair sampled at M times, t [B][M], out [B][M][2 n_dof], reach_time [B] (may be
+ * NULL).  t <= 0: a; t >= T: b; an infinite pair: a at every time.
+ *
+ * B == 0, M == 0 or n_pts == 0 is RKH_OK.  RKH_ERR_BAD_ARG: space->struct_size != sizeof(rkh_svp_space), n_dof not in
+ * [1, 12] or not the scene's, min_interval not positive and finite, lower > upper, a negative or non-finite limit, k or
+ * direction out of range, a NULL required pointer.  Not built: the order-2 space (SAP), the temporal spaces,
+ * move_pt_back_to, the rate-limited sampler, and the batch planners over this space. */
+rkh_status rkh_svp_in_bounds(const rkh_svp_space* space, const double* pts /* [B][2 n_dof] */, uint32_t B, uint8_t* ok /* [B] */);
+rkh_status rkh_svp_reach_time(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
+                              double* time /* [B] */, double* peak /* [B][n_dof], may be NULL */);
+rkh_status rkh_svp_nearest(rkh_ctx* ctx, const rkh_svp_space* space, const double* points /* [n_pts][2 n_dof] */,
+                           uint32_t n_pts, const double* queries /* [B][2 n_dof] */, uint32_t B, uint32_t k, int32_t direction,
+                           uint32_t* idx /* [B][k] */, double* dist /* [B][k] */);
+rkh_status rkh_svp_nearest_async(rkh_ctx* ctx, const rkh_svp_space* space, const double* d_points, uint32_t n_pts,
+                                 const double* d_queries, uint32_t B, uint32_t k, int32_t direction, uint32_t* d_idx,
+                                 double* d_dist);
+rkh_status rkh_svp_edge_check(rkh_scene* scene, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
+                              const double* fraction /* [B], NULL = 1.0 */, double* out /* [B][2 n_dof] */,
+                              double* reach_time /* [B] */, uint32_t* n_checked /* [B] */, uint8_t* reached /* [B] */);
+rkh_status rkh_svp_interpolate(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
+                               const double* t /* [B][M] */, uint32_t M, double* out /* [B][M][2 n_dof] */,
+                               double* reach_time /* [B] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,20 @@ typedef struct rkh_qs_space {
   double speed_limits[RKH_MAX_DOF];
 } rkh_qs_space;
 
+/* The order-1 rate-limited joint space with sustained-velocity-pulse (SVP) interpolation the reference's manipulator
+ * applications plan in (Ndof_rl_space<., 1> under ctrl/interpolation/svp_Ndof_reach_topologies.hpp;
+ * ctrl/topologies/manip_workspaces.hpp:227-245).  A point is (p0, v0, p1, v1, ...) with p_i = q_i / speed_limits[i] and
+ * v_i = qd_i / accel_limits[i]; positions move at rate v_i / vm_i, vm_i = speed_limits[i] / accel_limits[i], velocities at
+ * rate +-1 or 0, |v_i| <= vm_i.  The model is posed at q_i = p_i speed_limits[i].  A limit of 0 (or 1) = unit limit, as
+ * rkh_qs_space::speed_limits.  The struct carries its own size; the rkh_svp_* entries (rkh.h) check it themselves. */
+typedef struct rkh_svp_space {
+  uint32_t struct_size; /* sizeof(rkh_svp_space) */
+  int32_t n_dof;
+  double min_interval;  /* travel time between two tested points of an edge */
+  double lower[RKH_MAX_DOF], upper[RKH_MAX_DOF]; /* position box, space coordinates */
+  double speed_limits[RKH_MAX_DOF], accel_limits[RKH_MAX_DOF];
+} rkh_svp_space;
+
 /* sample_based_planner options (ctrl/path_planning/motion_planner_base.hpp:400-422) and the
  * point-to-point query (ctrl/path_planning/p2p_planning_query.hpp:74-229). */
 typedef struct rkh_rrt_params {

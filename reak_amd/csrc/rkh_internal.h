@@ -267,6 +267,8 @@ struct rkh_ctx {
   // over on one scene then maps its memory once (at 512 problems x 100 000 vertices a planner holds 26 GB).  At most
   // kArenaCacheSlots; rkh_ctx_release_cached_memory, an allocation that runs out of memory and rkh_ctx_destroy free them.
   std::vector<rkh::DeviceArena> arena_cache;
+  // the slices' partial lists of rkh_svp_nearest_async (svp_space.hip); grows with the largest request
+  rkh::DeviceBuffer<void> svp_ws;
 };
 
 namespace rkh {

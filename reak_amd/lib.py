@@ -90,6 +90,8 @@ EXPORTS = [
     "rkh_shortcut_paths", "rkh_diag_shortcut_dp", "rkh_diag_shortcut_ms",
     "rkh_direct_kinematics", "rkh_direct_kinematics_2d", "rkh_jacobians", "rkh_jacobians_2d", "rkh_inverse_kinematics",
     "rkh_diag_kinematics_ms", "rkh_diag_ik_ms",
+    "rkh_svp_in_bounds", "rkh_svp_reach_time", "rkh_svp_nearest", "rkh_svp_nearest_async", "rkh_svp_edge_check",
+    "rkh_svp_interpolate",
 ]
 
 
@@ -209,6 +211,13 @@ def load():
     lib.rkh_diag_kinematics_ms.argtypes = [vp, dp, dp, u32, i32p, u32, u32, C.POINTER(C.c_float)]
     lib.rkh_diag_ik_ms.argtypes = [vp, C.c_int32, C.POINTER(T.Pose), u32, dp, u32, dp, dp, C.POINTER(T.IkParams), u32,
                                    C.POINTER(C.c_float)]
+    svp = C.POINTER(T.SvpSpace)
+    lib.rkh_svp_in_bounds.argtypes = [svp, dp, u32, u8p]
+    lib.rkh_svp_reach_time.argtypes = [vp, svp, dp, dp, u32, dp, dp]
+    lib.rkh_svp_nearest.argtypes = [vp, svp, dp, u32, dp, u32, u32, C.c_int32, u32p, dp]
+    lib.rkh_svp_nearest_async.argtypes = [vp, svp, vp, u32, vp, u32, u32, C.c_int32, vp, vp]
+    lib.rkh_svp_edge_check.argtypes = [vp, svp, dp, dp, u32, dp, dp, dp, u32p, u8p]
+    lib.rkh_svp_interpolate.argtypes = [vp, svp, dp, dp, u32, dp, u32, dp, dp]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -772,6 +781,75 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+class SvpSpace:
+    """The order-1 rate-limited joint space with SVP profiles (rkh_svp_*): points are [2 n] rows (p0, v0, p1, v1, ...) in
+    space coordinates.  `space` is a T.SvpSpace (T.make_svp_space); `ctx` serves reach_time, nearest and interpolate,
+    `scene` (optional) the edge walk; in_bounds needs neither."""
+
+    def __init__(self, space, ctx=None, scene=None):
+        self.lib = load()
+        self.space, self.ctx, self.scene = space, ctx if ctx is not None else (scene.ctx if scene is not None else None), scene
+        self.n = int(space.n_dof)
+
+    def _rows(self, x):
+        return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, 2 * self.n))
+
+    def in_bounds(self, pts):
+        pts = self._rows(pts)
+        ok = np.zeros(max(len(pts), 1), dtype=np.uint8)
+        _check(self.lib.rkh_svp_in_bounds(C.byref(self.space), T.dptr(pts), len(pts), ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return ok[:len(pts)].astype(bool)
+
+    def reach_time(self, a, b, peaks=True):
+        """(time [B], peak [B][n]) of d(a_e -> b_e); +inf and a row of zeros where the pair is infeasible."""
+        a, b = self._rows(a), self._rows(b)
+        B = len(a)
+        time, peak = np.zeros(max(B, 1)), np.zeros((max(B, 1), self.n))
+        _check(self.lib.rkh_svp_reach_time(self.ctx.h, C.byref(self.space), T.dptr(a), T.dptr(b), B, T.dptr(time),
+                                           T.dptr(peak) if peaks else None))
+        return (time[:B], peak[:B]) if peaks else time[:B]
+
+    def nearest(self, points, queries, k, direction=0):
+        """(idx [B][k], dist [B][k]) by d(point -> query) (direction 0) or d(query -> point) (1), ascending by (distance,
+        index); padded with 0xFFFFFFFF / +inf."""
+        points, queries = self._rows(points), self._rows(queries)
+        B = len(queries)
+        idx, dist = np.zeros((max(B, 1), k), dtype=np.uint32), np.zeros((max(B, 1), k))
+        _check(self.lib.rkh_svp_nearest(self.ctx.h, C.byref(self.space), T.dptr(points), len(points), T.dptr(queries), B, int(k),
+                                        int(direction), T.u32ptr(idx), T.dptr(dist)))
+        return idx[:B], dist[:B]
+
+    def nearest_async(self, d_points, n_pts, d_queries, B, k, direction, d_idx, d_dist):
+        """Device pointers (integers), enqueued on the context's stream."""
+        _check(self.lib.rkh_svp_nearest_async(self.ctx.h, C.byref(self.space), d_points, int(n_pts), d_queries, int(B), int(k),
+                                              int(direction), d_idx, d_dist))
+
+    def edge_check(self, a, b, fraction=None):
+        """The collision-tested walk: (out [B][2n], reach_time [B], n_checked [B], reached [B])."""
+        a, b = self._rows(a), self._rows(b)
+        B = len(a)
+        out, rt = np.zeros((max(B, 1), 2 * self.n)), np.zeros(max(B, 1))
+        nc, re = np.zeros(max(B, 1), dtype=np.uint32), np.zeros(max(B, 1), dtype=np.uint8)
+        fr = None
+        if fraction is not None:
+            fr = np.ascontiguousarray(np.broadcast_to(np.asarray(fraction, dtype=np.float64), (B,)))
+        _check(self.lib.rkh_svp_edge_check(self.scene.h, C.byref(self.space), T.dptr(a), T.dptr(b), B,
+                                           T.dptr(fr) if fr is not None else None, T.dptr(out), T.dptr(rt), T.u32ptr(nc),
+                                           re.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out[:B], rt[:B], nc[:B], re[:B]
+
+    def interpolate(self, a, b, t):
+        """(out [B][M][2n], reach_time [B]): the profile of each pair at the times t [B][M]."""
+        a, b = self._rows(a), self._rows(b)
+        B = len(a)
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(B, -1))
+        M = t.shape[1]
+        out, rt = np.zeros((max(B, 1), max(M, 1), 2 * self.n)), np.zeros(max(B, 1))
+        _check(self.lib.rkh_svp_interpolate(self.ctx.h, C.byref(self.space), T.dptr(a), T.dptr(b), B, T.dptr(t) if M else None, M,
+                                            T.dptr(out), T.dptr(rt)))
+        return out[:B, :M], rt[:B]
 
 
 def make_qs_space(n_dof, lower, upper, min_interval, speed_limits=None):

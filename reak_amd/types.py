@@ -106,6 +106,23 @@ def make_ik_params(max_iters=100, damping=0.02, max_step=0.5, tol_pos=1e-6, tol_
                     max_step=float(max_step), tol_pos=float(tol_pos), tol_rot=float(tol_rot))
 
 
+class SvpSpace(C.Structure):
+    """rkh_svp_space (include/rkh_types.h): the order-1 rate-limited joint space with SVP profiles."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_dof", C.c_int32), ("min_interval", C.c_double),
+                ("lower", C.c_double * RKH_MAX_DOF), ("upper", C.c_double * RKH_MAX_DOF),
+                ("speed_limits", C.c_double * RKH_MAX_DOF), ("accel_limits", C.c_double * RKH_MAX_DOF)]
+
+
+def make_svp_space(n_dof, lower, upper, min_interval, speed_limits=None, accel_limits=None):
+    """lower / upper: the position box in space coordinates; limits None or 0: unit limits."""
+    sp = SvpSpace(struct_size=C.sizeof(SvpSpace), n_dof=int(n_dof), min_interval=float(min_interval))
+    for i in range(int(n_dof)):
+        sp.lower[i], sp.upper[i] = float(lower[i]), float(upper[i])
+        sp.speed_limits[i] = 0.0 if speed_limits is None else float(speed_limits[i])
+        sp.accel_limits[i] = 0.0 if accel_limits is None else float(accel_limits[i])
+    return sp
+
+
 def make_pose(pos=(0.0, 0.0, 0.0), quat=(1.0, 0.0, 0.0, 0.0)):
     p = Pose()
     p.pos[:] = [float(v) for v in pos]
