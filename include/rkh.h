@@ -637,7 +637,7 @@ rkh_status rkh_inverse_kinematics(rkh_scene* scene, int32_t frame, const rkh_pos
  * B == 0, M == 0 or n_pts == 0 is RKH_OK.  RKH_ERR_BAD_ARG: space->struct_size != sizeof(rkh_svp_space), n_dof not in
  * [1, 12] or not the scene's, min_interval not positive and finite, lower > upper, a negative or non-finite limit, k or
  * direction out of range, a NULL required pointer.  Not built: the order-2 space (SAP), the temporal spaces,
- * move_pt_back_to, the rate-limited sampler, and the batch planners over this space. */
+ * move_pt_back_to, and batch planners over this space other than the RRT below. */
 rkh_status rkh_svp_in_bounds(const rkh_svp_space* space, const double* pts /* [B][2 n_dof] */, uint32_t B, uint8_t* ok /* [B] */);
 rkh_status rkh_svp_reach_time(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
                               double* time /* [B] */, double* peak /* [B][n_dof], may be NULL */);
@@ -653,6 +653,61 @@ rkh_status rkh_svp_edge_check(rkh_scene* scene, const rkh_svp_space* space, cons
 rkh_status rkh_svp_interpolate(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
                                const double* t /* [B][M] */, uint32_t M, double* out /* [B][M][2 n_dof] */,
                                double* reach_time /* [B] */);
+
+/* ---- batch RRT over the SVP space: device-resident trees, P problems per launch ------------------------------------------
+ * P independent problems (rkh_svp_rrt_params, rkh_types.h) on one scene and one space grow in lock step, one RRT iteration
+ * of every unfinished problem per round; trees, sample streams and all per-problem state stay on the device.  Each
+ * problem's tree is, bit for bit, the tree of this sequential loop, whatever P is and whatever the other problems do:
+ *
+ *   sample stream: std::mt19937(seed); draw j gives u = y 2^-32; candidate k takes draws k D .. k D + D - 1 (D = 2 n_dof)
+ *     in point order, coordinate c = lo_c + u (hi_c - lo_c) with (lo, hi) = (lower[i], upper[i]) for p_i and
+ *     (-vm_i, +vm_i) for v_i: the rate-limited sampler (draw from the box, reject with rkh_svp_in_bounds), every draw an
+ *     iteration.
+ *   before the loop: has_goal and the whole edge start -> goal is free (rkh_svp_edge_check, fraction 1, reached): goal_parent = 0.
+ *   while the goal is not reached, n_vertices < max_vertices and iterations < max_iterations:
+ *     take the next candidate, ++iterations; not rkh_svp_in_bounds: next iteration;
+ *     the 1-nearest vertex by d(vertex -> candidate), ties to the lower index; every distance +inf: next iteration;
+ *     fraction = asked > 0 ? min(1, max_edge_time / asked) : 1; walk vertex -> candidate with that fraction as
+ *     rkh_svp_edge_check does; n_checked == 0: next iteration;
+ *     travelled = d(vertex -> out); commit only if it is finite, < 2 asked fraction and > steer_tol asked fraction:
+ *     append out with its parent and travelled; has_goal and the whole edge out -> goal is free: goal_parent = the new vertex.
+ *
+ * rkh_svp_rrt_create_batch: P in [1, 16384]; runs the probes before the loop.  One arena of the context per planner.
+ * rkh_svp_rrt_solve: rounds until every problem has ended or max_rounds of them have run (max_rounds < 0: no limit); a
+ * later call resumes where the last stopped.  stats (may be NULL) are totals since create.  A round draws at most 1024
+ * candidates per problem: a problem that found none in bounds among them makes no extension in that round.
+ * rkh_svp_rrt_get_status: per problem; any pointer may be NULL.  goal_parent 0xFFFFFFFF: the goal is not reached.
+ * rkh_svp_rrt_get_tree: the first min(V, capacity) vertices of one problem ([.][2 n_dof]), their parents (0xFFFFFFFF for
+ * the start) and edge times (d(parent -> vertex); 0 for the start); *n_vertices = V.  Output pointers may be NULL.
+ * rkh_svp_rrt_get_solution: start ... goal, the goal last, [n_points][2 n_dof]; duration = the sum of the edges' reach
+ * times in path order.  n_points = 0 (and duration = 0) when the goal has not been reached; more points than capacity:
+ * RKH_ERR_CAPACITY with *n_points set.
+ *
+ * RKH_ERR_BAD_ARG: a NULL required pointer, a struct of another size (space or any params), n_dof not the scene's,
+ * max_vertices == 0, a start that is not finite or fails rkh_svp_in_bounds, P == 0 or P > 16384.  RKH_ERR_CAPACITY: an
+ * edge with more than 1 048 576 points to test (the planner then refuses further rounds).  A failed create leaves no
+ * planner behind (*out = NULL). */
+typedef struct rkh_svp_rrt rkh_svp_rrt;
+typedef struct rkh_svp_rrt_stats {
+  uint64_t rounds;            /* rounds run */
+  uint64_t problems_finished; /* problems that have ended */
+  uint64_t iterations;        /* candidates drawn, over all problems */
+  uint64_t vertices;          /* vertices, over all problems (the starts included) */
+  uint64_t walk_passes;       /* passes of the staged walk, extensions and probes */
+  uint64_t tested_points;     /* points tested by the walks */
+  uint64_t window_refills;    /* refills of the problems' sample windows (64 candidates each) */
+} rkh_svp_rrt_stats;
+rkh_status rkh_svp_rrt_create_batch(rkh_scene* scene, const rkh_svp_space* space, const rkh_svp_rrt_params* params /* [P] */,
+                                    uint32_t P, rkh_svp_rrt** out);
+void rkh_svp_rrt_destroy(rkh_svp_rrt* planner);
+rkh_status rkh_svp_rrt_solve(rkh_svp_rrt* planner, int64_t max_rounds, rkh_svp_rrt_stats* stats);
+rkh_status rkh_svp_rrt_get_status(rkh_svp_rrt* planner, uint32_t* n_vertices /* [P] */, uint32_t* iterations /* [P] */,
+                                  uint32_t* goal_parent /* [P] */);
+rkh_status rkh_svp_rrt_get_tree(rkh_svp_rrt* planner, uint32_t problem, double* vertices /* [capacity][2 n_dof] */,
+                                uint32_t* parent /* [capacity] */, double* edge_time /* [capacity] */, uint32_t capacity,
+                                uint32_t* n_vertices);
+rkh_status rkh_svp_rrt_get_solution(rkh_svp_rrt* planner, uint32_t problem, double* points /* [capacity][2 n_dof] */,
+                                    uint32_t capacity, uint32_t* n_points, double* duration);
 
 #ifdef __cplusplus
 }

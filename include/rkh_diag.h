@@ -163,6 +163,10 @@ rkh_status rkh_diag_kinematics_ms(rkh_scene* scene, const double* q, const doubl
 rkh_status rkh_diag_ik_ms(rkh_scene* scene, int32_t frame, const rkh_pose* targets, uint32_t T, const double* seeds, uint32_t S,
                           const double* lower, const double* upper, const rkh_ik_params* params, uint32_t runs,
                           float* ms /* [runs][2] */);
+/* The split of the batch SVP RRT's rounds (tools/measure_svp_rrt.py): enable = 1 brackets the phases of every later round
+ * of the planner with events on the context's stream; ms (may be NULL) receives the totals so far of {sample, nearest +
+ * steer, extension walk, commit, probe walk, finish} in milliseconds (the walks include their read-backs). */
+rkh_status rkh_diag_svp_rrt_profile(rkh_svp_rrt* planner, int32_t enable, double* ms /* [6] */);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,22 @@ typedef struct rkh_svp_space {
   double speed_limits[RKH_MAX_DOF], accel_limits[RKH_MAX_DOF];
 } rkh_svp_space;
 
+/* One problem of the batch RRT over that space (rkh_svp_rrt_*, rkh.h): the loop of examples/plan_svp_rrt.py with the
+ * library's own sample stream.  Points are [2 n_dof] (p0, v0, p1, v1, ...) in space coordinates.  The struct carries its
+ * own size. */
+typedef struct rkh_svp_rrt_params {
+  uint32_t struct_size;    /* sizeof(rkh_svp_rrt_params) */
+  uint32_t seed;           /* std::mt19937(seed) */
+  uint32_t max_vertices;   /* the tree stops growing at this many vertices (the start included); >= 1 */
+  uint32_t max_iterations; /* candidates drawn at most, rejected ones included */
+  double max_edge_time;    /* travel time of an extension at most (the steer fraction is min(1, max_edge_time / asked)) */
+  double steer_tol;        /* progress rule: travelled > steer_tol x asked x fraction (and < 2 x asked x fraction) */
+  uint32_t has_goal;       /* 0: no goal probes, the tree grows to max_vertices */
+  uint32_t pad;
+  double start[RKH_MAX_STATE];
+  double goal[RKH_MAX_STATE];
+} rkh_svp_rrt_params;
+
 /* sample_based_planner options (ctrl/path_planning/motion_planner_base.hpp:400-422) and the
  * point-to-point query (ctrl/path_planning/p2p_planning_query.hpp:74-229). */
 typedef struct rkh_rrt_params {

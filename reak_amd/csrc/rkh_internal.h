@@ -536,4 +536,39 @@ rkh_status launch_edge_check(hipStream_t s, const rkh_scene& scene, const QsDev&
 rkh_status launch_min_distance(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, double* d_dist);
 }  // namespace planar_prismatic
 rkh_status build_dyn_dev(const rkh_dyn_space& sp, double fraction, DynDev* out);
+
+// ---- the staged walk of the SVP space (svp_space.hip) ----------------------------------------------------------------------
+struct SvpDev;  // svp_device.h
+// everything the rkh_svp_* entries check about a space, and its device form.  scene_n < 0: no scene to agree with
+rkh_status svp_space_dev(const char* who, const rkh_svp_space* sp, int scene_n, SvpDev* out);
+struct SvpWalk {  // the walk's workspace: device pointers into the caller's memory, by value
+  const double* a;         // [B][2n]
+  const double* b;
+  const double* fraction;  // [B] or null = 1.0
+  double* T;               // [B]
+  double* peak;            // [B][n]
+  double* dt;              // [B] T fraction
+  uint32_t* K;             // [B] points of the edge's loop
+  uint32_t* k_done;        // [B] points that passed
+  double* d_next;          // [B] travel time of point k_done
+  double* last;            // [B][2n] last point that passed
+  double* out;             // [B][2n]
+  uint32_t* n_checked;     // [B]
+  uint8_t* reached;        // [B]
+  uint32_t* list[2];       // [B] live edges of this pass / the next
+  uint32_t* counters;      // [0], [1]: entries of list[0], list[1]; [2]: an edge with more than kSvpMaxPoints points
+  double* pts;             // [live][kSvpPass][2n] space coordinates
+  double* pts_model;       // the same in model units
+  uint8_t* inb;            // [live][kSvpPass]
+  double* dist;            // [live][kSvpPass]
+  uint32_t B;
+};
+// Bytes of a workspace for at most B edges of n_dof joints (256-byte aligned ranges, no guard tail); with base, *w points
+// into it (fraction null unless with_fraction; w->B = B).
+size_t svp_walk_layout(int n_dof, uint32_t B, bool with_fraction, void* base, SvpWalk* w);
+// The walk of rkh_svp_edge_check over the rows w.a, w.b, w.fraction of the first w.B edges, already on the device: the solve
+// launch and the passes on the scene's context's stream, one read-back of the live count per pass; the stream is idle on
+// return.  Results in w.out, w.T, w.n_checked, w.reached.  passes (may be null): passes run.  RKH_ERR_CAPACITY: an edge with
+// more than 1 048 576 points to test.
+rkh_status launch_svp_walk(const char* who, const rkh_scene& scene, const SvpDev& sp, const SvpWalk& w, uint32_t* passes);
 }  // namespace rkh

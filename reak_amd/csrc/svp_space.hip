@@ -13,6 +13,8 @@
 //   svp_walk_scan_kernel     one lane per live edge: the pass's verdicts in order; first failure, last good point, count;
 //                            unfinished edges enter the next pass's list
 //   svp_interp_kernel        one lane per (pair, time)
+// The walk's launches are launch_svp_walk (rkh_internal.h), over device rows and a caller-owned workspace: rkh_svp_edge_check
+// wraps it with the arena and the copies, the batch RRT (svp_planner.hip) calls it on its own rows.
 #include <cmath>
 #include <cstring>
 
@@ -152,29 +154,7 @@ __global__ __launch_bounds__(256) void svp_nearest_merge_kernel(const double* __
 }
 
 // ---- the walk -----------------------------------------------------------------------------------------------------------
-struct SvpWalk {  // device pointers into the call's arena, by value
-  const double* a;         // [B][2n]
-  const double* b;
-  const double* fraction;  // [B] or null = 1.0
-  double* T;               // [B]
-  double* peak;            // [B][n]
-  double* dt;              // [B] T fraction
-  uint32_t* K;             // [B] points of the edge's loop
-  uint32_t* k_done;        // [B] points that passed
-  double* d_next;          // [B] travel time of point k_done
-  double* last;            // [B][2n] last point that passed
-  double* out;             // [B][2n]
-  uint32_t* n_checked;     // [B]
-  uint8_t* reached;        // [B]
-  uint32_t* list[2];       // [B] live edges of this pass / the next
-  uint32_t* counters;      // [0], [1]: entries of list[0], list[1]; [2]: an edge with more than kSvpMaxPoints points
-  double* pts;             // [live][kSvpPass][2n] space coordinates
-  double* pts_model;       // the same in model units
-  uint8_t* inb;            // [live][kSvpPass]
-  double* dist;            // [live][kSvpPass]
-  uint32_t B;
-};
-
+// (SvpWalk, the workspace the three kernels share: rkh_internal.h)
 __device__ __forceinline__ double svp_fraction(const SvpWalk& w, uint32_t e) { return w.fraction ? w.fraction[e] : 1.0; }
 
 // what the walk returns after its loop: b, a, or the (untested) point at dt
@@ -321,6 +301,8 @@ rkh_status bad(const char* who, const char* what) {
   return RKH_ERR_BAD_ARG;
 }
 
+}  // namespace
+
 // everything the entries check about a space, and its device form.  scene_n < 0: no scene to agree with
 rkh_status svp_space_dev(const char* who, const rkh_svp_space* sp, int scene_n, SvpDev* out) {
   if (!sp) return bad(who, "space is NULL");
@@ -346,6 +328,80 @@ rkh_status svp_space_dev(const char* who, const rkh_svp_space* sp, int scene_n, 
   }
   return RKH_OK;
 }
+
+size_t svp_walk_layout(int n_dof, uint32_t B, bool with_fraction, void* base, SvpWalk* w) {
+  const size_t D = 2 * size_t(n_dof), n = size_t(n_dof);
+  size_t cur = 0;
+  auto take = [&cur](size_t bytes) {
+    ArenaRange r;
+    r.off = cur, r.bytes = bytes;
+    cur = arena_align_up(cur + bytes);
+    return r;
+  };
+  const size_t rows = size_t(B) * kSvpPass;
+  const ArenaRange r_a = take(B * D * 8), r_b = take(B * D * 8), r_f = take(with_fraction ? size_t(B) * 8 : 0), r_T = take(size_t(B) * 8),
+                   r_peak = take(B * n * 8), r_dt = take(size_t(B) * 8), r_K = take(size_t(B) * 4), r_kd = take(size_t(B) * 4),
+                   r_dn = take(size_t(B) * 8), r_last = take(B * D * 8), r_out = take(B * D * 8), r_nc = take(size_t(B) * 4),
+                   r_re = take(B), r_l0 = take(size_t(B) * 4), r_l1 = take(size_t(B) * 4), r_cnt = take(3 * 4),
+                   r_pts = take(rows * D * 8), r_ptm = take(rows * D * 8), r_inb = take(rows), r_dist = take(rows * 8);
+  if (base && w) {
+    char* const p = static_cast<char*>(base);
+    auto at = [p](const ArenaRange& r) { return r.bytes ? static_cast<void*>(p + r.off) : nullptr; };
+    w->a = static_cast<double*>(at(r_a)), w->b = static_cast<double*>(at(r_b)), w->fraction = static_cast<double*>(at(r_f));
+    w->T = static_cast<double*>(at(r_T)), w->peak = static_cast<double*>(at(r_peak)), w->dt = static_cast<double*>(at(r_dt));
+    w->K = static_cast<uint32_t*>(at(r_K)), w->k_done = static_cast<uint32_t*>(at(r_kd)), w->d_next = static_cast<double*>(at(r_dn));
+    w->last = static_cast<double*>(at(r_last)), w->out = static_cast<double*>(at(r_out));
+    w->n_checked = static_cast<uint32_t*>(at(r_nc)), w->reached = static_cast<uint8_t*>(at(r_re));
+    w->list[0] = static_cast<uint32_t*>(at(r_l0)), w->list[1] = static_cast<uint32_t*>(at(r_l1));
+    w->counters = static_cast<uint32_t*>(at(r_cnt));
+    w->pts = static_cast<double*>(at(r_pts)), w->pts_model = static_cast<double*>(at(r_ptm));
+    w->inb = static_cast<uint8_t*>(at(r_inb)), w->dist = static_cast<double*>(at(r_dist));
+    w->B = B;
+  }
+  return cur;
+}
+
+rkh_status launch_svp_walk(const char* who, const rkh_scene& scene, const SvpDev& sp, const SvpWalk& w, uint32_t* passes) {
+  const uint32_t B = w.B;
+  hipStream_t s = scene.ctx->stream;
+  if (passes) *passes = 0;
+  if (B == 0) return RKH_OK;
+  StreamWait wait_on_exit{s};
+  RKH_HIP(hipMemsetAsync(w.counters, 0, 3 * 4, s));
+  hipLaunchKernelGGL(svp_walk_solve_kernel, dim3((B + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w);
+  RKH_HIP(hipGetLastError());
+  uint32_t cnt[3] = {0, 0, 0};
+  RKH_HIP(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, s));
+  RKH_HIP(hipStreamSynchronize(s));
+  if (cnt[2]) {
+    set_error(std::string(who) + ": an edge has more than 1 048 576 points to test (min_interval against its reach time)");
+    return RKH_ERR_CAPACITY;
+  }
+  const int has_dist = scene.n_pairs > 0 ? 1 : 0;
+  uint32_t pass = 0;
+  for (uint32_t live = cnt[0], c = 0; live > 0; c = 1 - c, ++pass) {
+    if (live > B || pass > kSvpMaxPoints / kSvpPass) {
+      set_error(std::string(who) + ": the live list is inconsistent");
+      return RKH_ERR_DEVICE;
+    }
+    const uint32_t n_rows = live * kSvpPass;
+    hipLaunchKernelGGL(svp_walk_points_kernel, dim3((n_rows + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w, c,
+                       live);
+    RKH_HIP(hipGetLastError());
+    if (has_dist) RKH_TRY(launch_min_distance(s, scene, w.pts_model, n_rows, w.dist));
+    RKH_HIP(hipMemsetAsync(w.counters + (1 - c), 0, 4, s));
+    hipLaunchKernelGGL(svp_walk_scan_kernel, dim3((live + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w, c, live,
+                       has_dist);
+    RKH_HIP(hipGetLastError());
+    RKH_HIP(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    RKH_HIP(hipStreamSynchronize(s));
+    live = cnt[1 - c];
+  }
+  if (passes) *passes = pass;
+  return RKH_OK;
+}
+
+namespace {
 
 rkh_status launch_svp_reach(hipStream_t s, const SvpDev& sp, const double* d_a, const double* d_b, uint32_t B, double* d_time,
                             double* d_peak) {
@@ -517,26 +573,14 @@ rkh_status rkh_svp_edge_check(rkh_scene* scene, const rkh_svp_space* space, cons
     set_error(std::string(who) + ": at most 16 777 216 edges per call");
     return RKH_ERR_CAPACITY;
   }
-  const size_t D = 2 * size_t(sp.n), n = size_t(sp.n);
+  const size_t D = 2 * size_t(sp.n);
   rkh_ctx* ctx = scene->ctx;
   hipStream_t s = ctx->stream;
   RKH_HIP(hipSetDevice(ctx->device));
   // one slab for the call
-  size_t cur = 0;
-  auto take = [&cur](size_t bytes) {
-    ArenaRange r;
-    r.off = cur, r.bytes = bytes;
-    cur = arena_align_up(cur + bytes);
-    return r;
-  };
-  const size_t rows = size_t(B) * kSvpPass;
-  const ArenaRange r_a = take(B * D * 8), r_b = take(B * D * 8), r_f = take(fraction ? size_t(B) * 8 : 0), r_T = take(size_t(B) * 8),
-                   r_peak = take(B * n * 8), r_dt = take(size_t(B) * 8), r_K = take(size_t(B) * 4), r_kd = take(size_t(B) * 4),
-                   r_dn = take(size_t(B) * 8), r_last = take(B * D * 8), r_out = take(B * D * 8), r_nc = take(size_t(B) * 4),
-                   r_re = take(B), r_l0 = take(size_t(B) * 4), r_l1 = take(size_t(B) * 4), r_cnt = take(3 * 4),
-                   r_pts = take(rows * D * 8), r_ptm = take(rows * D * 8), r_inb = take(rows), r_dist = take(rows * 8);
+  const size_t bytes = svp_walk_layout(sp.n, B, fraction != nullptr, nullptr, nullptr);
   DeviceArena arena;
-  RKH_TRY(ctx_take_arena(ctx, cur + kArenaGuardBytes, true, &arena));
+  RKH_TRY(ctx_take_arena(ctx, bytes + kArenaGuardBytes, true, &arena));
   struct GiveBack {  // the stream is idle before the slab goes back to its context
     rkh_ctx* ctx;
     hipStream_t s;
@@ -547,48 +591,11 @@ rkh_status rkh_svp_edge_check(rkh_scene* scene, const rkh_svp_space* space, cons
     }
   } give_back{ctx, s, &arena};
   SvpWalk w;
-  w.a = arena.at<double>(r_a), w.b = arena.at<double>(r_b), w.fraction = arena.at<double>(r_f);
-  w.T = arena.at<double>(r_T), w.peak = arena.at<double>(r_peak), w.dt = arena.at<double>(r_dt);
-  w.K = arena.at<uint32_t>(r_K), w.k_done = arena.at<uint32_t>(r_kd), w.d_next = arena.at<double>(r_dn);
-  w.last = arena.at<double>(r_last), w.out = arena.at<double>(r_out), w.n_checked = arena.at<uint32_t>(r_nc);
-  w.reached = arena.at<uint8_t>(r_re);
-  w.list[0] = arena.at<uint32_t>(r_l0), w.list[1] = arena.at<uint32_t>(r_l1), w.counters = arena.at<uint32_t>(r_cnt);
-  w.pts = arena.at<double>(r_pts), w.pts_model = arena.at<double>(r_ptm), w.inb = arena.at<uint8_t>(r_inb);
-  w.dist = arena.at<double>(r_dist);
-  w.B = B;
+  svp_walk_layout(sp.n, B, fraction != nullptr, arena.get(), &w);
   RKH_HIP(hipMemcpyAsync(const_cast<double*>(w.a), a, B * D * 8, hipMemcpyHostToDevice, s));
   RKH_HIP(hipMemcpyAsync(const_cast<double*>(w.b), b, B * D * 8, hipMemcpyHostToDevice, s));
   if (fraction) RKH_HIP(hipMemcpyAsync(const_cast<double*>(w.fraction), fraction, size_t(B) * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemsetAsync(w.counters, 0, 3 * 4, s));
-  hipLaunchKernelGGL(svp_walk_solve_kernel, dim3((B + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w);
-  RKH_HIP(hipGetLastError());
-  uint32_t cnt[3] = {0, 0, 0};
-  RKH_HIP(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  if (cnt[2]) {
-    set_error(std::string(who) + ": an edge has more than 1 048 576 points to test (min_interval against its reach time)");
-    return RKH_ERR_CAPACITY;
-  }
-  const int has_dist = scene->n_pairs > 0 ? 1 : 0;
-  uint32_t pass = 0;
-  for (uint32_t live = cnt[0], c = 0; live > 0; c = 1 - c, ++pass) {
-    if (live > B || pass > kSvpMaxPoints / kSvpPass) {
-      set_error(std::string(who) + ": the live list is inconsistent");
-      return RKH_ERR_DEVICE;
-    }
-    const uint32_t n_rows = live * kSvpPass;
-    hipLaunchKernelGGL(svp_walk_points_kernel, dim3((n_rows + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w, c,
-                       live);
-    RKH_HIP(hipGetLastError());
-    if (has_dist) RKH_TRY(launch_min_distance(s, *scene, w.pts_model, n_rows, w.dist));
-    RKH_HIP(hipMemsetAsync(w.counters + (1 - c), 0, 4, s));
-    hipLaunchKernelGGL(svp_walk_scan_kernel, dim3((live + kSvpThreads - 1) / kSvpThreads), dim3(kSvpThreads), 0, s, sp, w, c, live,
-                       has_dist);
-    RKH_HIP(hipGetLastError());
-    RKH_HIP(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipStreamSynchronize(s));
-    live = cnt[1 - c];
-  }
+  RKH_TRY(launch_svp_walk(who, *scene, sp, w, nullptr));
   RKH_HIP(hipMemcpyAsync(out, w.out, B * D * 8, hipMemcpyDeviceToHost, s));
   if (reach_time) RKH_HIP(hipMemcpyAsync(reach_time, w.T, size_t(B) * 8, hipMemcpyDeviceToHost, s));
   if (n_checked) RKH_HIP(hipMemcpyAsync(n_checked, w.n_checked, size_t(B) * 4, hipMemcpyDeviceToHost, s));

@@ -51,6 +51,13 @@ class BiRrtStats(C.Structure):
                 ("edges_checked", C.c_uint64), ("best_cost", C.c_double)]
 
 
+class SvpRrtStats(C.Structure):
+    """rkh_svp_rrt_stats (include/rkh.h): totals since the planner was created."""
+    _fields_ = [("rounds", C.c_uint64), ("problems_finished", C.c_uint64), ("iterations", C.c_uint64),
+                ("vertices", C.c_uint64), ("walk_passes", C.c_uint64), ("tested_points", C.c_uint64),
+                ("window_refills", C.c_uint64)]
+
+
 class PlannerStats(C.Structure):
     _fields_ = [
         ("num_vertices", C.c_uint64),
@@ -92,6 +99,8 @@ EXPORTS = [
     "rkh_diag_kinematics_ms", "rkh_diag_ik_ms",
     "rkh_svp_in_bounds", "rkh_svp_reach_time", "rkh_svp_nearest", "rkh_svp_nearest_async", "rkh_svp_edge_check",
     "rkh_svp_interpolate",
+    "rkh_svp_rrt_create_batch", "rkh_svp_rrt_destroy", "rkh_svp_rrt_solve", "rkh_svp_rrt_get_status", "rkh_svp_rrt_get_tree",
+    "rkh_svp_rrt_get_solution", "rkh_diag_svp_rrt_profile",
 ]
 
 
@@ -218,6 +227,14 @@ def load():
     lib.rkh_svp_nearest_async.argtypes = [vp, svp, vp, u32, vp, u32, u32, C.c_int32, vp, vp]
     lib.rkh_svp_edge_check.argtypes = [vp, svp, dp, dp, u32, dp, dp, dp, u32p, u8p]
     lib.rkh_svp_interpolate.argtypes = [vp, svp, dp, dp, u32, dp, u32, dp, dp]
+    lib.rkh_svp_rrt_create_batch.argtypes = [vp, svp, C.POINTER(T.SvpRrtParams), u32, C.POINTER(vp)]
+    lib.rkh_svp_rrt_destroy.argtypes = [vp]
+    lib.rkh_svp_rrt_destroy.restype = None
+    lib.rkh_svp_rrt_solve.argtypes = [vp, C.c_int64, C.POINTER(SvpRrtStats)]
+    lib.rkh_svp_rrt_get_status.argtypes = [vp, u32p, u32p, u32p]
+    lib.rkh_svp_rrt_get_tree.argtypes = [vp, u32, dp, u32p, dp, u32, u32p]
+    lib.rkh_svp_rrt_get_solution.argtypes = [vp, u32, dp, u32, u32p, dp]
+    lib.rkh_diag_svp_rrt_profile.argtypes = [vp, C.c_int32, dp]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -850,6 +867,72 @@ class SvpSpace:
         _check(self.lib.rkh_svp_interpolate(self.ctx.h, C.byref(self.space), T.dptr(a), T.dptr(b), B, T.dptr(t) if M else None, M,
                                             T.dptr(out), T.dptr(rt)))
         return out[:B, :M], rt[:B]
+
+
+class SvpRrt:
+    """Batch RRT over the SVP space (rkh_svp_rrt_*): `params` is one T.SvpRrtParams (T.make_svp_rrt_params) or a list of
+    them, independent problems on one scene that share every launch; trees and sample streams stay on the device."""
+    NO_INDEX = 0xFFFFFFFF
+    PHASES = ("sample", "nearest", "extend_walk", "commit", "probe_walk", "finish")
+
+    def __init__(self, scene, space, params):
+        self.lib = load()
+        self.scene, self.space = scene, space
+        plist = list(params) if isinstance(params, (list, tuple)) else [params]
+        self.P, self.n = len(plist), int(space.n_dof)
+        arr = (T.SvpRrtParams * max(self.P, 1))(*plist)
+        self.max_vertices = [int(p.max_vertices) for p in plist]
+        self.h = C.c_void_p()
+        _check(self.lib.rkh_svp_rrt_create_batch(scene.h, C.byref(self.space), arr, self.P, C.byref(self.h)))
+        self.stats = SvpRrtStats()
+
+    def solve(self, max_rounds=-1):
+        """Rounds until every problem has ended or max_rounds have run (< 0: no limit); resumes where it stopped."""
+        _check(self.lib.rkh_svp_rrt_solve(self.h, int(max_rounds), C.byref(self.stats)))
+        return self.stats
+
+    @property
+    def finished(self):
+        return self.stats.problems_finished == self.P
+
+    def status(self):
+        """(n_vertices [P], iterations [P], goal_parent [P]); goal_parent 0xFFFFFFFF: not reached"""
+        nv, it, gp = (np.zeros(self.P, dtype=np.uint32) for _ in range(3))
+        _check(self.lib.rkh_svp_rrt_get_status(self.h, T.u32ptr(nv), T.u32ptr(it), T.u32ptr(gp)))
+        return nv, it, gp
+
+    def tree(self, problem=0):
+        """{"vertices" [V][2n], "parent" [V], "edge_time" [V]} of one problem"""
+        cap = self.max_vertices[problem]
+        verts, parent, et = np.zeros((cap, 2 * self.n)), np.zeros(cap, dtype=np.uint32), np.zeros(cap)
+        V = C.c_uint32(0)
+        _check(self.lib.rkh_svp_rrt_get_tree(self.h, int(problem), T.dptr(verts), T.u32ptr(parent), T.dptr(et), cap, C.byref(V)))
+        return {"vertices": verts[:V.value], "parent": parent[:V.value], "edge_time": et[:V.value]}
+
+    def solution(self, problem=0):
+        """(points [n_points][2n] start ... goal, duration); (empty, 0.0) when the goal has not been reached"""
+        cap = self.max_vertices[problem] + 1
+        pts = np.zeros((cap, 2 * self.n))
+        n_pts, dur = C.c_uint32(0), C.c_double(0.0)
+        _check(self.lib.rkh_svp_rrt_get_solution(self.h, int(problem), T.dptr(pts), cap, C.byref(n_pts), C.byref(dur)))
+        return pts[:n_pts.value], dur.value
+
+    def profile(self, enable=True):
+        """Brackets the phases of later rounds with stream events; returns {phase: ms so far}."""
+        ms = np.zeros(len(self.PHASES))
+        _check(self.lib.rkh_diag_svp_rrt_profile(self.h, 1 if enable else 0, T.dptr(ms)))
+        return dict(zip(self.PHASES, ms.tolist()))
+
+    def close(self):
+        if self.h:
+            self.lib.rkh_svp_rrt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def make_qs_space(n_dof, lower, upper, min_interval, speed_limits=None):

@@ -123,6 +123,26 @@ def make_svp_space(n_dof, lower, upper, min_interval, speed_limits=None, accel_l
     return sp
 
 
+class SvpRrtParams(C.Structure):
+    """rkh_svp_rrt_params (include/rkh_types.h): one problem of the batch RRT over the SVP space."""
+    _fields_ = [("struct_size", C.c_uint32), ("seed", C.c_uint32), ("max_vertices", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("max_edge_time", C.c_double), ("steer_tol", C.c_double), ("has_goal", C.c_uint32), ("pad", C.c_uint32),
+                ("start", C.c_double * RKH_MAX_STATE), ("goal", C.c_double * RKH_MAX_STATE)]
+
+
+def make_svp_rrt_params(start, goal=None, seed=1, max_vertices=200, max_iterations=20000, max_edge_time=1.0, steer_tol=0.1):
+    """start / goal: points (p0, v0, p1, v1, ...) in space coordinates; goal None: no goal probes"""
+    pr = SvpRrtParams(struct_size=C.sizeof(SvpRrtParams), seed=int(seed), max_vertices=int(max_vertices),
+                      max_iterations=int(max_iterations), max_edge_time=float(max_edge_time), steer_tol=float(steer_tol),
+                      has_goal=0 if goal is None else 1)
+    for i, v in enumerate(start):
+        pr.start[i] = float(v)
+    if goal is not None:
+        for i, v in enumerate(goal):
+            pr.goal[i] = float(v)
+    return pr
+
+
 def make_pose(pos=(0.0, 0.0, 0.0), quat=(1.0, 0.0, 0.0, 0.0)):
     p = Pose()
     p.pos[:] = [float(v) for v in pos]
