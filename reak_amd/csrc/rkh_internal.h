@@ -471,7 +471,7 @@ rkh_status launch_gjk_pair_depth(hipStream_t s, const rkh_shape* d_a, const rkh_
 rkh_status launch_min_distance_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, RecordOut out);
 rkh_status launch_collision_records_2d(hipStream_t s, const rkh_scene& scene, const double* d_x, uint32_t B, uint32_t cap,
                                        RecordOut out);
-// The same four compiled for chains with prismatic joints (propagate_prismatic.hip); the ones above hand these scenes on.
+// The same four for chains with prismatic joints (propagate_prismatic.hip); the ones above hand these scenes on.
 namespace prismatic {
 rkh_status launch_propagate(hipStream_t s, const rkh_scene& scene, SteerMapping m, const DynDev& dyn, const EdgeIO& io,
                             uint32_t grid_edges, uint32_t grid_b, const EdgeIO* tab_a, const EdgeIO* tab_b,

@@ -1,5 +1,5 @@
 """The depth forms of the record kernels (propagate_depth.hip: min_distance_depth_kernel, collision_depth_kernel and the
-pair-by-pair gjk_pair_depth_kernel, instantiated from propagate.hip's text in a module of their own): they spill no vector
+pair-by-pair gjk_pair_depth_kernel, over the record bodies of propagate_records.h in a module of their own): they spill no vector
 and no scalar register, stay within 256 registers, and their private segment is what the polytope cap of
 reak_amd/csrc/epa_device.h implies.  The figures are those of profiles/r17_depth_kernel_resources.txt.  The kernels that
 existed before must be the code they were: every row of profiles/r03_kernel_resources.txt and
