@@ -23,6 +23,7 @@
 
 #include "kinematics_device.h"
 #include "rkh_internal.h"
+#include "staged_call.h"
 
 namespace rkh {
 namespace {
@@ -228,11 +229,6 @@ __global__ __launch_bounds__(kKinThreads) void kinematics_ik_kernel(const KinCha
   out.flags[sidx] = conv;
 }
 
-struct StreamWait {  // no early return leaves work in flight on buffers that are about to be freed
-  hipStream_t s;
-  ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
-
 rkh_status kind_supported(const rkh_scene* scene, bool planar_entry, const char* who) {
   if ((scene->host.planar != 0) == planar_entry) return RKH_OK;
   set_error(std::string(who) + (planar_entry ? ": not supported for 3D scenes: their frames come from the entries without _2d"
@@ -281,40 +277,30 @@ rkh_status frames_run(const char* who, bool planar_entry, rkh_scene* scene, cons
   const size_t slots = size_t(B) * F;
   hipStream_t s = scene->ctx->stream;
   RKH_HIP(hipSetDevice(scene->ctx->device));
-  DeviceBuffer<double> d_q, d_qd, d_pos, d_rot, d_vel, d_w, d_jac, d_jdot;
-  DeviceBuffer<KinFrameRef> d_refs;
-  RKH_TRY(d_q.alloc(size_t(B) * n));
-  if (qd) RKH_TRY(d_qd.alloc(size_t(B) * n));
-  RKH_TRY(d_refs.alloc(F));
-  if (pos) RKH_TRY(d_pos.alloc(slots * pd));
-  if (rot) RKH_TRY(d_rot.alloc(slots * rd));
-  if (vel) RKH_TRY(d_vel.alloc(slots * pd));
-  if (ang_vel) RKH_TRY(d_w.alloc(slots * wd));
-  if (jac) RKH_TRY(d_jac.alloc(slots * rows * n));
-  if (jac_dot) RKH_TRY(d_jdot.alloc(slots * rows * n));
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_q.get(), q, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  if (qd) RKH_HIP(hipMemcpyAsync(d_qd.get(), qd, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_refs.get(), refs.data(), size_t(F) * sizeof(KinFrameRef), hipMemcpyHostToDevice, s));
+  StagedCall call(s);  // (refs was declared before it)
+  const double* d_q = call.in(q, size_t(B) * n);
+  const double* d_qd = qd ? call.in(qd, size_t(B) * n) : nullptr;
+  const KinFrameRef* d_refs = call.in(refs.data(), F);
   KinOut out;
-  out.pos = pos ? d_pos.get() : nullptr;
-  out.rot = rot ? d_rot.get() : nullptr;
-  out.vel = vel ? d_vel.get() : nullptr;
-  out.ang_vel = ang_vel ? d_w.get() : nullptr;
-  out.jac = jac ? d_jac.get() : nullptr;
-  out.jac_dot = jac_dot ? d_jdot.get() : nullptr;
+  out.pos = pos ? call.out(pos, slots * pd) : nullptr;
+  out.rot = rot ? call.out(rot, slots * rd) : nullptr;
+  out.vel = vel ? call.out(vel, slots * pd) : nullptr;
+  out.ang_vel = ang_vel ? call.out(ang_vel, slots * wd) : nullptr;
+  out.jac = jac ? call.out(jac, slots * rows * n) : nullptr;
+  out.jac_dot = jac_dot ? call.out(jac_dot, slots * rows * n) : nullptr;
+  RKH_TRY(call.status());
   // NULL qd = zero rates: the walk then carries zeros for the rates, and JacDot is the clear below
   const bool rates = qd && (vel || ang_vel || jac_dot);
   auto launch = [&]() -> rkh_status {
-    if (jac) RKH_HIP(hipMemsetAsync(d_jac.get(), 0, slots * rows * n * 8, s));
-    if (jac_dot) RKH_HIP(hipMemsetAsync(d_jdot.get(), 0, slots * rows * n * 8, s));
+    if (jac) RKH_HIP(hipMemsetAsync(out.jac, 0, slots * rows * n * 8, s));
+    if (jac_dot) RKH_HIP(hipMemsetAsync(out.jac_dot, 0, slots * rows * n * 8, s));
     const dim3 grid(blocks_b * F), block(kKinThreads);
     if (planar_entry) {
-      if (rates) hipLaunchKernelGGL(kinematics_frames_planar_kernel<true>, grid, block, 0, s, scene->d_kin.get(), d_refs.get(), d_q.get(), d_qd.get(), B, F, blocks_b, out);
-      else hipLaunchKernelGGL(kinematics_frames_planar_kernel<false>, grid, block, 0, s, scene->d_kin.get(), d_refs.get(), d_q.get(), (const double*)nullptr, B, F, blocks_b, out);
+      if (rates) hipLaunchKernelGGL(kinematics_frames_planar_kernel<true>, grid, block, 0, s, scene->d_kin.get(), d_refs, d_q, d_qd, B, F, blocks_b, out);
+      else hipLaunchKernelGGL(kinematics_frames_planar_kernel<false>, grid, block, 0, s, scene->d_kin.get(), d_refs, d_q, (const double*)nullptr, B, F, blocks_b, out);
     } else {
-      if (rates) hipLaunchKernelGGL(kinematics_frames_kernel<true>, grid, block, 0, s, scene->d_kin.get(), d_refs.get(), d_q.get(), d_qd.get(), B, F, blocks_b, out);
-      else hipLaunchKernelGGL(kinematics_frames_kernel<false>, grid, block, 0, s, scene->d_kin.get(), d_refs.get(), d_q.get(), (const double*)nullptr, B, F, blocks_b, out);
+      if (rates) hipLaunchKernelGGL(kinematics_frames_kernel<true>, grid, block, 0, s, scene->d_kin.get(), d_refs, d_q, d_qd, B, F, blocks_b, out);
+      else hipLaunchKernelGGL(kinematics_frames_kernel<false>, grid, block, 0, s, scene->d_kin.get(), d_refs, d_q, (const double*)nullptr, B, F, blocks_b, out);
     }
     RKH_HIP(hipGetLastError());
     return RKH_OK;
@@ -338,14 +324,7 @@ rkh_status frames_run(const char* who, bool planar_entry, rkh_scene* scene, cons
     for (auto& e : ev) (void)hipEventDestroy(e);
     RKH_TRY(st);
   }
-  if (pos) RKH_HIP(hipMemcpyAsync(pos, d_pos.get(), slots * pd * 8, hipMemcpyDeviceToHost, s));
-  if (rot) RKH_HIP(hipMemcpyAsync(rot, d_rot.get(), slots * rd * 8, hipMemcpyDeviceToHost, s));
-  if (vel) RKH_HIP(hipMemcpyAsync(vel, d_vel.get(), slots * pd * 8, hipMemcpyDeviceToHost, s));
-  if (ang_vel) RKH_HIP(hipMemcpyAsync(ang_vel, d_w.get(), slots * wd * 8, hipMemcpyDeviceToHost, s));
-  if (jac) RKH_HIP(hipMemcpyAsync(jac, d_jac.get(), slots * rows * n * 8, hipMemcpyDeviceToHost, s));
-  if (jac_dot) RKH_HIP(hipMemcpyAsync(jac_dot, d_jdot.get(), slots * rows * n * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 // rkh_inverse_kinematics; ms != null: the solve launch and the distance launch are repeated `runs` times between events
@@ -411,41 +390,34 @@ rkh_status ik_run(const char* who, rkh_scene* scene, int32_t frame, const rkh_po
   for (int j = 0; j < n; ++j) P.lower[j] = lower[j], P.upper[j] = upper[j];
   hipStream_t s = scene->ctx->stream;
   RKH_HIP(hipSetDevice(scene->ctx->device));
-  DeviceBuffer<IkDev> d_P;
-  DeviceBuffer<rkh_pose> d_tg;
-  DeviceBuffer<double> d_seeds, d_q, d_x, d_rp, d_rr, d_dist;
-  DeviceBuffer<uint32_t> d_it, d_fl;
+  const bool has_pairs = scene->n_pairs > 0;
+  std::vector<double> dist(N, INFINITY);  // a scene without pairs: free
+  std::vector<uint32_t> fl(N);
+  DeviceBuffer<IkDev> d_P;  // uploaded once the arrays it points to exist
   RKH_TRY(d_P.alloc(1));
-  RKH_TRY(d_tg.alloc(T));
-  RKH_TRY(d_seeds.alloc(size_t(N) * n));
-  RKH_TRY(d_q.alloc(size_t(N) * n));
-  RKH_TRY(d_x.alloc(size_t(N) * 2 * n));
-  RKH_TRY(d_rp.alloc(N));
-  RKH_TRY(d_rr.alloc(N));
-  RKH_TRY(d_dist.alloc(N));
-  RKH_TRY(d_it.alloc(N));
-  RKH_TRY(d_fl.alloc(N));
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_tg.get(), targets, size_t(T) * sizeof(rkh_pose), hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_seeds.get(), seeds, size_t(N) * n * 8, hipMemcpyHostToDevice, s));
+  StreamWait d_P_idle{s};
+  StagedCall call(s);
+  const rkh_pose* d_tg = call.in(targets, T);
+  const double* d_seeds = call.in(seeds, size_t(N) * n);
   IkOut& out = P.out;
-  out.q = d_q.get();
-  out.x = d_x.get();
-  out.res_pos = d_rp.get();
-  out.res_rot = d_rr.get();
-  out.iters = d_it.get();
-  out.flags = d_fl.get();
+  out.q = call.out(q_out, size_t(N) * n);
+  out.x = call.scratch<double>(size_t(N) * 2 * n);
+  out.res_pos = call.out(res_pos, N);
+  out.res_rot = call.out(res_rot, N);
+  out.iters = call.out(iters, N);
+  out.flags = call.out(fl.data(), N);
+  double* d_dist = call.out(has_pairs ? dist.data() : nullptr, N);
+  RKH_TRY(call.status());
   RKH_HIP(hipMemcpyAsync(d_P.get(), &P, sizeof(P), hipMemcpyHostToDevice, s));
   const size_t lds = size_t(8) * n * kKinThreads * sizeof(double);  // at most 48 KB (12 joints)
-  const bool has_pairs = scene->n_pairs > 0;
   auto launch_solve = [&]() -> rkh_status {
     hipLaunchKernelGGL(kinematics_ik_kernel, dim3((N + kKinThreads - 1) / kKinThreads), dim3(kKinThreads), lds, s,
-                       scene->d_kin.get(), d_P.get(), d_tg.get(), d_seeds.get(), N, S);
+                       scene->d_kin.get(), d_P.get(), d_tg, d_seeds, N, S);
     RKH_HIP(hipGetLastError());
     return RKH_OK;
   };
   auto launch_dist = [&]() -> rkh_status {
-    return has_pairs ? launch_min_distance(s, *scene, d_x.get(), N, d_dist.get()) : RKH_OK;
+    return has_pairs ? launch_min_distance(s, *scene, out.x, N, d_dist) : RKH_OK;
   };
   RKH_TRY(launch_solve());
   RKH_TRY(launch_dist());
@@ -469,15 +441,7 @@ rkh_status ik_run(const char* who, rkh_scene* scene, int32_t frame, const rkh_po
     for (auto& e : ev) (void)hipEventDestroy(e);
     RKH_TRY(st);
   }
-  std::vector<double> dist(N, INFINITY);
-  std::vector<uint32_t> fl(N);
-  RKH_HIP(hipMemcpyAsync(q_out, d_q.get(), size_t(N) * n * 8, hipMemcpyDeviceToHost, s));
-  if (res_pos) RKH_HIP(hipMemcpyAsync(res_pos, d_rp.get(), size_t(N) * 8, hipMemcpyDeviceToHost, s));
-  if (res_rot) RKH_HIP(hipMemcpyAsync(res_rot, d_rr.get(), size_t(N) * 8, hipMemcpyDeviceToHost, s));
-  if (iters) RKH_HIP(hipMemcpyAsync(iters, d_it.get(), size_t(N) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(fl.data(), d_fl.get(), size_t(N) * 4, hipMemcpyDeviceToHost, s));
-  if (has_pairs) RKH_HIP(hipMemcpyAsync(dist.data(), d_dist.get(), size_t(N) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
+  RKH_TRY(call.fetch());
   for (uint32_t k = 0; k < N; ++k) fl[k] = (fl[k] & 1u) | (dist[k] > 0.0 ? 2u : 0u);  // a scene without pairs: free
   if (flags) std::memcpy(flags, fl.data(), size_t(N) * 4);
   if (best)

@@ -72,6 +72,7 @@
 #include "nn_device.h"
 #include "nn_mirror.h"
 #include "rkh_internal.h"
+#include "staged_call.h"
 
 namespace rkh {
 
@@ -536,42 +537,29 @@ extern "C" rkh_status rkh_diag_nn_mirror_query(rkh_ctx* ctx, const double* pts, 
   for (uint64_t i = 0; i < n; ++i)
     for (int d = 0; d < D; ++d) rows[i * DP + d] = pts[i * D + d];
   const uint32_t Bp = (B + 7u) / 8u * 8u;
-  DeviceBuffer<double> d_pos, d_q, d_dist;
-  DeviceBuffer<void> d_mirror, d_scratch;
-  DeviceBuffer<uint32_t> d_idx, d_yb, d_dx;
-  DeviceBuffer<NnArgs> d_tab;
-  const size_t scratch_bytes = nn1_mirror_query_bytes() * Bp;
-  RKH_TRY(d_pos.alloc(rows.size()));
-  RKH_TRY(d_q.alloc(size_t(B) * D));
-  RKH_TRY(d_dist.alloc(B));
-  RKH_TRY(d_idx.alloc(B));
-  RKH_TRY(d_scratch.alloc_zeroed(scratch_bytes));
-  RKH_TRY(d_yb.alloc(2));
-  RKH_TRY(d_dx.alloc_zeroed(1));
-  RKH_TRY(d_tab.alloc(1));
-  RKH_TRY(d_mirror.alloc(nn1_mirror_bytes(n)));
-  RKH_HIP(hipMemcpy(d_pos.get(), rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(d_q.get(), q, size_t(B) * D * sizeof(double), hipMemcpyHostToDevice));
   const uint32_t yb[2] = {0u, (B + nn1_mirror_queries() - 1) / nn1_mirror_queries()};
-  RKH_HIP(hipMemcpy(d_yb.get(), yb, sizeof(yb), hipMemcpyHostToDevice));
-  NnArgs a;
-  a.pos = d_pos.get();
+  NnArgs a;  // filled below; like rows and yb declared before the call that uploads it
+  StagedCall call(s);
+  a.pos = call.in(rows.data(), rows.size());
   a.n = n;
-  a.q = d_q.get();
+  a.q = call.in(q, size_t(B) * D);
   a.B = B;
-  a.idx = d_idx.get();
-  a.dist = d_dist.get();
-  a.mirror = d_mirror.get();
-  a.dx_max_bits = d_dx.get();
-  nn1_mirror_carve(d_scratch.get(), Bp, &a);
-  RKH_HIP(hipMemcpy(d_tab.get(), &a, sizeof(a), hipMemcpyHostToDevice));
-  RKH_TRY(launch_mirror_fill(s, d_mirror.get(), n));
+  a.idx = call.out(idx, B);
+  a.dist = call.out(dist, B);
+  void* d_scratch = call.scratch<char>(nn1_mirror_query_bytes() * Bp, 0, 0);
+  const uint32_t* d_yb = call.in(yb, 2);
+  uint32_t* d_dx = call.scratch<uint32_t>(1, 0, 0);
+  void* d_mirror = call.scratch<char>(nn1_mirror_bytes(n));
+  RKH_TRY(call.status());
+  a.dx_max_bits = d_dx;
+  a.mirror = d_mirror;
+  nn1_mirror_carve(d_scratch, Bp, &a);
+  const NnArgs* d_tab = call.in(&a, 1);
+  RKH_TRY(call.status());
+  RKH_TRY(launch_mirror_fill(s, d_mirror, n));
   const double scale = mirror_prescale(coord_bound);
-  RKH_TRY(launch_mirror_build(s, d_mirror.get(), d_pos.get(), n, D, DP, scale, d_dx.get()));
-  RKH_TRY(launch_nn1_mirror(s, D, d_tab.get(), 1, n, B, std::sqrt(double(D)) * coord_bound, scale, d_yb.get(),
-                            nn1_mirror_open_lists(), nullptr, nullptr));
-  RKH_HIP(hipStreamSynchronize(s));
-  RKH_HIP(hipMemcpy(idx, d_idx.get(), size_t(B) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  RKH_HIP(hipMemcpy(dist, d_dist.get(), size_t(B) * sizeof(double), hipMemcpyDeviceToHost));
-  return RKH_OK;
+  RKH_TRY(launch_mirror_build(s, d_mirror, a.pos, n, D, DP, scale, d_dx));
+  RKH_TRY(launch_nn1_mirror(s, D, d_tab, 1, n, B, std::sqrt(double(D)) * coord_bound, scale, d_yb, nn1_mirror_open_lists(), nullptr,
+                            nullptr));
+  return call.fetch();
 }

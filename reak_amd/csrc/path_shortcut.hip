@@ -26,6 +26,7 @@
 
 #include "path_shortcut.h"
 #include "rkh_internal.h"
+#include "staged_call.h"
 
 namespace rkh {
 
@@ -183,13 +184,6 @@ __global__ __launch_bounds__(kShortcutThreads) void shortcut_dp_kernel(ShortcutD
 
 namespace {
 
-// Waits for the stream when its scope ends, on every way out: the copies enqueued from host vectors and from the caller's
-// memory are done before those go away, also where a later step fails.  Declared behind the buffers it protects.
-struct StreamWait {
-  hipStream_t s;
-  ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
-
 // The pair offsets of B paths, and everything both entry points check about path_ptr before anything is launched.
 rkh_status shortcut_layout(const char* who, const uint32_t* path_ptr, uint32_t B, uint32_t max_span,
                            std::vector<uint32_t>* pair_ptr) {
@@ -262,65 +256,48 @@ rkh_status shortcut_run(const char* who, rkh_scene* scene, const rkh_qs_space* s
     qs.upper[d] = space->upper[d];
   }
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> d_pts, d_w, d_xout, d_cin, d_cout;
-  DeviceBuffer<uint32_t> d_path_ptr, d_pair_ptr, d_src, d_tgt, d_nchk, d_keep, d_nkeep, d_nblk;
-  DeviceBuffer<uint8_t> d_acc;
   // per pair: two row indices, the weight, the verdict byte, and what every walk writes (end point, points tested):
   // 8 n + 25 bytes.  A call that does not fit the device's memory is refused with RKH_ERR_OOM (rkh.h says so).
-  const size_t Ea = std::max<size_t>(E, 1);
-  RKH_TRY(d_pts.alloc(size_t(T) * n));
-  RKH_TRY(d_path_ptr.alloc(size_t(B) + 1));
-  RKH_TRY(d_pair_ptr.alloc(size_t(B) + 1));
-  RKH_TRY(d_src.alloc(Ea));
-  RKH_TRY(d_tgt.alloc(Ea));
-  RKH_TRY(d_w.alloc(Ea));
-  RKH_TRY(d_xout.alloc(Ea * n));
-  RKH_TRY(d_nchk.alloc(Ea));
-  RKH_TRY(d_acc.alloc(Ea));
-  RKH_TRY(d_keep.alloc(T));
-  RKH_TRY(d_nkeep.alloc(B));
-  RKH_TRY(d_cin.alloc(B));
-  RKH_TRY(d_cout.alloc(B));
-  RKH_TRY(d_nblk.alloc(B));
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_pts.get(), points, size_t(T) * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_path_ptr.get(), path_ptr, (size_t(B) + 1) * 4, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_pair_ptr.get(), pair_ptr.data(), (size_t(B) + 1) * 4, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemsetAsync(d_cin.get(), 0, size_t(B) * 8, s));  // a path of one point has no pair: its input cost is 0
-  RKH_HIP(hipMemsetAsync(d_acc.get(), 0, Ea, s));
-  RKH_HIP(hipMemsetAsync(d_keep.get(), 0xFF, size_t(T) * 4, s));  // the slots behind n_keep hold 0xFFFFFFFF
+  StagedCall call(s);  // (pair_ptr was declared before it)
+  const double* d_pts = call.in(points, size_t(T) * n);
+  const uint32_t* d_path_ptr = call.in(path_ptr, size_t(B) + 1);
+  const uint32_t* d_pair_ptr = call.in(pair_ptr.data(), size_t(B) + 1);
+  uint32_t* d_src = call.scratch<uint32_t>(E, 1);
+  uint32_t* d_tgt = call.scratch<uint32_t>(E, 1);
+  double* d_w = call.scratch<double>(E, 1);
+  double* d_cin = call.out(cost_in, B, 0, 0);  // a path of one point has no pair: its input cost is 0
 
   EdgeIO io;  // pair e walks row src_idx[e] -> row tgt_idx[e] of the one point table
-  io.src = d_pts.get();
-  io.src_idx = d_src.get();
+  io.src = d_pts;
+  io.src_idx = d_src;
   io.src_stride = uint32_t(n);
-  io.tgt = d_pts.get();
-  io.tgt_idx = d_tgt.get();
+  io.tgt = d_pts;
+  io.tgt_idx = d_tgt;
   io.tgt_stride = uint32_t(n);
   io.B = E;
-  io.x_out = d_xout.get();
-  io.steps_free = d_nchk.get();
-  io.accept = d_acc.get();
+  io.x_out = call.scratch<double>(size_t(E) * n, n);
+  io.steps_free = call.scratch<uint32_t>(E, 1);
+  io.accept = call.scratch<uint8_t>(E, 1, 0);
   io.mode = EDGE_STEER_BOTH;
   io.err_flag = scene->d_err.get();
   ShortcutDpArgs dp;
-  dp.path_ptr = d_path_ptr.get();
-  dp.pair_ptr = d_pair_ptr.get();
+  dp.path_ptr = d_path_ptr;
+  dp.pair_ptr = d_pair_ptr;
   dp.B = B;
   dp.max_span = max_span;
-  dp.acc = d_acc.get();
-  dp.w = d_w.get();
+  dp.acc = io.accept;
+  dp.w = d_w;
   dp.ok_mask = 2u;  // EDGE_STEER_BOTH: the walk ran to its end
   dp.min_interval = space->min_interval;
-  dp.keep = d_keep.get();
-  dp.n_keep = d_nkeep.get();
-  dp.cost_out = d_cout.get();
-  dp.n_blocked = d_nblk.get();
+  dp.keep = call.out(keep, T, 0, 0xFF);  // the slots behind n_keep hold 0xFFFFFFFF
+  dp.n_keep = call.out(n_keep, B);
+  dp.cost_out = call.out(cost_out, B);
+  dp.n_blocked = call.out(n_blocked, B);
+  RKH_TRY(call.status());
   auto launch_pairs = [&]() -> rkh_status {
     if (E == 0) return RKH_OK;
     hipLaunchKernelGGL(shortcut_pairs_kernel, dim3((E + kShortcutThreads - 1) / kShortcutThreads), dim3(kShortcutThreads), 0, s,
-                       d_pts.get(), n, d_path_ptr.get(), d_pair_ptr.get(), B, max_span, d_src.get(), d_tgt.get(), d_w.get(),
-                       d_cin.get());
+                       d_pts, n, d_path_ptr, d_pair_ptr, B, max_span, d_src, d_tgt, d_w, d_cin);
     RKH_HIP(hipGetLastError());
     return RKH_OK;
   };
@@ -351,13 +328,7 @@ rkh_status shortcut_run(const char* who, rkh_scene* scene, const rkh_qs_space* s
     for (auto& e : ev) (void)hipEventDestroy(e);
     RKH_TRY(st);
   }
-  RKH_HIP(hipMemcpyAsync(keep, d_keep.get(), size_t(T) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(n_keep, d_nkeep.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(cost_out, d_cout.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  if (cost_in) RKH_HIP(hipMemcpyAsync(cost_in, d_cin.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  if (n_blocked) RKH_HIP(hipMemcpyAsync(n_blocked, d_nblk.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 }  // namespace
@@ -398,46 +369,23 @@ rkh_status rkh_diag_shortcut_dp(rkh_ctx* ctx, const uint32_t* path_ptr, uint32_t
       return RKH_ERR_BAD_ARG;
     }
   hipStream_t s = ctx->stream;
-  DeviceBuffer<uint32_t> d_path_ptr, d_pair_ptr, d_keep, d_nkeep, d_nblk;
-  DeviceBuffer<uint8_t> d_ok;
-  DeviceBuffer<double> d_w, d_cout;
-  const size_t Ea = std::max<size_t>(E, 1);
-  RKH_TRY(d_path_ptr.alloc(size_t(B) + 1));
-  RKH_TRY(d_pair_ptr.alloc(size_t(B) + 1));
-  RKH_TRY(d_ok.alloc(Ea));
-  RKH_TRY(d_w.alloc(Ea));
-  RKH_TRY(d_keep.alloc(T));
-  RKH_TRY(d_nkeep.alloc(B));
-  RKH_TRY(d_cout.alloc(B));
-  RKH_TRY(d_nblk.alloc(B));
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_path_ptr.get(), path_ptr, (size_t(B) + 1) * 4, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_pair_ptr.get(), pair_ptr.data(), (size_t(B) + 1) * 4, hipMemcpyHostToDevice, s));
-  if (E) {
-    RKH_HIP(hipMemcpyAsync(d_ok.get(), ok, E, hipMemcpyHostToDevice, s));
-    RKH_HIP(hipMemcpyAsync(d_w.get(), w, size_t(E) * 8, hipMemcpyHostToDevice, s));
-  }
-  RKH_HIP(hipMemsetAsync(d_keep.get(), 0xFF, size_t(T) * 4, s));  // the slots behind n_keep hold 0xFFFFFFFF
+  StagedCall call(s);  // (pair_ptr was declared before it)
   ShortcutDpArgs dp;
-  dp.path_ptr = d_path_ptr.get();
-  dp.pair_ptr = d_pair_ptr.get();
+  dp.path_ptr = call.in(path_ptr, size_t(B) + 1);
+  dp.pair_ptr = call.in(pair_ptr.data(), size_t(B) + 1);
   dp.B = B;
   dp.max_span = max_span;
-  dp.acc = d_ok.get();
-  dp.w = d_w.get();
+  dp.acc = call.in(ok, E, 1);
+  dp.w = call.in(w, E, 1);
   dp.ok_mask = 0xFFu;  // any non-zero byte is a true verdict
   dp.min_interval = 0.0;
-  dp.keep = d_keep.get();
-  dp.n_keep = d_nkeep.get();
-  dp.cost_out = d_cout.get();
-  dp.n_blocked = d_nblk.get();
+  dp.keep = call.out(keep, T, 0, 0xFF);  // the slots behind n_keep hold 0xFFFFFFFF
+  dp.n_keep = call.out(n_keep, B);
+  dp.cost_out = call.out(cost_out, B);
+  dp.n_blocked = call.out(n_blocked, B);
+  RKH_TRY(call.status());
   RKH_TRY(launch_shortcut_dp(s, dp));
-  RKH_HIP(hipMemcpyAsync(keep, d_keep.get(), size_t(T) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(n_keep, d_nkeep.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(cost_out, d_cout.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  if (n_blocked) RKH_HIP(hipMemcpyAsync(n_blocked, d_nblk.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 }  // extern "C"

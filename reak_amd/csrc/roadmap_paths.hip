@@ -30,6 +30,7 @@
 
 #include "roadmap_csr.h"
 #include "roadmap_paths.h"
+#include "staged_call.h"
 
 namespace rkh {
 
@@ -194,49 +195,35 @@ rkh_status rkh_diag_sssp(rkh_ctx* ctx, uint32_t n, const uint32_t* row_ptr, cons
     return RKH_ERR_BAD_ARG;
   }
   hipStream_t s = ctx->stream;
-  DeviceBuffer<uint32_t> d_row, d_col, d_sv, d_pred, d_rounds;
-  DeviceBuffer<double> d_w, d_sd, d_dist;
-  DeviceBuffer<SsspJob> d_jobs;
-  RKH_TRY(d_row.alloc(size_t(n) + 1));
-  RKH_TRY(d_col.alloc(std::max<size_t>(nnz, 1)));
-  RKH_TRY(d_w.alloc(std::max<size_t>(nnz, 1)));
-  RKH_TRY(d_sv.alloc(std::max<size_t>(n_seeds, 1)));
-  RKH_TRY(d_sd.alloc(std::max<size_t>(n_seeds, 1)));
-  RKH_TRY(d_dist.alloc(size_t(S) * n));
-  RKH_TRY(d_pred.alloc(size_t(S) * n));
-  RKH_TRY(d_rounds.alloc(S));
-  RKH_TRY(d_jobs.alloc(S));
-  RKH_HIP(hipMemcpyAsync(d_row.get(), row_ptr, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
-  if (nnz) {
-    RKH_HIP(hipMemcpyAsync(d_col.get(), col, size_t(nnz) * 4, hipMemcpyHostToDevice, s));
-    RKH_HIP(hipMemcpyAsync(d_w.get(), w, size_t(nnz) * 8, hipMemcpyHostToDevice, s));
-  }
-  if (n_seeds) {
-    RKH_HIP(hipMemcpyAsync(d_sv.get(), seed_v, size_t(n_seeds) * 4, hipMemcpyHostToDevice, s));
-    RKH_HIP(hipMemcpyAsync(d_sd.get(), seed_d, size_t(n_seeds) * 8, hipMemcpyHostToDevice, s));
-  }
-  std::vector<SsspJob> jobs(S);
+  std::vector<SsspJob> jobs(S);  // filled below; declared before the call that uploads it
+  StagedCall call(s);
+  const uint32_t* d_row = call.in(row_ptr, size_t(n) + 1);
+  const uint32_t* d_col = call.in(col, nnz, 1);
+  const double* d_w = call.in(w, nnz, 1);
+  const uint32_t* d_sv = call.in(seed_v, n_seeds, 1);
+  const double* d_sd = call.in(seed_d, n_seeds, 1);
+  double* d_dist = call.out(dist, size_t(S) * n);
+  uint32_t* d_pred = call.out(pred, size_t(S) * n);
+  uint32_t* d_rounds = call.out(rounds, S);
+  RKH_TRY(call.status());
   for (uint32_t i = 0; i < S; ++i) {
     SsspJob& j = jobs[i];
-    j.row_ptr = d_row.get();
-    j.col = d_col.get();
-    j.w = d_w.get();
+    j.row_ptr = d_row;
+    j.col = d_col;
+    j.w = d_w;
     j.n = n;
     j.n_seeds = seed_ptr[i + 1] - seed_ptr[i];
-    j.seed_v = d_sv.get() + seed_ptr[i];
-    j.seed_d = d_sd.get() + seed_ptr[i];
+    j.seed_v = d_sv + seed_ptr[i];
+    j.seed_d = d_sd + seed_ptr[i];
     j.seed_mark = seed_mark[i];
-    j.dist = d_dist.get() + size_t(i) * n;
-    j.pred = d_pred.get() + size_t(i) * n;
-    j.rounds = d_rounds.get() + i;
+    j.dist = d_dist + size_t(i) * n;
+    j.pred = d_pred + size_t(i) * n;
+    j.rounds = d_rounds + i;
   }
-  RKH_HIP(hipMemcpyAsync(d_jobs.get(), jobs.data(), size_t(S) * sizeof(SsspJob), hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_roadmap_sssp(s, d_jobs.get(), S, n));
-  if (dist) RKH_HIP(hipMemcpyAsync(dist, d_dist.get(), size_t(S) * n * 8, hipMemcpyDeviceToHost, s));
-  if (pred) RKH_HIP(hipMemcpyAsync(pred, d_pred.get(), size_t(S) * n * 4, hipMemcpyDeviceToHost, s));
-  if (rounds) RKH_HIP(hipMemcpyAsync(rounds, d_rounds.get(), size_t(S) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));  // (also keeps `jobs` alive until its copy is done)
-  return RKH_OK;
+  const SsspJob* d_jobs = call.in(jobs.data(), S);
+  RKH_TRY(call.status());
+  RKH_TRY(launch_roadmap_sssp(s, d_jobs, S, n));
+  return call.fetch();
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include "proximity_device.h"
 #include "rkh_internal.h"
+#include "staged_call.h"
 
 using namespace rkh;
 
@@ -394,6 +395,34 @@ static rkh_status create_planar_scene(rkh_ctx* ctx, const rkh_kte_op* prog, int 
   return upload_scene(ctx, std::move(sc), pairs, out, pair_ids);
 }
 
+// The three rkh_diag_gjk_* entries after their checks: the distance alone (point1 = point2 = null), with the witness points,
+// or with the points and the normal of the depth form.
+static rkh_status gjk_pairs_run(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n, const double* mesh_vertices,
+                                uint32_t n_mesh_vertices, double* dist, double* point1, double* point2, double* normal) {
+  if (n == 0) return RKH_OK;
+  RKH_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StagedCall call(s);
+  const rkh_shape* da = call.in(a, n);
+  const rkh_shape* db = call.in(b, n);
+  const double* dv = call.in(mesh_vertices, size_t(n_mesh_vertices) * 3, 1);
+  double* dd = call.out(dist, n);
+  double* dp1 = point1 ? call.out(point1, size_t(n) * 3) : nullptr;
+  double* dp2 = point2 ? call.out(point2, size_t(n) * 3) : nullptr;
+  double* dn3 = normal ? call.out(normal, size_t(n) * 3) : nullptr;
+  RKH_TRY(call.status());
+  if (!point1) {
+    hipLaunchKernelGGL(rkh::gjk_pairs_kernel, dim3((n + 63) / 64), dim3(64), 0, s, da, db, n, dv, dd);
+    RKH_HIP(hipGetLastError());
+  } else if (!normal) {
+    hipLaunchKernelGGL(rkh::gjk_pair_records_kernel, dim3((n + 63) / 64), dim3(64), 0, s, da, db, n, dv, dd, dp1, dp2);
+    RKH_HIP(hipGetLastError());
+  } else {
+    RKH_TRY(launch_gjk_pair_depth(s, da, db, n, dv, dd, dp1, dp2, dn3));
+  }
+  return call.fetch();
+}
+
 extern "C" {
 
 rkh_status rkh_scene_create(rkh_ctx* ctx, const rkh_kte_op* prog, int n_ops, const rkh_chain_base* base,
@@ -757,75 +786,19 @@ rkh_status rkh_scene_create_with_meshes(rkh_ctx* ctx, const rkh_kte_op* prog, in
 rkh_status rkh_diag_gjk_distance(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n,
                                  const double* mesh_vertices, uint32_t n_mesh_vertices, double* dist) {
   if (!ctx || !a || !b || !dist) return RKH_ERR_BAD_ARG;
-  if (n == 0) return RKH_OK;
-  RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<rkh_shape> da, db;
-  DeviceBuffer<double> dv, dd;
-  RKH_TRY(da.alloc(n));
-  RKH_TRY(db.alloc(n));
-  RKH_TRY(dd.alloc(n));
-  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
-  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(rkh::gjk_pairs_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, da.get(), db.get(), n, dv.get(),
-                     dd.get());
-  RKH_HIP(hipGetLastError());
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipStreamSynchronize(ctx->stream));
-  return RKH_OK;
+  return gjk_pairs_run(ctx, a, b, n, mesh_vertices, n_mesh_vertices, dist, nullptr, nullptr, nullptr);
 }
 
 rkh_status rkh_diag_gjk_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n, const double* mesh_vertices,
                                 uint32_t n_mesh_vertices, double* dist, double* point1, double* point2) {
   if (!ctx || !a || !b || !dist || !point1 || !point2) return RKH_ERR_BAD_ARG;
-  if (n == 0) return RKH_OK;
-  RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<rkh_shape> da, db;
-  DeviceBuffer<double> dv, dd, dp1, dp2;
-  RKH_TRY(da.alloc(n));
-  RKH_TRY(db.alloc(n));
-  RKH_TRY(dd.alloc(n));
-  RKH_TRY(dp1.alloc(size_t(n) * 3));
-  RKH_TRY(dp2.alloc(size_t(n) * 3));
-  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
-  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(rkh::gjk_pair_records_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, da.get(), db.get(), n,
-                     dv.get(), dd.get(), dp1.get(), dp2.get());
-  RKH_HIP(hipGetLastError());
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipStreamSynchronize(ctx->stream));
-  return RKH_OK;
+  return gjk_pairs_run(ctx, a, b, n, mesh_vertices, n_mesh_vertices, dist, point1, point2, nullptr);
 }
 
 rkh_status rkh_diag_gjk_depth_records(rkh_ctx* ctx, const rkh_shape* a, const rkh_shape* b, uint32_t n, const double* mesh_vertices,
                                       uint32_t n_mesh_vertices, double* dist, double* point1, double* point2, double* normal) {
   if (!ctx || !a || !b || !dist || !point1 || !point2 || !normal) return RKH_ERR_BAD_ARG;
-  if (n == 0) return RKH_OK;
-  RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<rkh_shape> da, db;
-  DeviceBuffer<double> dv, dd, dp1, dp2, dn3;
-  RKH_TRY(da.alloc(n));
-  RKH_TRY(db.alloc(n));
-  RKH_TRY(dd.alloc(n));
-  RKH_TRY(dp1.alloc(size_t(n) * 3));
-  RKH_TRY(dp2.alloc(size_t(n) * 3));
-  RKH_TRY(dn3.alloc(size_t(n) * 3));
-  RKH_TRY(dv.alloc(std::max<size_t>(1, size_t(n_mesh_vertices) * 3)));
-  RKH_HIP(hipMemcpy(da.get(), a, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  RKH_HIP(hipMemcpy(db.get(), b, n * sizeof(rkh_shape), hipMemcpyHostToDevice));
-  if (n_mesh_vertices) RKH_HIP(hipMemcpy(dv.get(), mesh_vertices, size_t(n_mesh_vertices) * 3 * sizeof(double), hipMemcpyHostToDevice));
-  RKH_TRY(launch_gjk_pair_depth(ctx->stream, da.get(), db.get(), n, dv.get(), dd.get(), dp1.get(), dp2.get(), dn3.get()));
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipMemcpyAsync(normal, dn3.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RKH_HIP(hipStreamSynchronize(ctx->stream));
-  return RKH_OK;
+  return gjk_pairs_run(ctx, a, b, n, mesh_vertices, n_mesh_vertices, dist, point1, point2, normal);
 }
 
 rkh_status rkh_scene_destroy(rkh_scene* scene) {
@@ -884,79 +857,28 @@ rkh_status records_2d_supported(const rkh_scene* scene, const char* entry) {
             "rkh_collision_records");
   return RKH_ERR_UNSUPPORTED;
 }
-// rkh_min_distance_records, rkh_min_distance_records_meshes and rkh_min_distance_records_depth after their checks: the
-// same transfers around the launch(stream, scene, d_x, B, out, d_normal); normal: the depth entry's, else nullptr
+// Every record entry after its checks: the same transfers around launch(stream, d_x, out, d_normal).  width: the doubles
+// of a point (3, planar scenes 2).  n_found = null: one record per state (the min-distance entries); else `cap` slots per
+// state and their count (the collision entries; cap = 0 still allocates an element each).  normal: the depth entries'.
 template <class Launch>
-rkh_status min_distance_records_3d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1, double* point2,
-                                   double* normal, uint32_t* shape1, uint32_t* shape2, Launch launch) {
+rkh_status records_run(rkh_scene* scene, int width, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found, double* dist,
+                       double* point1, double* point2, double* normal, uint32_t* shape1, uint32_t* shape2, Launch launch) {
   if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
+  const size_t slots = n_found ? size_t(B) * cap : size_t(B), min_n = n_found ? 1 : 0;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
-  DeviceBuffer<uint32_t> ds1, ds2;
-  if (normal) RKH_TRY(dn3.alloc(size_t(B) * 3));
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dd.alloc(size_t(B)));
-  RKH_TRY(dp1.alloc(size_t(B) * 3));
-  RKH_TRY(dp2.alloc(size_t(B) * 3));
-  RKH_TRY(ds1.alloc(size_t(B)));
-  RKH_TRY(ds2.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * scene->host.n_dof);
   RecordOut out;
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch(s, *scene, dx.get(), B, out, dn3.get()));
-  if (normal) RKH_HIP(hipMemcpyAsync(normal, dn3.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 3 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
-}
-// and the same for rkh_collision_records, rkh_collision_records_meshes and rkh_collision_records_depth:
-// launch(stream, scene, d_x, B, cap, out, d_normal)
-template <class Launch>
-rkh_status collision_records_3d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found, double* dist,
-                                double* point1, double* point2, double* normal, uint32_t* shape1, uint32_t* shape2, Launch launch) {
-  if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
-  const size_t slots = size_t(B) * cap;
-  hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
-  DeviceBuffer<uint32_t> dn, ds1, ds2;
-  if (normal) RKH_TRY(dn3.alloc(std::max<size_t>(1, slots * 3)));
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dn.alloc(size_t(B)));
-  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 3)));
-  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 3)));
-  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RecordOut out;
-  out.n_found = dn.get();
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch(s, *scene, dx.get(), B, cap, out, dn3.get()));
-  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  if (slots) {
-    if (normal) RKH_HIP(hipMemcpyAsync(normal, dn3.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 3 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
-  }
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  if (n_found) out.n_found = call.out(n_found, size_t(B));
+  double* dn3 = normal ? call.out(normal, slots * 3, min_n) : nullptr;
+  out.dist = call.out(dist, slots, min_n);
+  out.point1 = call.out(point1, slots * width, min_n);
+  out.point2 = call.out(point2, slots * width, min_n);
+  out.shape1 = call.out(shape1, slots, min_n);
+  out.shape2 = call.out(shape2, slots, min_n);
+  RKH_TRY(call.status());
+  RKH_TRY(launch(s, dx, out, dn3));
+  return call.fetch();
 }
 }  // namespace
 
@@ -969,19 +891,15 @@ rkh_status rkh_state_derivative(rkh_scene* scene, const double* x, const double*
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, du, dpd, dM, df;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(du.alloc(size_t(B) * n));
-  RKH_TRY(dpd.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dM.alloc(size_t(B) * n * n));
-  RKH_TRY(df.alloc(size_t(B) * n));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(du.get(), u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_state_derivative(s, *scene, dx.get(), du.get(), B, dpd.get(), dM.get(), df.get(), scene->d_err.get()));
-  RKH_HIP(hipMemcpyAsync(pd, dpd.get(), size_t(B) * 2 * n * 8, hipMemcpyDeviceToHost, s));
-  if (M) RKH_HIP(hipMemcpyAsync(M, dM.get(), size_t(B) * n * n * 8, hipMemcpyDeviceToHost, s));
-  if (f) RKH_HIP(hipMemcpyAsync(f, df.get(), size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * n);
+  const double* du = call.in(u, size_t(B) * n);
+  double* dpd = call.out(pd, size_t(B) * 2 * n);
+  double* dM = call.out(M, size_t(B) * n * n);
+  double* df = call.out(f, size_t(B) * n);
+  RKH_TRY(call.status());
+  RKH_TRY(launch_state_derivative(s, *scene, dx, du, B, dpd, dM, df, scene->d_err.get()));
+  RKH_TRY(call.fetch());
   return check_err_flag(scene);
 }
 
@@ -990,41 +908,42 @@ rkh_status rkh_min_distance(rkh_scene* scene, const double* x, uint32_t B, doubl
   if (B == 0) return RKH_OK;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dd.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_min_distance(s, *scene, dx.get(), B, dd.get()));
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * n);
+  double* dd = call.out(dist, size_t(B));
+  RKH_TRY(call.status());
+  RKH_TRY(launch_min_distance(s, *scene, dx, B, dd));
+  return call.fetch();
 }
 
 rkh_status rkh_min_distance_records(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
                                     double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_min_distance_records"));
-  return min_distance_records_3d(scene, x, B, dist, point1, point2, nullptr, shape1, shape2,
-                                 [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, RecordOut out, double*) {
-                                   return launch_min_distance_records(s, sc, dx, b, out);
-                                 });
+  return records_run(scene, 3, x, B, 0, nullptr, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_min_distance_records(s, *scene, dx, B, out);
+                     });
 }
 
 rkh_status rkh_min_distance_records_meshes(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
                                            double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_min_distance_records_meshes"));
-  return min_distance_records_3d(scene, x, B, dist, point1, point2, nullptr, shape1, shape2,
-                                 [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, RecordOut out, double*) {
-                                   return launch_min_distance_records_meshes(s, sc, dx, b, out);
-                                 });
+  return records_run(scene, 3, x, B, 0, nullptr, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_min_distance_records_meshes(s, *scene, dx, B, out);
+                     });
 }
 
 rkh_status rkh_min_distance_records_depth(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
                                           double* point2, double* normal, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !normal || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_min_distance_records_depth"));
-  return min_distance_records_3d(scene, x, B, dist, point1, point2, normal, shape1, shape2, launch_min_distance_records_depth);
+  return records_run(scene, 3, x, B, 0, nullptr, dist, point1, point2, normal, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double* dn3) {
+                       return launch_min_distance_records_depth(s, *scene, dx, B, out, dn3);
+                     });
 }
 
 rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_t B, int records, uint32_t runs, float* ms) {
@@ -1034,32 +953,26 @@ rkh_status rkh_diag_distance_query_ms(rkh_scene* scene, const double* x, uint32_
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
   const bool depth = records == 2 && !planar;  // the depth form of the 3D record kernel
-  DeviceBuffer<double> dx, dd, dp1, dp2, dn3;
-  DeviceBuffer<uint32_t> ds1, ds2;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dd.alloc(size_t(B)));
-  RKH_TRY(dp1.alloc(size_t(B) * 3));
-  RKH_TRY(dp2.alloc(size_t(B) * 3));
-  if (depth) RKH_TRY(dn3.alloc(size_t(B) * 3));
-  RKH_TRY(ds1.alloc(size_t(B)));
-  RKH_TRY(ds2.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
+  StagedCall call(s);  // nothing is copied back: the times are the answer
+  const double* dx = call.in(x, size_t(B) * 2 * n);
   RecordOut out;
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
+  out.dist = call.scratch<double>(size_t(B));
+  out.point1 = call.scratch<double>(size_t(B) * 3);
+  out.point2 = call.scratch<double>(size_t(B) * 3);
+  double* dn3 = depth ? call.scratch<double>(size_t(B) * 3) : nullptr;
+  out.shape1 = call.scratch<uint32_t>(size_t(B));
+  out.shape2 = call.scratch<uint32_t>(size_t(B));
+  RKH_TRY(call.status());
   hipEvent_t e0 = nullptr, e1 = nullptr;
   RKH_HIP(hipEventCreate(&e0));
   RKH_HIP(hipEventCreate(&e1));
   rkh_status st = RKH_OK;
   for (uint32_t r = 0; r < runs && st == RKH_OK; ++r) {
     hipError_t err = hipEventRecord(e0, s);
-    st = !records ? launch_min_distance(s, *scene, dx.get(), B, dd.get())
-         : planar ? launch_min_distance_records_2d(s, *scene, dx.get(), B, out)
-         : depth  ? launch_min_distance_records_depth(s, *scene, dx.get(), B, out, dn3.get())
-                  : launch_min_distance_records_meshes(s, *scene, dx.get(), B, out);  // (no meshes: the plain kernel)
+    st = !records ? launch_min_distance(s, *scene, dx, B, out.dist)
+         : planar ? launch_min_distance_records_2d(s, *scene, dx, B, out)
+         : depth  ? launch_min_distance_records_depth(s, *scene, dx, B, out, dn3)
+                  : launch_min_distance_records_meshes(s, *scene, dx, B, out);  // (no meshes: the plain kernel)
     if (err == hipSuccess) err = hipEventRecord(e1, s);
     if (err == hipSuccess) err = hipEventSynchronize(e1);
     if (err == hipSuccess) err = hipEventElapsedTime(&ms[r], e0, e1);
@@ -1077,22 +990,20 @@ rkh_status rkh_collision_records(rkh_scene* scene, const double* x, uint32_t B, 
                                  double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_supported(scene, "rkh_collision_records"));
-  return collision_records_3d(
-      scene, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
-      [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, uint32_t c, RecordOut out, double*) {
-        return launch_collision_records(s, sc, dx, b, c, out);
-      });
+  return records_run(scene, 3, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_collision_records(s, *scene, dx, B, cap, out);
+                     });
 }
 
 rkh_status rkh_collision_records_meshes(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
                                         double* dist, double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_collision_records_meshes"));
-  return collision_records_3d(
-      scene, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
-      [](hipStream_t s, const rkh_scene& sc, const double* dx, uint32_t b, uint32_t c, RecordOut out, double*) {
-        return launch_collision_records_meshes(s, sc, dx, b, c, out);
-      });
+  return records_run(scene, 3, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_collision_records_meshes(s, *scene, dx, B, cap, out);
+                     });
 }
 
 rkh_status rkh_collision_records_depth(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
@@ -1100,78 +1011,30 @@ rkh_status rkh_collision_records_depth(rkh_scene* scene, const double* x, uint32
                                        uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !normal || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_meshes_supported(scene, "rkh_collision_records_depth"));
-  return collision_records_3d(scene, x, B, cap, n_found, dist, point1, point2, normal, shape1, shape2,
-                              launch_collision_records_depth);
+  return records_run(scene, 3, x, B, cap, n_found, dist, point1, point2, normal, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double* dn3) {
+                       return launch_collision_records_depth(s, *scene, dx, B, cap, out, dn3);
+                     });
 }
 
 rkh_status rkh_min_distance_records_2d(rkh_scene* scene, const double* x, uint32_t B, double* dist, double* point1,
                                        double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_2d_supported(scene, "rkh_min_distance_records_2d"));
-  if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
-  hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
-  DeviceBuffer<uint32_t> ds1, ds2;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dd.alloc(size_t(B)));
-  RKH_TRY(dp1.alloc(size_t(B) * 2));
-  RKH_TRY(dp2.alloc(size_t(B) * 2));
-  RKH_TRY(ds1.alloc(size_t(B)));
-  RKH_TRY(ds2.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RecordOut out;
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch_min_distance_records_2d(s, *scene, dx.get(), B, out));
-  RKH_HIP(hipMemcpyAsync(dist, dd.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point1, dp1.get(), size_t(B) * 2 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(point2, dp2.get(), size_t(B) * 2 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return records_run(scene, 2, x, B, 0, nullptr, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_min_distance_records_2d(s, *scene, dx, B, out);
+                     });
 }
 
 rkh_status rkh_collision_records_2d(rkh_scene* scene, const double* x, uint32_t B, uint32_t cap, uint32_t* n_found,
                                     double* dist, double* point1, double* point2, uint32_t* shape1, uint32_t* shape2) {
   if (!scene || !x || !n_found || !dist || !point1 || !point2 || !shape1 || !shape2) return RKH_ERR_BAD_ARG;
   RKH_TRY(records_2d_supported(scene, "rkh_collision_records_2d"));
-  if (B == 0) return RKH_OK;
-  const int n = scene->host.n_dof;
-  const size_t slots = size_t(B) * cap;
-  hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, dd, dp1, dp2;
-  DeviceBuffer<uint32_t> dn, ds1, ds2;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dn.alloc(size_t(B)));
-  RKH_TRY(dd.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(dp1.alloc(std::max<size_t>(1, slots * 2)));
-  RKH_TRY(dp2.alloc(std::max<size_t>(1, slots * 2)));
-  RKH_TRY(ds1.alloc(std::max<size_t>(1, slots)));
-  RKH_TRY(ds2.alloc(std::max<size_t>(1, slots)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RecordOut out;
-  out.n_found = dn.get();
-  out.dist = dd.get();
-  out.point1 = dp1.get();
-  out.point2 = dp2.get();
-  out.shape1 = ds1.get();
-  out.shape2 = ds2.get();
-  RKH_TRY(launch_collision_records_2d(s, *scene, dx.get(), B, cap, out));
-  RKH_HIP(hipMemcpyAsync(n_found, dn.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  if (slots) {
-    RKH_HIP(hipMemcpyAsync(dist, dd.get(), slots * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point1, dp1.get(), slots * 2 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(point2, dp2.get(), slots * 2 * 8, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape1, ds1.get(), slots * 4, hipMemcpyDeviceToHost, s));
-    RKH_HIP(hipMemcpyAsync(shape2, ds2.get(), slots * 4, hipMemcpyDeviceToHost, s));
-  }
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return records_run(scene, 2, x, B, cap, n_found, dist, point1, point2, nullptr, shape1, shape2,
+                     [&](hipStream_t s, const double* dx, RecordOut out, double*) {
+                       return launch_collision_records_2d(s, *scene, dx, B, cap, out);
+                     });
 }
 
 rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const double* a, const double* b, uint32_t B,
@@ -1188,43 +1051,31 @@ rkh_status rkh_propagate(rkh_scene* scene, const rkh_dyn_space* space, const dou
   const int n = scene->host.n_dof, D = 2 * n;
   const int rec_stride = space->steps_per_edge + 1;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> da, db, dxo, drec;
-  DeviceBuffer<uint32_t> dsf;
-  RKH_TRY(da.alloc(size_t(B) * D));
-  RKH_TRY(db.alloc(size_t(B) * D));
-  RKH_TRY(dxo.alloc(size_t(B) * D));
-  RKH_TRY(dsf.alloc(size_t(B)));
-  if (record) {
-    RKH_TRY(drec.alloc(size_t(B) * rec_stride * D));
-    RKH_HIP(hipMemsetAsync(drec.get(), 0, size_t(B) * rec_stride * D * 8, s));
-  }
-  RKH_HIP(hipMemcpyAsync(da.get(), a, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(db.get(), b, size_t(B) * D * 8, hipMemcpyHostToDevice, s));
+  StagedCall call(s);
   EdgeIO io;
-  io.src = da.get();
+  io.src = call.in(a, size_t(B) * D);
   io.src_stride = D;
-  io.tgt = db.get();
+  io.tgt = call.in(b, size_t(B) * D);
   io.tgt_stride = D;
   io.B = B;
-  io.x_out = dxo.get();
-  io.steps_free = dsf.get();
-  io.record = record ? drec.get() : nullptr;
+  io.x_out = call.out(x_out, size_t(B) * D);
+  io.steps_free = call.out(steps_free, size_t(B));
+  io.record = record ? call.out(record, size_t(B) * rec_stride * D, 0, 0) : nullptr;
   io.record_stride = rec_stride;
   io.err_flag = scene->d_err.get();
+  RKH_TRY(call.status());
   // the mapping (identical results): by default a call of few edges -- the adaptors steer ONE edge per call -- takes the
   // lowest-latency one (steer_mapping)
   const SteerMapping m = steer_mapping(scene->host, SteerEntry::Propagate, steer_request(), B, 1, 0);
   note_steer_mapping(m);
-  DeviceBuffer<void> dws;
+  DeviceBuffer<void> dws;  // the two-lanes form's workspace
+  StreamWait dws_idle{s};
   if (m == SteerMapping::Pair) RKH_TRY(dws.alloc(propagate_pairs_workspace_bytes(n, B, 0, 1)));
   KernelGate gate;  // no gate; the two-lanes form carries its clearance bound unless RKH_STEER_CLEARANCE=0
   gate.clearance = steer_request().clearance;
   gate.clear_stats = scene->d_clear_stats.get();
   RKH_TRY(launch_propagate(s, *scene, m, dyn, io, B, 0, nullptr, nullptr, 1, static_cast<double*>(dws.get()), gate));
-  RKH_HIP(hipMemcpyAsync(x_out, dxo.get(), size_t(B) * D * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(steps_free, dsf.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  if (record) RKH_HIP(hipMemcpyAsync(record, drec.get(), size_t(B) * rec_stride * D * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
+  RKH_TRY(call.fetch());
   return check_err_flag(scene);
 }
 
@@ -1234,30 +1085,25 @@ rkh_status rkh_diag_feval_cycles(rkh_scene* scene, const double* x, const double
   if (!scene || !x || !u || !cycles || B == 0) return RKH_ERR_BAD_ARG;
   const int n = scene->host.n_dof;
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx, du, dsink;
-  DeviceBuffer<unsigned long long> dout;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(du.alloc(size_t(B) * n));
-  RKH_TRY(dout.alloc(size_t(B) * 8));
-  RKH_TRY(dsink.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(du.get(), u, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  rkh_status st;
+  // the two-lanes-per-edge kernel writes one record of 8 counters per wave of states, and the two-waves-per-edge kernel
+  // rows 2 b / 2 b + 1 for B / 2 states: both into zeroed rows
   const SteerMapping m = steer_mapping(scene->host, SteerEntry::CycleProbe, steer_request(), B, 1, 0);
-  if (m == SteerMapping::Pair) {  // two-lanes-per-edge kernel: one record of 8 counters per wave of states
-    RKH_HIP(hipMemsetAsync(dout.get(), 0, size_t(B) * 8 * 8, s));
-    st = launch_pair_cycles(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get());
-  } else if (m == SteerMapping::Duo) {  // two waves per edge: B / 2 states, rows 2 b / 2 b + 1 = the two waves' counters
-    RKH_HIP(hipMemsetAsync(dout.get(), 0, size_t(B) * 8 * 8, s));
-    st = (B >= 2) ? launch_feval_cycles_duo(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get())
-                  : RKH_ERR_BAD_ARG;
+  const bool sparse = m == SteerMapping::Pair || m == SteerMapping::Duo;
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * n);
+  const double* du = call.in(u, size_t(B) * n);
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied as they are");
+  unsigned long long* dout = call.out(reinterpret_cast<unsigned long long*>(cycles), size_t(B) * 8, 0, sparse ? 0 : StagedCall::kNoFill);
+  double* dsink = call.scratch<double>(size_t(B));
+  RKH_TRY(call.status());
+  if (m == SteerMapping::Pair) {
+    RKH_TRY(launch_pair_cycles(s, *scene, dx, du, B, iters, dout, dsink));
+  } else if (m == SteerMapping::Duo) {
+    RKH_TRY((B >= 2) ? launch_feval_cycles_duo(s, *scene, dx, du, B, iters, dout, dsink) : RKH_ERR_BAD_ARG);
   } else {
-    st = launch_feval_cycles(s, *scene, dx.get(), du.get(), B, iters, dout.get(), dsink.get());
+    RKH_TRY(launch_feval_cycles(s, *scene, dx, du, B, iters, dout, dsink));
   }
-  if (st != RKH_OK) return st;
-  RKH_HIP(hipMemcpyAsync(cycles, dout.get(), size_t(B) * 8 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 const char* rkh_steer_mapping_name(void) {
@@ -1281,15 +1127,12 @@ rkh_status rkh_diag_proximity_counts(rkh_scene* scene, const double* x, uint32_t
     return RKH_ERR_UNSUPPORTED;
   }
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx;
-  DeviceBuffer<unsigned long long> dout;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dout.alloc(8));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemsetAsync(dout.get(), 0, 8 * 8, s));
-  RKH_TRY(launch_pair_counts(s, *scene, dx.get(), B, dout.get()));
-  RKH_HIP(hipMemcpyAsync(counts, dout.get(), 8 * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * n);
+  unsigned long long* dout = call.out(reinterpret_cast<unsigned long long*>(counts), 8, 0, 0);
+  RKH_TRY(call.status());
+  RKH_TRY(launch_pair_counts(s, *scene, dx, B, dout));
+  RKH_TRY(call.fetch());
   // what the host knows: proxy pairs of the scene, and the ones inside the shapes' static reach
   counts[5] = uint64_t(scene->n_pairs);
   counts[6] = uint64_t(scene->n_pairs_verdict);
@@ -1306,17 +1149,13 @@ rkh_status rkh_diag_proximity_clearance(rkh_scene* scene, const double* x, uint3
     return RKH_ERR_UNSUPPORTED;
   }
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> dx;
-  DeviceBuffer<unsigned long long> dcnt;
-  DeviceBuffer<float> dout;
-  RKH_TRY(dx.alloc(size_t(B) * 2 * n));
-  RKH_TRY(dcnt.alloc(8));
-  RKH_TRY(dout.alloc(B));
-  RKH_HIP(hipMemcpyAsync(dx.get(), x, size_t(B) * 2 * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemsetAsync(dcnt.get(), 0, 8 * 8, s));
-  RKH_TRY(launch_pair_counts(s, *scene, dx.get(), B, dcnt.get(), dout.get()));
-  RKH_HIP(hipMemcpyAsync(out, dout.get(), size_t(B) * sizeof(float), hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
+  StagedCall call(s);
+  const double* dx = call.in(x, size_t(B) * 2 * n);
+  unsigned long long* dcnt = call.scratch<unsigned long long>(8, 0, 0);
+  float* dout = call.out(out, size_t(B));
+  RKH_TRY(call.status());
+  RKH_TRY(launch_pair_counts(s, *scene, dx, B, dcnt, dout));
+  RKH_TRY(call.fetch());
   if (!scene->host.has_clearance)  // the kernels carry nothing in such a scene
     for (uint32_t i = 0; i < B; ++i) out[i] = 0.0f;
   return RKH_OK;
@@ -1349,28 +1188,19 @@ rkh_status rkh_edge_check(rkh_scene* scene, const double* lower, const double* u
     qs.upper[i] = upper[i];
   }
   hipStream_t s = scene->ctx->stream;
-  DeviceBuffer<double> da, db, dxo;
-  DeviceBuffer<uint32_t> dnc;
-  RKH_TRY(da.alloc(size_t(B) * n));
-  RKH_TRY(db.alloc(size_t(B) * n));
-  RKH_TRY(dxo.alloc(size_t(B) * n));
-  RKH_TRY(dnc.alloc(size_t(B)));
-  RKH_HIP(hipMemcpyAsync(da.get(), a, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(db.get(), b, size_t(B) * n * 8, hipMemcpyHostToDevice, s));
+  StagedCall call(s);
   EdgeIO io;
-  io.src = da.get();
+  io.src = call.in(a, size_t(B) * n);
   io.src_stride = n;
-  io.tgt = db.get();
+  io.tgt = call.in(b, size_t(B) * n);
   io.tgt_stride = n;
   io.B = B;
-  io.x_out = dxo.get();
-  io.steps_free = dnc.get();
+  io.x_out = call.out(out, size_t(B) * n);
+  io.steps_free = call.out(n_checked, size_t(B));
   io.err_flag = scene->d_err.get();
+  RKH_TRY(call.status());
   RKH_TRY(launch_edge_check(s, *scene, qs, io, B));
-  RKH_HIP(hipMemcpyAsync(out, dxo.get(), size_t(B) * n * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(n_checked, dnc.get(), size_t(B) * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "rkh_internal.h"
+#include "staged_call.h"
 #include "svp_device.h"
 
 namespace rkh {
@@ -291,11 +292,6 @@ __global__ __launch_bounds__(256) void svp_interp_kernel(const SvpDev sp, const 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-struct StreamWait {  // no early return leaves work in flight on buffers that are about to be freed
-  hipStream_t s;
-  ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
-
 rkh_status bad(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
   return RKH_ERR_BAD_ARG;
@@ -485,19 +481,14 @@ rkh_status rkh_svp_reach_time(rkh_ctx* ctx, const rkh_svp_space* space, const do
   const size_t D = 2 * size_t(sp.n);
   hipStream_t s = ctx->stream;
   RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<double> d_a, d_b, d_t, d_p;
-  RKH_TRY(d_a.alloc(B * D));
-  RKH_TRY(d_b.alloc(B * D));
-  RKH_TRY(d_t.alloc(B));
-  if (peak) RKH_TRY(d_p.alloc(size_t(B) * sp.n));
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_a.get(), a, B * D * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_b.get(), b, B * D * 8, hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_svp_reach(s, sp, d_a.get(), d_b.get(), B, d_t.get(), d_p.get()));
-  RKH_HIP(hipMemcpyAsync(time, d_t.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  if (peak) RKH_HIP(hipMemcpyAsync(peak, d_p.get(), size_t(B) * sp.n * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  StagedCall call(s);
+  const double* d_a = call.in(a, B * D);
+  const double* d_b = call.in(b, B * D);
+  double* d_t = call.out(time, B);
+  double* d_p = peak ? call.out(peak, size_t(B) * sp.n) : nullptr;
+  RKH_TRY(call.status());
+  RKH_TRY(launch_svp_reach(s, sp, d_a, d_b, B, d_t, d_p));
+  return call.fetch();
 }
 
 rkh_status rkh_svp_nearest(rkh_ctx* ctx, const rkh_svp_space* space, const double* points, uint32_t n_pts, const double* queries,
@@ -518,25 +509,16 @@ rkh_status rkh_svp_nearest(rkh_ctx* ctx, const rkh_svp_space* space, const doubl
   const size_t D = 2 * size_t(sp.n);
   hipStream_t s = ctx->stream;
   RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<double> d_pts, d_q, d_dist, d_pd;
-  DeviceBuffer<uint32_t> d_idx, d_pi;
-  RKH_TRY(d_pts.alloc(n_pts * D));
-  RKH_TRY(d_q.alloc(B * D));
-  RKH_TRY(d_dist.alloc(size_t(B) * k));
-  RKH_TRY(d_idx.alloc(size_t(B) * k));
-  if (plan.part_entries) {
-    RKH_TRY(d_pd.alloc(plan.part_entries));
-    RKH_TRY(d_pi.alloc(plan.part_entries));
-  }
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_pts.get(), points, n_pts * D * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_q.get(), queries, B * D * 8, hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_svp_nearest(s, sp, plan, d_pts.get(), n_pts, d_q.get(), B, k, direction, d_pd.get(), d_pi.get(), d_idx.get(),
-                             d_dist.get()));
-  RKH_HIP(hipMemcpyAsync(idx, d_idx.get(), size_t(B) * k * 4, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipMemcpyAsync(dist, d_dist.get(), size_t(B) * k * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  StagedCall call(s);
+  const double* d_pts = call.in(points, n_pts * D);
+  const double* d_q = call.in(queries, B * D);
+  uint32_t* d_idx = call.out(idx, size_t(B) * k);
+  double* d_dist = call.out(dist, size_t(B) * k);
+  double* d_pd = plan.part_entries ? call.scratch<double>(plan.part_entries) : nullptr;  // the slices' lists
+  uint32_t* d_pi = plan.part_entries ? call.scratch<uint32_t>(plan.part_entries) : nullptr;
+  RKH_TRY(call.status());
+  RKH_TRY(launch_svp_nearest(s, sp, plan, d_pts, n_pts, d_q, B, k, direction, d_pd, d_pi, d_idx, d_dist));
+  return call.fetch();
 }
 
 rkh_status rkh_svp_nearest_async(rkh_ctx* ctx, const rkh_svp_space* space, const double* d_points, uint32_t n_pts,
@@ -620,30 +602,22 @@ rkh_status rkh_svp_interpolate(rkh_ctx* ctx, const rkh_svp_space* space, const d
   }
   hipStream_t s = ctx->stream;
   RKH_HIP(hipSetDevice(ctx->device));
-  DeviceBuffer<double> d_a, d_b, d_T, d_p, d_t, d_out;
-  RKH_TRY(d_a.alloc(B * D));
-  RKH_TRY(d_b.alloc(B * D));
-  RKH_TRY(d_T.alloc(B));
-  RKH_TRY(d_p.alloc(size_t(B) * sp.n));
   const size_t samples = size_t(B) * M;
+  StagedCall call(s);
+  const double* d_a = call.in(a, B * D);
+  const double* d_b = call.in(b, B * D);
+  double* d_T = call.out(reach_time, B);
+  double* d_p = call.scratch<double>(size_t(B) * sp.n);
+  const double* d_t = M ? call.in(t, samples) : nullptr;
+  double* d_out = M ? call.out(out, samples * D) : nullptr;
+  RKH_TRY(call.status());
+  RKH_TRY(launch_svp_reach(s, sp, d_a, d_b, B, d_T, d_p));
   if (M) {
-    RKH_TRY(d_t.alloc(samples));
-    RKH_TRY(d_out.alloc(samples * D));
-  }
-  StreamWait wait_on_exit{s};
-  RKH_HIP(hipMemcpyAsync(d_a.get(), a, B * D * 8, hipMemcpyHostToDevice, s));
-  RKH_HIP(hipMemcpyAsync(d_b.get(), b, B * D * 8, hipMemcpyHostToDevice, s));
-  RKH_TRY(launch_svp_reach(s, sp, d_a.get(), d_b.get(), B, d_T.get(), d_p.get()));
-  if (M) {
-    RKH_HIP(hipMemcpyAsync(d_t.get(), t, samples * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(svp_interp_kernel, dim3(uint32_t((samples + kSvpThreads - 1) / kSvpThreads)), dim3(kSvpThreads), 0, s, sp,
-                       d_a.get(), d_b.get(), d_T.get(), d_p.get(), d_t.get(), B, M, d_out.get());
+                       d_a, d_b, d_T, d_p, d_t, B, M, d_out);
     RKH_HIP(hipGetLastError());
-    RKH_HIP(hipMemcpyAsync(out, d_out.get(), samples * D * 8, hipMemcpyDeviceToHost, s));
   }
-  if (reach_time) RKH_HIP(hipMemcpyAsync(reach_time, d_T.get(), size_t(B) * 8, hipMemcpyDeviceToHost, s));
-  RKH_HIP(hipStreamSynchronize(s));
-  return RKH_OK;
+  return call.fetch();
 }
 
 }  // extern "C"
