@@ -4,7 +4,8 @@ stay on the device, every launch serves all unfinished problems.
 
     python examples/plan_svp_rrt_batch.py [problems] [max_vertices]
 
-Prints vertices, iterations and trajectory duration per problem, then samples the shortest trajectory with
+Prints vertices, iterations and trajectory duration per problem, shortcuts all found solutions in one
+rkh_svp_shortcut_paths call (duration before and after), then samples the shortest shortcut trajectory with
 rkh_svp_interpolate.  (The sample stream is the library's own, std::mt19937 per problem: the trees are not those of the
 host loop in plan_svp_rrt.py, which draws from numpy's generator.)"""
 import os
@@ -37,19 +38,21 @@ def main():
     nv, it, gp = planner.status()
     print("%d problems in %d rounds: %d iterations, %d vertices, %d points tested" %
           (P, stats.rounds, stats.iterations, stats.vertices, stats.tested_points))
+    cut = planner.shortcut_solutions()   # every found solution, all their vertex pairs walked, in one call
     best, best_dur = -1, np.inf
     for i in range(P):
-        pts, dur = planner.solution(i)
-        if len(pts):
-            print("problem %d (seed %d): vertices %d, iterations %d, path of %d edges, duration %.6f s" %
-                  (i, 1 + i, nv[i], it[i], len(pts) - 1, dur))
-            if dur < best_dur:
-                best, best_dur = i, dur
+        if i in cut:
+            c = cut[i]
+            print("problem %d (seed %d): vertices %d, iterations %d, path of %d edges, duration %.6f s; shortcut to %d edges, "
+                  "%.6f s%s" % (i, 1 + i, nv[i], it[i], len(c["points"]) - 1, c["duration"], len(c["keep"]) - 1, c["time_out"],
+                                " (%d hops fail the re-walk)" % c["n_blocked"] if c["n_blocked"] else ""))
+            if c["time_out"] < best_dur:
+                best, best_dur = i, c["time_out"]
         else:
             print("problem %d (seed %d): vertices %d, iterations %d, no path to the goal" % (i, 1 + i, nv[i], it[i]))
     if best < 0:
         return
-    pts, _ = planner.solution(best)
+    pts = cut[best]["points"][cut[best]["keep"]]
     space = lib.SvpSpace(cs, scene=scene)
     a, b = pts[:-1], pts[1:]
     times = space.reach_time(a, b, peaks=False)

@@ -709,6 +709,41 @@ rkh_status rkh_svp_rrt_get_tree(rkh_svp_rrt* planner, uint32_t problem, double* 
 rkh_status rkh_svp_rrt_get_solution(rkh_svp_rrt* planner, uint32_t problem, double* points /* [capacity][2 n_dof] */,
                                     uint32_t capacity, uint32_t* n_points, double* duration);
 
+/* ---- Shortcutting under the reach-time metric: a solution of the RRT above is a tree branch, a sequence of short extensions
+ * towards random candidates, and far from the shortest duration its own vertices allow.  This entry is rkh_shortcut_paths
+ * for paths of SVP points, B paths at once, exactly; that entry's definition holds with these substitutions and additions.
+ * Input: path b is the L_b >= 1 points points[path_ptr[b] .. path_ptr[b + 1]), each [2 n_dof], start first (the rows of
+ * rkh_svp_rrt_get_solution).
+ * Weight: w(i, j) = the reach time d(p_i -> p_j), for i < j only (time runs forward; d is not symmetric): bit for bit what
+ * rkh_svp_reach_time returns for the pair.  It may be +inf.
+ * Strict verdict: ok(i, j) is the `reached` byte of rkh_svp_edge_check(p_i, p_j, fraction = NULL): the bounds rule and the
+ * distance query at the travel times min_interval, + min_interval, ... below T all pass.  T < min_interval tests nothing
+ * and gives true; T = +inf gives false.  The end points themselves are not tested, as in rkh_svp_edge_check.
+ * Candidates: the span, the pair order and the walk of every pair are those of rkh_shortcut_paths.
+ * Search: unchanged -- dist[0] = 0, dist[j] = min over the allowed i < j of dist[i] + w(i, j), allowed = j == i + 1 or
+ * ok(i, j) within the span, the lowest i wins ties under strict <.  x + inf < y is never true, so an infinite weight is
+ * never taken: a vertex behind an infinite consecutive hop is reachable only through a shortcut that bypasses it.
+ * Outputs per path: keep / n_keep as there; time_in = the left-to-right sum of the consecutive hops' reach times (+inf if
+ * any of them is); time_out = dist[L - 1] <= time_in; n_blocked = the hops of the RETURNED path whose strict verdict is
+ * false.  They can only be input hops, and they do occur on planner output: a tree edge re-walked to its stored end point is
+ * a new profile with new test points, not the extension the planner tested (0: the returned trajectory passed the walk hop by
+ * hop).  A path of one point: n_keep = 1, keep = {0}, both times 0.
+ * Unreachable goal: time_out = +inf means the points are not a trajectory and no shortcut repairs them: n_keep[b] = 0,
+ * n_blocked[b] = 0 and every slot of keep that belongs to the path holds 0xFFFFFFFF.  The call is still RKH_OK and the other
+ * paths are served.
+ * B == 0 is RKH_OK.  RKH_ERR_BAD_ARG: everything the rkh_svp_* entries above refuse about a space (n_dof not the scene's
+ * included); a NULL scene, points, path_ptr, keep, n_keep or time_out; path_ptr not ascending from 0; an empty path; a
+ * coordinate that is not finite.  RKH_ERR_CAPACITY: a path of more than 1024 points; more than 2147483647 candidate pairs in
+ * the call; an edge with more than 1 048 576 points to test.
+ * Memory: the pairs go through the walk in chunks of 262 144, so a call takes 9 bytes per pair, 16 n_dof bytes per point and
+ * (1096 n_dof + 333) min(pairs, 262 144) bytes of walk workspace: at most 1.81 GB for a 6-joint chain.
+ * Not built: pruning of candidate pairs, shortcuts through new intermediate points. */
+rkh_status rkh_svp_shortcut_paths(rkh_scene* scene, const rkh_svp_space* space, const double* points /* [path_ptr[B]][2 n_dof] */,
+                                  const uint32_t* path_ptr /* [B+1] */, uint32_t B, uint32_t max_span,
+                                  uint32_t* keep /* [path_ptr[B]] */, uint32_t* n_keep /* [B] */,
+                                  double* time_in /* [B], may be NULL */, double* time_out /* [B] */,
+                                  uint32_t* n_blocked /* [B], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

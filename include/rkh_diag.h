@@ -167,6 +167,19 @@ rkh_status rkh_diag_ik_ms(rkh_scene* scene, int32_t frame, const rkh_pose* targe
  * of the planner with events on the context's stream; ms (may be NULL) receives the totals so far of {sample, nearest +
  * steer, extension walk, commit, probe walk, finish} in milliseconds (the walks include their read-backs). */
 rkh_status rkh_diag_svp_rrt_profile(rkh_svp_rrt* planner, int32_t enable, double* ms /* [6] */);
+/* rkh_svp_shortcut_paths (rkh.h) with the chunk size as an argument: the candidate pairs go through the walk's workspace
+ * chunk_pairs at a time (the entry itself uses 262 144), so that tests can put chunk boundaries inside a path's rows and
+ * between paths.  chunk_pairs in [1, 16 777 216]; everything else, results included, as there. */
+rkh_status rkh_diag_svp_shortcut_chunked(rkh_scene* scene, const rkh_svp_space* space, const double* points,
+                                         const uint32_t* path_ptr, uint32_t B, uint32_t max_span, uint32_t chunk_pairs,
+                                         uint32_t* keep, uint32_t* n_keep, double* time_in, double* time_out,
+                                         uint32_t* n_blocked);
+/* Time of the phases of rkh_svp_shortcut_paths on the same arguments (tools/measure_svp_shortcut.py): after one warm-up
+ * of the whole sequence, `runs` times the pair kernel, the walk (its launches and the read-back of the live count per pass)
+ * and the search with the input-time kernel, each between two events on the context's stream and summed over the chunks:
+ * ms[runs][3] = pairs, walks, search.  The copies of the call are not timed.  B > 0. */
+rkh_status rkh_diag_svp_shortcut_ms(rkh_scene* scene, const rkh_svp_space* space, const double* points, const uint32_t* path_ptr,
+                                    uint32_t B, uint32_t max_span, uint32_t runs, float* ms /* [runs][3] */);
 
 #ifdef __cplusplus
 }

@@ -65,23 +65,7 @@ __global__ __launch_bounds__(kShortcutThreads) void shortcut_pairs_kernel(
   }
 }
 
-// One launch of the search.  All pointers are device pointers.  ok(i, j) = (acc[pair] & ok_mask) != 0 || w < min_interval:
-// the accept bytes of an EDGE_STEER_BOTH walk with ok_mask = 2 and the space's min_interval, or a caller's verdict bytes
-// with ok_mask = 0xFF and min_interval = 0 (rkh_diag_shortcut_dp).
-struct ShortcutDpArgs {
-  const uint32_t* path_ptr;  // [B + 1] rows of the point table
-  const uint32_t* pair_ptr;  // [B + 1] pairs of the pair arrays
-  uint32_t B, max_span;
-  const uint8_t* acc;        // per pair
-  const double* w;           // per pair
-  uint32_t ok_mask;
-  double min_interval;
-  uint32_t* keep;            // [path_ptr[B]], path b at path_ptr[b]
-  uint32_t* n_keep;          // [B]
-  double* cost_out;          // [B]
-  uint32_t* n_blocked;       // [B] or null
-};
-
+// (ShortcutDpArgs, the arguments of one launch of the search: rkh_internal.h -- svp_shortcut.hip launches it as well)
 __global__ __launch_bounds__(kShortcutThreads) void shortcut_dp_kernel(ShortcutDpArgs a) {
   __shared__ double s_pub[2];
   __shared__ uint32_t s_pred[kShortcutMaxPoints];
@@ -182,9 +166,7 @@ __global__ __launch_bounds__(kShortcutThreads) void shortcut_dp_kernel(ShortcutD
   }
 }
 
-namespace {
-
-// The pair offsets of B paths, and everything both entry points check about path_ptr before anything is launched.
+// The pair offsets of B paths, and everything the entry points check about path_ptr before anything is launched.
 rkh_status shortcut_layout(const char* who, const uint32_t* path_ptr, uint32_t B, uint32_t max_span,
                            std::vector<uint32_t>* pair_ptr) {
   if (path_ptr[0] != 0) {
@@ -220,6 +202,8 @@ rkh_status launch_shortcut_dp(hipStream_t s, const ShortcutDpArgs& a) {
   RKH_HIP(hipGetLastError());
   return RKH_OK;
 }
+
+namespace {
 
 // rkh_shortcut_paths, and with ms != null its three launches timed `runs` times between events after one warm-up
 // (rkh_diag_shortcut_ms): ms[r][0..2] = pairs, walks, search.

@@ -571,4 +571,26 @@ size_t svp_walk_layout(int n_dof, uint32_t B, bool with_fraction, void* base, Sv
 // return.  Results in w.out, w.T, w.n_checked, w.reached.  passes (may be null): passes run.  RKH_ERR_CAPACITY: an edge with
 // more than 1 048 576 points to test.
 rkh_status launch_svp_walk(const char* who, const rkh_scene& scene, const SvpDev& sp, const SvpWalk& w, uint32_t* passes);
+
+// ---- the search of path shortcutting (path_shortcut.hip; the index rules are path_shortcut.h's) ----------------------------
+// One launch of the search.  All pointers are device pointers.  ok(i, j) = (acc[pair] & ok_mask) != 0 || w < min_interval:
+// the accept bytes of an EDGE_STEER_BOTH walk with ok_mask = 2 and the space's min_interval (rkh_shortcut_paths), or verdict
+// bytes with ok_mask = 0xFF and min_interval = 0 (rkh_diag_shortcut_dp; rkh_svp_shortcut_paths with the walk's `reached`).
+struct ShortcutDpArgs {
+  const uint32_t* path_ptr;  // [B + 1] rows of the point table
+  const uint32_t* pair_ptr;  // [B + 1] pairs of the pair arrays
+  uint32_t B, max_span;
+  const uint8_t* acc;        // per pair
+  const double* w;           // per pair
+  uint32_t ok_mask;
+  double min_interval;
+  uint32_t* keep;            // [path_ptr[B]], path b at path_ptr[b]
+  uint32_t* n_keep;          // [B]
+  double* cost_out;          // [B]
+  uint32_t* n_blocked;       // [B] or null
+};
+// The pair offsets of B paths, and everything the shortcut entries check about path_ptr before anything is launched.
+rkh_status shortcut_layout(const char* who, const uint32_t* path_ptr, uint32_t B, uint32_t max_span,
+                           std::vector<uint32_t>* pair_ptr);
+rkh_status launch_shortcut_dp(hipStream_t s, const ShortcutDpArgs& a);
 }  // namespace rkh

@@ -101,6 +101,7 @@ EXPORTS = [
     "rkh_svp_interpolate",
     "rkh_svp_rrt_create_batch", "rkh_svp_rrt_destroy", "rkh_svp_rrt_solve", "rkh_svp_rrt_get_status", "rkh_svp_rrt_get_tree",
     "rkh_svp_rrt_get_solution", "rkh_diag_svp_rrt_profile",
+    "rkh_svp_shortcut_paths", "rkh_diag_svp_shortcut_chunked", "rkh_diag_svp_shortcut_ms",
 ]
 
 
@@ -235,6 +236,9 @@ def load():
     lib.rkh_svp_rrt_get_tree.argtypes = [vp, u32, dp, u32p, dp, u32, u32p]
     lib.rkh_svp_rrt_get_solution.argtypes = [vp, u32, dp, u32, u32p, dp]
     lib.rkh_diag_svp_rrt_profile.argtypes = [vp, C.c_int32, dp]
+    lib.rkh_svp_shortcut_paths.argtypes = [vp, svp, dp, u32p, u32, u32, u32p, u32p, dp, dp, u32p]
+    lib.rkh_diag_svp_shortcut_chunked.argtypes = [vp, svp, dp, u32p, u32, u32, u32, u32p, u32p, dp, dp, u32p]
+    lib.rkh_diag_svp_shortcut_ms.argtypes = [vp, svp, dp, u32p, u32, u32, u32, C.POINTER(C.c_float)]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -868,6 +872,33 @@ class SvpSpace:
                                             T.dptr(out), T.dptr(rt)))
         return out[:B, :M], rt[:B]
 
+    def shortcut_paths(self, paths, max_span=0, chunk_pairs=None):
+        """rkh_svp_shortcut_paths: `paths` is a list of [L][2n] arrays of points, start first.  Returns (keep: one array of
+        path-local indices per path, time_in [B], time_out [B], n_blocked [B]); the shortcut trajectory b is
+        paths[b][keep[b]], empty where time_out[b] is +inf (the points are not a trajectory).  max_span: the longest hop
+        tried, in vertices (0: all).  chunk_pairs: rkh_diag_svp_shortcut_chunked with that many pairs per walk."""
+        pts, path_ptr = _path_table(paths, 2 * self.n)
+        B = len(path_ptr) - 1
+        keep = np.zeros(max(int(path_ptr[B]), 1), dtype=np.uint32)
+        n_keep, n_blocked = np.zeros(max(B, 1), dtype=np.uint32), np.zeros(max(B, 1), dtype=np.uint32)
+        time_in, time_out = np.zeros(max(B, 1)), np.zeros(max(B, 1))
+        head = (self.scene.h, C.byref(self.space), T.dptr(pts), T.u32ptr(path_ptr), B, int(max_span))
+        tail = (T.u32ptr(keep), T.u32ptr(n_keep), T.dptr(time_in), T.dptr(time_out), T.u32ptr(n_blocked))
+        if chunk_pairs is None:
+            _check(self.lib.rkh_svp_shortcut_paths(*head, *tail))
+        else:
+            _check(self.lib.rkh_diag_svp_shortcut_chunked(*head, int(chunk_pairs), *tail))
+        return _keep_lists(keep, n_keep[:B], path_ptr), time_in[:B], time_out[:B], n_blocked[:B]
+
+    def shortcut_ms(self, paths, max_span=0, runs=5):
+        """rkh_diag_svp_shortcut_ms: ms [runs][3] of the pair kernel, the walks and the search, summed over the chunks."""
+        pts, path_ptr = _path_table(paths, 2 * self.n)
+        ms = np.zeros((int(runs), 3), dtype=np.float32)
+        _check(self.lib.rkh_diag_svp_shortcut_ms(self.scene.h, C.byref(self.space), T.dptr(pts), T.u32ptr(path_ptr),
+                                                 len(path_ptr) - 1, int(max_span), int(runs),
+                                                 ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
+
 
 class SvpRrt:
     """Batch RRT over the SVP space (rkh_svp_rrt_*): `params` is one T.SvpRrtParams (T.make_svp_rrt_params) or a list of
@@ -916,6 +947,19 @@ class SvpRrt:
         n_pts, dur = C.c_uint32(0), C.c_double(0.0)
         _check(self.lib.rkh_svp_rrt_get_solution(self.h, int(problem), T.dptr(pts), cap, C.byref(n_pts), C.byref(dur)))
         return pts[:n_pts.value], dur.value
+
+    def shortcut_solutions(self, max_span=0):
+        """The solutions of all problems that reached their goal, shortcut in ONE rkh_svp_shortcut_paths call.  Returns
+        {problem: {"points" [L][2n], "duration", "keep", "time_in", "time_out", "n_blocked"}}; the shortcut trajectory is
+        points[keep]."""
+        _, _, gp = self.status()
+        solved = [i for i in range(self.P) if gp[i] != self.NO_INDEX]
+        sols = [self.solution(i) for i in solved]
+        if not solved:
+            return {}
+        keep, t_in, t_out, blocked = SvpSpace(self.space, scene=self.scene).shortcut_paths([p for p, _ in sols], max_span)
+        return {i: {"points": sols[k][0], "duration": sols[k][1], "keep": keep[k], "time_in": float(t_in[k]),
+                    "time_out": float(t_out[k]), "n_blocked": int(blocked[k])} for k, i in enumerate(solved)}
 
     def profile(self, enable=True):
         """Brackets the phases of later rounds with stream events; returns {phase: ms so far}."""
