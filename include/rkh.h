@@ -631,13 +631,27 @@ rkh_status rkh_inverse_kinematics(rkh_scene* scene, int32_t frame, const rkh_pos
  * fraction == 1.0 returns b, fraction == 0.0 returns a, any other the (untested) point at dt.  out [B][2 n_dof];
  * reach_time [B]; n_checked [B]: points tested, the failing one included; reached [B]: 1 where the loop ran to dt without a
  * failure.  Every output but out may be NULL.  An edge with more than 1 048 576 points to test: RKH_ERR_CAPACITY.
+ * rkh_svp_edge_check_back: the same arguments, outputs, NULL rules and refusals; it stands in for move_pt_back_to
+ * (svp_Ndof_reach_topologies.hpp) over is_free: the profile a -> b walked from its end backwards, the last free point kept.
+ * In fp64 with these groupings:
+ *     T, peak = reach(a, b)                       the common-time solve of d(a -> b)
+ *     T == +inf:  out = b, n_checked = 0, reached = 0
+ *     dt = T * (1.0 - fraction)                   fraction NULL: 1.0
+ *     d = T - min_interval;  last = b
+ *     while d > dt:                               strict
+ *         x = point(a, b, peak, T, d);  ++n_checked
+ *         not in bounds, or a proxy pair closer than 0 at x in model units:  out = last, reached = 0, stop
+ *         last = x;  d -= min_interval            repeated subtraction
+ *     reached = 1;  out = a if fraction == 1.0, b if fraction == 0.0, else point(a, b, peak, T, dt)   (untested, as forward)
+ * More than 1 048 576 points to test (counted by the same repeated subtraction): RKH_ERR_CAPACITY.
  * rkh_svp_interpolate: the profile of each pair sampled at M times, t [B][M], out [B][M][2 n_dof], reach_time [B] (may be
  * NULL).  t <= 0: a; t >= T: b; an infinite pair: a at every time.
  *
  * B == 0, M == 0 or n_pts == 0 is RKH_OK.  RKH_ERR_BAD_ARG: space->struct_size != sizeof(rkh_svp_space), n_dof not in
  * [1, 12] or not the scene's, min_interval not positive and finite, lower > upper, a negative or non-finite limit, k or
- * direction out of range, a NULL required pointer.  Not built: the order-2 space (SAP), the temporal spaces,
- * move_pt_back_to, and batch planners over this space other than the RRT below. */
+ * direction out of range, a NULL required pointer.  Not built: the order-2 space (SAP), the temporal spaces, and batch
+ * planners over this space other than the RRT and the bidirectional RRT below (no RRT*, PRM or SBA* over it), a walk
+ * fused into one launch. */
 rkh_status rkh_svp_in_bounds(const rkh_svp_space* space, const double* pts /* [B][2 n_dof] */, uint32_t B, uint8_t* ok /* [B] */);
 rkh_status rkh_svp_reach_time(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
                               double* time /* [B] */, double* peak /* [B][n_dof], may be NULL */);
@@ -650,6 +664,9 @@ rkh_status rkh_svp_nearest_async(rkh_ctx* ctx, const rkh_svp_space* space, const
 rkh_status rkh_svp_edge_check(rkh_scene* scene, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
                               const double* fraction /* [B], NULL = 1.0 */, double* out /* [B][2 n_dof] */,
                               double* reach_time /* [B] */, uint32_t* n_checked /* [B] */, uint8_t* reached /* [B] */);
+rkh_status rkh_svp_edge_check_back(rkh_scene* scene, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
+                                   const double* fraction /* [B], NULL = 1.0 */, double* out /* [B][2 n_dof] */,
+                                   double* reach_time /* [B] */, uint32_t* n_checked /* [B] */, uint8_t* reached /* [B] */);
 rkh_status rkh_svp_interpolate(rkh_ctx* ctx, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
                                const double* t /* [B][M] */, uint32_t M, double* out /* [B][M][2 n_dof] */,
                                double* reach_time /* [B] */);
@@ -708,6 +725,73 @@ rkh_status rkh_svp_rrt_get_tree(rkh_svp_rrt* planner, uint32_t problem, double* 
                                 uint32_t* n_vertices);
 rkh_status rkh_svp_rrt_get_solution(rkh_svp_rrt* planner, uint32_t problem, double* points /* [capacity][2 n_dof] */,
                                     uint32_t capacity, uint32_t* n_points, double* duration);
+
+/* ---- batch bidirectional RRT over the SVP space: two device-resident trees per problem ---------------------------------------
+ * The reach time is not symmetric, so a tree rooted at the goal cannot grow with forward walks: every edge of it must be a
+ * profile that runs towards the goal.  Here tree 0 is rooted at the start and grows forward; tree 1 is rooted at the goal
+ * and grows backward with rkh_svp_edge_check_back: the edge of its vertex v is the profile v -> parent(v), and
+ * edge_time[v] = d(v -> parent(v)).  (The progress rule is steer_back_to_position's, the alternation
+ * generate_bidirectional_rrt's; the reference's own bidirectional RRT steers both trees forward, which on this space gives
+ * goal-tree edges nobody can traverse.)  One problem is a rkh_svp_rrt_params with has_goal = 1; max_vertices bounds each
+ * tree; seed, max_iterations, max_edge_time and steer_tol mean what they do for rkh_svp_rrt.  One std::mt19937(seed)
+ * candidate stream per problem, exactly the RRT's; both sides consume it in loop order.  Each problem's two trees are, bit
+ * for bit, those of this sequential loop, whatever P is and whatever the other problems do:
+ *
+ *   target[0] = (goal, vertex 0 of tree 1);  target[1] = (start, vertex 0 of tree 0);  side = 0;  iterations = 0
+ *   loop:
+ *     n0 >= max_vertices or n1 >= max_vertices: end "max_vertices"
+ *     (tp, tv) = target[side]
+ *     tv is none:                                             # a sample is needed
+ *         iterations >= max_iterations: end "max_iterations"
+ *         ++iterations; q = next candidate; not rkh_svp_in_bounds(q): continue loop (same side)
+ *         tp = q
+ *     side 0: (idx, asked) = argmin over tree 0 of d(vertex -> tp); side 1: argmin over tree 1 of d(tp -> vertex)
+ *             ties to the lower index; every distance +inf: not moved
+ *     else:
+ *         f = asked > 0 ? min(1, max_edge_time / asked) : 1          # rl1rrt_fraction
+ *         side 0: forward walk (a = vertex, b = tp, f);  side 1: backward walk (a = tp, b = vertex, f)
+ *         tv is a vertex and f == 1.0 and reached:  join = (idx, tv) on side 0, (tv, idx) on side 1;
+ *                                                   join_time = asked;  end "joined"   # nothing is appended
+ *         n_checked == 0: not moved
+ *         else travelled = d(vertex -> out) on side 0, d(out -> vertex) on side 1;
+ *              rl1rrt_progress(travelled, asked, f, steer_tol): append out to tree `side` with parent idx and
+ *              edge time travelled: moved;  otherwise not moved
+ *     target[1 - side] = moved ? (out, the new vertex) : none;   side = 1 - side
+ *
+ * A join does not look at n_checked: a connection shorter than min_interval tests nothing and counts, as the RRT's goal
+ * probe does.  max_iterations ends a problem only when a sample is needed and none is left: a problem whose targets are
+ * vertices goes on past iterations == max_iterations, and with max_iterations == 0 it runs until its first failed half
+ * step.  There is no probe before the loop: the first half step is the attempt start -> goal.
+ * What this planner is not known to be: faster.  On the C2 scene the unidirectional rkh_svp_rrt often needs fewer vertices,
+ * because its goal probe walks the whole edge whatever max_edge_time is; nobody has measured either planner on a scene
+ * where the goal sits in a pocket the probe rarely sees.
+ *
+ * rkh_svp_birrt_create_batch: P in [1, 16384].  One arena of the context per planner.
+ * rkh_svp_birrt_solve: rounds (one half step of every unfinished problem) until every problem has ended or max_rounds have
+ * run (< 0: no limit); a later call resumes.  stats (may be NULL): rkh_svp_rrt_stats, totals since create; vertices counts
+ * both trees, roots included.  A round draws at most 1024 candidates per problem, as the RRT's.
+ * rkh_svp_birrt_get_status: per problem; any pointer may be NULL.  join0 / join1: the joined vertices of tree 0 and tree 1,
+ * 0xFFFFFFFF: no join.
+ * rkh_svp_birrt_get_tree: as rkh_svp_rrt_get_tree, of tree 0 or 1.
+ * rkh_svp_birrt_get_solution: the points start ... join0, join1 ... goal; duration summed in path order: tree-0 edge times
+ * from the start, then join_time, then tree-1 edge times towards the goal.  n_points = 0 and duration = 0 without a join;
+ * more points than capacity: RKH_ERR_CAPACITY with *n_points set.
+ *
+ * RKH_ERR_BAD_ARG: what rkh_svp_rrt_create_batch refuses, and has_goal == 0, a goal that is not finite or fails
+ * rkh_svp_in_bounds (the message names "problem i"), tree > 1.  RKH_ERR_CAPACITY: an edge with more than 1 048 576 points to
+ * test (the planner then refuses further rounds).  A failed create leaves no planner behind (*out = NULL). */
+typedef struct rkh_svp_birrt rkh_svp_birrt;
+rkh_status rkh_svp_birrt_create_batch(rkh_scene* scene, const rkh_svp_space* space, const rkh_svp_rrt_params* params /* [P] */,
+                                      uint32_t P, rkh_svp_birrt** out);
+void rkh_svp_birrt_destroy(rkh_svp_birrt* planner);
+rkh_status rkh_svp_birrt_solve(rkh_svp_birrt* planner, int64_t max_rounds, rkh_svp_rrt_stats* stats);
+rkh_status rkh_svp_birrt_get_status(rkh_svp_birrt* planner, uint32_t* n_vertices0 /* [P] */, uint32_t* n_vertices1 /* [P] */,
+                                    uint32_t* iterations /* [P] */, uint32_t* join0 /* [P] */, uint32_t* join1 /* [P] */);
+rkh_status rkh_svp_birrt_get_tree(rkh_svp_birrt* planner, uint32_t problem, uint32_t tree /* 0 | 1 */,
+                                  double* vertices /* [capacity][2 n_dof] */, uint32_t* parent /* [capacity] */,
+                                  double* edge_time /* [capacity] */, uint32_t capacity, uint32_t* n_vertices);
+rkh_status rkh_svp_birrt_get_solution(rkh_svp_birrt* planner, uint32_t problem, double* points /* [capacity][2 n_dof] */,
+                                      uint32_t capacity, uint32_t* n_points, double* duration);
 
 /* ---- Shortcutting under the reach-time metric: a solution of the RRT above is a tree branch, a sequence of short extensions
  * towards random candidates, and far from the shortest duration its own vertices allow.  This entry is rkh_shortcut_paths

@@ -180,6 +180,18 @@ rkh_status rkh_diag_svp_shortcut_chunked(rkh_scene* scene, const rkh_svp_space* 
  * ms[runs][3] = pairs, walks, search.  The copies of the call are not timed.  B > 0. */
 rkh_status rkh_diag_svp_shortcut_ms(rkh_scene* scene, const rkh_svp_space* space, const double* points, const uint32_t* path_ptr,
                                     uint32_t B, uint32_t max_span, uint32_t runs, float* ms /* [runs][3] */);
+/* The directed walk launch with a direction byte per row from the host: back[e] != 0 walks row e as
+ * rkh_svp_edge_check_back does, 0 as rkh_svp_edge_check does, bit for bit, in one launch; back NULL: every row forward.
+ * Everything else as rkh_svp_edge_check.  For the tests and the measurement of launches that hold both directions (the
+ * rounds of rkh_svp_birrt_*). */
+rkh_status rkh_diag_svp_edge_check_dir(rkh_scene* scene, const rkh_svp_space* space, const double* a, const double* b, uint32_t B,
+                                       const double* fraction /* [B], NULL = 1.0 */, const uint8_t* back /* [B] */,
+                                       double* out /* [B][2 n_dof] */, double* reach_time /* [B] */,
+                                       uint32_t* n_checked /* [B] */, uint8_t* reached /* [B] */);
+/* The split of the batch bidirectional SVP RRT's rounds (tools/measure_svp_birrt.py), as rkh_diag_svp_rrt_profile: ms (may
+ * be NULL) receives the totals so far of {sample, nearest, steer, walk, commit} in milliseconds (the walk includes its
+ * read-backs). */
+rkh_status rkh_diag_svp_birrt_profile(rkh_svp_birrt* planner, int32_t enable, double* ms /* [5] */);
 
 #ifdef __cplusplus
 }

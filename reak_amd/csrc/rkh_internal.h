@@ -571,6 +571,11 @@ size_t svp_walk_layout(int n_dof, uint32_t B, bool with_fraction, void* base, Sv
 // return.  Results in w.out, w.T, w.n_checked, w.reached.  passes (may be null): passes run.  RKH_ERR_CAPACITY: an edge with
 // more than 1 048 576 points to test.
 rkh_status launch_svp_walk(const char* who, const rkh_scene& scene, const SvpDev& sp, const SvpWalk& w, uint32_t* passes);
+// The same walk with a direction per row (svp_walk_dir.hip, the rules are svp_walk_rules.h's): d_back [w.B] on the device,
+// d_back[e] != 0 walks the profile a_e -> b_e backward from b_e (rkh_svp_edge_check_back), 0 forward as launch_svp_walk does,
+// bit for bit; d_back null: every row forward.  Same workspace, results, passes and errors.
+rkh_status launch_svp_walk_dir(const char* who, const rkh_scene& scene, const SvpDev& sp, const SvpWalk& w, const uint8_t* d_back,
+                               uint32_t* passes);
 
 // ---- the search of path shortcutting (path_shortcut.hip; the index rules are path_shortcut.h's) ----------------------------
 // One launch of the search.  All pointers are device pointers.  ok(i, j) = (acc[pair] & ok_mask) != 0 || w < min_interval:

@@ -102,6 +102,9 @@ EXPORTS = [
     "rkh_svp_rrt_create_batch", "rkh_svp_rrt_destroy", "rkh_svp_rrt_solve", "rkh_svp_rrt_get_status", "rkh_svp_rrt_get_tree",
     "rkh_svp_rrt_get_solution", "rkh_diag_svp_rrt_profile",
     "rkh_svp_shortcut_paths", "rkh_diag_svp_shortcut_chunked", "rkh_diag_svp_shortcut_ms",
+    "rkh_svp_edge_check_back", "rkh_diag_svp_edge_check_dir",
+    "rkh_svp_birrt_create_batch", "rkh_svp_birrt_destroy", "rkh_svp_birrt_solve", "rkh_svp_birrt_get_status",
+    "rkh_svp_birrt_get_tree", "rkh_svp_birrt_get_solution", "rkh_diag_svp_birrt_profile",
 ]
 
 
@@ -239,6 +242,16 @@ def load():
     lib.rkh_svp_shortcut_paths.argtypes = [vp, svp, dp, u32p, u32, u32, u32p, u32p, dp, dp, u32p]
     lib.rkh_diag_svp_shortcut_chunked.argtypes = [vp, svp, dp, u32p, u32, u32, u32, u32p, u32p, dp, dp, u32p]
     lib.rkh_diag_svp_shortcut_ms.argtypes = [vp, svp, dp, u32p, u32, u32, u32, C.POINTER(C.c_float)]
+    lib.rkh_svp_edge_check_back.argtypes = [vp, svp, dp, dp, u32, dp, dp, dp, u32p, u8p]
+    lib.rkh_diag_svp_edge_check_dir.argtypes = [vp, svp, dp, dp, u32, dp, u8p, dp, dp, u32p, u8p]
+    lib.rkh_svp_birrt_create_batch.argtypes = [vp, svp, C.POINTER(T.SvpRrtParams), u32, C.POINTER(vp)]
+    lib.rkh_svp_birrt_destroy.argtypes = [vp]
+    lib.rkh_svp_birrt_destroy.restype = None
+    lib.rkh_svp_birrt_solve.argtypes = [vp, C.c_int64, C.POINTER(SvpRrtStats)]
+    lib.rkh_svp_birrt_get_status.argtypes = [vp, u32p, u32p, u32p, u32p, u32p]
+    lib.rkh_svp_birrt_get_tree.argtypes = [vp, u32, u32, dp, u32p, dp, u32, u32p]
+    lib.rkh_svp_birrt_get_solution.argtypes = [vp, u32, dp, u32, u32p, dp]
+    lib.rkh_diag_svp_birrt_profile.argtypes = [vp, C.c_int32, dp]
     lib.rkh_planner_num_problems.restype = u32
     lib.rkh_planner_num_problems.argtypes = [vp]
     lib.rkh_planner_destroy.argtypes = [vp]
@@ -861,6 +874,32 @@ class SvpSpace:
                                            re.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out[:B], rt[:B], nc[:B], re[:B]
 
+    def edge_check_back(self, a, b, fraction=None):
+        """rkh_svp_edge_check_back: the profile a -> b walked from b backwards; outputs as edge_check."""
+        return self._edge_check_dir(a, b, fraction, True)
+
+    def edge_check_dir(self, a, b, back, fraction=None):
+        """rkh_diag_svp_edge_check_dir: row e backward where back[e] != 0, forward where 0, in one launch."""
+        return self._edge_check_dir(a, b, fraction, np.ascontiguousarray(np.asarray(back, dtype=np.uint8)))
+
+    def _edge_check_dir(self, a, b, fraction, back):
+        a, b = self._rows(a), self._rows(b)
+        B = len(a)
+        out, rt = np.zeros((max(B, 1), 2 * self.n)), np.zeros(max(B, 1))
+        nc, re = np.zeros(max(B, 1), dtype=np.uint32), np.zeros(max(B, 1), dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        fr = None
+        if fraction is not None:
+            fr = np.ascontiguousarray(np.broadcast_to(np.asarray(fraction, dtype=np.float64), (B,)))
+        head = (self.scene.h, C.byref(self.space), T.dptr(a), T.dptr(b), B, T.dptr(fr) if fr is not None else None)
+        tail = (T.dptr(out), T.dptr(rt), T.u32ptr(nc), re.ctypes.data_as(u8))
+        if back is True:
+            _check(self.lib.rkh_svp_edge_check_back(*head, *tail))
+        else:
+            assert len(back) == B
+            _check(self.lib.rkh_diag_svp_edge_check_dir(*head, back.ctypes.data_as(u8), *tail))
+        return out[:B], rt[:B], nc[:B], re[:B]
+
     def interpolate(self, a, b, t):
         """(out [B][M][2n], reach_time [B]): the profile of each pair at the times t [B][M]."""
         a, b = self._rows(a), self._rows(b)
@@ -970,6 +1009,76 @@ class SvpRrt:
     def close(self):
         if self.h:
             self.lib.rkh_svp_rrt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SvpBiRrt:
+    """Batch bidirectional RRT over the SVP space (rkh_svp_birrt_*): `params` is one T.SvpRrtParams with a goal
+    (T.make_svp_rrt_params) or a list of them, independent problems on one scene that share every launch.  Tree 0 grows
+    forward from the start, tree 1 backward from the goal (the edge of its vertex v is the profile v -> parent(v))."""
+    NO_INDEX = 0xFFFFFFFF
+    PHASES = ("sample", "nearest", "steer", "walk", "commit")
+
+    def __init__(self, scene, space, params):
+        self.lib = load()
+        self.scene, self.space = scene, space
+        plist = list(params) if isinstance(params, (list, tuple)) else [params]
+        self.P, self.n = len(plist), int(space.n_dof)
+        arr = (T.SvpRrtParams * max(self.P, 1))(*plist)
+        self.max_vertices = [int(p.max_vertices) for p in plist]
+        self.h = C.c_void_p()
+        _check(self.lib.rkh_svp_birrt_create_batch(scene.h, C.byref(self.space), arr, self.P, C.byref(self.h)))
+        self.stats = SvpRrtStats()
+        _check(self.lib.rkh_svp_birrt_solve(self.h, 0, C.byref(self.stats)))   # no round: the totals after create
+
+    def solve(self, max_rounds=-1):
+        """Rounds (one half step of every unfinished problem) until every problem has ended or max_rounds have run (< 0: no
+        limit); resumes where it stopped."""
+        _check(self.lib.rkh_svp_birrt_solve(self.h, int(max_rounds), C.byref(self.stats)))
+        return self.stats
+
+    @property
+    def finished(self):
+        return self.stats.problems_finished == self.P
+
+    def status(self):
+        """(n_vertices0 [P], n_vertices1 [P], iterations [P], join0 [P], join1 [P]); a join of 0xFFFFFFFF: none"""
+        out = tuple(np.zeros(self.P, dtype=np.uint32) for _ in range(5))
+        _check(self.lib.rkh_svp_birrt_get_status(self.h, *(T.u32ptr(x) for x in out)))
+        return out
+
+    def tree(self, problem=0, which=0):
+        """{"vertices" [V][2n], "parent" [V], "edge_time" [V]} of tree `which` (0: from the start, 1: from the goal)"""
+        cap = self.max_vertices[problem]
+        verts, parent, et = np.zeros((cap, 2 * self.n)), np.zeros(cap, dtype=np.uint32), np.zeros(cap)
+        V = C.c_uint32(0)
+        _check(self.lib.rkh_svp_birrt_get_tree(self.h, int(problem), int(which), T.dptr(verts), T.u32ptr(parent), T.dptr(et),
+                                               cap, C.byref(V)))
+        return {"vertices": verts[:V.value], "parent": parent[:V.value], "edge_time": et[:V.value]}
+
+    def solution(self, problem=0):
+        """(points [n_points][2n] start ... join0, join1 ... goal, duration); (empty, 0.0) without a join"""
+        cap = 2 * self.max_vertices[problem]
+        pts = np.zeros((cap, 2 * self.n))
+        n_pts, dur = C.c_uint32(0), C.c_double(0.0)
+        _check(self.lib.rkh_svp_birrt_get_solution(self.h, int(problem), T.dptr(pts), cap, C.byref(n_pts), C.byref(dur)))
+        return pts[:n_pts.value], dur.value
+
+    def profile(self, enable=True):
+        """Brackets the phases of later rounds with stream events; returns {phase: ms so far}."""
+        ms = np.zeros(len(self.PHASES))
+        _check(self.lib.rkh_diag_svp_birrt_profile(self.h, 1 if enable else 0, T.dptr(ms)))
+        return dict(zip(self.PHASES, ms.tolist()))
+
+    def close(self):
+        if self.h:
+            self.lib.rkh_svp_birrt_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
